@@ -11,6 +11,10 @@ torch.distributed.run, barrier + synchronize on both sides of the timed region, 
 default; cfg3 = the data-parallel training step, see run_training; cfg4 = 64x64 LR views, 8 per GPU; cfg5 = 9x9 views); explicit
 --ang/--lr/--scale/--batch/--precision flags override the named shape.
 
+--dump-outputs DIR writes what the timed path returned in its last step (inference: the SR output; training: the loss, the SR
+output of that step's forward and the updated weights) as float32 DIR/<name>.npy on rank 0; inputs and weights are seeded, so
+two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0 with the extra objects
   roofline     : for the dominant kernel (largest share of GPU time).  Its algorithmic FLOPs and HBM bytes per launch
                  decide the bound -- dense bf16 MFMA peak 2.5 PFLOP/s (fp32 path 157.3 TFLOP/s) or HBM 8 TB/s -- and
@@ -403,6 +407,27 @@ def note(msg: str) -> None:
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64_000_000       # --dump-outputs: all files together (npy headers included) stay below 64 MB
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: what the timed path returned in its last step, one float32 ``<name>.npy`` per array.  If they do not
+    fit in DUMP_MAX_BYTES together, the largest is replaced by ``<name>_sample.npy``: its elements at a fixed, seeded set of
+    flat indices (ascending), the same set for the same shape in every run."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    big = max(arrays, key=lambda k: arrays[k].nbytes)
+    rest = sum(a.nbytes + 128 for k, a in arrays.items() if k != big)
+    room = (DUMP_MAX_BYTES - rest - 128) // 4
+    if arrays[big].size > room:
+        idx = np.sort(np.random.default_rng(0).choice(arrays[big].size, size=room, replace=False))
+        arrays[big + "_sample"] = arrays.pop(big).reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    note(f"outputs of the last timed step -> {path}: " + ", ".join(f"{k} {a.shape}" for k, a in arrays.items()))
+
+
 CONFIGS = {   # BASELINE.json configs by name: (kind, angRes, scale, LR view size, patches per GPU and step, precision)
     "cfg1": ("infer", 5, 2, 32, 1, "fp32"),    # configs[0]: single 32x32 patch, 2x, batch 1 (the reference's CPU-runnable case, here on the GPU)
     "cfg2": ("infer", 5, 4, 32, 4, "bf16"),    # configs[1]: the metric's own configuration
@@ -456,12 +481,23 @@ def run_training(args, rank, world, dev, dist, rehearsal):
         sync()
         return time.perf_counter() - t0, loss
 
+    init = (ts.flat_params.clone(), ts.t)
     t_settle = time.perf_counter()                 # the same a-priori settle as the inference protocol: one second of load
     while time.perf_counter() - t_settle < SETTLE_SECONDS:
         ts.step(lr, hr)
         torch.cuda.synchronize()
+    # back to the seeded weights and a fresh optimiser (in place: the captured graphs keep their buffers), so that the timed steps,
+    # and the loss and --dump-outputs of the last one, do not depend on how many steps the time-bounded settle ran
+    with torch.no_grad():
+        ts.flat_params.copy_(init[0])
+        ts.m.zero_()
+        ts.v.zero_()
+    ts.t = init[1]
+    net._packed = None
     dt, loss = timed(args.steps, args.warmup)
     assert bool(torch.isfinite(loss).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "output": ts.last_out, "params": ts.flat_params})
     ranks_ms = per_rank_ms(dt, args.steps, world, dist, torch.device("cpu") if rehearsal else dev)
     dt_max = dp.barrier_max_seconds(dt, torch.device("cpu") if rehearsal else dev)
     ar = None
@@ -543,7 +579,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the parity_path, latency_path and train objects (A/B timing runs)")
     ap.add_argument("--settle-seconds", type=float, default=None, help="untimed load in front of --warmup (default SETTLE_SECONDS; profiling passes under counters use a short one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, < 64 MB in all; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global SETTLE_SECONDS
     if args.settle_seconds is not None:
         SETTLE_SECONDS = args.settle_seconds
@@ -610,6 +650,8 @@ def main():
     dt, out = timed_protocol(step, lr, args, sync)
     net.check_status()                            # non-finite activations / outputs (an fp16 overflow) anywhere in the run: loud error
     assert bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": out})
     note(f"rank {rank}: {args.steps} steps in {dt:.3f} s")
     ranks_ms = per_rank_ms(dt, args.steps, world, dist, torch.device("cpu") if rehearsal else dev)
     dt = dp.barrier_max_seconds(dt, torch.device("cpu") if rehearsal else dev)          # MAX over ranks

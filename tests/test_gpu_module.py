@@ -331,3 +331,51 @@ def test_bench_spawns_its_own_ranks():
     ar = j["allreduce"]
     assert ar and sum(ar["buckets_bytes"]) == 4 * 1_114_240 and ar["ms_alone"] > 0 and ar["step_ms_with_exchange"] > 0
     assert len(j["per_rank_ms"]) == 2 and j["value"] > 0 and j["loss"] > 0
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_computes(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's outputs: for the headline (cfg2, two captured forwards in
+    flight) exactly the eager forward of the same seeded batch and weights; for the training step (cfg3) exactly the loss,
+    SR output and weights of a fresh TrainStep after --warmup + --steps steps from the seeded weights.  --steps sets the timed
+    steps, and ms_per_step is in the line."""
+    import json
+    import subprocess
+    import sys
+    from model import LFT
+    from lft_amd import train as T
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def bench(d, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--warmup", "1", "--settle-seconds", "0.1",
+                            "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d), *extra],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1500:]
+        return json.loads(lines[0])
+
+    j = bench(tmp_path / "infer", "--steps", "3")
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and abs(j["value"] - 4 * 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    assert sorted(os.listdir(tmp_path / "infer")) == ["output.npy"]
+    got = np.load(tmp_path / "infer" / "output.npy")
+    net = LFT.get_model(SimpleNamespace(channels=64, angRes=5, scale_factor=4), precision="bf16")
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in deterministic_state(64, 4, seed=1).items()})
+    with torch.no_grad():
+        ref = net.to("cuda:0").eval()(torch.from_numpy(synthetic_lr(4, 5, 32, 32, seed=0)).to("cuda:0")).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == (4, 1, 640, 640) and np.array_equal(got, ref)
+
+    j = bench(tmp_path / "train", "--config", "cfg3", "--batch", "2", "--steps", "2")
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+    d = {k: np.load(tmp_path / "train" / f"{k}.npy") for k in ("loss", "output", "params")}
+    assert sorted(os.listdir(tmp_path / "train")) == ["loss.npy", "output.npy", "params.npy"]
+    net = LFT.get_model(SimpleNamespace(channels=64, angRes=5, scale_factor=2))
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in deterministic_state(64, 2, seed=1).items()})
+    ts = T.TrainStep(net.to("cuda:0").train(), lr=2e-4, math="fp32", graph=True)          # bench.py's defaults
+    lr = torch.from_numpy(synthetic_lr(2, 5, 32, 32, seed=0)).to("cuda:0")
+    hr = torch.from_numpy(np.random.Generator(np.random.PCG64([2, 0])).random((2, 1, 320, 320), dtype=np.float32)).to("cuda:0")
+    for _ in range(1 + 2):
+        loss = ts.step(lr, hr)
+    torch.cuda.synchronize()
+    assert d["loss"].shape == (1,) and np.array_equal(d["loss"], loss.cpu().numpy()) and d["loss"].item() == j["loss"]
+    assert d["output"].shape == (2, 1, 320, 320) and np.array_equal(d["output"], ts.last_out.cpu().numpy())
+    assert d["params"].shape == (1_114_240,) and np.array_equal(d["params"], ts.flat_params.cpu().numpy())

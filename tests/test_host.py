@@ -154,19 +154,26 @@ def test_gradient_buckets_tile_the_flat_buffer():
     assert L.lft_train_grad_bucket(2, 3, ctypes.byref(first), ctypes.byref(count)) != 0
 
 
-def test_no_asm_loaded_register_is_read_before_its_wait():
+@pytest.fixture(scope="module")
+def isa_env(tmp_path_factory):
+    """The hazard tools' --build listings in a directory of this test run (LFT_ISA_DIR): never another tree's or user's listings."""
+    return dict(os.environ, LFT_ISA_DIR=str(tmp_path_factory.mktemp("isa")))
+
+
+def test_no_asm_loaded_register_is_read_before_its_wait(isa_env):
     """Both units assembled with the product flags (no GPU needed): a register filled by an inline-asm global load must not be
     read -- hipcc copies such registers to set up tied asm operands -- before the counted s_waitcnt that guards it
     (tools/asm_load_hazards.py; the first k_linr did exactly that and passed every test in fp32)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "asm_load_hazards.py"), "--build"], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "asm_load_hazards.py"), "--build"], capture_output=True, text=True,
+                       env=isa_env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "0 suspicious read(s)" in r.stdout
 
 
-def test_lds_dma_pipelines_are_covered_by_counted_waits_and_barriers():
+def test_lds_dma_pipelines_are_covered_by_counted_waits_and_barriers(isa_env):
     """Static check of every LDS-DMA pipeline in the product listing (tools/lds_dma_hazards.py; the listings of the test above are
     re-used): each slot is read only after all pieces of its fill were retired by a counted vmcnt wait AND published by a barrier,
     and refilled only after its reads were waited for and a barrier passed.  The check must also bite: with every counted wait of
@@ -176,10 +183,11 @@ def test_lds_dma_pipelines_are_covered_by_counted_waits_and_barriers():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tool = os.path.join(root, "tools", "lds_dma_hazards.py")
-    r = subprocess.run([sys.executable, tool, "--build"], capture_output=True, text=True, env=dict(os.environ, LFT_HAZARD_REUSE="1"))
+    r = subprocess.run([sys.executable, tool, "--build"], capture_output=True, text=True, env=dict(isa_env, LFT_HAZARD_REUSE="1"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "0 LDS-DMA protocol violation(s)" in r.stdout
-    lines = open("/tmp/lft_isa/hz1.s").read().split("\n")
+    isa = isa_env["LFT_ISA_DIR"]
+    lines = open(os.path.join(isa, "hz1.s")).read().split("\n")
     start = next(i for i, l in enumerate(lines) if l.startswith("_ZN12_GLOBAL__N_17k_spa_bIDF16bLb0ELb1ELb0E"))
     n = 0
     for i in range(start, len(lines)):
@@ -190,6 +198,6 @@ def test_lds_dma_pipelines_are_covered_by_counted_waits_and_barriers():
             lines[i] = lines[i].replace(m.group(0), "vmcnt(%d)" % (int(m.group(1)) + 1))
             n += 1
     assert n >= 10
-    open("/tmp/lft_isa/hz1_mut.s", "w").write("\n".join(lines))
-    r = subprocess.run([sys.executable, tool, "/tmp/lft_isa/hz1_mut.s", "k_spa_bIDF16bLb0ELb1ELb0E"], capture_output=True, text=True)
+    open(os.path.join(isa, "hz1_mut.s"), "w").write("\n".join(lines))
+    r = subprocess.run([sys.executable, tool, os.path.join(isa, "hz1_mut.s"), "k_spa_bIDF16bLb0ELb1ELb0E"], capture_output=True, text=True)
     assert r.returncode == 1 and "USE of" in r.stdout, r.stdout[-2000:]

@@ -16,6 +16,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# assembly listings of --build: inside the tree by default (git-ignored), LFT_ISA_DIR elsewhere (the tests use their own)
+ISA_DIR = os.environ.get("LFT_ISA_DIR") or os.path.join(ROOT, "_build", "isa")
 VM = re.compile(r"^\s*(global_load|global_store|buffer_load|buffer_store|scratch_load|scratch_store|flat_load|flat_store|global_atomic)")
 REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
@@ -97,10 +99,10 @@ def main():
     if args and args[0] == "--build":
         sys.path.insert(0, ROOT)
         from lft_amd import _lib
-        os.makedirs("/tmp/lft_isa", exist_ok=True)
+        os.makedirs(ISA_DIR, exist_ok=True)
         bad = []
         for unit in (1, 2):
-            out = f"/tmp/lft_isa/hz{unit}.s"
+            out = os.path.join(ISA_DIR, f"hz{unit}.s")
             subprocess.run(["/opt/rocm/bin/hipcc", *_lib.COMMON_FLAGS, *_lib.UNIT_FLAGS[unit], f"-DLFT_TU={unit}", "--cuda-device-only", "-S",
                             os.path.join(_lib.CSRC, "lft_api.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
             bad += check(out, args[1:])

@@ -4,7 +4,7 @@ other VALU, SALU, LDS, vector-memory, waits and barriers between a kernel's labe
 which for these straight-line (fully unrolled) kernels is close to what one wave executes.
 
   tools/isa_mix.py file.s [substring ...]        kernels whose demangled name contains every substring
-  tools/isa_mix.py --build [substring ...]       compile the inference unit with the product flags first (to /tmp/lft_isa)
+  tools/isa_mix.py --build [substring ...]       compile the inference unit with the product flags first (to _build/isa/)
   tools/isa_mix.py --phases [substring ...]      the same build with -DLFT_EXPERIMENT -DLFT_ISA_MARKS: every LFT_STAMP(n) of a
                                                  kernel becomes a mark in the listing and the counts are given per phase
                                                  (the instructions between mark n and the next one; "pre" = before the first)
@@ -16,13 +16,15 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# assembly listings of --build: inside the tree by default (git-ignored), LFT_ISA_DIR elsewhere (the tests use their own)
+ISA_DIR = os.environ.get("LFT_ISA_DIR") or os.path.join(ROOT, "_build", "isa")
 
 
 def build(extra=()):
     sys.path.insert(0, ROOT)
     from lft_amd import _lib
-    os.makedirs("/tmp/lft_isa", exist_ok=True)
-    out = "/tmp/lft_isa/tu1.s"
+    os.makedirs(ISA_DIR, exist_ok=True)
+    out = os.path.join(ISA_DIR, "tu1.s")
     cmd = ["/opt/rocm/bin/hipcc", *_lib.COMMON_FLAGS, *_lib.UNIT_FLAGS[1], "-DLFT_TU=1", "--cuda-device-only", "-S",
            os.path.join(_lib.CSRC, "lft_api.hip"), "-o", out] + [a for a in sys.argv[1:] if a.startswith("-D")] + list(extra)
     subprocess.run(cmd, check=True)

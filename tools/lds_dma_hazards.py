@@ -25,6 +25,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# assembly listings of --build: inside the tree by default (git-ignored), LFT_ISA_DIR elsewhere (the tests use their own)
+ISA_DIR = os.environ.get("LFT_ISA_DIR") or os.path.join(ROOT, "_build", "isa")
 VM = re.compile(r"^\s*(global_load|global_store|buffer_load|buffer_store|scratch_load|scratch_store|flat_load|flat_store|global_atomic)")
 NOTE = re.compile(r";\s*LFT_NOTE (\w+) ring=(\d+) slot=(\d+)")
 RING = {0: "WRing", 1: "WRingPipe", 2: "K/V buffer", 3: "conv input", 4: "k_ang weights"}
@@ -134,9 +136,9 @@ def main():
     if args and args[0] == "--build":
         sys.path.insert(0, ROOT)
         from lft_amd import _lib
-        os.makedirs("/tmp/lft_isa", exist_ok=True)
+        os.makedirs(ISA_DIR, exist_ok=True)
         for unit in (1, 2):
-            out = f"/tmp/lft_isa/hz{unit}.s"
+            out = os.path.join(ISA_DIR, f"hz{unit}.s")
             if not os.environ.get("LFT_HAZARD_REUSE") or not os.path.exists(out):
                 subprocess.run(["/opt/rocm/bin/hipcc", *_lib.COMMON_FLAGS, *_lib.UNIT_FLAGS[unit], f"-DLFT_TU={unit}", "--cuda-device-only", "-S",
                                 os.path.join(_lib.CSRC, "lft_api.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
