@@ -142,12 +142,11 @@ _SIGS = {
     "lft_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_void_p]),
     "lft_view_metrics_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "lft_view_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
-    # test-only entry points (include/lft_hip_test.h)
-    "lft_debug_conv64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # test-only entry point (include/lft_hip_test.h)
     "lft_mfma_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
-TEST_EXPORTS = ("lft_debug_conv64", "lft_mfma_selftest")         # declared in include/lft_hip_test.h, not in the product header
+TEST_EXPORTS = ("lft_mfma_selftest",)                           # declared in include/lft_hip_test.h, not in the product header
 BLOCK_UPSAMPLE, BLOCK_SPA, BLOCK_ANG, BLOCK_INIT = 0, 1, 2, 3    # LFT_BLOCK_* of include/lft_hip.h
 GRAD_BUCKETS = 3
 BUCKET_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_size_t, c_size_t)     # lft_bucket_fn of include/lft_hip.h: 0 = go on, else stop
@@ -163,12 +162,9 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
         L.lft_version.restype, L.lft_version.argtypes = c_int, []
         got = L.lft_version()
-        # (tools/ab_build.py times inference kernels of older experiment builds: LFT_AB_ANY_ABI=1 lets it load them -- never set it elsewhere)
-        if got != ABI_VERSION and not (os.environ.get("LFT_AB_ANY_ABI") == "1" and os.environ.get("LFT_LIB_PATH")):   # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
+        if got != ABI_VERSION:              # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
             raise LftError(f"{LIB_PATH} reports ABI version {got}, this binding needs {ABI_VERSION}: rebuild it (__graft_entry__.build())")
         for name, (res, args) in _SIGS.items():
-            if not hasattr(L, name) and got != ABI_VERSION:
-                continue                        # an older experiment build under LFT_AB_ANY_ABI
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -20,6 +20,7 @@
 #include <set>
 #include <string>
 #include <algorithm>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -93,11 +94,21 @@ inline void prof_mark(const char* name) {
 
 constexpr int kLayers = 4;   // reference LFT.py:15
 
-// Run `expr` with T bound to the element type of precision `prec` (validated by make_dims beforehand).
-#define LFT_BY_PREC(prec, ...)                                                                \
-    ((prec) == LFT_PREC_F32    ? ([&] { using T = float; return __VA_ARGS__; })()            \
-     : (prec) == LFT_PREC_BF16 ? ([&] { using T = bf16_t; return __VA_ARGS__; })()           \
-                               : ([&] { using T = f16_t; return __VA_ARGS__; })())
+// Compile-time dispatch: f(std::integral_constant<decltype(V), V>{}) for the V of Vs that equals the runtime value v, so that a
+// generic lambda can name the kernel variant, e.g. dispatch<true, false>(lm, [&](auto LM) { k<T, LM><<<...>>>(...); return 0; }).
+// Vs lists every value a caller passes; any other is an internal error.
+template <auto... Vs, typename V, typename F> int dispatch(V v, F&& f) {
+    int rc = 0;
+    if (((v == Vs && ((rc = f(std::integral_constant<decltype(Vs), Vs>{})), true)) || ...)) return rc;
+    return fail(LFT_ERR_ARG, "internal: no kernel variant for %d", (int)v);
+}
+template <int V> using int_c = std::integral_constant<int, V>;
+// f(T{}) with T the element type of precision `prec` (validated by make_dims beforehand).
+template <typename F> int by_prec(int prec, F&& f) {
+    if (prec == LFT_PREC_F32) return f(float{});
+    if (prec == LFT_PREC_BF16) return f(bf16_t{});
+    return f(f16_t{});
+}
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Dims {
@@ -230,41 +241,30 @@ int run_pack(std::vector<PackOp>& ops, T* dst, int expect_frags, hipStream_t st)
     return 0;
 }
 
-#ifndef LFT_TOKLM
-#define LFT_TOKLM 1
-#endif
-#ifndef LFT_YLM
-#define LFT_YLM 1
-#endif
 // Lane-major hand-off of the spatial tokens from k_spa1 to part B: every workgroup tile of k_spa1 must be full, and the bf16
 // consumer (k_spa_b, 8 x 4 blocks) additionally needs a tile to be 32 columns of ONE image row.
 template <typename T> bool tok_lane_major(const Dims& d) {
-    return LFT_TOKLM && d.hw % (32 * kNwSpa1) == 0 && (sizeof(T) == 4 || d.w % 32 == 0);
+    return d.hw % (32 * kNwSpa1) == 0 && (sizeof(T) == 4 || d.w % 32 == 0);
 }
 // k_spa1 launch with the ring chunk size that fits best: 16-fragment chunks if two workgroups then still share a CU
 // (<= 80 KiB each) or if they are the only ones fitting at all... else 8-fragment chunks (wide views, fp32).
 template <typename T, bool PE_ONLY>
 int launch_spa1(unsigned nwg, const T* in, const T* ws, const float* ln, const T* petok, T* tok, T* q, T* k, T* v, T* pe_out,
                 int nimg, const Dims& d, hipStream_t st, unsigned* status) {
-#ifndef LFT_SPA1_EXTRA_LDS
-#define LFT_SPA1_EXTRA_LDS 0
-#endif
-    const size_t l16 = lds_spa1<T, 16>(d.w) + LFT_SPA1_EXTRA_LDS, l8 = lds_spa1<T, 8>(d.w) + LFT_SPA1_EXTRA_LDS;
-    const size_t share = kMaxLds / LFT_SPA_OCC;                           // LDS per workgroup if LFT_SPA_OCC of them share a CU
+    const size_t l16 = lds_spa1<T, 16>(d.w), l8 = lds_spa1<T, 8>(d.w);
+    const size_t share = kMaxLds / kSpaOcc;                               // LDS per workgroup if kSpaOcc of them share a CU
     const bool use8 = (l16 > share && l8 <= share) || l16 > kMaxLds;
-    int rc;
     const bool lm = !PE_ONLY && tok_lane_major<T>(d);      // hand the token tile to part B in lane-major tile form
-    // 16-bit with the lane-major hand-off: part B (k_spa_b) computes Q from the token tile itself; k_spa1 then skips that projection
-#define LFT_LAUNCH_SPA1(CHV, LMV, LDSV)                                                                                     \
-    do {                                                                                                                    \
-        constexpr bool WQ = !(LMV && sizeof(T) == 2);                                                                       \
-        if ((rc = allow_lds(k_spa1<T, PE_ONLY, CHV, LMV, WQ>, LDSV, "k_spa1"))) return rc;                                  \
-        k_spa1<T, PE_ONLY, CHV, LMV, WQ><<<nwg, 64 * kNwSpa1, LDSV, st>>>(in, ws, ln, petok, tok, q, k, v, pe_out, nimg, d.h, d.w, status); \
-    } while (0)
-    if (use8) { if (lm) LFT_LAUNCH_SPA1(8, true, l8); else LFT_LAUNCH_SPA1(8, false, l8); }
-    else { if (lm) LFT_LAUNCH_SPA1(16, true, l16); else LFT_LAUNCH_SPA1(16, false, l16); }
-#undef LFT_LAUNCH_SPA1
-    return 0;
+    return dispatch<8, 16>(use8 ? 8 : 16, [&](auto CH) {
+        return dispatch<true, false>(lm, [&](auto LM) {
+            // 16-bit with the lane-major hand-off: part B (k_spa_b) computes Q from the token tile itself; k_spa1 then skips that projection
+            constexpr bool WQ = !(LM && sizeof(T) == 2);
+            const size_t lds = CH == 8 ? l8 : l16;
+            if (int rc = allow_lds(k_spa1<T, PE_ONLY, CH, LM, WQ>, lds, "k_spa1")) return rc;
+            k_spa1<T, PE_ONLY, CH, LM, WQ><<<nwg, 64 * kNwSpa1, lds, st>>>(in, ws, ln, petok, tok, q, k, v, pe_out, nimg, d.h, d.w, status);
+            return 0;
+        });
+    });
 }
 
 template <typename T>
@@ -368,7 +368,7 @@ int init_features(const void* packed, const PackedLayout& L, const float* lr, T*
     LFT_LAUNCH_OK("k_conv64");
     return 0;
 }
-template <typename T, int CT>
+template <typename T, int CT, int LL>      // LL: score registers of the last key tile that can hold a view, which covers rows acc_row(i, 0) and acc_row(i, 1) = +4 of register i
 int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* out, const Dims& d, hipStream_t st, unsigned* status) {
     constexpr bool WLDS = sizeof(T) == 2;                                   // fp32 weights (128 KiB) stay in L2
     constexpr int NG = (sizeof(T) == 2 && CT <= 3) ? 2 : 1;                 // positions per workgroup (they share the LDS weights)
@@ -377,39 +377,29 @@ int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* 
     const int npix = d.B * d.hw;
     int rc;
     const unsigned grid = std::min<unsigned>(blocks_for(npix, NG), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds));
-    // score registers of the last key tile that can hold a view: register i covers rows acc_row(i, 0) and acc_row(i, 1) = +4
-    const int rows_last = d.V - 32 * (CT - 1);                              // 1 .. 32 by the choice of CT
-#define LFT_LAUNCH_ANGM(LL)                                                                                             \
-    do {                                                                                                                \
-        if ((rc = allow_lds(k_ang_multi<T, CT, WLDS, NG, LL>, lds, "k_ang_multi"))) return rc;                            \
-        k_ang_multi<T, CT, WLDS, NG, LL><<<grid, 64 * CT * NG, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]),              \
-                                                                         at<float>(packed, L.ln_ang[l]), at<float>(packed, L.ang_pe), d.V, d.hw, npix, status); \
-    } while (0)
-    if (rows_last <= 17) LFT_LAUNCH_ANGM(9);          // e.g. 9 x 9 = 81 views: 17 rows in the third tile
-    else if (rows_last <= 25) LFT_LAUNCH_ANGM(13);
-    else LFT_LAUNCH_ANGM(16);
-#undef LFT_LAUNCH_ANGM
+    if ((rc = allow_lds(k_ang_multi<T, CT, WLDS, NG, LL>, lds, "k_ang_multi"))) return rc;
+    k_ang_multi<T, CT, WLDS, NG, LL><<<grid, 64 * CT * NG, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]), at<float>(packed, L.ln_ang[l]),
+                                                                     at<float>(packed, L.ang_pe), d.V, d.hw, npix, status);
     LFT_LAUNCH_OK("k_ang");
     return 0;
 }
 template <typename T>
 int ang_block(const void* packed, const PackedLayout& L, int l, const T* in, T* out, const Dims& d, hipStream_t st, unsigned* status = nullptr) {
-    if (d.V > 96) return ang_multi<T, 4>(packed, L, l, in, out, d, st, status);
-    if (d.V > 64) return ang_multi<T, 3>(packed, L, l, in, out, d, st, status);      // 9x9 = 81 views
-    if (d.V > 32) return ang_multi<T, 2>(packed, L, l, in, out, d, st, status);
+    // V = A*A (make_dims): above 32 views only 36, 49 | 64 | 81 | 100 | 121 occur, with 4, 17 | 32 | 17 | 4 | 25 rows in the last key tile
+    auto multi = [&](auto CT, auto LL) { return ang_multi<T, CT, LL>(packed, L, l, in, out, d, st, status); };
+    if (d.V > 100) return multi(int_c<4>{}, int_c<13>{});
+    if (d.V > 96) return multi(int_c<4>{}, int_c<9>{});
+    if (d.V > 64) return multi(int_c<3>{}, int_c<9>{});
+    if (d.V == 64) return multi(int_c<2>{}, int_c<16>{});
+    if (d.V > 32) return multi(int_c<2>{}, int_c<9>{});
     const int npix = d.B * d.hw;
     const size_t lds = lds_ang<T>();
     int rc;
     const unsigned grid = std::min<unsigned>(blocks_for(npix, 4), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds));
-    if (d.V <= 25) {                                                  // 5 x 5 and smaller: score rows 25..31 are never a view
-        if ((rc = allow_lds(k_ang<T, 13>, lds, "k_ang"))) return rc;
-        k_ang<T, 13><<<grid, 256, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]), at<float>(packed, L.ln_ang[l]),
-                                             at<float>(packed, L.ang_pe), d.V, d.hw, npix, status);
-    } else {
-        if ((rc = allow_lds(k_ang<T, 16>, lds, "k_ang"))) return rc;
-        k_ang<T, 16><<<grid, 256, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]), at<float>(packed, L.ln_ang[l]),
-                                             at<float>(packed, L.ang_pe), d.V, d.hw, npix, status);
-    }
+    // V <= 25 (5 x 5 and smaller): score rows 25..31 are never a view
+    if ((rc = allow_lds(k_ang<T, 13>, lds, "k_ang"))) return rc;
+    k_ang<T, 13><<<grid, 256, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]), at<float>(packed, L.ln_ang[l]),
+                                         at<float>(packed, L.ang_pe), d.V, d.hw, npix, status);
     LFT_LAUNCH_OK("k_ang");
     return 0;
 }
@@ -423,31 +413,35 @@ int spa_part_a(const void* packed, const PackedLayout& L, int l, const T* in, vo
     LFT_LAUNCH_OK("k_spa1");
     return 0;
 }
+// k_spa_b / k_spa2 variants: launch(SKIP, TOKLM, YLM) as integral constants.  A lane-major output (YLM, the up-sampler's input)
+// is only produced by the skip variant from lane-major tokens.
+template <typename F> int with_tail_variant(bool skip, bool tok_lm, bool out_lm, F&& launch) {
+    if (out_lm) {
+        if (!(skip && tok_lm)) return fail(LFT_ERR_ARG, "internal: lane-major output needs the skip variant and lane-major tokens");
+        return launch(std::true_type{}, std::true_type{}, std::true_type{});
+    }
+    return dispatch<true, false>(skip, [&](auto SK) {
+        return dispatch<true, false>(tok_lm, [&](auto LM) { return launch(SK, LM, std::false_type{}); });
+    });
+}
 template <typename T>
 int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, T* out, void* ws, const WorkLayout& W,
                const Dims& d, hipStream_t st, bool out_lm = false) {      // out_lm: lane-major output tiles, only for the up-sampler
     const int nimg = d.B * d.V;
     T *tok = at<T>(ws, W.tok), *q = at<T>(ws, W.q), *k = at<T>(ws, W.k), *v = at<T>(ws, W.v), *o = at<T>(ws, W.o);
     const float* ln = at<float>(packed, L.ln_spa[l]);
+    const bool lm = tok_lane_major<T>(d);      // must match launch_spa1's choice
     int rc;
     if constexpr (sizeof(T) == 2) {
         // bf16: windowed attention + out_proj + FFN + 1x1x1 conv in ONE kernel (the attention output stays in registers)
         const unsigned ntile = (unsigned)(nimg * ((d.h + kAttTY - 1) / kAttTY) * ((d.w + kAttTX - 1) / kAttTX));
-#ifndef LFT_SPAB_EXTRA_LDS
-#define LFT_SPAB_EXTRA_LDS 0                 // experiments: pad the request so that fewer workgroups share a CU
-#endif
-        const size_t lds = kSpaBLds + LFT_SPAB_EXTRA_LDS;
-#define LFT_LAUNCH_SPAB(SKV, LMV, YLV)                                                                                      \
-    do {                                                                                                                    \
-        if ((rc = allow_lds(k_spa_b<T, SKV, LMV, YLV>, lds, "k_spa_b"))) return rc;                                            \
-        k_spa_b<T, SKV, LMV, YLV><<<ntile, 256, lds, st>>>(tok, q, k, v, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.h, d.w, at<unsigned>(ws, W.status), \
-                                                           at<T>(packed, L.s_spa1[l]) + (size_t)kFragsSpa1NoQ * 512, at<T>(packed, L.petok[l])); \
-    } while (0)
-        const bool tlm = tok_lane_major<T>(d);
-        if (out_lm && !(skip && tlm)) return fail(LFT_ERR_ARG, "internal: lane-major output needs the skip variant and lane-major tokens");
-        if (skip) { if (out_lm) LFT_LAUNCH_SPAB(true, true, true); else if (tlm) LFT_LAUNCH_SPAB(true, true, false); else LFT_LAUNCH_SPAB(true, false, false); }
-        else { if (tlm) LFT_LAUNCH_SPAB(false, true, false); else LFT_LAUNCH_SPAB(false, false, false); }
-#undef LFT_LAUNCH_SPAB
+        if ((rc = with_tail_variant(skip, lm, out_lm, [&](auto SK, auto LM, auto YL) {
+                 if (int r = allow_lds(k_spa_b<T, SK, LM, YL>, kSpaBLds, "k_spa_b")) return r;
+                 k_spa_b<T, SK, LM, YL><<<ntile, 256, kSpaBLds, st>>>(tok, q, k, v, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.h, d.w,
+                                                                      at<unsigned>(ws, W.status), at<T>(packed, L.s_spa1[l]) + (size_t)kFragsSpa1NoQ * 512,
+                                                                      at<T>(packed, L.petok[l]));
+                 return 0;
+             }))) return rc;
         LFT_LAUNCH_OK("k_spa_b");
         return 0;
     } else {
@@ -457,20 +451,15 @@ int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, 
         k_win_attn_lds<0, true><<<dim3(tiles, 4), 256, kWaLds, st>>>(reinterpret_cast<const float*>(q), reinterpret_cast<const float*>(k),
                                                                      reinterpret_cast<const float*>(v), reinterpret_cast<float*>(o),
                                                                      nullptr, nullptr, nullptr, nullptr, nullptr, d.h, d.w, 128);
-    LFT_LAUNCH_OK("k_spa_attn");
-    const unsigned nb = blocks_for(d.ntok, 32 * kNwSpa2);
-    const bool lm = tok_lane_major<T>(d);      // must match launch_spa1's choice
-#define LFT_LAUNCH_SPA2(SKV, LMV, YLV)                                                                                      \
-    do {                                                                                                                    \
-        if ((rc = allow_lds(k_spa2<T, SKV, LMV, YLV>, lds_spa2<T>(), "k_spa2"))) return rc;                                 \
-        k_spa2<T, SKV, LMV, YLV><<<nb, 64 * kNwSpa2, lds_spa2<T>(), st>>>(tok, o, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.ntok, at<unsigned>(ws, W.status)); \
-    } while (0)
-    if (out_lm && !(skip && lm)) return fail(LFT_ERR_ARG, "internal: lane-major output needs the skip variant and full tiles");
-    if (skip) { if (out_lm) LFT_LAUNCH_SPA2(true, true, true); else if (lm) LFT_LAUNCH_SPA2(true, true, false); else LFT_LAUNCH_SPA2(true, false, false); }
-    else { if (lm) LFT_LAUNCH_SPA2(false, true, false); else LFT_LAUNCH_SPA2(false, false, false); }
-#undef LFT_LAUNCH_SPA2
-    LFT_LAUNCH_OK("k_spa2");
-    return 0;
+        LFT_LAUNCH_OK("k_spa_attn");
+        const unsigned nb = blocks_for(d.ntok, 32 * kNwSpa2);
+        if ((rc = with_tail_variant(skip, lm, out_lm, [&](auto SK, auto LM, auto YL) {
+                 if (int r = allow_lds(k_spa2<T, SK, LM, YL>, lds_spa2<T>(), "k_spa2")) return r;
+                 k_spa2<T, SK, LM, YL><<<nb, 64 * kNwSpa2, lds_spa2<T>(), st>>>(tok, o, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.ntok, at<unsigned>(ws, W.status));
+                 return 0;
+             }))) return rc;
+        LFT_LAUNCH_OK("k_spa2");
+        return 0;
     }
 }
 template <typename T>
@@ -485,15 +474,14 @@ int upsample(const void* packed, const PackedLayout& L, const T* body, const flo
              const Dims& d, hipStream_t st, bool in_lm = false) {
     float* g = at<float>(ws, W.g);
     const unsigned nb = blocks_for(d.ntok, 32 * kNwUp);
-    int rc;
-#define LFT_LAUNCH_UP(GTV, LMV)                                                                                              \
-    do {                                                                                                                    \
-        if ((rc = allow_lds(k_up<T, GTV, LMV>, lds_up<T>(), "k_up"))) return rc;                                            \
-        k_up<T, GTV, LMV><<<nb, 64 * kNwUp, lds_up<T>(), st>>>(body, at<T>(packed, L.s_up), g, d.ntok, d.nchunk, d.gp);     \
-    } while (0)
-    if (d.gt == 1) { if (in_lm) LFT_LAUNCH_UP(1, true); else LFT_LAUNCH_UP(1, false); }
-    else { if (in_lm) LFT_LAUNCH_UP(2, true); else LFT_LAUNCH_UP(2, false); }
-#undef LFT_LAUNCH_UP
+    int rc = dispatch<1, 2>(d.gt, [&](auto GT) {
+        return dispatch<true, false>(in_lm, [&](auto LM) {
+            if (int r = allow_lds(k_up<T, GT, LM>, lds_up<T>(), "k_up")) return r;
+            k_up<T, GT, LM><<<nb, 64 * kNwUp, lds_up<T>(), st>>>(body, at<T>(packed, L.s_up), g, d.ntok, d.nchunk, d.gp);
+            return 0;
+        });
+    });
+    if (rc) return rc;
     LFT_LAUNCH_OK("k_up");
     launch_assemble(lr, g, out, d.B, d.A, d.h, d.w, d.s, st, 0, at<unsigned>(ws, W.status));
     LFT_LAUNCH_OK("k_assemble");
@@ -511,10 +499,10 @@ int forward_impl(const void* packed, const float* lr, float* out, void* ws, cons
     for (int l = 0; l < kLayers; ++l) {                  // angular first, then spatial (reference LFT.py:249-250)
         if ((rc = ang_block<T>(packed, L, l, cur, xa, d, st, at<unsigned>(ws, W.status)))) return rc;
         const bool last = l == kLayers - 1;                  // its output only feeds the up-sampler: same 32-token tiling, lane-major tiles
-        if ((rc = spa_block<T>(packed, L, l, xa, last ? feat : nullptr, xb, ws, W, d, st, last && LFT_YLM && tok_lane_major<T>(d)))) return rc;
+        if ((rc = spa_block<T>(packed, L, l, xa, last ? feat : nullptr, xb, ws, W, d, st, last && tok_lane_major<T>(d)))) return rc;
         cur = xb;
     }
-    return upsample<T>(packed, L, xb, lr, out, ws, W, d, st, LFT_YLM && tok_lane_major<T>(d));
+    return upsample<T>(packed, L, xb, lr, out, ws, W, d, st, tok_lane_major<T>(d));
 }
 
 // Mean duration of ONE kernel of the forward, launched `reps` times back to back between two HIP events on `stream` (no
@@ -591,7 +579,7 @@ int lft_pack_weights(const float* const* params, int nparams, void* packed, int 
         if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
     if ((rc = make_dims(1, A, h, w, s, prec, &d))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, pack_impl<T>(params, packed, d, prec, st));
+    return by_prec(prec, [&](auto t) { using T = decltype(t); return pack_impl<T>(params, packed, d, prec, st); });
 }
 
 int lft_forward(const void* packed, const float* lr, float* out, void* workspace, int B, int A, int h, int w, int s, int prec, void* stream) {
@@ -599,7 +587,7 @@ int lft_forward(const void* packed, const float* lr, float* out, void* workspace
     if (!packed || !lr || !out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
     if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, forward_impl<T>(packed, lr, out, workspace, d, prec, st));
+    return by_prec(prec, [&](auto t) { using T = decltype(t); return forward_impl<T>(packed, lr, out, workspace, d, prec, st); });
 }
 
 int lft_status_reset(void* workspace, int B, int A, int h, int w, int s, int prec, void* stream) {
@@ -654,7 +642,7 @@ int lft_kernel_time(const char* kernel, const void* packed, void* workspace, int
     if (!kernel || !packed || !workspace || !ms_out || reps < 1) return fail(LFT_ERR_ARG, "bad argument");
     if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, kernel_time_impl<T>(kernel, packed, workspace, d, prec, reps, st, ms_out));
+    return by_prec(prec, [&](auto t) { using T = decltype(t); return kernel_time_impl<T>(kernel, packed, workspace, d, prec, reps, st, ms_out); });
 }
 
 int lft_bicubic_fwd(const float* lr, float* out, int B, int A, int h, int w, int s, void* stream) {
@@ -675,8 +663,10 @@ int lft_init_features_fwd(const void* packed, const float* lr, void* act_out, vo
     const PackedLayout L = packed_layout(d, prec);
     const WorkLayout W = work_layout(d, prec);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, init_features<T>(packed, L, lr, at<T>(workspace, W.x0), at<T>(workspace, W.xa), at<T>(workspace, W.xb),
-                                              static_cast<T*>(act_out), d, st));
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        return init_features<T>(packed, L, lr, at<T>(workspace, W.x0), at<T>(workspace, W.xa), at<T>(workspace, W.xb), static_cast<T*>(act_out), d, st);
+    });
 }
 
 int lft_ang_block_fwd(const void* packed, int layer, const void* act_in, void* act_out, int B, int A, int h, int w, int s, int prec,
@@ -687,7 +677,10 @@ int lft_ang_block_fwd(const void* packed, int layer, const void* act_in, void* a
     if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
     const PackedLayout L = packed_layout(d, prec);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, ang_block<T>(packed, L, layer, static_cast<const T*>(act_in), static_cast<T*>(act_out), d, st));
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        return ang_block<T>(packed, L, layer, static_cast<const T*>(act_in), static_cast<T*>(act_out), d, st);
+    });
 }
 
 int lft_spa_block_fwd(const void* packed, int layer, const void* act_in, const void* skip, void* act_out, void* workspace, int B, int A,
@@ -699,8 +692,10 @@ int lft_spa_block_fwd(const void* packed, int layer, const void* act_in, const v
     const PackedLayout L = packed_layout(d, prec);
     const WorkLayout W = work_layout(d, prec);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, spa_block<T>(packed, L, layer, static_cast<const T*>(act_in), static_cast<const T*>(skip),
-                                          static_cast<T*>(act_out), workspace, W, d, st));
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        return spa_block<T>(packed, L, layer, static_cast<const T*>(act_in), static_cast<const T*>(skip), static_cast<T*>(act_out), workspace, W, d, st);
+    });
 }
 
 int lft_upsample_fwd(const void* packed, const void* act_in, const float* lr, float* out, void* workspace, int B, int A, int h, int w,
@@ -711,31 +706,10 @@ int lft_upsample_fwd(const void* packed, const void* act_in, const float* lr, fl
     const PackedLayout L = packed_layout(d, prec);
     const WorkLayout W = work_layout(d, prec);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return LFT_BY_PREC(prec, upsample<T>(packed, L, static_cast<const T*>(act_in), lr, out, workspace, W, d, st));
-}
-
-// Debug aid (tools/stress_conv.py): one k_conv64 launch. which = 0..2 selects the weight stream, with_res the variant,
-// extra_lds pads the dynamic LDS request (e.g. to force one workgroup per CU).
-int lft_debug_conv64(const void* packed, int which, int with_res, const void* in, const void* res, void* out, int B, int A, int h,
-                     int w, int s, int prec, int extra_lds, void* stream) {
-    Dims d; int rc;
-    if (!packed || !in || !out || which < 0 || which > 2) return fail(LFT_ERR_ARG, "bad argument");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
-    rc = LFT_BY_PREC(prec, [&]() -> int {
-        const size_t lds = lds_conv64<T>(d.w) + extra_lds;
-        int r;
-        if ((r = allow_lds(k_conv64<T, false>, lds, "k_conv64"))) return r;
-        if ((r = allow_lds(k_conv64<T, true>, lds, "k_conv64"))) return r;
-        if (with_res) k_conv64<T, true><<<nwg, 64 * kNwConv, lds, st>>>((const T*)in, (T*)out, (const T*)res, at<T>(packed, L.s_conv[which]), nimg, d.h, d.w);
-        else k_conv64<T, false><<<nwg, 64 * kNwConv, lds, st>>>((const T*)in, (T*)out, nullptr, at<T>(packed, L.s_conv[which]), nimg, d.h, d.w);
-        return 0;
-    }());
-    if (rc) return rc;
-    LFT_LAUNCH_OK("k_conv64");
-    return 0;
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        return upsample<T>(packed, L, static_cast<const T*>(act_in), lr, out, workspace, W, d, st);
+    });
 }
 
 #if defined(LFT_EXPERIMENT) && !defined(LFT_ISA_MARKS)

@@ -22,26 +22,9 @@
 #include <utility>
 
 typedef __bf16 bf16_t;
-// Register pairs for the vector-instruction-bound phases.  LFT_PK = 1: a real 2-vector (v_pk_add_f32 / v_pk_mul_f32 /
-// v_pk_fma_f32: one instruction per pair); 0: two scalars with the same interface.
-#ifndef LFT_PK
-#define LFT_PK 1
-#endif
-#if LFT_PK
+// Register pairs for the vector-instruction-bound phases: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32, one instruction per pair.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 p2_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-#else
-struct f32x2 {
-    float v[2];
-    __device__ __forceinline__ float& operator[](int i) { return v[i]; }
-    __device__ __forceinline__ const float& operator[](int i) const { return v[i]; }
-};
-__device__ __forceinline__ f32x2 operator-(f32x2 a, f32x2 b) { return f32x2{a.v[0] - b.v[0], a.v[1] - b.v[1]}; }
-__device__ __forceinline__ f32x2 operator+(f32x2 a, f32x2 b) { return f32x2{a.v[0] + b.v[0], a.v[1] + b.v[1]}; }
-__device__ __forceinline__ f32x2 operator*(f32x2 a, f32x2 b) { return f32x2{a.v[0] * b.v[0], a.v[1] * b.v[1]}; }
-__device__ __forceinline__ f32x2& operator+=(f32x2& a, f32x2 b) { a.v[0] += b.v[0]; a.v[1] += b.v[1]; return a; }
-__device__ __forceinline__ f32x2 p2_fma(f32x2 a, f32x2 b, f32x2 c) { return f32x2{__builtin_fmaf(a.v[0], b.v[0], c.v[0]), __builtin_fmaf(a.v[1], b.v[1], c.v[1])}; }
-#endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -832,17 +815,12 @@ LFT_DEV float max_fast(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, 
 // ds_bpermute_b32 round trip through the LDS crossbar and the lgkmcnt wait behind it.  From inline asm: the builtin of
 // this hipcc (ROCm 7.2) returns its first result twice.  s_nop 1: wait states between the VALU writes of the operands
 // and the swap, as the compiler inserts for the builtin.
-#ifndef LFT_XHALF_BPERMUTE
 LFT_DEV void xhalf_split(float v, float& lo, float& hi) {
     lo = v; hi = v;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
 }
 LFT_DEV float xhalf_sum(float v) { float lo, hi; xhalf_split(v, lo, hi); return lo + hi; }
 LFT_DEV float xhalf_max(float v) { float lo, hi; xhalf_split(v, lo, hi); return max_fast(lo, hi); }
-#else
-LFT_DEV float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
-LFT_DEV float xhalf_max(float v) { return fmaxf(v, __shfl_xor(v, 32, 64)); }
-#endif
 
 // ------------------------------------------------------------------------------------------
 // 16-column MFMA forms (v_mfma_f32_16x16x16_{bf16,f16}, v_mfma_f32_16x16x32_{bf16,f16}) for the windowed attention's score

@@ -263,14 +263,8 @@ LFT_DEV void conv3x3_tile(const char* lds_in, const char* zero_row, int tl, int 
 // conv_init[i]: 64 -> 64 + LeakyReLU(0.2); the last one adds conv_init0's output (reference LFT.py:26-33,66).
 // A workgroup = NW waves x 32 consecutive tokens of one view image; all its waves share one weight ring, so the
 // packed weights are streamed into the CU once per 32*NW tokens.
-#ifndef LFT_NW_CONV
-#define LFT_NW_CONV 4
-#endif
-constexpr int kNwConv = LFT_NW_CONV;
-#ifndef LFT_CONV64_CHUNK
-#define LFT_CONV64_CHUNK (LFT_NW_CONV == 4 ? 12 : LFT_NW_CONV)
-#endif
-constexpr int kConv64Chunk = LFT_CONV64_CHUNK;   // 72 fragments; NW = 4: 6 chunks of 12, 3-slot ring = 36 KiB (bf16) so two workgroups share a CU
+constexpr int kNwConv = 4;
+constexpr int kConv64Chunk = 12;   // 72 fragments: 6 chunks of 12, 3-slot ring = 36 KiB (bf16) so two workgroups share a CU
 template <typename T, bool RES, int NW = kNwConv>
 __global__ __launch_bounds__(64 * NW) void k_conv64(const T* __restrict__ in, T* __restrict__ out, const T* __restrict__ res,
                                                    const T* __restrict__ wstream, int nimg, int h, int w) {

@@ -14,31 +14,15 @@
 // WITH_Q = false (16-bit path with lane-major hand-off): Q is NOT produced here -- k_spa_b computes it from the token tile it
 // loads anyway (one tensor less written and read back: -52 MB per layer at B = 4); the ring then ends after Wk (208 fragments).
 // ------------------------------------------------------------------------------------------
-#ifndef LFT_UP_CHUNK
-#define LFT_UP_CHUNK 8
-#endif
-constexpr int kUpChunk = LFT_UP_CHUNK;    // k_up uses few registers: a smaller ring lets more workgroups share a CU
-#ifndef LFT_SPA_CHUNK
-#define LFT_SPA_CHUNK 16
-#endif
-#ifndef LFT_SPA_OCC
-#define LFT_SPA_OCC 2
-#endif
-constexpr int kSpaChunk = LFT_SPA_CHUNK;   // fragments per ring chunk: one conv tap (4 k-steps x 4 row tiles), half an in_proj matrix
+constexpr int kUpChunk = 8;       // k_up uses few registers: a smaller ring lets more workgroups share a CU
+constexpr int kSpaChunk = 16;     // fragments per ring chunk: one conv tap (4 k-steps x 4 row tiles), half an in_proj matrix
+constexpr int kSpaOcc = 2;        // k_spa1 / k_spa2 workgroups per CU (launch bounds; launch_spa1's choice of ring chunk)
 // Waves per workgroup (x 32 tokens each).  All waves of a workgroup share one weight ring: the packed weights are
 // streamed into the CU once per 32*NW tokens, and one ring barrier serves NW waves.
-#ifndef LFT_NW_SPA1
-#define LFT_NW_SPA1 4
-#endif
-#ifndef LFT_NW_SPA2
-#define LFT_NW_SPA2 4
-#endif
-#ifndef LFT_NW_UP
-#define LFT_NW_UP 8      // k_up is light on registers: eight waves share one weight stream (48 -> 42 us at B = 4)
-#endif
-constexpr int kNwSpa1 = LFT_NW_SPA1, kNwSpa2 = LFT_NW_SPA2, kNwUp = LFT_NW_UP;
+// k_up is light on registers: eight waves share one weight stream (48 -> 42 us at B = 4).
+constexpr int kNwSpa1 = 4, kNwSpa2 = 4, kNwUp = 8;
 template <typename T, bool PE_ONLY, int CH = kSpaChunk, bool TOKLM = false, bool WITH_Q = true, int NW = kNwSpa1>   // TOKLM: the token tile goes to part B in lane-major tile format
-__global__ __launch_bounds__(64 * NW, LFT_SPA_OCC) void k_spa1(const T* __restrict__ X, const T* __restrict__ ws,
+__global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa1(const T* __restrict__ X, const T* __restrict__ ws,
                                               const float* __restrict__ ln, const T* __restrict__ petok,
                                               T* __restrict__ TOK, T* __restrict__ Q, T* __restrict__ K, T* __restrict__ Vv,
                                               T* __restrict__ pe_out, int nimg, int h, int w, unsigned* __restrict__ status) {
@@ -155,7 +139,7 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // Stream: Wo[4x8, natural k] {W1c[2x8] W2c[4x4]} x4  Wl[2x8]  (176 fragments).
 // ------------------------------------------------------------------------------------------
 template <typename T, bool SKIP, bool TOKLM = false, bool YLM = false, int NW = kNwSpa2>   // YLM: output tile in lane-major form (consumer: k_up)
-__global__ __launch_bounds__(64 * NW, LFT_SPA_OCC) void k_spa2(const T* __restrict__ TOK, const T* __restrict__ O, const T* __restrict__ ws,
+__global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa2(const T* __restrict__ TOK, const T* __restrict__ O, const T* __restrict__ ws,
                                               const float* __restrict__ ln, const T* __restrict__ skip, T* __restrict__ Y,
                                               long long ntok, unsigned* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -222,26 +206,19 @@ __global__ __launch_bounds__(64 * NW, LFT_SPA_OCC) void k_spa2(const T* __restri
 // ring + K/V halo tiles stay below 80 KiB and two workgroups share a CU.  TOK / skip / Y are row-major [token][channel];
 // a wave's 8 x 4 block is two 4 x 4 blocks side by side (BlkRows: token 16 b + 4 py + px).
 // ------------------------------------------------------------------------------------------
-#ifndef LFT_SPAB_CHUNK
-#define LFT_SPAB_CHUNK 8
-#endif
-constexpr int kSpaBChunk = LFT_SPAB_CHUNK;                     // fragments per ring chunk in phase B
+constexpr int kSpaBChunk = 8;                                 // fragments per ring chunk in phase B
 constexpr int kAdTile = kAttHR * kAttHC * 64;                 // one tensor's halo tile in LDS: 8 x 36 tokens x 64 B
 constexpr int kAdPerWave = 2 * kAdTile / 1024 / 4;            // LDS-DMA pieces per wave and head pair (9)
 static_assert(2 * kAdTile == 4 * kAdPerWave * 1024, "the K and V tiles must split into whole pieces over 4 waves");
 constexpr int kSpaBLds = 4 * kAdTile + 2048;                  // two K+V buffers + both LayerNorms' parameters (FFN: first KiB; norm: second)
-// Phase B re-uses the two K / V buffers (36 KiB each): ring slots 0 .. kSpaBSlotsA-1 in buffer A, the others in buffer B from
-// its start; the tile I/O scratch sits 16 KiB into buffer B -- behind the slots there (8-fragment chunks), or on top of the
-// LAST slot (16-fragment chunks), which is not filled before every wave has passed the first ring barrier (TOK tile loaded)
-// and has had its last chunk consumed well before the final store.
+// Phase B re-uses the two K / V buffers (36 KiB each): ring slots 0 .. kSpaBSlotsA-1 in buffer A, kSpaBSlotsB more in buffer B
+// from its start; the tile I/O scratch sits 16 KiB into buffer B, behind the slots there.
 constexpr int kSpaBSlotsA = (2 * kAdTile) / (kSpaBChunk * 1024);
-constexpr int kSpaBSlotsB = kSpaBChunk == 8 ? 2 : 2 * kAdTile / (kSpaBChunk * 1024);
+constexpr int kSpaBSlotsB = 2;
 constexpr int kSpaBSlots = kSpaBSlotsA + kSpaBSlotsB;
 constexpr int kSpaBScratchOfs = 16384;
-static_assert(kSpaBChunk == 8 || kSpaBChunk == 16, "phase-B ring chunk: 8 or 16 fragments");
 static_assert(kSpaBScratchOfs + 4 * TileIO<4, bf16_t>::BYTES <= 2 * kAdTile, "scratch must fit buffer B");
-static_assert(kSpaBChunk == 8 ? kSpaBSlotsB * kSpaBChunk * 1024 <= kSpaBScratchOfs : (kSpaBSlotsB - 1) * kSpaBChunk * 1024 <= kSpaBScratchOfs,
-              "scratch may only overlap the last ring slot");
+static_assert(kSpaBSlotsB * kSpaBChunk * 1024 <= kSpaBScratchOfs, "the ring slots in buffer B must end before the scratch");
 
 // Two 16-byte query fragments of one head pair, loaded by inline asm so that hipcc neither counts them nor drains the
 // LDS-DMA in flight when they are used (it waits vmcnt(0) for ordinary loads while a global_load_lds is outstanding).
@@ -440,13 +417,9 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
         ld16_async_x8(wsrc + 8 * 1024, wqb);                              // head pair 1
         stage(0, bufA);
         stage(1, bufB);
-#ifdef LFT_SPAB_EARLY_SETUP
-        // EXPERIMENT (round 4, not adopted): the pure vector work that needs none of the data in flight (window bias tiles, LDS read
-        // bases: ~300 instructions) here, under the first memory round trip, instead of behind the Q projection.  With 52 asm loads
+        // (setup_tiles() stays behind the Q projection.  Round 4 tried it here, under the first memory round trip: with 52 asm loads
         // pending and 32 more live registers hipcc spilled (132 B of scratch) and MOVED asm-loaded registers before their counted wait:
-        // tools/asm_load_hazards.py reports 57 reads of in-flight registers for this variant.  The block therefore stays behind Q.
-        setup_tiles();
-#endif
+        // tools/asm_load_hazards.py reported 57 reads of in-flight registers.  Not adopted.)
         // (No LFT_STAMP between here and the last Wq wait: a stamp is compiler-visible code with live registers of its own -- in the
         // diagnostic build it made hipcc spill and MOVE asm-loaded registers that were still in flight, and the kernel faulted on a
         // garbage address.  Run tools/asm_load_hazards.py on a diagnostic listing before launching it.)
@@ -491,9 +464,6 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
         lnv = params_load(ln + 256, 256);
         stage(0, bufA);
         stage(1, bufB);
-#ifdef LFT_SPAB_EARLY_SETUP
-        setup_tiles();
-#endif
     }
     Ring ring;
     ring.setup(ws, smem, kSpaBSlotsA, 2 * kAdTile - kSpaBSlotsA * kSpaBChunk * 1024);
@@ -502,9 +472,7 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
     rows.nrow = max(0, min(4, h - y0)); rows.ncol = max(0, min(8, w - (x0 + bxl)));
     if (rows.ncol == 0) rows.nrow = 0;
     const long long tok0 = img0 + (long long)min(y0, h - 1) * w + min(x0 + bxl, w - 1);
-#ifndef LFT_SPAB_EARLY_SETUP
     setup_tiles();
-#endif
     LFT_STAMP(17);
     raw16 qa, qb;
     if constexpr (!TOKLM) q_load_async(qptr, qptr + kQHead, qa, qb);
@@ -550,13 +518,11 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
                 }
             xrow_combine2(m0, m1, [](float a, float b) { return max_fast(a, b); });
             m0 = fmaxf(m0, -1.0e30f); m1 = fmaxf(m1, -1.0e30f);              // empty window: keep exp2(-inf - m) = 0, not NaN
-            // this phase is bound by vector-instruction issue: subtract and sum as register pairs (v_pk_add_f32)
-            float sum[2];
+            // this phase is bound by vector-instruction issue: subtract as register pairs (v_pk_add_f32)
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 const float m = b ? m1 : m0;
                 const f32x2 mm = {m, m};
-                f32x2 sum2 = {0.0f, 0.0f};
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -564,24 +530,13 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
                         f32x2 d = f32x2{S[b][t][e], S[b][t][e + 1]} - mm;
                         d[0] = fast_exp2(d[0]); d[1] = fast_exp2(d[1]);
                         S[b][t][e] = d[0]; S[b][t][e + 1] = d[1];
-#ifdef LFT_SPAB_VALU_SUM
-                        sum2 += d;
-#endif
                     }
-                sum[b] = sum2[0] + sum2[1];
             }
-#ifdef LFT_SPAB_VALU_SUM
-            xrow_combine2(sum[0], sum[1], [](float a, float b) { return a + b; });
-#endif
             typedef typename H16<T>::v4 V4;
             u32x2 ob[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-#ifdef LFT_SPAB_VALU_SUM
-                const float inv = sum[b] > 0.0f ? fast_rcp(sum[b]) : 0.0f;     // empty window (h < w quirk): 0, as the pinned reference
-#else
                 f32x4 osum[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
-#endif
                 f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {                                  // O^T[d, q] += V^T P^T over key tiles 2 u, 2 u + 1 (k = 8 g + j: tile 2 u + (j >> 2), key 4 g + (j & 3))
@@ -594,21 +549,17 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { pf[e] = (T)S[b][2 * u][e]; pf[4 + e] = (T)S[b][2 * u + 1][e]; }
                     o = mfma16k32(vf, pf, o);
-#ifndef LFT_SPAB_VALU_SUM
                     {   // the softmax denominators from the matrix pipe: with an all-ones A operand every row of the product is the column
                         // sum of P^T, i.e. each lane gets its query's sum over the tile pair's 32 keys with no cross-lane step (-16 packed
                         // adds and one 7-instruction exchange per head for 4 small MFMAs; the sum is that of the ROUNDED probabilities, so
-                        // the weights that multiply V add up to 1 exactly).  -DLFT_SPAB_VALU_SUM: the vector-unit form.
+                        // the weights that multiply V add up to 1 exactly)
                         V8 ones;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) ones[e] = (T)1.0f;
                         osum[b] = mfma16k32(ones, pf, osum[b]);
                     }
-#endif
                 }
-#ifndef LFT_SPAB_VALU_SUM
-                const float inv = osum[b][0] > 0.0f ? fast_rcp(osum[b][0]) : 0.0f;
-#endif
+                const float inv = osum[b][0] > 0.0f ? fast_rcp(osum[b][0]) : 0.0f;     // empty window (h < w quirk): 0, as the pinned reference
                 V4 oc;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) oc[e] = (T)(o[e] * inv);
@@ -620,11 +571,7 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
             frag_to_blocks(fo);                                                // the same row exchange, read the other way round
             of[2 * hg + hl].v = __builtin_bit_cast(V8, fo);
             // (No scheduling fence between the two heads of a pair any more: with 32 score registers per head instead of 48 the
-            // scheduler may overlap one head's MFMAs with the other's softmax without spilling -- measured +1 % on the bench.
-            // -DLFT_SPAB_HEAD_FENCE restores it for experiments.)
-#ifdef LFT_SPAB_HEAD_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            // scheduler may overlap one head's MFMAs with the other's softmax without spilling -- measured +1 % on the bench.)
         }
         LFT_STAMP(19 + 2 * hg);
         LFT_NOTE_ASM_("DONE", kNoteKV, hg & 1);

@@ -239,23 +239,25 @@ int run_lin(const TrainCtx& c, int view, int ot0, int nOT, const float* X, int l
     // generic loop consumes two k-steps per iteration, so the stream length taps * KS must be even
     const bool ring = N > 65536 && (full4 || last2) && (v.taps == 1 || (nOT == v.OT && v.OT == nt)) && (v.taps * v.KS) % 2 == 0;
     const bool tiled = v.taps == 1 && v.KS % 4 == 0 && N <= 65536;       // measured: +7 % at 25.6 k tokens, -4 % at 205 k
-#define LFT_LAUNCH_LIN(NTV)                                                                                          \
-    do {                                                                                                             \
-        if (mm == 1) { if (tiled) k_lin<NTV, 1, true><<<g, 256, 0, c.st>>>(p); else k_lin<NTV, 1, false><<<g, 256, 0, c.st>>>(p); }      \
-        else if (mm == 2) { if (tiled) k_lin<NTV, 2, true><<<g, 256, 0, c.st>>>(p); else k_lin<NTV, 2, false><<<g, 256, 0, c.st>>>(p); } \
-        else { if (tiled) k_lin<NTV, 0, true><<<g, 256, 0, c.st>>>(p); else k_lin<NTV, 0, false><<<g, 256, 0, c.st>>>(p); }     \
-    } while (0)
+    int rc;
     if (ring) {
         p.gy = nOT / nt;
         const dim3 g1((unsigned)((gx + 7) / 8 * 8 * p.gy));
         // 3x3 on 32-wide views (a wave's 32 tokens = one image row): the row fragments are loaded once per tap row (k_linr<.., KS>)
         const int ks3 = (v.taps == 9 && c.d.w == 32 && (v.KS == 4 || v.KS == 8)) ? v.KS : 0;
-#define LFT_LAUNCH_R(NTV, KSV) do { if (mm == 1) k_linr<NTV, 1, KSV><<<g1, 256, 0, c.st>>>(p); else if (mm == 2) k_linr<NTV, 2, KSV><<<g1, 256, 0, c.st>>>(p); else k_linr<NTV, 0, KSV><<<g1, 256, 0, c.st>>>(p); } while (0)
-        if (nt == 4) { if (ks3 == 4) LFT_LAUNCH_R(4, 4); else LFT_LAUNCH_R(4, 0); }     // (no 3x3 view has 128 inputs and 128 outputs)
-        else { if (ks3 == 4) LFT_LAUNCH_R(2, 4); else if (ks3 == 8) LFT_LAUNCH_R(2, 8); else LFT_LAUNCH_R(2, 0); }
-#undef LFT_LAUNCH_R
-    } else if (nt == 4) LFT_LAUNCH_LIN(4); else if (nt == 2) LFT_LAUNCH_LIN(2); else LFT_LAUNCH_LIN(1);
-#undef LFT_LAUNCH_LIN
+        auto linr = [&](auto NT, auto KS) {
+            return dispatch<1, 2, 0>(mm, [&](auto MM) { k_linr<NT, MM, KS><<<g1, 256, 0, c.st>>>(p); return 0; });
+        };
+        if (nt == 4) rc = ks3 == 4 ? linr(int_c<4>{}, int_c<4>{}) : linr(int_c<4>{}, int_c<0>{});   // (no 3x3 view has 128 inputs and 128 outputs)
+        else rc = dispatch<4, 8, 0>(ks3, [&](auto KS) { return linr(int_c<2>{}, KS); });
+    } else {
+        rc = dispatch<4, 2, 1>(nt, [&](auto NT) {
+            return dispatch<1, 2, 0>(mm, [&](auto MM) {
+                return dispatch<true, false>(tiled, [&](auto TILED) { k_lin<NT, MM, TILED><<<g, 256, 0, c.st>>>(p); return 0; });
+            });
+        });
+    }
+    if (rc) return rc;
     LFT_LAUNCH_OK(prof_name("k_lin", "k_lin:%d>%d%s%s%s", v.KS * 16, nOT * 32, v.taps == 9 ? " 3x3" : "", R ? " +R" : "", M ? " *M" : ""));
     return 0;
 }
@@ -300,25 +302,26 @@ int wgrad(const TrainCtx& c, const float* dY, int Co, const float* X, int Ci, in
     hipStream_t ws = c.st;
     WgP p{dY, Co, X, Ci, c.F(c.T.part) + poff, wsize, Ci * taps, taps, 1, Co, Ci, taps, c.d.h, c.d.w, N, len, 1, nch, 1};
     const int mm = c.math == LFT_MATH_BF16X3 ? 1 : c.math == LFT_MATH_BF16X6 ? 2 : 0;
-#define LFT_LAUNCH_WG(NIV, TXV)                                                                                        \
-    do {                                                                                                               \
-        const size_t lds = (size_t)3 * TXV * NIV * 16 * 64 * sizeof(float);                                            \
-        const dim3 g((unsigned)((nch + 7) / 8 * 8 * p.gy * TXV));                                                       \
-        if (mm == 1) { if ((rc = allow_lds(k_wgrad<NIV, 1, TXV>, lds, "k_wgrad"))) return rc; k_wgrad<NIV, 1, TXV><<<g, 256, lds, ws>>>(p); }   \
-        else if (mm == 2) { if ((rc = allow_lds(k_wgrad<NIV, 2, TXV>, lds, "k_wgrad"))) return rc; k_wgrad<NIV, 2, TXV><<<g, 256, lds, ws>>>(p); }   \
-        else { if ((rc = allow_lds(k_wgrad<NIV, 0, TXV>, lds, "k_wgrad"))) return rc; k_wgrad<NIV, 0, TXV><<<g, 256, lds, ws>>>(p); }    \
-    } while (0)
+    auto launch = [&](auto NI, auto TX) {
+        const size_t lds = (size_t)3 * TX * NI * 16 * 64 * sizeof(float);
+        const dim3 g((unsigned)((nch + 7) / 8 * 8 * p.gy * TX));
+        return dispatch<1, 2, 0>(mm, [&](auto MM) {
+            if (int r = allow_lds(k_wgrad<NI, MM, TX>, lds, "k_wgrad")) return r;
+            k_wgrad<NI, MM, TX><<<g, 256, lds, ws>>>(p);
+            return 0;
+        });
+    };
     if (taps == 9) {
         p.igroups = 1; p.gy = Co / 32;
-        LFT_LAUNCH_WG(2, 3);
+        rc = launch(int_c<2>{}, int_c<3>{});
     } else if (Ci % 128 == 0) {
         p.igroups = Ci / 128; p.gy = Co / 32 * p.igroups;
-        LFT_LAUNCH_WG(4, 1);
+        rc = launch(int_c<4>{}, int_c<1>{});
     } else {
         p.igroups = Ci / 64; p.gy = Co / 32 * p.igroups;
-        LFT_LAUNCH_WG(2, 1);
+        rc = launch(int_c<2>{}, int_c<1>{});
     }
-#undef LFT_LAUNCH_WG
+    if (rc) return rc;
     LFT_LAUNCH_OK(prof_name("k_wgrad", "k_wgrad:%dx%d%s", Co, Ci, taps == 9 ? " 3x3" : ""));
     return red_push(c, poff, nch, (int)wsize, (int)wsize, dW, accumulate);
 }

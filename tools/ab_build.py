@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
 """A/B harness: liblft_hip variants built with extra -D flags, timed by bench.py's per-kernel breakdown, each run
-in a fresh subprocess, several interleaved rounds; prints one line per variant and round.  Variants that change results
-(LFT_EXP_*) are for timing experiments only.
+in a fresh subprocess, several interleaved rounds; prints one line per variant and round.
 
   tools/ab_build.py --build name1:-DFLAG1,-DFLAG2 name2: ...   build only (hipcc cross-compiles without a GPU) into ab_so/
   tools/ab_build.py name1:-DFLAG1 name2: ...                   build what is missing, then time (GPU box)
   AB_ROUNDS=3 AB_TEST=1 ...                                    rounds; AB_TEST=1 also runs the GPU parity tests per variant
-("name:" = no extra flags).  ab_so/ is git-ignored but travels with gpurun, so variants are built here, not on GPU time."""
+("name:" = no extra flags).  ab_so/ is git-ignored; build the variants on a build machine, not on GPU time."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 outdir = os.path.join(ROOT, "ab_so"); os.makedirs(outdir, exist_ok=True)

@@ -1,5 +1,5 @@
 """Bit-level regression check of the training kernels: output and flat gradients of one forward + backward pass (cfg 3 shape,
-B = 8, both math modes) -> a file; run once per library (LFT_LIB_PATH=ab_so/liblft_ref.so for the reference build) and give the
+B = 8, all three math modes) -> a file; run once per library (LFT_LIB_PATH=ab_so/liblft_ref.so for the reference build) and give the
 second run the first one's file: it prints whether forward and gradients are bit-identical.  For changes that must not change
 a single bit (re-ordered loads, re-used operands, new addressing): GPU box.
 
@@ -17,7 +17,7 @@ lr = torch.from_numpy(synthetic_lr(B, A, h, w, seed=0)).to(dev)
 g = torch.Generator(device="cpu").manual_seed(5)
 dout = torch.randn(B, 1, A * h * s, A * w * s, generator=g).to(dev) * 1e-3
 res = {}
-for math in ("fp32", "bf16x3"):
+for math in ("fp32", "bf16x3", "bf16x6"):
     out, tape = T.train_forward(ps, lr, A, s, math=math)
     res[math] = (out.cpu(), T.train_backward(ps, lr, tape, dout, A, s, math=math).cpu())
 torch.save(res, sys.argv[1])

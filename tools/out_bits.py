@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Bit-level regression of the inference output against another build: the forward of BASELINE configs[1] (and a ragged 2x shape that
-takes the kernels' general paths) under each library given, each in its own process; prints whether the outputs are bit-identical.
+"""Bit-level regression of the inference output against another build: the forward of BASELINE configs[1], a ragged 2x shape that
+takes the kernels' general paths, and one small shape per angular kernel variant (k_ang for up to 25 views, every k_ang_multi
+form from 36 to 121 views) under each library given, each in its own process; prints whether the outputs are bit-identical.
   tools/out_bits.py ab_so/liblft_base0.so lft_amd/liblft_hip.so"""
 import hashlib
 import os
@@ -16,7 +17,8 @@ def child():
     import torch
     from model import LFT
     from lft_amd.params import deterministic_state, synthetic_lr
-    for A, s, B, h, w in ((5, 4, 2, 32, 32), (3, 2, 1, 13, 22), (2, 4, 1, 6, 12)):
+    for A, s, B, h, w in ((5, 4, 2, 32, 32), (3, 2, 1, 13, 22), (2, 4, 1, 6, 12),
+                          (6, 2, 1, 8, 8), (8, 2, 1, 8, 8), (9, 2, 1, 8, 8), (10, 2, 1, 8, 8), (11, 2, 1, 8, 8)):
         for prec in ("bf16", "fp16", "fp32"):
             net = LFT.get_model(SimpleNamespace(channels=64, angRes=A, scale_factor=s), precision=prec, streams=1).cuda().eval()
             net.load_state_dict({k: torch.from_numpy(v) for k, v in deterministic_state(64, s, seed=1).items()})
@@ -31,7 +33,7 @@ if __name__ == "__main__":
         raise SystemExit(0)
     outs = []
     for lib in sys.argv[1:]:
-        env = dict(os.environ, LFT_LIB_PATH=os.path.abspath(lib), LFT_AB_ANY_ABI="1")
+        env = dict(os.environ, LFT_LIB_PATH=os.path.abspath(lib))
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, cwd=ROOT)
         if r.returncode:
             raise SystemExit(f"{lib} failed:\n{r.stderr[-2000:]}")
