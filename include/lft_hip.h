@@ -133,7 +133,8 @@ int lft_scene_integrate(const float* sr_patches, float* sr_scene, int A, int h0,
  * lft_train_forward : lr [B,1,A*h,A*w] -> out [B,1,A*h*s,A*w*s] (same function as lft_forward, unfused fp32 kernels).
  * lft_train_backward: dout [B,1,A*h*s,A*w*s] -> grads = ONE flat fp32 buffer (lft_train_grad_floats) holding the 78
  *                     parameter gradients back to back in state_dict order, fully overwritten (not accumulated).
- *                     A data-parallel job all-reduces this one buffer.  No gradient flows to lr.
+ *                     A data-parallel job all-reduces this one buffer.  It computes no gradient for lr:
+ *                     lft_train_backward_input below is the same pass plus d lr.
  *                     Every kernel of the pass runs on `stream` (its gradient tensors live in an arena of the tape and are re-used as
  *                     they die; ABI 4 still carried the second stream of round 2 as an ignored argument -- gone in ABI 5).
  * lft_train_tape_offset: float offset of a saved activation inside the tape, for tests ("feat", "ang0.y", "spa2.tok", ...). */
@@ -144,6 +145,13 @@ int lft_train_forward(const float* const* params, int nparams, const float* lr, 
                       int B, int A, int h, int w, int s, int math, void* stream);
 int lft_train_backward(const float* const* params, int nparams, const float* lr, void* tape, const float* dout, float* grads,
                        int B, int A, int h, int w, int s, int math, void* stream);
+/* lft_train_backward plus the gradient of the LR input: d_lr [B,1,A*h,A*w] fp32 (overwritten).  grads are bit-identical
+ * to lft_train_backward's for the same tape and dout. */
+int lft_train_backward_input(const float* const* params, int nparams, const float* lr, void* tape, const float* dout,
+                             float* grads, float* d_lr, int B, int A, int h, int w, int s, int math, void* stream);
+/* Stage entry (the _bwd counterpart of lft_bicubic_fwd + conv_init0): d_lr = conv0^T(dx0) + bicubic^T(dout).
+ * dx0 [B*A*A*h*w, 64] channels-last; w0 = conv_init0.0.weight [64*9]; dout may be NULL (conv term only). */
+int lft_lr_grad_bwd(const float* w0, const float* dx0, const float* dout, float* d_lr, int B, int A, int h, int w, int s, void* stream);
 /* The same pass for data-parallel training (the reference's DP recipe, SURVEY.md section 8e: gradients summed over ranks):
  * the flat gradient buffer is finished in LFT_GRAD_BUCKETS contiguous ranges, in this order --
  *   bucket 0: altblock.2, altblock.3, upsampling   (after the backward of layer 2)

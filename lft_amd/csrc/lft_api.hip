@@ -857,6 +857,23 @@ int lft_train_backward(const float* const* params, int nparams, const float* lr,
     if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
     return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream));
 }
+int lft_train_backward_input(const float* const* params, int nparams, const float* lr, void* tape, const float* dout,
+                             float* grads, float* d_lr, int B, int A, int h, int w, int s, int math, void* stream) {
+    Dims d; int rc;
+    if (!params || !lr || !tape || !dout || !grads || !d_lr) return fail(LFT_ERR_ARG, "null pointer");
+    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
+    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
+    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
+    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
+    return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream), nullptr, nullptr,
+                          false, nullptr, nullptr, nullptr, d_lr);
+}
+int lft_lr_grad_bwd(const float* w0, const float* dx0, const float* dout, float* d_lr, int B, int A, int h, int w, int s, void* stream) {
+    Dims d; int rc;
+    if (!w0 || !dx0 || !d_lr) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
+    return lr_grad(d, w0, dx0, dout, d_lr, static_cast<hipStream_t>(stream));
+}
 int lft_train_backward_buckets(const float* const* params, int nparams, const float* lr, void* tape, const float* dout, float* grads,
                                int B, int A, int h, int w, int s, int math, void* stream,
                                lft_bucket_fn on_bucket, void* user) {

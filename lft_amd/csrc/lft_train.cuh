@@ -1304,6 +1304,132 @@ __global__ __launch_bounds__(256) void k_conv0_wgrad(const float* __restrict__ d
     for (int t = 0; t < 9; ++t) part[wv * 576 + c * 9 + t] = dw[t];
 }
 
+// Gradient of the LR input (reference LFT.py:54 and :65: lr feeds the bicubic skip and conv_init0, nothing else), per view:
+//   d_lr[y][x] = sum_tap sum_c W0[c][tap] dX0[token(y - dy, x - dx)][c]       conv_init0^T, zero padding at the view border
+//              + sum_{oy, ox} Wy[oy][y] Wx[ox][x] dout[oy][ox]               bicubic^T (the skip's taps are clamped to the view)
+// Wx[ox][x] is the sum of the cubic coefficients of those taps of output column ox that clamp onto x (source (ox + 0.5)/s - 0.5,
+// taps floor - 1 .. floor + 2, as bicubic_at), so a border column collects every clamped tap.  Column ox reaches x only when
+// (x - 2) s <= ox < (x + 3) s: 5 s terms per LR pixel and pass.  A gather with a fixed order of additions -- no atomics, every
+// element of d_lr written once.  One workgroup per (image, view, 16 x 16 LR tile):
+//   1. the dX0 rows of the tile-plus-halo tokens (16 lanes x 16 B per token, coalesced) are folded with W0 into 9 tap partials
+//      per token, reduced across the 16 lanes, and staged in LDS (0 outside the view);
+//   2. the tile's HR footprint of dout is staged in LDS and contracted separably, columns first, then rows;
+//   3. each thread sums its pixel's 9 shifted tap partials and adds the bicubic term.
+// dout may be null: the conv term alone (lft_lr_grad_bwd).
+constexpr int kLrTile = 16;
+template <int S>
+__global__ __launch_bounds__(256) void k_lr_grad(const float* __restrict__ dX0, const float* __restrict__ w0, const float* __restrict__ dout,
+                                                 float* __restrict__ d_lr, int A, int h, int w) {
+    constexpr int T = kLrTile, PH = T + 2, NK = 5 * S, FD = (T + 4) * S;   // tile, partial staging edge, bicubic reach, footprint edge
+    __shared__ float pt[9 * PH * PH];        // [tap][PH][PH]: tap partials of tokens (y0 - 1 .., x0 - 1 ..)
+    __shared__ float dv[FD * FD];            // dout footprint [nfy][nfx]
+    __shared__ float rr[FD * T];             // columns contracted: [nfy][T]
+    __shared__ float wt[2 * T * NK];         // bicubic weights: x then y, [T][NK] each
+    const int tid = threadIdx.x, V = A * A;
+    const int tiles_x = (w + T - 1) / T, tiles = tiles_x * ((h + T - 1) / T);
+    const int bid = xcd_tile(blockIdx.x, gridDim.x);            // a view's tiles share halo rows: keep them on one L2
+    const int img = bid / tiles, tile = bid - img * tiles;      // img = b * V + view
+    const int y0 = (tile / tiles_x) * T, x0 = (tile % tiles_x) * T;
+    const int b = img / V, v = img - b * V, a1 = v / A, a2 = v - a1 * A;
+    const int HS = h * S, WS = w * S;
+    for (int i = tid; i < 9 * PH * PH; i += 256) pt[i] = 0.0f;
+    // HR footprint of the tile: output rows / columns that can reach it, clipped to the view
+    const int fy0 = max(0, (y0 - 2) * S), fy1 = min(HS, (y0 + T + 2) * S), fx0 = max(0, (x0 - 2) * S), fx1 = min(WS, (x0 + T + 2) * S);
+    const int nfy = fy1 - fy0, nfx = fx1 - fx0;
+    if (dout) {
+        const float* dsrc = dout + (size_t)b * (A * HS) * (A * WS) + (size_t)(a1 * HS + fy0) * (A * WS) + (size_t)a2 * WS + fx0;
+        const int nf = nfy * nfx;
+        for (int i0 = 0; i0 < nf; i0 += 8 * 256) {              // eight loads in flight per thread before the first LDS write
+            float r[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = min(i0 + u * 256 + tid, nf - 1), ry = i / nfx;
+                r[u] = dsrc[(size_t)ry * (A * WS) + (i - ry * nfx)];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (i0 + u * 256 + tid < nf) dv[i0 + u * 256 + tid] = r[u];
+        }
+        for (int i = tid; i < 2 * T * NK; i += 256) {
+            const int which = i / (T * NK), j = i - which * T * NK, l = j / NK, k = j - l * NK;
+            const int n = which ? h : w, X = (which ? y0 : x0) + l, o = (X - 2) * S + k;
+            float acc = 0.0f;
+            if (X < n && o >= 0 && o < n * S) {
+                const float src = ((float)o + 0.5f) / (float)S - 0.5f, f = floorf(src);
+                float c[4];
+                cubic_coef(src - f, c);
+                const int i0 = (int)f - 1;
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+                    if (min(max(i0 + a, 0), n - 1) == X) acc += c[a];
+            }
+            wt[i] = acc;
+        }
+    }
+    __syncthreads();                                            // partials zeroed before the fill below
+    {
+        const int hy0 = max(y0 - 1, 0), hx0 = max(x0 - 1, 0), nhx = min(x0 + T + 1, w) - hx0;
+        const int ntk = (min(y0 + T + 1, h) - hy0) * nhx, q = tid & 15;     // q: this lane's channel quad
+        float wq[4][9];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 9; ++t) wq[j][t] = w0[(4 * q + j) * 9 + t];
+        const float* X = dX0 + (size_t)img * h * w * 64 + 4 * q;
+        for (int k0 = 0; k0 < ntk; k0 += 64) {                   // 16 tokens per workgroup pass, four passes' loads in flight
+            f32x4 g[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int k = min(k0 + 16 * u + (tid >> 4), ntk - 1), ty = hy0 + k / nhx, tx = hx0 + k % nhx;
+                g[u] = load4(X + ((size_t)ty * w + tx) * 64);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float p[9];
+#pragma unroll
+                for (int t = 0; t < 9; ++t) p[t] = wq[0][t] * g[u][0] + wq[1][t] * g[u][1] + wq[2][t] * g[u][2] + wq[3][t] * g[u][3];
+#pragma unroll
+                for (int m = 8; m >= 1; m >>= 1)
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) p[t] += __shfl_xor(p[t], m);
+                float mine = p[0];
+#pragma unroll
+                for (int t = 1; t < 9; ++t) mine = q == t ? p[t] : mine;
+                const int k = k0 + 16 * u + (tid >> 4);
+                if (k < ntk && q < 9) {
+                    const int ty = hy0 + k / nhx, tx = hx0 + k % nhx;
+                    pt[q * PH * PH + (ty - y0 + 1) * PH + (tx - x0 + 1)] = mine;
+                }
+            }
+        }
+    }
+    if (dout) {                                                 // columns: rr[r][l] = sum_k Wx[l][k] dv[r][(x0 + l - 2) S + k - fx0]
+        for (int i = tid; i < nfy * T; i += 256) {
+            const int r = i / T, l = i - r * T, o0 = (x0 + l - 2) * S - fx0;
+            float acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                if (o0 + k >= 0 && o0 + k < nfx) acc += wt[l * NK + k] * dv[r * nfx + o0 + k];
+            rr[i] = acc;
+        }
+    }
+    __syncthreads();
+    const int ly = tid / T, lx = tid - ly * T, y = y0 + ly, x = x0 + lx;
+    if (y >= h || x >= w) return;
+    float acc = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc += pt[t * PH * PH + (ly + 2 - t / 3) * PH + (lx + 2 - t % 3)];
+    if (dout) {                                                 // rows: sum_k Wy[ly][k] rr[(y - 2) S + k - fy0][lx]
+        const int o0 = (y - 2) * S - fy0;
+        float bic = 0.0f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            if (o0 + k >= 0 && o0 + k < nfy) bic += wt[T * NK + ly * NK + k] * rr[(o0 + k) * T + lx];
+        acc += bic;
+    }
+    d_lr[(size_t)b * (A * h) * (A * w) + (size_t)(a1 * h + y) * (A * w) + a2 * w + x] = acc;
+}
+
 // L1 loss (reference LFT.py:269-277) and its gradient: loss = mean |sr - hr|; dsr = sign(sr - hr) * gscale.
 __global__ __launch_bounds__(256) void k_l1_partial(const float* __restrict__ sr, const float* __restrict__ hr, float* __restrict__ dsr,
                                                     float gscale, long long n, float* __restrict__ part) {

@@ -515,13 +515,25 @@ struct BwdArena {
     }
 };
 
+// d_lr = conv_init0^T(dx0) + bicubic^T(dout), the gradient of the LR input (dout null: the conv term alone); d_lr is overwritten.
+int lr_grad(const Dims& d, const float* w0, const float* dx0, const float* dout, float* d_lr, hipStream_t st) {
+    const unsigned grid = (unsigned)((long long)d.B * d.V * ((d.h + kLrTile - 1) / kLrTile) * ((d.w + kLrTile - 1) / kLrTile));
+    if (d.s == 2) k_lr_grad<2><<<grid, 256, 0, st>>>(dx0, w0, dout, d_lr, d.A, d.h, d.w);
+    else k_lr_grad<4><<<grid, 256, 0, st>>>(dx0, w0, dout, d_lr, d.A, d.h, d.w);
+    LFT_LAUNCH_OK("k_lr_grad");
+    return 0;
+}
+
 // dry: the allocation sequence only (P, lr, tape, dout, G may be null) -- returns the arena's peak through *peak_out.
 // One block of the pass on its own (lft_train_block_backward): its incoming gradient comes from the caller, its outgoing gradient
 // goes to the caller, only its own parameter gradients are produced.  The tape must hold a full forward.
+// d_lr (full pass only; caller memory, so the sizing run does not see it): also the gradient of the LR input [B,1,A*h,A*w], from dx0
+// and dout at the end of the pass.  Null: nothing of it is launched.
 struct BlockSel { int block, layer; const float* d_out; float* d_in; };
 int train_backward(const float* const* P, const float* lr, float* tape, const float* dout, float* G, const Dims& d, int math,
                    hipStream_t st, BucketFn on_bucket = nullptr, void* user = nullptr,
-                   bool dry = false, size_t* peak_out = nullptr, size_t* part_peak_out = nullptr, const BlockSel* sel = nullptr) {
+                   bool dry = false, size_t* peak_out = nullptr, size_t* part_peak_out = nullptr, const BlockSel* sel = nullptr,
+                   float* d_lr = nullptr) {
     TrainLayout Tdry{};
     const TrainLayout T = dry ? Tdry : train_layout(d);
     if (T.rc) return T.rc;
@@ -753,6 +765,10 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
         k_conv0_wgrad<<<kTailWaves / 4, 256, 0, st>>>(dx0, lr, c.F(T.part) + poff, d.B, d.A, d.h, d.w, per);
         LFT_LAUNCH_OK("k_conv0_wgrad");
         TRY(red_push(c, poff, kTailWaves, 576, 576, g(P_CONV0), 0));
+    }
+    if (d_lr && !sel) {                                              // dx0 is final and still held (never released)
+        if (int ok_ = c.launch_ok()) return ok_;
+        TRY(lr_grad(d, P[P_CONV0], dx0, dout, d_lr, st));
     }
     TRY(end_bucket(2));
 #undef TRY

@@ -43,6 +43,11 @@ class get_model(nn.Module):
     ``precision``: 'fp32' (exact-fp32 MFMA; 3e-7 of the reference, default), 'fp16' (IEEE-half MFMA operands and
     inter-kernel tensors, fp32 accumulation; ~2e-4 of the reference at the speed of 'bf16') or 'bf16' (bf16 operands
     and tensors; ~1.7e-3).  May also be given as ``args.lft_precision``.
+
+    Gradients: under autograd, ``forward`` records a graph when a parameter needs a gradient in training mode, or when the
+    input itself requires grad (in either mode: attribution maps, adversarial evaluation, a trainable front-end).  Such a
+    forward runs the fp32 training kernels at ``train_math``, whatever ``precision`` says -- there is no 16-bit tape -- and
+    ``backward`` fills ``lr.grad`` as well as the parameters' gradients.
     """
 
     def __init__(self, args, precision: Optional[str] = None, streams: Optional[int] = None):
@@ -157,11 +162,12 @@ class get_model(nn.Module):
         B, _, H, W = lr.shape
         if H % A or W % A:
             raise ValueError(f"mosaic {H}x{W} is not divisible by angRes {A}")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            # training (reference train.py:89-107; nn.Module starts in training mode, as the reference's net does): the
-            # fp32 forward-with-tape / backward kernels, whatever self.precision says; gradients reach the 78 parameters,
-            # none flows to the input (the reference's data has none either).  After net.eval() (reference test.py:53)
-            # forward is the inference path and builds no autograd graph, with or without torch.no_grad().
+        if torch.is_grad_enabled() and (lr.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+            # training (reference train.py:89-107; nn.Module starts in training mode, as the reference's net does), or an input
+            # that needs a gradient in either mode: the fp32 forward-with-tape / backward kernels, whatever self.precision says;
+            # gradients reach the parameters that need them and, when it requires grad, the input.  Otherwise -- after
+            # net.eval() (reference test.py:53) with an input that needs no gradient -- forward is the inference path and
+            # builds no autograd graph, with or without torch.no_grad().
             from .train import LFTFunction
             return LFTFunction.apply(lr.contiguous().float(), A, s, self.train_math, *self._params_in_order())
         h, w = H // A, W // A

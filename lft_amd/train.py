@@ -77,18 +77,37 @@ def train_forward(ps, lr, A, s, tape=None, math="fp32"):
     return out, tape
 
 
-def train_backward(ps, lr, tape, dout, A, s, grads=None, math="fp32"):
-    """lft_train_backward: returns the flat gradient buffer (78 gradients back to back, state_dict order)."""
+def train_backward(ps, lr, tape, dout, A, s, grads=None, math="fp32", d_lr=None):
+    """lft_train_backward: returns the flat gradient buffer (78 gradients back to back, state_dict order).
+    d_lr (contiguous float32, lr's shape): also the gradient of the input, written there (lft_train_backward_input)."""
     B, _, H, W = lr.shape
     h, w = H // A, W // A
     dev = lr.device
     if grads is None:
         grads = torch.empty(grad_floats(s), dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.lib().lft_train_backward(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(), grads.data_ptr(),
-                                             B, A, h, w, s, MATH[math], stream),
-               "lft_train_backward")
+    if d_lr is None:
+        _lib.check(_lib.lib().lft_train_backward(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(), grads.data_ptr(),
+                                                 B, A, h, w, s, MATH[math], stream),
+                   "lft_train_backward")
+    else:
+        if d_lr.shape != lr.shape or d_lr.dtype != torch.float32 or not d_lr.is_contiguous() or d_lr.device != dev:
+            raise _lib.LftError(f"d_lr must be a contiguous float32 tensor of shape {tuple(lr.shape)} on {dev}")
+        _lib.check(_lib.lib().lft_train_backward_input(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(),
+                                                       grads.data_ptr(), d_lr.data_ptr(), B, A, h, w, s, MATH[math], stream),
+                   "lft_train_backward_input")
     return grads
+
+
+def lr_grad_bwd(w0, dx0, dout, A, s, B, h, w):
+    """lft_lr_grad_bwd: d lr = conv_init0^T(dx0) + bicubic^T(dout) as a new [B,1,A*h,A*w] tensor.  dx0 [B*A*A*h*w, 64] channels-last,
+    w0 = conv_init0.0.weight; dout [B,1,A*h*s,A*w*s] or None (the conv term alone)."""
+    dev = dx0.device
+    d_lr = torch.empty((B, 1, A * h, A * w), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(_lib.lib().lft_lr_grad_bwd(w0.data_ptr(), dx0.data_ptr(), None if dout is None else dout.data_ptr(), d_lr.data_ptr(),
+                                          B, A, h, w, s, stream), "lft_lr_grad_bwd")
+    return d_lr
 
 
 def block_backward(ps, lr, tape, block, layer, d_out, A, s, grads, math="fp32"):
@@ -143,7 +162,8 @@ def train_backward_buckets(ps, lr, tape, dout, A, s, grads, on_bucket, math="fp3
 
 
 class LFTFunction(torch.autograd.Function):
-    """autograd node of the whole network: forward saves the tape, backward returns the 78 parameter gradients."""
+    """autograd node of the whole network: forward saves the tape, backward returns the 78 parameter gradients (None for a
+    parameter that does not need one) and, when the input needs one, the gradient of lr (lft_train_backward_input)."""
 
     @staticmethod
     def forward(ctx, lr, A, s, math, *params):
@@ -157,14 +177,15 @@ class LFTFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         ps = [p.detach() for p in ctx.saved_tensors]
+        d_lr = torch.empty_like(ctx.lr) if ctx.needs_input_grad[0] else None
         with torch.cuda.device(dout.device):
-            flat = train_backward(ps, ctx.lr, ctx.tape, dout.contiguous().float(), ctx.A, ctx.s, math=ctx.math)
+            flat = train_backward(ps, ctx.lr, ctx.tape, dout.contiguous().float(), ctx.A, ctx.s, math=ctx.math, d_lr=d_lr)
         ctx.tape = None
         grads, off = [], 0
-        for p in ps:
-            grads.append(flat[off:off + p.numel()].view(p.shape))
+        for i, p in enumerate(ps):
+            grads.append(flat[off:off + p.numel()].view(p.shape) if ctx.needs_input_grad[4 + i] else None)
             off += p.numel()
-        return (None, None, None, None, *grads)
+        return (d_lr, None, None, None, *grads)
 
 
 class TrainStep:
