@@ -15,13 +15,23 @@ default; cfg3 = the data-parallel training step, see run_training; cfg4 = 64x64 
 output of that step's forward and the updated weights) as float32 DIR/<name>.npy on rank 0; inputs and weights are seeded, so
 two builds run with the same arguments can be compared output for output.
 
-Prints ONE JSON line on rank 0 with the extra objects
-  roofline     : for the dominant kernel (largest share of GPU time).  Its algorithmic FLOPs and HBM bytes per launch
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: it sets up, settles, warms up, times --steps,
+writes --dump-outputs and prints `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `per_rank_ms` (every
+rank's own ms per step: a straggler shows here; `ms_per_step` is the maximum) and `config`; cfg3 adds the step's `loss`,
+`tape_bytes` and `algorithmic_tflops`.
+
+--full also measures everything else, in runs of its own after the headline's (--no-extras and --no-cpu-baseline trim it):
+  allreduce    : cfg3 with more than one rank: the three bucket all-reduces timed alone and the step with and without the
+                 exchange (see run_training), also as the flat `allreduce_*` keys.
+and for inference the objects
+  roofline     : for the dominant kernel (largest share of GPU time; `config.algorithmic_gflop_per_patch` comes from the same
+                 per-kernel breakdown).  Its algorithmic FLOPs and HBM bytes per launch
                  decide the bound -- dense bf16 MFMA peak 2.5 PFLOP/s (fp32 path 157.3 TFLOP/s) or HBM 8 TB/s -- and
                  `achieved`/`frac` are quoted against that peak.  `launch_ms` = mean of 50 launches of that kernel back to
                  back between two HIP events on the launch stream (lft_kernel_time: no event between launches, so it is
                  comparable with the rocprofv3 kernel trace under profiles/).  `traffic` = HBM-side bytes per launch from the
                  committed PMC passes, only when they were taken on the very sources that are being timed (`source_hash`).
+and, on one GPU only:
   parity_path  : the paths that meet BASELINE.json's 1e-3 relative tolerance, same workload, same run, SAME timing protocol as the
                  headline (settle, --warmup, --steps, steps in flight): the fp16 path (the headline kernels with IEEE-half operands
                  and tensors) with patches/s and its measured error against the CPU oracle on one patch (max-norm and element-wise on
@@ -32,10 +42,10 @@ Prints ONE JSON line on rank 0 with the extra objects
                  batch whole (`unsplit`) and as two half-batches on two streams inside the step (`split2`); value = the better.
   sustained_path : the headline's step over a timed region of >= 3 000 steps (> 1 s); `value` itself is timed behind one second of
                  settle load (timed_protocol), so the two must agree.  burst_path: the round-3 protocol (100 settle steps from idle).
-  per_rank_ms  : every rank's own ms per step (a straggler shows here; `ms_per_step` is the maximum).
   train        : BASELINE configs[2] on this GPU (A5, 2x, batch 8, Adam; one process = no all-reduce partner): ms/step, patches/s.
   cpu_baseline : the CPU oracle (a port of the reference's operator sequence, oracle/lft_oracle.py) timed on
-                 this node's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                 this node's host cores on a bounded sample of the same workload.
+  psnr_delta_db : cfg2: per-view PSNR of each precision against the CPU oracle on a small model trained in the run.
 """
 from __future__ import annotations
 
@@ -450,8 +460,8 @@ def per_rank_ms(dt: float, steps: int, world: int, dist, device) -> list:
 def run_training(args, rank, world, dev, dist, rehearsal):
     """BASELINE configs[2]: the data-parallel training step (reference train.py:89-107 per rank + the gradient exchange of SURVEY
     8e).  A step = forward-with-tape, L1 loss and its gradient, backward, the flat gradient buffer summed over the ranks in the
-    three buckets the backward pass finishes (each all-reduce started while the next bucket's kernels run), fused Adam.  Beside
-    the contract's fields the line reports `allreduce`: the three bucket all-reduces timed alone, the step timed with and without
+    three buckets the backward pass finishes (each all-reduce started while the next bucket's kernels run), fused Adam.  With --full
+    the line also reports `allreduce`: the three bucket all-reduces timed alone, the step timed with and without
     the exchange, and from those the share of the exchange that is hidden under the backward pass."""
     import numpy as np
     from lft_amd import dp, train as T
@@ -501,7 +511,7 @@ def run_training(args, rank, world, dev, dist, rehearsal):
     ranks_ms = per_rank_ms(dt, args.steps, world, dist, torch.device("cpu") if rehearsal else dev)
     dt_max = dp.barrier_max_seconds(dt, torch.device("cpu") if rehearsal else dev)
     ar = None
-    if dp.dp_active(ts.group):
+    if args.full and dp.dp_active(ts.group):
         # the exchange alone: the three bucket all-reduces back to back on an otherwise idle GPU
         buckets = [T.grad_bucket(S, b) for b in range(3)]
         reps = 20
@@ -550,14 +560,146 @@ def run_training(args, rank, world, dev, dist, rehearsal):
            "config": {"workload": f"LFT {A}x{A} angRes {S}xSR training step (Adam, bucketed gradient all-reduce), batch={B} per GPU, {H}x{W} LR patches",
                       "name": args.config, "global_batch": world * B, "parallelism": f"dp{world} (flat gradient buffer summed in 3 buckets under the backward pass)",
                       "hip_graph": not args.no_graph, "algorithmic_gflop_per_patch_step": 3 * flops_fwd / 1e9},
-           "allreduce": ar,
-           # the exchange's figures again as flat top-level keys, so that a record which keeps only scalars / lists still shows them
-           "allreduce_hidden_frac": ar["hidden_frac"] if ar else None, "allreduce_ms_alone": ar["ms_alone"] if ar else None,
-           "allreduce_ms_exposed": ar["ms_exposed"] if ar else None, "allreduce_bucket_ms": ar["bucket_ms_alone"] if ar else None,
-           "allreduce_bucket_bytes": ar["buckets_bytes"] if ar else None,
+           **({} if not args.full else {
+               "allreduce": ar,
+               # the exchange's figures again as flat top-level keys, so that a record which keeps only scalars / lists still shows them
+               "allreduce_hidden_frac": ar["hidden_frac"] if ar else None, "allreduce_ms_alone": ar["ms_alone"] if ar else None,
+               "allreduce_ms_exposed": ar["ms_exposed"] if ar else None, "allreduce_bucket_ms": ar["bucket_ms_alone"] if ar else None,
+               "allreduce_bucket_bytes": ar["buckets_bytes"] if ar else None}),
            "tape_bytes": T.tape_bytes(B, A, H, W, S), "loss": float(loss),
            "algorithmic_tflops": 3 * flops_fwd * world * B * args.steps / dt_max / 1e12}
     print(json.dumps(out), flush=True)
+
+
+def full_objects(args, dev, net, lr, world, result) -> None:
+    """--full: the figures beside the headline that take runs of their own (module docstring), added to `result` on rank 0
+    after the headline's timed region."""
+    V = A * A
+    ntok = args.batch * V * H * W
+    fpt = flops_per_token(S, V, mean_window(H, W), q_in_part_b=args.precision != "fp32" and W % 32 == 0 and (H * W) % 128 == 0)
+    with torch.no_grad():
+        kb = kernel_breakdown(net, lr, reps=10)
+    total_ms = sum(ms * cnt for ms, cnt in kb.values())
+    note("kernel ms/launch: " + ", ".join(f"{k}={ms:.3f}x{c}" for k, (ms, c) in kb.items()))
+    dom = max(kb, key=lambda k: kb[k][0] * kb[k][1])
+    dom_ev_ms, dom_cnt = kb[dom]
+    with torch.no_grad():
+        dom_ms = kernel_time_ms(net, lr, dom)                       # back-to-back launches, no events in between
+    timing = "50 back-to-back launches between two HIP events (lft_kernel_time)"
+    if dom_ms is None:
+        dom_ms, timing = dom_ev_ms, "HIP event after every kernel (lft_forward_profiled)"
+    peak = PEAK_TFLOPS[args.precision]
+    bpt = bytes_per_token(S, 4 if args.precision == "fp32" else 2)
+
+    def roof(k, ms):
+        """Roofline of one kernel: the larger of (FLOPs / MFMA peak) and (bytes / HBM peak) names the bound."""
+        gflop = fpt[k] * ntok / 1e9
+        gbyte = bpt[k] * ntok / 1e9
+        t_mfma, t_hbm = gflop / (peak * 1e3), gbyte / HBM_PEAK_GBS
+        if t_mfma >= t_hbm:
+            return {"bound": "mfma", "achieved": gflop / ms, "peak": peak, "unit": "TFLOP/s", "frac": gflop / ms / peak}
+        return {"bound": "hbm", "achieved": gbyte / (ms * 1e-3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": gbyte / (ms * 1e-3) / HBM_PEAK_GBS}
+
+    flops_patch = sum(fpt[k] * (V * H * W) * c for k, (_, c) in kb.items())
+    result["config"]["algorithmic_gflop_per_patch"] = flops_patch / 1e9
+    result["roofline"] = dict(roof(dom, dom_ms), kernel=dom, **traffic_from_profile(dom, args), launch_ms=dom_ms, launch_ms_method=timing,
+                              launch_ms_with_events=dom_ev_ms, launches_per_forward=dom_cnt, gpu_ms_per_forward=total_ms,
+                              algorithmic_per_launch={"gflop": fpt[dom] * ntok / 1e9, "gbyte": bpt[dom] * ntok / 1e9},
+                              # SURVEY.md 8(d): a fully fused SpaTrans / AngTrans block would read x and write x once
+                              compulsory_gbyte_fused_block=2 * 64 * (4 if args.precision == "fp32" else 2) * ntok / 1e9,
+                              kernels={k: dict(ms=round(ms, 4), n=c, **{kk: (round(vv, 3) if isinstance(vv, float) else vv)
+                                                                          for kk, vv in roof(k, ms).items() if kk in ("bound", "achieved", "frac")})
+                                       for k, (ms, c) in kb.items()})
+    tr = result["roofline"].get("traffic")
+    if tr:
+        result["roofline"]["wasted_traffic_ratio_vs_kernel_contract"] = tr / (bpt[dom] * ntok)
+    outs = None
+    extras = world == 1 and not args.no_extras
+    if extras and not args.no_graph:
+        note("timing the strictly sequential path (one step in flight) ...")
+        step1, owner1 = make_step(net, lr, args, 1)
+        dt1, _ = timed_protocol(step1, lr, args, torch.cuda.synchronize)
+        del step1, owner1
+        # the same, with the batch split over two HIP streams INSIDE the captured step (module option `streams`): the two
+        # half-batches' kernels fill each other's partial rounds the way two steps in flight do, without a second step
+        net2 = make_net(args.precision, dev, streams=2)
+        step1s, owner1s = make_step(net2, lr, args, 1)
+        dt1s, _ = timed_protocol(step1s, lr, args, torch.cuda.synchronize)
+        del step1s, owner1s, net2
+        best = min(dt1, dt1s)
+        result["latency_path"] = {"value": args.batch * args.steps / best, "unit": "patches/s", "ms_per_step": best / args.steps * 1e3,
+                                  "steps_in_flight": 1, "batch_split_over_streams": 2 if dt1s <= dt1 else 1,
+                                  "unsplit": {"value": args.batch * args.steps / dt1, "ms_per_step": dt1 / args.steps * 1e3},
+                                  "split2": {"value": args.batch * args.steps / dt1s, "ms_per_step": dt1s / args.steps * 1e3},
+                                  "note": "one captured forward replayed strictly one after the other: ms_per_step is the latency of a batch"}
+    if extras and not args.no_graph:
+        # cross-checks of the protocol: the same step over a region of more than a second (must agree with `value`, which is
+        # timed behind SETTLE_SECONDS of load), and the round-3 protocol's burst window (100 settle steps, then --steps)
+        note("timing a long region (sustained rate) and the burst window ...")
+        n_long = max(args.steps, 3000)
+        step2, owner2 = make_step(net, lr, args, args.inflight)
+        with torch.no_grad():
+            settle(step2, lr)
+            t0 = time.perf_counter()
+            for _ in range(n_long):
+                step2(lr)
+            torch.cuda.synchronize()
+            dt2 = time.perf_counter() - t0
+        result["sustained_path"] = {"value": args.batch * n_long / dt2, "unit": "patches/s", "steps": n_long, "ms_per_step": dt2 / n_long * 1e3,
+                                    "note": "same step as the headline, timed over a region of more than a second"}
+        time.sleep(0.5)                                              # let the card idle, as at the start of a process
+        with torch.no_grad():
+            for _ in range(100 + args.warmup):
+                step2(lr)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step2(lr)
+            torch.cuda.synchronize()
+            dt3 = time.perf_counter() - t0
+        result["burst_path"] = {"value": args.batch * args.steps / dt3, "unit": "patches/s", "steps": args.steps, "ms_per_step": dt3 / args.steps * 1e3,
+                                "note": "round-3 protocol: 100 settle steps from idle, --warmup, --steps -- the window between clock ramp-up and power settling; NOT the headline"}
+        del step2, owner2
+    if extras and args.precision == "bf16":
+        note("timing the fp16 and exact-fp32 parity paths ...")
+        result["parity_path"], outs = parity_path(args, dev, lr, net)
+    if extras and args.config == "cfg2":
+        note("timing the training step (BASELINE configs[2] shape) ...")
+        result["train"] = train_object(dev, "fp32", with_roofline=True)
+        result["train"]["bf16x3"] = {k: v for k, v in train_object(dev, "bf16x3", with_roofline=True).items()
+                                      if k in ("ms_per_step", "patches_per_s", "algorithmic_tflops", "roofline")}
+        result["train"]["bf16x6"] = {k: v for k, v in train_object(dev, "bf16x6").items() if k in ("ms_per_step", "patches_per_s", "algorithmic_tflops")}
+    if world == 1 and not args.no_cpu_baseline:
+        note("timing the CPU oracle on host cores ...")
+        result["cpu_baseline"], ref = cpu_baseline(args.cpu_seconds, lr[:1].cpu())
+        if outs is not None:                                        # the oracle as the checker of all three paths (patch 0)
+            result["parity_path"].update(error_figures(outs["fp16"], ref))
+            result["parity_path"]["exact_fp32"].update(error_figures(outs["fp32"], ref))
+            head = error_figures(outs["headline"], ref)
+            result["parity_path"]["headline_path_rel_max_err_vs_oracle"] = head["rel_max_err_vs_oracle"]
+            result["parity_path"]["headline_path_elementwise_rel_err_on_ref_ge_0.05"] = head["elementwise_rel_err_on_ref_ge_0.05"]
+            # `value` is the configuration BASELINE names (bf16); north_star's tolerance is 1e-3: say which it is
+            result["meets_tolerance"] = head["rel_max_err_vs_oracle"] <= 1e-3
+            ok16 = result["parity_path"]["rel_max_err_vs_oracle"] <= 1e-3
+            result["value_within_tolerance"] = (result["value"] if result["meets_tolerance"]
+                                                else result["parity_path"]["value"] if ok16 else result["parity_path"]["exact_fp32"]["value"])
+            result["value_within_tolerance_path"] = (args.precision if result["meets_tolerance"] else "fp16" if ok16 else "fp32")
+        if extras and args.config == "cfg2":
+            # north_star's second parity form, "PSNR within 0.01 dB": a small 5x5 2x model trained here by the repo's own trainer,
+            # held-out synthetic scenes through lft_amd.evaluate in each precision and through the CPU oracle (the checker);
+            # per view |PSNR(path, HR) - PSNR(oracle, HR)| (tests/psnr_util.py; tests/test_gpu_psnr.py gates the same figure)
+            note("PSNR-delta check against the CPU oracle on trained weights ...")
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import psnr_util as PU
+            pd = {}
+            for fam, fmax in (("hard_scenes", 0.25), ("smooth_scenes", 0.06)):
+                sd_t, hist = PU.train_small_model(dev, fmax=fmax)
+                r = PU.psnr_delta(dev, sd_t, PU.held_out_scenes(n=1, size=32, fmax=fmax))
+                pd[fam] = {"train_loss_first_last": [hist[0], hist[-1]], **{p: {k: round(v, 5) if isinstance(v, float) else v for k, v in d.items()} for p, d in r.items()}}
+            result["psnr_delta_db"] = dict(pd, tolerance_db=0.01,
+                                           note="max over views of |PSNR(path, HR) - PSNR(oracle, HR)|; A5 2x model trained in this run (20 epochs, synthetic light fields), "
+                                                "one held-out 5x5x32x32 scene per family through LFdivide / network / LFintegrate")
 
 
 def main():
@@ -575,9 +717,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from the host each step instead of replaying a HIP graph")
     ap.add_argument("--inflight", type=int, default=2, help="steps in flight: captured forwards replayed round-robin on this many streams (1 = strictly one after the other)")
     ap.add_argument("--train-math", default="fp32", choices=["fp32", "bf16x3", "bf16x6"], help="cfg3: GEMM arithmetic of the training kernels")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity_path, latency_path and train objects (A/B timing runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: roofline, the one-GPU paths, train, CPU baseline, "
+                         "PSNR check (inference), the all-reduce figures (cfg3)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: seconds of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip every object beside roofline and cpu_baseline (A/B timing runs)")
     ap.add_argument("--settle-seconds", type=float, default=None, help="untimed load in front of --warmup (default SETTLE_SECONDS; profiling passes under counters use a short one)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, < 64 MB in all; rank 0)")
@@ -658,34 +803,6 @@ def main():
 
     result = None
     if rank == 0:
-        V = A * A
-        ntok = args.batch * V * H * W
-        fpt = flops_per_token(S, V, mean_window(H, W), q_in_part_b=args.precision != "fp32" and W % 32 == 0 and (H * W) % 128 == 0)
-        with torch.no_grad():
-            kb = kernel_breakdown(net, lr, reps=10)
-        total_ms = sum(ms * cnt for ms, cnt in kb.values())
-        note("kernel ms/launch: " + ", ".join(f"{k}={ms:.3f}x{c}" for k, (ms, c) in kb.items()))
-        dom = max(kb, key=lambda k: kb[k][0] * kb[k][1])
-        dom_ev_ms, dom_cnt = kb[dom]
-        with torch.no_grad():
-            dom_ms = kernel_time_ms(net, lr, dom)                       # back-to-back launches, no events in between
-        timing = "50 back-to-back launches between two HIP events (lft_kernel_time)"
-        if dom_ms is None:
-            dom_ms, timing = dom_ev_ms, "HIP event after every kernel (lft_forward_profiled)"
-        peak = PEAK_TFLOPS[args.precision]
-        bpt = bytes_per_token(S, 4 if args.precision == "fp32" else 2)
-
-        def roof(k, ms):
-            """Roofline of one kernel: the larger of (FLOPs / MFMA peak) and (bytes / HBM peak) names the bound."""
-            gflop = fpt[k] * ntok / 1e9
-            gbyte = bpt[k] * ntok / 1e9
-            t_mfma, t_hbm = gflop / (peak * 1e3), gbyte / HBM_PEAK_GBS
-            if t_mfma >= t_hbm:
-                return {"bound": "mfma", "achieved": gflop / ms, "peak": peak, "unit": "TFLOP/s", "frac": gflop / ms / peak}
-            return {"bound": "hbm", "achieved": gbyte / (ms * 1e-3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": gbyte / (ms * 1e-3) / HBM_PEAK_GBS}
-
-        flops_patch = sum(fpt[k] * (V * H * W) * c for k, (_, c) in kb.items())
         result = {
             "metric": f"LF patches/sec ({A}x{A} angRes, {H}x{W} LR, {S}xSR)",
             "value": world * args.batch * args.steps / dt,
@@ -697,106 +814,10 @@ def main():
             "dtype": args.precision, "data": "synthetic",
             "config": {"workload": f"LFT {A}x{A} angRes {S}xSR inference, batch={args.batch} per GPU, {H}x{W} LR patches", "name": args.config,
                        "global_batch": world * args.batch, "parallelism": f"dp{world} (independent shards)",
-                       "streams_per_gpu": args.streams, "hip_graph": not args.no_graph, "steps_in_flight": (args.inflight if not args.no_graph else 1),
-                       "algorithmic_gflop_per_patch": flops_patch / 1e9},
-            "roofline": dict(roof(dom, dom_ms), kernel=dom, **traffic_from_profile(dom, args), launch_ms=dom_ms, launch_ms_method=timing,
-                             launch_ms_with_events=dom_ev_ms, launches_per_forward=dom_cnt, gpu_ms_per_forward=total_ms,
-                             algorithmic_per_launch={"gflop": fpt[dom] * ntok / 1e9, "gbyte": bpt[dom] * ntok / 1e9},
-                             # a fully fused SpaTrans / AngTrans block would read x and write x once
-                             compulsory_gbyte_fused_block=2 * 64 * (4 if args.precision == "fp32" else 2) * ntok / 1e9,
-                             kernels={k: dict(ms=round(ms, 4), n=c, **{kk: (round(vv, 3) if isinstance(vv, float) else vv)
-                                                                         for kk, vv in roof(k, ms).items() if kk in ("bound", "achieved", "frac")})
-                                      for k, (ms, c) in kb.items()}),
+                       "streams_per_gpu": args.streams, "hip_graph": not args.no_graph, "steps_in_flight": (args.inflight if not args.no_graph else 1)},
         }
-        tr = result["roofline"].get("traffic")
-        if tr:
-            result["roofline"]["wasted_traffic_ratio_vs_kernel_contract"] = tr / (bpt[dom] * ntok)
-        outs = None
-        extras = world == 1 and not args.no_extras
-        if extras and not args.no_graph:
-            note("timing the strictly sequential path (one step in flight) ...")
-            step1, owner1 = make_step(net, lr, args, 1)
-            dt1, _ = timed_protocol(step1, lr, args, torch.cuda.synchronize)
-            del step1, owner1
-            # the same, with the batch split over two HIP streams INSIDE the captured step (module option `streams`): the two
-            # half-batches' kernels fill each other's partial rounds the way two steps in flight do, without a second step
-            net2 = make_net(args.precision, dev, streams=2)
-            step1s, owner1s = make_step(net2, lr, args, 1)
-            dt1s, _ = timed_protocol(step1s, lr, args, torch.cuda.synchronize)
-            del step1s, owner1s, net2
-            best = min(dt1, dt1s)
-            result["latency_path"] = {"value": args.batch * args.steps / best, "unit": "patches/s", "ms_per_step": best / args.steps * 1e3,
-                                      "steps_in_flight": 1, "batch_split_over_streams": 2 if dt1s <= dt1 else 1,
-                                      "unsplit": {"value": args.batch * args.steps / dt1, "ms_per_step": dt1 / args.steps * 1e3},
-                                      "split2": {"value": args.batch * args.steps / dt1s, "ms_per_step": dt1s / args.steps * 1e3},
-                                      "note": "one captured forward replayed strictly one after the other: ms_per_step is the latency of a batch"}
-        if extras and not args.no_graph:
-            # cross-checks of the protocol: the same step over a region of more than a second (must agree with `value`, which is
-            # timed behind SETTLE_SECONDS of load), and the round-3 protocol's burst window (100 settle steps, then --steps)
-            note("timing a long region (sustained rate) and the burst window ...")
-            n_long = max(args.steps, 3000)
-            step2, owner2 = make_step(net, lr, args, args.inflight)
-            with torch.no_grad():
-                settle(step2, lr)
-                t0 = time.perf_counter()
-                for _ in range(n_long):
-                    step2(lr)
-                torch.cuda.synchronize()
-                dt2 = time.perf_counter() - t0
-            result["sustained_path"] = {"value": args.batch * n_long / dt2, "unit": "patches/s", "steps": n_long, "ms_per_step": dt2 / n_long * 1e3,
-                                        "note": "same step as the headline, timed over a region of more than a second"}
-            time.sleep(0.5)                                              # let the card idle, as at the start of a process
-            with torch.no_grad():
-                for _ in range(100 + args.warmup):
-                    step2(lr)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.steps):
-                    step2(lr)
-                torch.cuda.synchronize()
-                dt3 = time.perf_counter() - t0
-            result["burst_path"] = {"value": args.batch * args.steps / dt3, "unit": "patches/s", "steps": args.steps, "ms_per_step": dt3 / args.steps * 1e3,
-                                    "note": "round-3 protocol: 100 settle steps from idle, --warmup, --steps -- the window between clock ramp-up and power settling; NOT the headline"}
-            del step2, owner2
-        if extras and args.precision == "bf16":
-            note("timing the fp16 and exact-fp32 parity paths ...")
-            result["parity_path"], outs = parity_path(args, dev, lr, net)
-        if extras and args.config == "cfg2":
-            note("timing the training step (BASELINE configs[2] shape) ...")
-            result["train"] = train_object(dev, "fp32", with_roofline=True)
-            result["train"]["bf16x3"] = {k: v for k, v in train_object(dev, "bf16x3", with_roofline=True).items()
-                                          if k in ("ms_per_step", "patches_per_s", "algorithmic_tflops", "roofline")}
-            result["train"]["bf16x6"] = {k: v for k, v in train_object(dev, "bf16x6").items() if k in ("ms_per_step", "patches_per_s", "algorithmic_tflops")}
-        if world == 1 and not args.no_cpu_baseline:
-            note("timing the CPU oracle on host cores ...")
-            result["cpu_baseline"], ref = cpu_baseline(args.cpu_seconds, lr[:1].cpu())
-            if outs is not None:                                        # the oracle as the checker of all three paths (patch 0)
-                result["parity_path"].update(error_figures(outs["fp16"], ref))
-                result["parity_path"]["exact_fp32"].update(error_figures(outs["fp32"], ref))
-                head = error_figures(outs["headline"], ref)
-                result["parity_path"]["headline_path_rel_max_err_vs_oracle"] = head["rel_max_err_vs_oracle"]
-                result["parity_path"]["headline_path_elementwise_rel_err_on_ref_ge_0.05"] = head["elementwise_rel_err_on_ref_ge_0.05"]
-                # `value` is the configuration BASELINE names (bf16); north_star's tolerance is 1e-3: say which it is
-                result["meets_tolerance"] = head["rel_max_err_vs_oracle"] <= 1e-3
-                ok16 = result["parity_path"]["rel_max_err_vs_oracle"] <= 1e-3
-                result["value_within_tolerance"] = (result["value"] if result["meets_tolerance"]
-                                                    else result["parity_path"]["value"] if ok16 else result["parity_path"]["exact_fp32"]["value"])
-                result["value_within_tolerance_path"] = (args.precision if result["meets_tolerance"] else "fp16" if ok16 else "fp32")
-            if extras and args.config == "cfg2":
-                # north_star's second parity form, "PSNR within 0.01 dB": a small 5x5 2x model trained here by the repo's own trainer,
-                # held-out synthetic scenes through lft_amd.evaluate in each precision and through the CPU oracle (the checker);
-                # per view |PSNR(path, HR) - PSNR(oracle, HR)| (tests/psnr_util.py; tests/test_gpu_psnr.py gates the same figure)
-                note("PSNR-delta check against the CPU oracle on trained weights ...")
-                sys.path.insert(0, os.path.join(ROOT, "tests"))
-                import psnr_util as PU
-                pd = {}
-                for fam, fmax in (("hard_scenes", 0.25), ("smooth_scenes", 0.06)):
-                    sd_t, hist = PU.train_small_model(dev, fmax=fmax)
-                    r = PU.psnr_delta(dev, sd_t, PU.held_out_scenes(n=1, size=32, fmax=fmax))
-                    pd[fam] = {"train_loss_first_last": [hist[0], hist[-1]], **{p: {k: round(v, 5) if isinstance(v, float) else v for k, v in d.items()} for p, d in r.items()}}
-                result["psnr_delta_db"] = dict(pd, tolerance_db=0.01,
-                                               note="max over views of |PSNR(path, HR) - PSNR(oracle, HR)|; A5 2x model trained in this run (20 epochs, synthetic light fields), "
-                                                    "one held-out 5x5x32x32 scene per family through LFdivide / network / LFintegrate")
+        if args.full:
+            full_objects(args, dev, net, lr, world, result)
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.barrier()

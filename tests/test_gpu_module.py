@@ -309,7 +309,7 @@ def test_bench_spawns_its_own_ranks():
     env = dict(os.environ, LFT_BENCH_ONE_GPU_REHEARSAL="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -321,7 +321,7 @@ def test_bench_spawns_its_own_ranks():
     assert len(j["per_rank_ms"]) == 2 and abs(max(j["per_rank_ms"]) - j["ms_per_step"]) < 1e-6 * j["ms_per_step"]
     assert j["config"]["name"] == "cfg2"
     # the training configuration by name: 2 ranks, bucketed gradient exchange (gloo through the host in this rehearsal)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "cfg3", "--batch", "1", "--steps", "4", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "cfg3", "--batch", "1", "--steps", "4", "--warmup", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -356,6 +356,7 @@ def test_bench_dump_outputs_are_what_the_timed_path_computes(tmp_path):
 
     j = bench(tmp_path / "infer", "--steps", "3")
     assert j["steps"] == 3 and j["ms_per_step"] > 0 and abs(j["value"] - 4 * 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    assert "roofline" not in j                    # without --full the run measures the headline alone
     assert sorted(os.listdir(tmp_path / "infer")) == ["output.npy"]
     got = np.load(tmp_path / "infer" / "output.npy")
     net = LFT.get_model(SimpleNamespace(channels=64, angRes=5, scale_factor=4), precision="bf16")

@@ -6,7 +6,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 for v in "$@"; do
   export LFT_LIB_PATH=ab_so/liblft_$v.so
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ser_$v -- python3 bench.py --steps 200 --warmup 20 --streams 1 --inflight 1 --no-cpu-baseline --no-extras > $out/ser_$v.log 2>&1 || { echo "$v failed"; tail -3 $out/ser_$v.log; exit 1; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ser_$v -- python3 bench.py --steps 200 --warmup 20 --streams 1 --inflight 1 --full --no-cpu-baseline --no-extras > $out/ser_$v.log 2>&1 || { echo "$v failed"; tail -3 $out/ser_$v.log; exit 1; }
   f=$(ls $out/ser_$v/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && python3 - "$f" "$v" <<'PY' >> $out/summary.txt
 import csv, sys
