@@ -211,6 +211,24 @@ int lft_view_metrics_scratch_bytes(int B, int A, int h, int w, size_t* out_bytes
 int lft_view_metrics(const float* label, const float* out, int B, int A, int h, int w, float ssim_range, float* psnr, float* ssim,
                      void* scratch, void* stream);
 
+/* ---- data preparation (reference Generate_Data_for_Training.m / Generate_Data_for_Test.m, per sub-aperture view) ----
+ * lf: the raw light field on the device in its stored class, LF[u][v][h][w][c] at element offset
+ *     u*strides[0] + v*strides[1] + h*strides[2] + w*strides[3] + c*strides[4] (strides: HOST array of 5; a v7.3 .mat's
+ *     reversed [C,W,H,V,U] array is read in place).  Only channels 0..2 are read; values enter as stored (uint8 as 0..255).
+ * Views: the centre A x A, starting at ((U-A)/2, (V-A)/2); U-A and V-A must be even.
+ * crops: HOST array of n_crops (y0, x0) origins of crop_h x crop_w regions inside every view.
+ * weights_* / indices_*: MATLAB's imresize contribution tables of one crop axis (fp64 [out, taps], int32 [out, taps], device),
+ *     out = ceil(crop / s) (lft_amd/prepare.py:contributions).
+ * Per crop n and view (u, v), in fp64: Y = rgb2ycbcr(rgb)[..., 0], hr = single(Y), lr = single(imresize(Y, 1/s)) with the
+ * rows resized first; outputs are fp32 mosaics in the MATLAB matrix orientation:
+ *     hr [n_crops, A*crop_h, A*crop_w], lr [n_crops, A*ceil(crop_h/s), A*ceil(crop_w/s)]. */
+#define LFT_LF_UINT8 0
+#define LFT_LF_FLOAT32 1
+#define LFT_LF_FLOAT64 2
+int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
+                   const int* crops, int n_crops, int crop_h, int crop_w, const double* weights_h, const int* indices_h, int taps_h,
+                   const double* weights_w, const int* indices_w, int taps_w, float* hr, float* lr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

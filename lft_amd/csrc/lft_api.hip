@@ -32,6 +32,7 @@ namespace {
 #include "lft_kernels_a.cuh"
 #include "lft_kernels_b.cuh"
 #include "lft_metrics.cuh"
+#include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
 #include "lft_train.cuh"     // training kernels; the fp32 inference path shares their LDS-tiled window attention
 }  // namespace
 
@@ -786,6 +787,53 @@ int lft_view_metrics(const float* label, const float* out, int B, int A, int h, 
     LFT_LAUNCH_OK("k_view_metrics");
     k_view_metrics_final<<<blocks_for(nviews, 64), 64, 0, st>>>(static_cast<const double*>(scratch), nviews, ntiles, h, w, psnr, ssim);
     LFT_LAUNCH_OK("k_view_metrics_final");
+    return 0;
+}
+int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
+                   const int* crops, int n_crops, int crop_h, int crop_w, const double* weights_h, const int* indices_h, int taps_h,
+                   const double* weights_w, const int* indices_w, int taps_w, float* hr, float* lr, void* stream) {
+    if (!lf || !strides || !crops || !weights_h || !indices_h || !weights_w || !indices_w || !hr || !lr)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: null pointer");
+    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", lf_class);
+    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", U, V, H, W, C);
+    for (int i = 0; i < 5; ++i)
+        if (strides[i] < 0) return fail(LFT_ERR_ARG, "lft_lf_prepare: stride %d is negative (%lld)", i, strides[i]);
+    if (s != 2 && s != 4) return fail(LFT_ERR_ARG, "lft_lf_prepare: scale factor must be 2 or 4, got %d", s);
+    if (A < 1 || A > U || A > V) return fail(LFT_ERR_ARG, "lft_lf_prepare: angRes %d outside the %d x %d views", A, U, V);
+    if ((U - A) % 2 || (V - A) % 2)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: U-A = %d and V-A = %d must be even (the scripts' centre-view index 0.5*(U-A+2) is not an integer)",
+                    U - A, V - A);
+    if (n_crops < 0 || crop_h < 1 || crop_w < 1 || crop_h > H || crop_w > W)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d crops of %d x %d in views of %d x %d", n_crops, crop_h, crop_w, H, W);
+    for (int i = 0; i < n_crops; ++i) {
+        const int y0 = crops[2 * i], x0 = crops[2 * i + 1];
+        if (y0 < 0 || x0 < 0 || y0 > H - crop_h || x0 > W - crop_w)
+            return fail(LFT_ERR_ARG, "lft_lf_prepare: crop %d at (%d, %d) of %d x %d is outside the %d x %d view", i, y0, x0, crop_h, crop_w, H, W);
+    }
+    if (taps_h < 1 || taps_w < 1 || taps_h > kPrepMaxTaps || taps_w > kPrepMaxTaps)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kPrepMaxTaps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PrepArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s;
+    a.ch = crop_h; a.cw = crop_w; a.oh = (crop_h + s - 1) / s; a.ow = (crop_w + s - 1) / s; a.ph = taps_h; a.pw = taps_w;
+    a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w; a.hr = hr; a.lr = lr;
+    const int TO = kPrepTileHr / s;
+    const unsigned tiles = (unsigned)(((a.oh + TO - 1) / TO) * ((a.ow + TO - 1) / TO));
+    for (int n0 = 0; n0 < n_crops; n0 += kPrepCrops) {
+        const int nb = std::min(kPrepCrops, n_crops - n0);
+        PrepCrops c{};
+        for (int i = 0; i < nb; ++i) { c.y0[i] = crops[2 * (n0 + i)]; c.x0[i] = crops[2 * (n0 + i) + 1]; }
+        a.n0 = n0;
+        const dim3 grid(tiles, (unsigned)(A * A), (unsigned)nb);
+        if (lf_class == LFT_LF_UINT8) k_lf_prepare<uint8_t><<<grid, 256, 0, st>>>(a, c);
+        else if (lf_class == LFT_LF_FLOAT32) k_lf_prepare<float><<<grid, 256, 0, st>>>(a, c);
+        else k_lf_prepare<double><<<grid, 256, 0, st>>>(a, c);
+        LFT_LAUNCH_OK("k_lf_prepare");
+    }
     return 0;
 }
 
