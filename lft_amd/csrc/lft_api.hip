@@ -92,6 +92,28 @@ inline void prof_mark(const char* name) {
         if (e_ != hipSuccess) return fail((int)e_, "launch %s: %s", name, hipGetErrorString(e_)); \
         prof_mark(name);                                                                     \
     } while (0)
+// run() with an event recorded on st after every kernel it launches, then synchronised: the first max_records launches' names
+// and times go to names_out / ms_out, their number to *n_out.  run()'s error comes first, then the synchronisation's.
+template <typename Run> int run_profiled(hipStream_t st, int max_records, float* ms_out, const char** names_out, int* n_out, Run&& run) {
+    g_prof.on = true; g_prof.st = st; g_prof.ev.clear(); g_prof.names.clear();
+    prof_mark("start");
+    const int rc = run();
+    g_prof.on = false;
+    hipError_t e = hipStreamSynchronize(st);
+    int n = 0;
+    for (size_t i = 1; i < g_prof.ev.size() && n < max_records; ++i, ++n) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, g_prof.ev[i - 1], g_prof.ev[i]);
+        ms_out[n] = ms;
+        names_out[n] = g_prof.names[i];
+    }
+    for (hipEvent_t ev : g_prof.ev) (void)hipEventDestroy(ev);
+    g_prof.ev.clear(); g_prof.names.clear();
+    *n_out = n;
+    if (rc) return rc;
+    if (e != hipSuccess) return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    return 0;
+}
 
 constexpr int kLayers = 4;   // reference LFT.py:15
 
@@ -616,25 +638,8 @@ int lft_status_read(const void* workspace, int B, int A, int h, int w, int s, in
 int lft_forward_profiled(const void* packed, const float* lr, float* out, void* workspace, int B, int A, int h, int w, int s, int prec,
                          void* stream, int max_records, float* ms_out, const char** names_out, int* n_out) {
     if (!ms_out || !names_out || !n_out) return fail(LFT_ERR_ARG, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    g_prof.on = true; g_prof.st = st; g_prof.ev.clear(); g_prof.names.clear();
-    prof_mark("start");
-    int rc = lft_forward(packed, lr, out, workspace, B, A, h, w, s, prec, stream);
-    g_prof.on = false;
-    hipError_t e = hipStreamSynchronize(st);
-    int n = 0;
-    for (size_t i = 1; i < g_prof.ev.size() && n < max_records; ++i, ++n) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, g_prof.ev[i - 1], g_prof.ev[i]);
-        ms_out[n] = ms;
-        names_out[n] = g_prof.names[i];
-    }
-    for (hipEvent_t ev : g_prof.ev) (void)hipEventDestroy(ev);
-    g_prof.ev.clear(); g_prof.names.clear();
-    *n_out = n;
-    if (rc) return rc;
-    if (e != hipSuccess) return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
-    return 0;
+    return run_profiled(static_cast<hipStream_t>(stream), max_records, ms_out, names_out, n_out,
+                        [&] { return lft_forward(packed, lr, out, workspace, B, A, h, w, s, prec, stream); });
 }
 
 int lft_kernel_time(const char* kernel, const void* packed, void* workspace, int B, int A, int h, int w, int s, int prec, int reps,
@@ -885,36 +890,35 @@ int lft_train_tape_offset(const char* name, int B, int A, int h, int w, int s, s
     } else return fail(LFT_ERR_ARG, "unknown tape field %s", name);
     return 0;
 }
+// The checks every training entry point shares, after its own null pointers: the parameter array, the shape, the math mode.
+static int train_args(const float* const* params, int nparams, int B, int A, int h, int w, int s, int math, Dims* d) {
+    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
+    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
+    if (int rc = make_dims(B, A, h, w, s, LFT_PREC_F32, d)) return rc;
+    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
+    return 0;
+}
 int lft_train_forward(const float* const* params, int nparams, const float* lr, float* out, void* tape,
                       int B, int A, int h, int w, int s, int math, void* stream) {
     Dims d; int rc;
     if (!params || !lr || !out || !tape) return fail(LFT_ERR_ARG, "null pointer");
-    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
-    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
-    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
-    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
+    if ((rc = train_args(params, nparams, B, A, h, w, s, math, &d))) return rc;
     return train_forward(params, lr, out, static_cast<float*>(tape), d, math, static_cast<hipStream_t>(stream));
 }
 int lft_train_backward(const float* const* params, int nparams, const float* lr, void* tape, const float* dout, float* grads,
                        int B, int A, int h, int w, int s, int math, void* stream) {
     Dims d; int rc;
     if (!params || !lr || !tape || !dout || !grads) return fail(LFT_ERR_ARG, "null pointer");
-    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
-    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
-    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
-    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
+    if ((rc = train_args(params, nparams, B, A, h, w, s, math, &d))) return rc;
     return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream));
 }
 int lft_train_backward_input(const float* const* params, int nparams, const float* lr, void* tape, const float* dout,
                              float* grads, float* d_lr, int B, int A, int h, int w, int s, int math, void* stream) {
     Dims d; int rc;
     if (!params || !lr || !tape || !dout || !grads || !d_lr) return fail(LFT_ERR_ARG, "null pointer");
-    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
-    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
-    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
-    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
-    return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream), nullptr, nullptr,
-                          false, nullptr, nullptr, nullptr, d_lr);
+    if ((rc = train_args(params, nparams, B, A, h, w, s, math, &d))) return rc;
+    BwdRequest rq; rq.d_lr = d_lr;
+    return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream), rq);
 }
 int lft_lr_grad_bwd(const float* w0, const float* dx0, const float* dout, float* d_lr, int B, int A, int h, int w, int s, void* stream) {
     Dims d; int rc;
@@ -927,11 +931,9 @@ int lft_train_backward_buckets(const float* const* params, int nparams, const fl
                                lft_bucket_fn on_bucket, void* user) {
     Dims d; int rc;
     if (!params || !lr || !tape || !dout || !grads || !on_bucket) return fail(LFT_ERR_ARG, "null pointer");
-    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
-    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
-    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
-    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
-    return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream), on_bucket, user);
+    if ((rc = train_args(params, nparams, B, A, h, w, s, math, &d))) return rc;
+    BwdRequest rq; rq.on_bucket = on_bucket; rq.user = user;
+    return train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, static_cast<hipStream_t>(stream), rq);
 }
 int lft_train_block_backward(const float* const* params, int nparams, const float* lr, void* tape, int block, int layer,
                              const float* d_out, float* d_in, float* grads,
@@ -941,41 +943,22 @@ int lft_train_block_backward(const float* const* params, int nparams, const floa
     if (block < LFT_BLOCK_UPSAMPLE || block > LFT_BLOCK_INIT) return fail(LFT_ERR_ARG, "block must be LFT_BLOCK_UPSAMPLE .. LFT_BLOCK_INIT, got %d", block);
     if ((block == LFT_BLOCK_SPA || block == LFT_BLOCK_ANG) && (layer < 0 || layer >= kLayers)) return fail(LFT_ERR_ARG, "layer %d out of range", layer);
     if (block != LFT_BLOCK_INIT && !d_in) return fail(LFT_ERR_ARG, "d_in is null");
-    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
-    for (int i = 0; i < nparams; ++i) if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
-    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
-    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
+    if ((rc = train_args(params, nparams, B, A, h, w, s, math, &d))) return rc;
     const BlockSel sel{block, layer, d_out, d_in};
+    BwdRequest rq; rq.sel = &sel;
     return train_backward(params, lr, static_cast<float*>(tape), block == LFT_BLOCK_UPSAMPLE ? d_out : nullptr, grads, d, math,
-                          static_cast<hipStream_t>(stream), nullptr, nullptr, false, nullptr, nullptr, &sel);
+                          static_cast<hipStream_t>(stream), rq);
 }
 int lft_train_step_profiled(const float* const* params, int nparams, const float* lr, float* out, void* tape, const float* dout, float* grads,
                             int B, int A, int h, int w, int s, int math, void* stream, int max_records, float* ms_out, const char** names_out, int* n_out) {
     Dims d; int rc;
     if (!params || !lr || !out || !tape || !dout || !grads || !ms_out || !names_out || !n_out) return fail(LFT_ERR_ARG, "null pointer");
-    if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
-    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
-    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "math must be LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6, got %d", math);
+    if ((rc = train_args(params, nparams, B, A, h, w, s, math, &d))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    g_prof.on = true; g_prof.st = st; g_prof.ev.clear(); g_prof.names.clear();
-    prof_mark("start");
-    rc = train_forward(params, lr, out, static_cast<float*>(tape), d, math, st);
-    if (!rc) rc = train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, st, nullptr);    // one stream: every kernel between two events
-    g_prof.on = false;
-    hipError_t e = hipStreamSynchronize(st);
-    int n = 0;
-    for (size_t i = 1; i < g_prof.ev.size() && n < max_records; ++i, ++n) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, g_prof.ev[i - 1], g_prof.ev[i]);
-        ms_out[n] = ms;
-        names_out[n] = g_prof.names[i];
-    }
-    for (hipEvent_t ev : g_prof.ev) (void)hipEventDestroy(ev);
-    g_prof.ev.clear(); g_prof.names.clear();
-    *n_out = n;
-    if (rc) return rc;
-    if (e != hipSuccess) return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
-    return 0;
+    return run_profiled(st, max_records, ms_out, names_out, n_out, [&] {     // one stream: every kernel between two events
+        int r = train_forward(params, lr, out, static_cast<float*>(tape), d, math, st);
+        return r ? r : train_backward(params, lr, static_cast<float*>(tape), dout, grads, d, math, st);
+    });
 }
 int lft_train_grad_bucket(int s, int bucket, size_t* first_float, size_t* n_floats) {
     if (!first_float || !n_floats) return fail(LFT_ERR_ARG, "null pointer");

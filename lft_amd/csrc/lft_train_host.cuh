@@ -111,7 +111,7 @@ struct TrainLayout {
     // backward scratch
     size_t bwd, bwd_floats, gu, stats, part, pgb;       // bwd: arena of the backward pass's gradient tensors (re-used as they die)
     size_t part_floats, total;                   // total in floats
-    int rc = 0;                                  // status of the sizing (dry) run of the backward pass: non-zero = the layout is not usable
+    int rc = 0;                                  // status of the sizing run of the backward pass: non-zero = the layout is not usable
 };
 constexpr int kWgChunksMax = 512;                // ... raised up to this for small matrices (wgrad)
 constexpr int kWgChunks = 128;                   // token chunks (= workgroups of 4 waves) of a weight-gradient launch
@@ -119,7 +119,7 @@ constexpr int kLnBlocks = 512;                   // workgroups (= partial rows) 
 constexpr int kTailWaves = 2048;                 // waves of the up-sampler / conv0 weight-gradient kernels
 inline int wg_chunks(long long N) { return (int)std::min<long long>(kWgChunks, std::max<long long>(4, N / 512)); }   // workgroups of 4 waves, >= 128 tokens per wave
 
-struct BwdSizes { size_t arena, part; int rc; };   // floats: peak live set of the gradient arena, high-water mark of the partial sums; rc of the dry run
+struct BwdSizes { size_t arena, part; int rc; };   // floats: peak live set of the gradient arena, high-water mark of the partial sums; rc of the sizing run
 BwdSizes bwd_sizes(const Dims& d);
 TrainLayout train_layout(const Dims& d) {
     TrainLayout T;
@@ -143,9 +143,10 @@ TrainLayout train_layout(const Dims& d) {
     T.skip = take((size_t)d.B * d.A * d.h * d.s * d.A * d.w * d.s);
     // The gradient tensors of the backward pass live in an arena and are released at their last use (train_backward: every
     // kernel of a pass runs on ONE stream, so a buffer may be handed out again as soon as its last reader is enqueued); the
-    // arena is as large as the pass's peak live set, found by running the pass's own allocation sequence without launching
-    // anything (bwd_sizes).  Round 2 gave every tensor a buffer of its own (40 KB per token) so that the weight-gradient
-    // kernels could run on a second stream: that overlap bought 3 % and cost half of the tape.
+    // arena is as large as the pass's peak live set in any of its modes (the full pass, each block on its own), found by running
+    // the pass's own allocation sequence without enqueueing anything (bwd_sizes).  Round 2 gave every tensor a buffer of its own
+    // (40 KB per token) so that the weight-gradient kernels could run on a second stream: that overlap bought 3 % and cost half of
+    // the tape.
     const BwdSizes bsz = bwd_sizes(d);
     T.rc = bsz.rc;                               // callers refuse a layout whose sizing run failed (the message is in lft_last_error)
     T.bwd_floats = bsz.arena;
@@ -153,7 +154,7 @@ TrainLayout train_layout(const Dims& d) {
     T.gu = take(n * 64 * ss);
     T.stats = take(n * 8 * 3);
     // Partial sums (weight gradients per token chunk, LayerNorm rows, tails) are reduced at the end of every LAYER of the
-    // backward pass (k_reduce_all) and the region is re-used by the next one: as large as the largest layer's, from the same dry
+    // backward pass (k_reduce_all) and the region is re-used by the next one: as large as the largest layer's, from the same sizing
     // run (round 2 kept all parameters' partials at once: 0.6 GB at B = 8).
     T.part_floats = bsz.part;
     T.part = take(T.part_floats);
@@ -186,23 +187,32 @@ int run_pack_split(std::vector<PackOp>& ops, float* dst, int expect_frags, hipSt
 // ---- launch helpers ----
 struct TrainCtx;
 int red_push(const TrainCtx& c, size_t part_off, int nch, int n, int stride, float* dst, int chain);
+// base + off (floats) into the tape, the gradient buffer or the backward arena, formed as a number: the sizing run has no memory
+// (null bases) and still hands out distinct addresses, which the gate keeps it from ever using.
+inline float* addr(const float* base, size_t off) { return reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(base) + off * sizeof(float)); }
 struct TrainCtx {
     const Dims& d;
-    float* tp;                 // tape base
+    float* tp;                 // tape base (null in the sizing run)
     const TrainLayout& T;
     const WViews& W;
     hipStream_t st;
-    int math;                  // LFT_MATH_F32 or LFT_MATH_BF16X3
+    int math;                  // LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6
     RedTab* red = nullptr;     // backward only: pending reductions (k_reduce_all) ...
     size_t* part_used = nullptr;   // ... and the next free float of the partial buffer
-    size_t* part_peak = nullptr;   // its high-water mark (the dry run sizes the buffer with it)
-    const float* gbase = nullptr;  // flat gradient buffer (segment destinations are offsets into it)
-    bool dry = false;              // sizing pass: allocation sequence only, nothing is launched
-    const bool* arena_overflow = nullptr;   // backward only: set by BwdArena::get when a request does not fit -- no kernel is launched after that
-    float* F(size_t off) const { return tp + off; }
-    int launch_ok() const {        // every launcher of the backward pass asks before it enqueues anything
+    size_t* part_peak = nullptr;   // its high-water mark (the sizing run sizes the buffer with it)
+    float* gbase = nullptr;        // flat gradient buffer (segment destinations are offsets into it)
+    bool dry = false;              // sizing run: allocation sequence only, nothing is enqueued
+    const bool* arena_overflow = nullptr;   // backward only: set by BwdArena::get when a request does not fit
+    float* F(size_t off) const { return addr(tp, off); }
+    // The gate of every enqueue of the backward pass (kernel launch, device copy, reduction, bucket callback): the sizing run
+    // enqueues nothing, and once an arena request has not fit nothing is enqueued at all.
+    template <typename L> int enqueue(L&& launch) const {
+        if (dry) return 0;
         if (arena_overflow && *arena_overflow) return fail(LFT_ERR_ARG, "internal: backward arena overflow (a request did not fit the sized arena); nothing launched for it");
-        return 0;
+        return launch();
+    }
+    template <typename K> int kernel(const char* name, K&& k) const {   // one kernel launch through the gate
+        return enqueue([&] { k(); LFT_LAUNCH_OK(name); return 0; });
     }
 };
 
@@ -217,8 +227,6 @@ int part_take(const TrainCtx& c, size_t n, size_t* off) {
 // Y[N][ldy cols o0..] = act(X W(view)^T) (+R).  ot0 / nOT select a block of the view's output tiles (taps == 1 only).
 int run_lin(const TrainCtx& c, int view, int ot0, int nOT, const float* X, int ldx, int flip, int act, const float* R, int ldr,
             float* Y, int ldy, long long N, const float* M = nullptr, int mact = 0) {
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
     const WView& v = c.W.v[view];
     if (nOT <= 0) nOT = v.OT;
     if ((v.taps != 1 && (ot0 || nOT != v.OT))) return fail(LFT_ERR_ARG, "run_lin: bad tile block (view %d)", view);
@@ -239,27 +247,29 @@ int run_lin(const TrainCtx& c, int view, int ot0, int nOT, const float* X, int l
     // generic loop consumes two k-steps per iteration, so the stream length taps * KS must be even
     const bool ring = N > 65536 && (full4 || last2) && (v.taps == 1 || (nOT == v.OT && v.OT == nt)) && (v.taps * v.KS) % 2 == 0;
     const bool tiled = v.taps == 1 && v.KS % 4 == 0 && N <= 65536;       // measured: +7 % at 25.6 k tokens, -4 % at 205 k
-    int rc;
-    if (ring) {
-        p.gy = nOT / nt;
-        const dim3 g1((unsigned)((gx + 7) / 8 * 8 * p.gy));
-        // 3x3 on 32-wide views (a wave's 32 tokens = one image row): the row fragments are loaded once per tap row (k_linr<.., KS>)
-        const int ks3 = (v.taps == 9 && c.d.w == 32 && (v.KS == 4 || v.KS == 8)) ? v.KS : 0;
-        auto linr = [&](auto NT, auto KS) {
-            return dispatch<1, 2, 0>(mm, [&](auto MM) { k_linr<NT, MM, KS><<<g1, 256, 0, c.st>>>(p); return 0; });
-        };
-        if (nt == 4) rc = ks3 == 4 ? linr(int_c<4>{}, int_c<4>{}) : linr(int_c<4>{}, int_c<0>{});   // (no 3x3 view has 128 inputs and 128 outputs)
-        else rc = dispatch<4, 8, 0>(ks3, [&](auto KS) { return linr(int_c<2>{}, KS); });
-    } else {
-        rc = dispatch<4, 2, 1>(nt, [&](auto NT) {
-            return dispatch<1, 2, 0>(mm, [&](auto MM) {
-                return dispatch<true, false>(tiled, [&](auto TILED) { k_lin<NT, MM, TILED><<<g, 256, 0, c.st>>>(p); return 0; });
+    // 3x3 on 32-wide views (a wave's 32 tokens = one image row): the row fragments are loaded once per tap row (k_linr<.., KS>)
+    const int ks3 = (v.taps == 9 && c.d.w == 32 && (v.KS == 4 || v.KS == 8)) ? v.KS : 0;
+    if (ring) p.gy = nOT / nt;
+    return c.enqueue([&] {
+        int rc;
+        if (ring) {
+            const dim3 g1((unsigned)((gx + 7) / 8 * 8 * p.gy));
+            auto linr = [&](auto NT, auto KS) {
+                return dispatch<1, 2, 0>(mm, [&](auto MM) { k_linr<NT, MM, KS><<<g1, 256, 0, c.st>>>(p); return 0; });
+            };
+            if (nt == 4) rc = ks3 == 4 ? linr(int_c<4>{}, int_c<4>{}) : linr(int_c<4>{}, int_c<0>{});   // (no 3x3 view has 128 inputs and 128 outputs)
+            else rc = dispatch<4, 8, 0>(ks3, [&](auto KS) { return linr(int_c<2>{}, KS); });
+        } else {
+            rc = dispatch<4, 2, 1>(nt, [&](auto NT) {
+                return dispatch<1, 2, 0>(mm, [&](auto MM) {
+                    return dispatch<true, false>(tiled, [&](auto TILED) { k_lin<NT, MM, TILED><<<g, 256, 0, c.st>>>(p); return 0; });
+                });
             });
-        });
-    }
-    if (rc) return rc;
-    LFT_LAUNCH_OK(prof_name("k_lin", "k_lin:%d>%d%s%s%s", v.KS * 16, nOT * 32, v.taps == 9 ? " 3x3" : "", R ? " +R" : "", M ? " *M" : ""));
-    return 0;
+        }
+        if (rc) return rc;
+        LFT_LAUNCH_OK(prof_name("k_lin", "k_lin:%d>%d%s%s%s", v.KS * 16, nOT * 32, v.taps == 9 ? " 3x3" : "", R ? " +R" : "", M ? " *M" : ""));
+        return 0;
+    });
 }
 // Linear / conv forward through view `view` (all of its output rows, or tiles [ot0, ot0 + nOT)): Y = act(X W^T) (+R)
 int lin_fwd(const TrainCtx& c, int view, const float* X, int act, const float* R, float* Y, long long N, int ot0 = 0, int nOT = 0) {
@@ -297,33 +307,32 @@ int wgrad(const TrainCtx& c, const float* dY, int Co, const float* X, int Ci, in
     size_t poff;
     int rc;
     if ((rc = part_take(c, (size_t)nch * wsize, &poff))) return rc;
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
-    hipStream_t ws = c.st;
-    WgP p{dY, Co, X, Ci, c.F(c.T.part) + poff, wsize, Ci * taps, taps, 1, Co, Ci, taps, c.d.h, c.d.w, N, len, 1, nch, 1};
-    const int mm = c.math == LFT_MATH_BF16X3 ? 1 : c.math == LFT_MATH_BF16X6 ? 2 : 0;
-    auto launch = [&](auto NI, auto TX) {
-        const size_t lds = (size_t)3 * TX * NI * 16 * 64 * sizeof(float);
-        const dim3 g((unsigned)((nch + 7) / 8 * 8 * p.gy * TX));
-        return dispatch<1, 2, 0>(mm, [&](auto MM) {
-            if (int r = allow_lds(k_wgrad<NI, MM, TX>, lds, "k_wgrad")) return r;
-            k_wgrad<NI, MM, TX><<<g, 256, lds, ws>>>(p);
-            return 0;
-        });
-    };
-    if (taps == 9) {
-        p.igroups = 1; p.gy = Co / 32;
-        rc = launch(int_c<2>{}, int_c<3>{});
-    } else if (Ci % 128 == 0) {
-        p.igroups = Ci / 128; p.gy = Co / 32 * p.igroups;
-        rc = launch(int_c<4>{}, int_c<1>{});
-    } else {
-        p.igroups = Ci / 64; p.gy = Co / 32 * p.igroups;
-        rc = launch(int_c<2>{}, int_c<1>{});
-    }
-    if (rc) return rc;
-    LFT_LAUNCH_OK(prof_name("k_wgrad", "k_wgrad:%dx%d%s", Co, Ci, taps == 9 ? " 3x3" : ""));
-    return red_push(c, poff, nch, (int)wsize, (int)wsize, dW, accumulate);
+    return c.enqueue([&] {
+        WgP p{dY, Co, X, Ci, c.F(c.T.part + poff), wsize, Ci * taps, taps, 1, Co, Ci, taps, c.d.h, c.d.w, N, len, 1, nch, 1};
+        const int mm = c.math == LFT_MATH_BF16X3 ? 1 : c.math == LFT_MATH_BF16X6 ? 2 : 0;
+        auto launch = [&](auto NI, auto TX) {
+            const size_t lds = (size_t)3 * TX * NI * 16 * 64 * sizeof(float);
+            const dim3 g((unsigned)((nch + 7) / 8 * 8 * p.gy * TX));
+            return dispatch<1, 2, 0>(mm, [&](auto MM) {
+                if (int r = allow_lds(k_wgrad<NI, MM, TX>, lds, "k_wgrad")) return r;
+                k_wgrad<NI, MM, TX><<<g, 256, lds, c.st>>>(p);
+                return 0;
+            });
+        };
+        if (taps == 9) {
+            p.igroups = 1; p.gy = Co / 32;
+            rc = launch(int_c<2>{}, int_c<3>{});
+        } else if (Ci % 128 == 0) {
+            p.igroups = Ci / 128; p.gy = Co / 32 * p.igroups;
+            rc = launch(int_c<4>{}, int_c<1>{});
+        } else {
+            p.igroups = Ci / 64; p.gy = Co / 32 * p.igroups;
+            rc = launch(int_c<2>{}, int_c<1>{});
+        }
+        if (rc) return rc;
+        LFT_LAUNCH_OK(prof_name("k_wgrad", "k_wgrad:%dx%d%s", Co, Ci, taps == 9 ? " 3x3" : ""));
+        return red_push(c, poff, nch, (int)wsize, (int)wsize, dW, accumulate);
+    });
 }
 int red_push(const TrainCtx& c, size_t part_off, int nch, int n, int stride, float* dst, int chain) {
     RedTab& t = *c.red;
@@ -352,29 +361,21 @@ int ln_bwd(const TrainCtx& c, int C, const float* X, const float* pe, int mode, 
     size_t poff;
     int rc;
     if ((rc = part_take(c, (size_t)nb * 2 * C, &poff))) return rc;
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
-    float* pgb = c.F(c.T.part) + poff;
-    if (C == 64) k_ln_bwd<64><<<nb, 256, 0, c.st>>>(X, pe, mode, g, dY, add, out, pgb, N, c.d.hw, c.d.V);
-    else k_ln_bwd<128><<<nb, 256, 0, c.st>>>(X, pe, mode, g, dY, add, out, pgb, N, c.d.hw, c.d.V);
-    LFT_LAUNCH_OK("k_ln_bwd");
-    // partial rows are [dgamma(C) | dbeta(C)] and the two gradients are neighbours in the flat buffer (norm.weight, norm.bias)
-    if (dbeta != dgamma + C) return fail(LFT_ERR_ARG, "internal: LayerNorm gradients are not adjacent");
-    return red_push(c, poff, nb, 2 * C, 2 * C, dgamma, 0);
+    return c.enqueue([&] {
+        float* pgb = c.F(c.T.part + poff);
+        if (C == 64) k_ln_bwd<64><<<nb, 256, 0, c.st>>>(X, pe, mode, g, dY, add, out, pgb, N, c.d.hw, c.d.V);
+        else k_ln_bwd<128><<<nb, 256, 0, c.st>>>(X, pe, mode, g, dY, add, out, pgb, N, c.d.hw, c.d.V);
+        LFT_LAUNCH_OK("k_ln_bwd");
+        // partial rows are [dgamma(C) | dbeta(C)] and the two gradients are neighbours in the flat buffer (norm.weight, norm.bias)
+        if (dbeta != dgamma + C) return fail(LFT_ERR_ARG, "internal: LayerNorm gradients are not adjacent");
+        return red_push(c, poff, nb, 2 * C, 2 * C, dgamma, 0);
+    });
 }
 int act_bwd(const TrainCtx& c, const float* g, const float* y, float* out, long long n, int mode) {
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
-    k_act_bwd<<<blocks_for(n / 4, 256), 256, 0, c.st>>>(g, y, out, n / 4, mode);
-    LFT_LAUNCH_OK("k_act_bwd");
-    return 0;
+    return c.kernel("k_act_bwd", [&] { k_act_bwd<<<blocks_for(n / 4, 256), 256, 0, c.st>>>(g, y, out, n / 4, mode); });
 }
 int add3(const TrainCtx& c, float* out, const float* a, const float* b, long long n) {
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
-    k_add3<<<blocks_for(n / 4, 256), 256, 0, c.st>>>(out, a, b, n / 4);
-    LFT_LAUNCH_OK("k_add3");
-    return 0;
+    return c.kernel("k_add3", [&] { k_add3<<<blocks_for(n / 4, 256), 256, 0, c.st>>>(out, a, b, n / 4); });
 }
 int add_to(const TrainCtx& c, float* a, const float* b, long long n) {
     k_add<<<blocks_for(n / 4, 256), 256, 0, c.st>>>(a, b, n / 4);
@@ -383,33 +384,65 @@ int add_to(const TrainCtx& c, float* a, const float* b, long long n) {
 }
 template <bool BWD>
 int ang_attn(const TrainCtx& c, const float* QK, const float* Vv, float* O, const float* dO, float* dQK, float* dV) {
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
     const int V = c.d.V, npix = c.d.B * c.d.hw;
-    int rc;
-    if (V <= 32) {
-        const size_t lds = BWD ? (size_t)(4 * 8 * kAngHS<32> + 8 * (32 * 3 + 1)) * 4 : (size_t)(2 * 8 * kAngHS<32>) * 4;
-        k_ang_attn<32, BWD><<<npix, 256, lds, c.st>>>(QK, Vv, O, dO, dQK, dV, V, c.d.hw);
-    } else {
-        const size_t lds = BWD ? (size_t)(4 * 8 * kAngHS<128> + 8 * (128 * 3 + 1)) * 4 : (size_t)(2 * 8 * kAngHS<128>) * 4;
-        if ((rc = allow_lds(k_ang_attn<128, BWD>, lds, "k_ang_attn"))) return rc;
-        k_ang_attn<128, BWD><<<npix, 1024, lds, c.st>>>(QK, Vv, O, dO, dQK, dV, V, c.d.hw);
-    }
-    LFT_LAUNCH_OK(prof_name("k_ang_attn", "k_ang_attn:%s", BWD ? "backward" : "forward"));
-    return 0;
+    return c.enqueue([&] {
+        if (V <= 32) {
+            const size_t lds = BWD ? (size_t)(4 * 8 * kAngHS<32> + 8 * (32 * 3 + 1)) * 4 : (size_t)(2 * 8 * kAngHS<32>) * 4;
+            k_ang_attn<32, BWD><<<npix, 256, lds, c.st>>>(QK, Vv, O, dO, dQK, dV, V, c.d.hw);
+        } else {
+            const size_t lds = BWD ? (size_t)(4 * 8 * kAngHS<128> + 8 * (128 * 3 + 1)) * 4 : (size_t)(2 * 8 * kAngHS<128>) * 4;
+            if (int rc = allow_lds(k_ang_attn<128, BWD>, lds, "k_ang_attn")) return rc;
+            k_ang_attn<128, BWD><<<npix, 1024, lds, c.st>>>(QK, Vv, O, dO, dQK, dV, V, c.d.hw);
+        }
+        LFT_LAUNCH_OK(prof_name("k_ang_attn", "k_ang_attn:%s", BWD ? "backward" : "forward"));
+        return 0;
+    });
 }
 
 template <int MODE>
 int win_attn(const TrainCtx& c, const float* Q, const float* K, const float* V, float* O, const float* dO, float* dQ, float* dK, float* dV) {   // Q | K and dQ | dK: [N][256]
-    if (c.dry) return 0;
-    if (int ok_ = c.launch_ok()) return ok_;
     const Dims& d = c.d;
     const unsigned tiles = (unsigned)(((d.w + kWaTX - 1) / kWaTX) * ((d.h + kWaTY - 1) / kWaTY) * d.B * d.V);
-    int rc;
-    if ((rc = allow_lds(k_win_attn_lds<MODE>, kWaLds, "k_win_attn_lds"))) return rc;
-    k_win_attn_lds<MODE><<<dim3(tiles, 4), 256, kWaLds, c.st>>>(Q, K, V, O, dO, dQ, dK, dV, c.F(c.T.stats), d.h, d.w, 256);
-    LFT_LAUNCH_OK(prof_name("k_win_attn_lds", "k_win_attn_lds:%s", MODE == 0 ? "forward" : MODE == 1 ? "bwd A (dQ)" : "bwd B (dK dV)"));
-    return 0;
+    return c.enqueue([&] {
+        if (int rc = allow_lds(k_win_attn_lds<MODE>, kWaLds, "k_win_attn_lds")) return rc;
+        k_win_attn_lds<MODE><<<dim3(tiles, 4), 256, kWaLds, c.st>>>(Q, K, V, O, dO, dQ, dK, dV, c.F(c.T.stats), d.h, d.w, 256);
+        LFT_LAUNCH_OK(prof_name("k_win_attn_lds", "k_win_attn_lds:%s", MODE == 0 ? "forward" : MODE == 1 ? "bwd A (dQ)" : "bwd B (dK dV)"));
+        return 0;
+    });
+}
+// the up-sampler tail's gather, transposed: dG [N][ld] from dout
+int up_gather_bwd(const TrainCtx& c, const float* dout, float* dG, int ld) {
+    const Dims& d = c.d;
+    return c.kernel("k_up_gather_bwd", [&] { k_up_gather_bwd<<<blocks_for(d.ntok * ld, 256), 256, 0, c.st>>>(dout, dG, d.B, d.A, d.h, d.w, d.s, ld); });
+}
+// upsampling.3.weight: the reduced overlap-add gradient dM folded onto the 3x3 taps
+int upm_fold(const TrainCtx& c, const float* dM, float* dw) {
+    return c.kernel("k_upm_fold", [&] { k_upm_fold<<<3, 256, 0, c.st>>>(dM, dw, c.d.s); });
+}
+// dpe [hw][128] = the sum of du [images][hw][128] over the images
+int sum_images(const TrainCtx& c, const float* du, float* dpe) {
+    const long long n = (long long)c.d.hw * 128;
+    return c.kernel("k_sum_images", [&] { k_sum_images<<<blocks_for(n, 256), 256, 0, c.st>>>(du, c.d.B * c.d.V, n, dpe); });
+}
+// the weight gradient of conv_init0 from dx0 and the LR input
+int conv0_wgrad(const TrainCtx& c, const float* dx0, const float* lr, float* dW) {
+    const Dims& d = c.d;
+    size_t poff;
+    if (int rc = part_take(c, (size_t)kTailWaves * 576, &poff)) return rc;
+    return c.enqueue([&] {
+        const long long per = (d.ntok + kTailWaves - 1) / kTailWaves;
+        k_conv0_wgrad<<<kTailWaves / 4, 256, 0, c.st>>>(dx0, lr, c.F(c.T.part + poff), d.B, d.A, d.h, d.w, per);
+        LFT_LAUNCH_OK("k_conv0_wgrad");
+        return red_push(c, poff, kTailWaves, 576, 576, dW, 0);
+    });
+}
+// the partial sums of table t into the flat gradient buffer
+int reduce_all(const TrainCtx& c, const RedTab& t) {
+    return c.kernel("k_reduce_all", [&] { k_reduce_all<<<t.nblk, 256, 0, c.st>>>(t, c.F(c.T.part), c.gbase); });
+}
+// device copy on the pass's stream
+int copy_dev(const TrainCtx& c, float* dst, const float* src, size_t floats) {
+    return c.enqueue([&] { LFT_HIP_OK(hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, c.st)); return 0; });
 }
 
 // ---------------------------------------------------------------------------- forward with tape
@@ -494,7 +527,7 @@ struct BwdArena {
     float* base = nullptr;
     size_t cap = 0, peak = 0;
     bool overflow = false;                           // a request went past `cap`: the pointer handed out is the arena's base (valid
-                                                     // memory) and TrainCtx::launch_ok() stops every launcher before it enqueues
+                                                     // memory) and the gate (TrainCtx::enqueue) enqueues nothing from then on
     std::vector<std::pair<size_t, size_t>> used;     // (offset, floats), sorted by offset
     float* get(size_t n) {
         n = (n + 63) & ~(size_t)63;
@@ -506,10 +539,10 @@ struct BwdArena {
         used.insert(used.begin() + (long)i, std::make_pair(off, n));
         peak = std::max(peak, off + n);
         if (off + n > cap) { overflow = true; return base; }
-        return base + off;
+        return addr(base, off);
     }
     void put(const float* p) {
-        const size_t off = (size_t)(p - base);
+        const size_t off = (reinterpret_cast<uintptr_t>(p) - reinterpret_cast<uintptr_t>(base)) / sizeof(float);
         for (size_t i = 0; i < used.size(); ++i)
             if (used[i].first == off) { used.erase(used.begin() + (long)i); return; }
     }
@@ -524,34 +557,36 @@ int lr_grad(const Dims& d, const float* w0, const float* dx0, const float* dout,
     return 0;
 }
 
-// dry: the allocation sequence only (P, lr, tape, dout, G may be null) -- returns the arena's peak through *peak_out.
-// One block of the pass on its own (lft_train_block_backward): its incoming gradient comes from the caller, its outgoing gradient
-// goes to the caller, only its own parameter gradients are produced.  The tape must hold a full forward.
-// d_lr (full pass only; caller memory, so the sizing run does not see it): also the gradient of the LR input [B,1,A*h,A*w], from dx0
-// and dout at the end of the pass.  Null: nothing of it is launched.
+// What a backward pass does besides the full pass's parameter gradients (BwdRequest{}: nothing else).
+// sel: one block of the pass on its own (lft_train_block_backward): its incoming gradient is d_out, its outgoing one goes to d_in
+// (null: not wanted), only its own parameter gradients are produced; the tape must hold a full forward.
 struct BlockSel { int block, layer; const float* d_out; float* d_in; };
-int train_backward(const float* const* P, const float* lr, float* tape, const float* dout, float* G, const Dims& d, int math,
-                   hipStream_t st, BucketFn on_bucket = nullptr, void* user = nullptr,
-                   bool dry = false, size_t* peak_out = nullptr, size_t* part_peak_out = nullptr, const BlockSel* sel = nullptr,
-                   float* d_lr = nullptr) {
-    TrainLayout Tdry{};
-    const TrainLayout T = dry ? Tdry : train_layout(d);
-    if (T.rc) return T.rc;
+struct BwdRequest {
+    BucketFn on_bucket = nullptr;    // full pass: told at the end of every gradient bucket (lft_train_backward_buckets) ...
+    void* user = nullptr;            // ... with this
+    const BlockSel* sel = nullptr;   // one block on its own
+    float* d_lr = nullptr;           // full pass: also the gradient of the LR input [B,1,A*h,A*w] (lft_train_backward_input)
+};
+
+// The pass.  sizes null: enqueued on st against the layout T.  sizes non-null (bwd_sizes): the allocation sequence alone, with no
+// memory at all (P, lr, tape, dout, G null; T read for offsets only) -- the arena's peak and the partial buffer's high-water mark
+// are returned there.
+int backward_pass(const float* const* P, const float* lr, float* tape, const float* dout, float* G, const Dims& d, int math,
+                  hipStream_t st, const BwdRequest& rq, const TrainLayout& T, BwdSizes* sizes) {
     const WViews WV = build_views(nullptr, d.s, nullptr);            // packed by this step's lft_train_forward
     RedTab red{};                                                    // every partial-sum producer registers a segment here
     size_t part_used = 0, part_peak = 0;
-    static float dummy_base[64];
-    TrainCtx c{d, dry ? dummy_base : tape, T, WV, st, math, &red, &part_used, &part_peak, G};
-    c.dry = dry;
-    const ParamInfo pi = param_info(d.s);
-    const long long N = d.ntok;
-    const int ss = d.s * d.s, nimg = d.B * d.V;
-    int rc;
-    auto g = [&](int idx) { return G + pi.off[idx]; };
     BwdArena A;
+    TrainCtx c{d, tape, T, WV, st, math, &red, &part_used, &part_peak, G, sizes != nullptr, &A.overflow};
+    const ParamInfo pi = param_info(d.s);
+    const BlockSel* sel = rq.sel;
+    const long long N = d.ntok;
+    const int ss = d.s * d.s;
+    int rc;
+#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
+    auto g = [&](int idx) { return addr(G, pi.off[idx]); };
     A.base = c.F(T.bwd);
-    A.cap = dry ? (size_t)-1 : T.bwd_floats;
-    c.arena_overflow = &A.overflow;
+    A.cap = sizes ? (size_t)-1 : T.bwd_floats;
     auto nb = [&](int width) { return A.get((size_t)N * width); };   // [N][width] gradient buffer; A.put() at its last use
     // End of a gradient bucket: the partial sums registered since the last bucket are reduced (one table-driven launch) and
     // their region is free again, then the caller is told -- everything enqueued before the callback belongs to the bucket,
@@ -559,7 +594,6 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
     int red_done = 0;
     float* dM = nullptr;
     auto flush = [&]() -> int {                                      // reduce the partial sums registered so far; their region is free again
-        if (dry) { part_used = 0; return 0; }
         RedTab sub{};
         for (int i = red_done; i < red.nseg; ++i) {
             sub.s[sub.nseg] = red.s[i];
@@ -568,37 +602,25 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
             ++sub.nseg;
         }
         red_done = red.nseg;
-        if (sub.nseg) {
-            k_reduce_all<<<sub.nblk, 256, 0, st>>>(sub, c.F(T.part), G);
-            LFT_LAUNCH_OK("k_reduce_all");
-        }
         part_used = 0;                                               // the next layer's partial sums overwrite these (stream order)
-        return 0;
+        return sub.nseg ? reduce_all(c, sub) : 0;
     };
     auto end_bucket = [&](int bucket) -> int {
-        if (int frc = flush()) return frc;
-        if (dry) return 0;
-        if (bucket == 0) {                                           // upsampling.3.weight: the reduced dM folded onto the 3x3 taps
-            k_upm_fold<<<3, 256, 0, st>>>(dM, g(P_UP3), d.s);
-            LFT_LAUNCH_OK("k_upm_fold");
-        }
-        if (on_bucket) {
+        TRY(flush());
+        if (bucket == 0) TRY(upm_fold(c, dM, g(P_UP3)));
+        if (!rq.on_bucket) return 0;
+        return c.enqueue([&] {
             size_t first, count;
             grad_bucket_range(d.s, bucket, &first, &count);
-            if (on_bucket(user, bucket, first, count) != 0)              // the caller asked to stop: enqueue nothing further
+            if (rq.on_bucket(rq.user, bucket, first, count) != 0)    // the caller asked to stop: enqueue nothing further
                 return fail(LFT_ERR_CALLBACK, "on_bucket asked to stop at bucket %d", bucket);
-        }
-        return 0;
+            return 0;
+        });
     };
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
     // Block selection (sel != null): `want(block, layer)` says whether a section runs; a selected section takes its incoming gradient
     // from the caller and hands its result back through `give` (a device copy on the pass's stream), then the partial sums are reduced.
     auto want = [&](int block, int layer) { return !sel || (sel->block == block && (block == LFT_BLOCK_UPSAMPLE || block == LFT_BLOCK_INIT || sel->layer == layer)); };
-    auto give = [&](const float* src, size_t floats) -> int {
-        if (!sel || !sel->d_in) return 0;
-        LFT_HIP_OK(hipMemcpyAsync(sel->d_in, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st));
-        return 0;
-    };
+    auto give = [&](const float* src) { return sel->d_in ? copy_dev(c, sel->d_in, src, (size_t)N * 64) : 0; };
     float* gskip = nullptr;
     const float* dy = sel ? sel->d_out : nullptr;
     if (want(LFT_BLOCK_UPSAMPLE, 0)) {
@@ -606,10 +628,7 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
     float* gu = c.F(T.gu);
     const int gt = (d.gp + 31) / 32;
     float* dG = nb(32 * gt);
-    if (!dry) {
-        k_up_gather_bwd<<<blocks_for(N * 32 * gt, 256), 256, 0, st>>>(dout, dG, d.B, d.A, d.h, d.w, d.s, 32 * gt);
-        LFT_LAUNCH_OK("k_up_gather_bwd");
-    }
+    TRY(up_gather_bwd(c, dout, dG, 32 * gt));
     dM = A.get((size_t)32 * gt * 64 * ss);                           // [32 gt][64 s^2], folded onto upsampling.3.weight at the end of bucket 0
     TRY(wgrad(c, dG, 32 * gt, c.F(T.act), 64 * ss, 1, dM, 0, N));
     TRY(run_lin(c, VW_UPM_B, 0, 0, dG, 32 * gt, 0, 0, nullptr, 0, gu, 64 * ss, N, c.F(T.act), 2));   // dU = (M^T dG) * lrelu'(U)
@@ -618,12 +637,7 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
     gskip = nb(64);                                                  // d body = d y3 = d feat (global skip): lives to the end of the pass
     TRY(lin_bwd(c, VW_UP_B, gu, nullptr, gskip, N));
     dy = gskip;
-    if (sel) {                                                       // the block on its own: fold dM now (the full pass does it at the end of bucket 0)
-        TRY(flush());
-        k_upm_fold<<<3, 256, 0, st>>>(dM, g(P_UP3), d.s);
-        LFT_LAUNCH_OK("k_upm_fold");
-        TRY(give(gskip, (size_t)N * 64));
-    }
+    if (sel) { TRY(flush()); TRY(upm_fold(c, dM, g(P_UP3))); TRY(give(gskip)); }   // on its own: dM folded now, not at the end of bucket 0
     }
     for (int l = kLayers - 1; l >= 0; --l) {
         // ================= SpaTrans backward: dy [N,64] -> dx =================
@@ -635,7 +649,7 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
             TRY(wgrad(c, dy, 64, c.F(sp.t2), 128, 1, g(pidx(l, S_LIN)), 0, N));
             float* dt2 = nb(128);
             TRY(lin_bwd(c, vw(l, SLIN_B), dy, nullptr, dt2, N));
-            if (dy != gskip) A.put(dy);
+            if (!sel && dy != gskip) A.put(dy);                       // (the caller's d_out and the global skip are not released here)
             TRY(wgrad(c, dt2, 128, c.F(sp.hdn), 256, 1, g(pidx(l, S_FF2)), 0, N));
             float* dhz = nb(256);
             TRY(lin_bwd(c, vw(l, SFF2_B), dt2, nullptr, dhz, N, c.F(sp.hdn), 1));           // d (W1 m) = d hdn * relu'()
@@ -651,8 +665,8 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
             TRY(lin_bwd(c, vw(l, SOUT_B), dt1, nullptr, dO, N));
             float* dqk = nb(256);
             float* dV = nb(128);
-            TRY(win_attn<1>(c, c.F(sp.qk), c.F(sp.qk) + 128, c.F(sp.v), nullptr, dO, dqk, nullptr, nullptr));        // dQ (+ row stats)
-            TRY(win_attn<2>(c, c.F(sp.qk), c.F(sp.qk) + 128, c.F(sp.v), nullptr, dO, nullptr, dqk + 128, dV));      // dK, dV
+            TRY(win_attn<1>(c, c.F(sp.qk), c.F(sp.qk + 128), c.F(sp.v), nullptr, dO, dqk, nullptr, nullptr));        // dQ (+ row stats)
+            TRY(win_attn<2>(c, c.F(sp.qk), c.F(sp.qk + 128), c.F(sp.v), nullptr, dO, nullptr, dqk + 128, dV));      // dK, dV
             A.put(dO);
             TRY(wgrad(c, dV, 128, c.F(sp.tok), 128, 1, gin + 256 * 128, 0, N));
             float* dtokA = nb(128);
@@ -666,10 +680,7 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
             TRY(ln_bwd(c, 128, c.F(sp.tok), c.F(sp.petok), 2, P ? P[pidx(l, S_N1W)] : nullptr, dn, nullptr, du, g(pidx(l, S_N1W)), g(pidx(l, S_N1B)), N));  // d(tok+pe)
             A.put(dn);
             float* dpe = A.get((size_t)d.hw * 128);
-            if (!dry) {
-                k_sum_images<<<blocks_for((long long)d.hw * 128, 256), 256, 0, st>>>(du, nimg, (long long)d.hw * 128, dpe);
-                LFT_LAUNCH_OK("k_sum_images");
-            }
+            TRY(sum_images(c, du, dpe));
             float* dtok = nb(128);
             TRY(add3(c, dtok, dtokA, du, N * 128));                                          // ... + d(tok+pe)
             A.put(dtokA); A.put(du);
@@ -679,13 +690,13 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
             dx = nb(64);
             TRY(lin_bwd(c, vw(l, MLP_B), dtok, nullptr, dx, N));
             A.put(dtok);
-            if (sel) { TRY(flush()); TRY(give(dx, (size_t)N * 64)); }
+            if (sel) { TRY(flush()); TRY(give(dx)); }
         }
         // ================= AngTrans backward: dx -> dy of the layer below =================
         if (want(LFT_BLOCK_ANG, l)) {
             if (sel) {                                               // the block on its own: its incoming gradient is the caller's (copied: the section releases dx)
                 dx = nb(64);
-                LFT_HIP_OK(hipMemcpyAsync(dx, sel->d_out, (size_t)N * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+                TRY(copy_dev(c, dx, sel->d_out, (size_t)N * 64));
             }
             const AngTape& a = T.ang[l];
             const float* xin = l == 0 ? c.F(T.feat) : c.F(T.spa[l - 1].y);
@@ -719,22 +730,18 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
             TRY(ln_bwd(c, 64, xin, c.F(T.pe_ang), 1, P ? P[pidx(l, A_N1W)] : nullptr, dn, dxa, dxo, g(pidx(l, A_N1W)), g(pidx(l, A_N1B)), N));   // ... + d LN(x + PE)
             A.put(dn); A.put(dxa);
             dy = dxo;
-            if (sel) { TRY(flush()); TRY(give(dxo, (size_t)N * 64)); }
+            if (sel) { TRY(flush()); TRY(give(dxo)); }
         }
         if (sel) continue;
         if (l == 2) { TRY(end_bucket(0)); A.put(dM); }
         else if (l == 0) TRY(end_bucket(1));
         else TRY(flush());
     }
-    if (!want(LFT_BLOCK_INIT, 0)) {                                  // a single block other than the feature extractor: done
-        if (peak_out) *peak_out = A.peak;
-        if (part_peak_out) *part_peak_out = part_peak;
-        return 0;
-    }
+    if (want(LFT_BLOCK_INIT, 0)) {
     // ---- initial feature extractor ----
     float* dfeat = nb(64);
     if (sel) {                                                       // the block on its own: d feat is the caller's
-        LFT_HIP_OK(hipMemcpyAsync(dfeat, sel->d_out, (size_t)N * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        TRY(copy_dev(c, dfeat, sel->d_out, (size_t)N * 64));
     } else {
         TRY(add3(c, dfeat, dy, gskip, N * 64));
         A.put(dy); A.put(gskip);
@@ -753,35 +760,43 @@ int train_backward(const float* const* P, const float* lr, float* tape, const fl
     float* dx0 = nb(64);
     TRY(lin_bwd(c, VW_CONV_B + 0, dz1, dfeat, dx0, N));                                    // d x0 = d feat + conv path
     A.put(dz1); A.put(dfeat);
-    size_t poff0;
-    TRY(part_take(c, (size_t)kTailWaves * 576, &poff0));
-    if (peak_out) *peak_out = A.peak;
-    if (part_peak_out) *part_peak_out = part_peak;
-    if (dry) return 0;
-    if (A.peak > T.bwd_floats) return fail(LFT_ERR_ARG, "internal: backward arena overflow (%zu > %zu)", A.peak, T.bwd_floats);
-    {
-        const long long per = (N + kTailWaves - 1) / kTailWaves;
-        const size_t poff = poff0;
-        k_conv0_wgrad<<<kTailWaves / 4, 256, 0, st>>>(dx0, lr, c.F(T.part) + poff, d.B, d.A, d.h, d.w, per);
-        LFT_LAUNCH_OK("k_conv0_wgrad");
-        TRY(red_push(c, poff, kTailWaves, 576, 576, g(P_CONV0), 0));
-    }
-    if (d_lr && !sel) {                                              // dx0 is final and still held (never released)
-        if (int ok_ = c.launch_ok()) return ok_;
-        TRY(lr_grad(d, P[P_CONV0], dx0, dout, d_lr, st));
-    }
+    TRY(conv0_wgrad(c, dx0, lr, g(P_CONV0)));
+    if (rq.d_lr && !sel) TRY(c.enqueue([&] { return lr_grad(d, P[P_CONV0], dx0, dout, rq.d_lr, st); }));   // dx0 is final and still held
     TRY(end_bucket(2));
+    }
 #undef TRY
+    if (sizes) { sizes->arena = A.peak; sizes->part = part_peak; }
     return 0;
 }
+int train_backward(const float* const* P, const float* lr, float* tape, const float* dout, float* G, const Dims& d, int math,
+                   hipStream_t st, const BwdRequest& rq = {}) {
+    const TrainLayout T = train_layout(d);
+    if (T.rc) return T.rc;
+    return backward_pass(P, lr, tape, dout, G, d, math, st, rq, T, nullptr);
+}
 BwdSizes bwd_sizes(const Dims& d) {
-    // the pass's own allocation sequence, nothing launched; cached for the last shape (every entry point computes the layout)
+    // the allocation sequence of every mode the pass runs in -- the full pass and each block on its own -- with nothing enqueued;
+    // the arena and the partial buffer take the largest of them.  Cached for the last shape (every entry point computes the layout).
     static thread_local Dims last{};
     static thread_local BwdSizes last_sz{};
     if (last_sz.arena && last.B == d.B && last.A == d.A && last.h == d.h && last.w == d.w && last.s == d.s) return last_sz;
+    const TrainLayout none{};                                        // the layout being sized: its offsets are never dereferenced here
     BwdSizes sz{};
-    sz.rc = train_backward(nullptr, nullptr, nullptr, nullptr, nullptr, d, LFT_MATH_F32, nullptr, nullptr, nullptr, true, &sz.arena, &sz.part);
-    if (sz.rc) { sz.arena = sz.part = 0; return sz; }             // not cached: the next call reports the failure again
+    auto size = [&](const BlockSel* sel) {
+        BwdRequest rq; rq.sel = sel;
+        BwdSizes m{};
+        if ((sz.rc = backward_pass(nullptr, nullptr, nullptr, nullptr, nullptr, d, LFT_MATH_F32, nullptr, rq, none, &m))) return false;
+        sz.arena = std::max(sz.arena, m.arena);
+        sz.part = std::max(sz.part, m.part);
+        return true;
+    };
+    bool ok = size(nullptr);
+    for (int b = LFT_BLOCK_UPSAMPLE; b <= LFT_BLOCK_INIT; ++b)          // each block on its own: the up-sampler, 4 SpaTrans, 4 AngTrans, the feature extractor
+        for (int l = 0; l < (b == LFT_BLOCK_SPA || b == LFT_BLOCK_ANG ? kLayers : 1); ++l) {
+            const BlockSel sel{b, l, nullptr, nullptr};
+            ok = ok && size(&sel);
+        }
+    if (!ok) { sz.arena = sz.part = 0; return sz; }                 // not cached: the next call reports the failure again
     last = d; last_sz = sz;
     return sz;
 }
