@@ -187,6 +187,25 @@ int lft_train_grad_bucket(int s, int bucket, size_t* first_float, size_t* n_floa
 int lft_train_block_backward(const float* const* params, int nparams, const float* lr, void* tape, int block, int layer,
                              const float* d_out, float* d_in, float* grads,
                              int B, int A, int h, int w, int s, int math, void* stream);
+/* ---- attention maps: the softmax weights nn.MultiheadAttention(need_weights=True) would return at reference LFT.py:183-187
+ * (SpaTrans) and :230-233 (AngTrans), computed from the Q | K that lft_train_forward left in the tape.  `tape` must hold a complete
+ * lft_train_forward of the same (B, A, h, w, s), in any math mode; it is only read (a backward pass after the call gives the same
+ * bits as without it).  block = LFT_BLOCK_ANG or LFT_BLOCK_SPA, layer = 0..3.  heads_mode: LFT_MAPS_MEAN = averaged over the 8
+ * heads (torch's default), LFT_MAPS_HEADS = one map per head (average_attn_weights=False); H below is a dimension of 8 that
+ * exists only in LFT_MAPS_HEADS.  fp32 scores and softmax with the row maximum subtracted.  Layout of `maps` (fp32, fully
+ * overwritten, lft_attn_maps_floats elements):
+ *   LFT_BLOCK_ANG: [B, h, w, (H,) V_query, V_key], V = A*A -- the reference's (b h w) batch order;
+ *   LFT_BLOCK_SPA: compact [B, V, (H,) h, w, 5, 5]: element (dy, dx) is the weight of query (y, x) on key (y+dy-2, x+dx-2), EXACTLY 0
+ *                  where that key is outside the view or outside the reference's clamped window (LFT.py:155 clamps the column range
+ *                  with h, not w; the window is always a subset of the centred 5x5, the dense [hw, hw] form is never built).  For
+ *                  h < w a query with x - 2 >= h has an empty window: all 25 are exactly 0 -- the twin of the forward's attention
+ *                  output 0 for such a query -- where torch's own need_weights path gives NaN.
+ * Enqueue-only on `stream`, no allocation, no synchronisation, graph-capturable. */
+#define LFT_MAPS_MEAN 0    /* averaged over the 8 heads: what nn.MultiheadAttention(need_weights=True) returns */
+#define LFT_MAPS_HEADS 1   /* one map per head (average_attn_weights=False) */
+int lft_attn_maps_floats(int block, int heads_mode, int B, int A, int h, int w, size_t* out_floats);
+int lft_train_attn_maps(const void* tape, int block, int layer, int heads_mode, float* maps,
+                        int B, int A, int h, int w, int s, void* stream);
 /* Profiling aid, NOT for the hot path (bench.py's `train.roofline`): lft_train_forward + lft_train_backward on ONE stream with a HIP
  * event after every kernel; SYNCHRONISES the stream and returns per-kernel milliseconds in launch order (host arrays of max_records
  * entries, names are static strings; a step has about 450 launches). */

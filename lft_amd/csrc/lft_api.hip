@@ -34,6 +34,9 @@ namespace {
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
 #include "lft_train.cuh"     // training kernels; the fp32 inference path shares their LDS-tiled window attention
+#if LFT_TU != 1
+#include "lft_attn_maps.cuh" // attention weights from the tape's Q | K (lft_train_attn_maps)
+#endif
 }  // namespace
 
 #if LFT_TU == 2
@@ -948,6 +951,52 @@ int lft_train_block_backward(const float* const* params, int nparams, const floa
     BwdRequest rq; rq.sel = &sel;
     return train_backward(params, lr, static_cast<float*>(tape), block == LFT_BLOCK_UPSAMPLE ? d_out : nullptr, grads, d, math,
                           static_cast<hipStream_t>(stream), rq);
+}
+// ---- attention maps from the tape (lft_attn_maps.cuh) ----
+static int attn_maps_args(int block, int heads_mode) {
+    if (block != LFT_BLOCK_ANG && block != LFT_BLOCK_SPA) return fail(LFT_ERR_ARG, "block must be LFT_BLOCK_ANG or LFT_BLOCK_SPA, got %d", block);
+    if (heads_mode != LFT_MAPS_MEAN && heads_mode != LFT_MAPS_HEADS) return fail(LFT_ERR_ARG, "heads_mode must be LFT_MAPS_MEAN or LFT_MAPS_HEADS, got %d", heads_mode);
+    return 0;
+}
+static size_t attn_maps_count(const Dims& d, int block, int heads_mode) {
+    const size_t H = heads_mode == LFT_MAPS_HEADS ? 8 : 1;
+    return block == LFT_BLOCK_ANG ? (size_t)d.B * d.hw * H * d.V * d.V : (size_t)d.ntok * H * 25;
+}
+int lft_attn_maps_floats(int block, int heads_mode, int B, int A, int h, int w, size_t* out_floats) {
+    Dims d; int rc;
+    if (!out_floats) return fail(LFT_ERR_ARG, "out_floats is null");
+    if ((rc = attn_maps_args(block, heads_mode))) return rc;
+    if ((rc = make_dims(B, A, h, w, 2, LFT_PREC_F32, &d))) return rc;      // the maps do not depend on the scale factor
+    *out_floats = attn_maps_count(d, block, heads_mode);
+    return 0;
+}
+int lft_train_attn_maps(const void* tape, int block, int layer, int heads_mode, float* maps, int B, int A, int h, int w, int s, void* stream) {
+    Dims d; int rc;
+    if (!tape || !maps) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = attn_maps_args(block, heads_mode))) return rc;
+    if (layer < 0 || layer >= kLayers) return fail(LFT_ERR_ARG, "layer %d out of range", layer);
+    if ((rc = make_dims(B, A, h, w, s, LFT_PREC_F32, &d))) return rc;
+    const TrainLayout T = train_layout(d);
+    if (T.rc) return T.rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float* tp = static_cast<const float*>(tape);
+    const bool mean = heads_mode == LFT_MAPS_MEAN;
+    if (block == LFT_BLOCK_ANG) {
+        const size_t lds = ang_maps_lds(d.V);
+        const unsigned npix = (unsigned)(d.B * d.hw);
+        return dispatch<true, false>(mean, [&](auto MEAN) {
+            if (int r = allow_lds(k_ang_maps<MEAN>, lds, "k_ang_maps")) return r;
+            k_ang_maps<MEAN><<<npix, kAmThreads, lds, st>>>(tp + T.ang[layer].qk, maps, d.V, d.hw);
+            LFT_LAUNCH_OK("k_ang_maps");
+            return 0;
+        });
+    }
+    const unsigned tiles = (unsigned)(((d.w + kWaTX - 1) / kWaTX) * ((d.h + kWaTY - 1) / kWaTY) * d.B * d.V);
+    return dispatch<true, false>(mean, [&](auto MEAN) {
+        k_win_maps<MEAN><<<dim3(tiles, MEAN ? 1 : 4), 256, 0, st>>>(tp + T.spa[layer].qk, maps, d.h, d.w);
+        LFT_LAUNCH_OK("k_win_maps");
+        return 0;
+    });
 }
 int lft_train_step_profiled(const float* const* params, int nparams, const float* lr, float* out, void* tape, const float* dout, float* grads,
                             int B, int A, int h, int w, int s, int math, void* stream, int max_records, float* ms_out, const char** names_out, int* n_out) {

@@ -202,6 +202,12 @@ class get_model(nn.Module):
                 self.check_status()                     # fp16 by default: an overflow raises here (synchronises, like the .cpu() that follows in test.py)
         return out
 
+    def attention_maps(self, lr: torch.Tensor, **kw):
+        """The softmax weights of the eight attention blocks for ``lr`` (what ``need_weights=True`` at reference LFT.py:183-187 and
+        :230-233 returns), as ``{"ang0": t, "spa0": t, ...}`` of device tensors: lft_amd.attention.attention_maps(self, lr, **kw)."""
+        from .attention import attention_maps
+        return attention_maps(self, lr, **kw)
+
 
 class GraphedForward:
     """Replay of one captured forward (HIP graph) for a fixed input shape: the ~22 launches per sub-batch and the
