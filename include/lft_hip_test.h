@@ -1,5 +1,6 @@
-/* lft_hip_test.h -- test-only entry point of liblft_hip.so (NOT part of the product ABI of lft_hip.h; no reference counterpart).
- * The library exports it for tests/ only: the MFMA fragment-layout self test the parity suite starts with. */
+/* lft_hip_test.h -- test-only entry points of liblft_hip.so (NOT part of the product ABI of lft_hip.h; no reference counterpart).
+ * The library exports them for tests/ only: the MFMA fragment-layout self test the parity suite starts with, and the two
+ * stages the composed 16-bit front end is compared against. */
 #ifndef LFT_HIP_TEST_H
 #define LFT_HIP_TEST_H
 #ifdef __cplusplus
@@ -8,6 +9,15 @@ extern "C" {
 
 /* MFMA fragment-layout self test: C = Am[32x16] * Bm[16x32], D = W2[32x32] * C.  All fp32 device buffers. */
 int lft_mfma_selftest(const float* Am, const float* Bm, const float* W2, float* C, float* D, int prec, void* stream);
+
+/* lft_init_features_fwd as it ran before conv_init0 was composed into conv_init.0 (and as fp32 still runs it): conv_init0 written
+ * to the workspace, then the three 64 -> 64 convolutions.  Same arguments as lft_init_features_fwd. */
+int lft_init_features_legacy_fwd(const void* packed, const float* lr, void* act_out, void* workspace, int B, int A, int h, int w, int s,
+                                 int prec, void* stream);
+
+/* conv_init0 alone, tokens [B*A*A*h*w][64] in the activation type: recomputed == 0 -- the stand-alone kernel; recomputed != 0 (16-bit
+ * only) -- the residual tile the last convolution of the front end computes from the LR pixels.  The two must be bit-identical. */
+int lft_conv0_fwd(const void* packed, const float* lr, void* x0_out, int recomputed, int B, int A, int h, int w, int s, int prec, void* stream);
 
 #ifdef __cplusplus
 }

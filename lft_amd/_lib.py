@@ -152,9 +152,11 @@ _SIGS = {
                                c_void_p, c_void_p, c_void_p]),
     # test-only entry point (include/lft_hip_test.h)
     "lft_mfma_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "lft_init_features_legacy_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lft_conv0_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
-TEST_EXPORTS = ("lft_mfma_selftest",)                           # declared in include/lft_hip_test.h, not in the product header
+TEST_EXPORTS = ("lft_mfma_selftest", "lft_init_features_legacy_fwd", "lft_conv0_fwd")   # declared in include/lft_hip_test.h, not in the product header
 BLOCK_UPSAMPLE, BLOCK_SPA, BLOCK_ANG, BLOCK_INIT = 0, 1, 2, 3    # LFT_BLOCK_* of include/lft_hip.h
 LF_UINT8, LF_FLOAT32, LF_FLOAT64 = 0, 1, 2                      # LFT_LF_* of include/lft_hip.h
 MAPS_MEAN, MAPS_HEADS = 0, 1                                    # LFT_MAPS_* of include/lft_hip.h
@@ -175,6 +177,8 @@ def lib() -> ctypes.CDLL:
         if got != ABI_VERSION:              # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
             raise LftError(f"{LIB_PATH} reports ABI version {got}, this binding needs {ABI_VERSION}: rebuild it (__graft_entry__.build())")
         for name, (res, args) in _SIGS.items():
+            if name in TEST_EXPORTS and not hasattr(L, name):
+                continue        # an older LFT_LIB_PATH build of the same ABI version (A/B runs): the product entry points are all there
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -161,6 +161,7 @@ inline int frags_up(const Dims& d) { return d.nchunk * (4 + 2 * d.gt); }
 
 struct PackedLayout {
     size_t conv0_w, ln_ang[kLayers], ln_spa[kLayers], ang_pe, petok[kLayers], spa_pe_img;
+    size_t w01, s_w01;          // 16-bit only: conv_init.0 composed with conv_init0, fp32 [64][kW01K], and its 12 fragments
     size_t s_conv[3], s_ang[kLayers], s_spa1[kLayers], s_spa2[kLayers], s_up, total;
 };
 
@@ -174,7 +175,12 @@ PackedLayout packed_layout(const Dims& d, int prec) {
     L.ang_pe = take((size_t)((d.V + 31) / 32) * 2048 * 4);                       // lane-major, per 32-view tile
     for (int l = 0; l < kLayers; ++l) L.petok[l] = take((size_t)((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1)) * kNwSpa1 * 4096 * esz);   // lane-major, per 32-token tile
     L.spa_pe_img = take((size_t)d.hw * 64 * esz);
-    for (int i = 0; i < 3; ++i) L.s_conv[i] = take(kFragsConv * fragb);
+    // The W01 fragments sit directly in front of conv_init.2's stream (fragb is a multiple of 256): k_conv64_lr reads both as one
+    const bool lp = prec != LFT_PREC_F32;
+    L.w01 = take(lp ? 64 * kW01K * 4 : 0);
+    L.s_conv[0] = take(kFragsConv * fragb);
+    L.s_w01 = take(lp ? kW01Frags * fragb : 0);
+    for (int i = 1; i < 3; ++i) L.s_conv[i] = take(kFragsConv * fragb);
     for (int l = 0; l < kLayers; ++l) {
         L.s_ang[l] = take(kFragsAng * fragb);
         L.s_spa1[l] = take(kFragsSpa1 * fragb);
@@ -205,6 +211,8 @@ WorkLayout work_layout(const Dims& d, int prec) {
 
 // Dynamic LDS sizes (bytes) and the opt-in above the 64 KiB default (a workgroup may use all 160 KiB of a CU).
 template <typename T> size_t lds_conv64(int w) { return WRing<T, kConv64Chunk, kNwConv>::LDS_BYTES + ConvIn<T, kNwConv>::bytes(w) + kNwConv * TileIO<2, T>::BYTES + kConvZeroRow; }
+// The 16-bit front end: k_conv64_lr adds the staged LR pixels, k_conv64<T, 2> conv_init0's weights; one size serves both
+template <typename T> size_t lds_conv64_lr(int w) { return lds_conv64<T>(w) + std::max<size_t>(LrStage<kNwConv>::bytes(w), kConv0WBytes); }
 constexpr size_t kLdsParams = 1024;   // 256 LayerNorm floats
 template <typename T, int CH = kSpaChunk> size_t lds_spa1(int w) {      // the tile I/O scratch aliases the conv input tile, which must be large enough for it
     return WRing<T, CH, kNwSpa1>::LDS_BYTES + std::max<size_t>(ConvIn<T, kNwSpa1>::bytes(w), (size_t)kNwSpa1 * TileIO<4, T>::BYTES) + kLdsParams + kConvZeroRow;
@@ -306,6 +314,12 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
         conv_ops(ops, P[1 + i], 64);
         if ((rc = run_pack<T>(ops, at<T>(packed, L.s_conv[i]), kFragsConv, st))) return rc;
     }
+    if constexpr (sizeof(T) == 2) {     // conv_init.0 o conv_init0, composed in fp32, then rounded to ConvLrOp (half, also in bf16 mode: lft_kernels_a.cuh)
+        k_compose_w01<<<blocks_for(64 * kW01K, 256), 256, 0, st>>>(P[0], P[1], at<float>(packed, L.w01));
+        LFT_LAUNCH_OK("k_compose_w01");
+        std::vector<PackOp> ops{lin_op(at<float>(packed, L.w01), 0, 64, kW01K, 0, kW01K / 16, 0, 1.0f)};
+        if ((rc = run_pack<ConvLrOp>(ops, at<ConvLrOp>(packed, L.s_w01), kW01Frags, st))) return rc;
+    }
     k_pe_tables<T><<<blocks_for(std::max<long long>((long long)((d.V + 31) / 32) * 2048, (long long)d.hw * 64), 256), 256, 0, st>>>(
         at<float>(packed, L.ang_pe), at<T>(packed, L.spa_pe_img), d.V, d.h, d.w);
     LFT_LAUNCH_OK("k_pe_tables");
@@ -377,22 +391,44 @@ void launch_assemble(const float* lr, const float* g, float* out, int B, int A, 
 }
 
 // ---------------------------------------------------------------------------- stages
+// The front end as it was before the composition, and as fp32 still runs it: conv_init0 to memory, three 64 -> 64 convs.
 template <typename T>
-int init_features(const void* packed, const PackedLayout& L, const float* lr, T* x0, T* ta, T* tb, T* feat, const Dims& d, hipStream_t st) {
+int init_features_x0(const void* packed, const PackedLayout& L, const float* lr, T* x0, T* ta, T* tb, T* feat, const Dims& d, hipStream_t st) {
     const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
     const size_t lds = lds_conv64<T>(d.w);
     int rc;
-    if ((rc = allow_lds(k_conv64<T, false>, lds, "k_conv64"))) return rc;
-    if ((rc = allow_lds(k_conv64<T, true>, lds, "k_conv64"))) return rc;
+    if ((rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64"))) return rc;
+    if ((rc = allow_lds(k_conv64<T, 1>, lds, "k_conv64"))) return rc;
     k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, st>>>(lr, at<float>(packed, L.conv0_w), x0, d.B, d.A, d.h, d.w);
     LFT_LAUNCH_OK("k_conv0");
-    k_conv64<T, false><<<nwg, 64 * kNwConv, lds, st>>>(x0, ta, nullptr, at<T>(packed, L.s_conv[0]), nimg, d.h, d.w);
+    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(x0, ta, nullptr, at<T>(packed, L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
     LFT_LAUNCH_OK("k_conv64");
-    k_conv64<T, false><<<nwg, 64 * kNwConv, lds, st>>>(ta, tb, nullptr, at<T>(packed, L.s_conv[1]), nimg, d.h, d.w);
+    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(ta, tb, nullptr, at<T>(packed, L.s_conv[1]), nimg, d.h, d.w, ConvLr{});
     LFT_LAUNCH_OK("k_conv64");
-    k_conv64<T, true><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, x0, at<T>(packed, L.s_conv[2]), nimg, d.h, d.w);
+    k_conv64<T, 1><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, x0, at<T>(packed, L.s_conv[2]), nimg, d.h, d.w, ConvLr{});
     LFT_LAUNCH_OK("k_conv64");
     return 0;
+}
+// 16-bit: two launches.  conv_init0 is composed into conv_init.0 (k_conv64_lr: LR mosaic -> tb) and recomputed for the
+// residual of conv_init.4 (k_conv64<T, 2>); x0 and ta are never written.  Both launches carry the name "k_conv64": the
+// benchmark's per-kernel tables are indexed by the names lft_forward_profiled returns.
+template <typename T>
+int init_features(const void* packed, const PackedLayout& L, const float* lr, T* x0, T* ta, T* tb, T* feat, const Dims& d, hipStream_t st) {
+    if constexpr (sizeof(T) == 4) return init_features_x0<T>(packed, L, lr, x0, ta, tb, feat, d, st);
+    else {
+        const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
+        const size_t lds = lds_conv64_lr<T>(d.w);
+        int rc;
+        if (L.s_w01 + kW01Frags * 1024 != L.s_conv[1]) return fail(LFT_ERR_ARG, "internal: W01 fragments are not in front of conv_init.2's stream");
+        if ((rc = allow_lds(k_conv64_lr<T>, lds, "k_conv64"))) return rc;
+        if ((rc = allow_lds(k_conv64<T, 2>, lds, "k_conv64"))) return rc;
+        k_conv64_lr<T><<<nwg, 64 * kNwConv, lds, st>>>(lr, tb, at<T>(packed, L.s_w01), d.A, nimg, d.h, d.w);
+        LFT_LAUNCH_OK("k_conv64");
+        k_conv64<T, 2><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, nullptr, at<T>(packed, L.s_conv[2]), nimg, d.h, d.w,
+                                                      ConvLr{lr, at<float>(packed, L.conv0_w), d.A});
+        LFT_LAUNCH_OK("k_conv64");
+        return 0;
+    }
 }
 template <typename T, int CT, int LL>      // LL: score registers of the last key tile that can hold a view, which covers rows acc_row(i, 0) and acc_row(i, 1) = +4 of register i
 int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* out, const Dims& d, hipStream_t st, unsigned* status) {
@@ -548,8 +584,9 @@ int kernel_time_impl(const char* name, const void* packed, void* ws, const Dims&
             const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
             const size_t lds = lds_conv64<T>(d.w);
             int rc;
-            if ((rc = allow_lds(k_conv64<T, false>, lds, "k_conv64"))) return rc;
-            k_conv64<T, false><<<nwg, 64 * kNwConv, lds, st>>>(x0, feat, nullptr, at<T>(packed, L.s_conv[0]), nimg, d.h, d.w);
+            if ((rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64"))) return rc;
+            // input: xb, which every forward writes (the 16-bit front end no longer writes x0); output: x0, which nothing reads
+            k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(xb, x0, nullptr, at<T>(packed, L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
             LFT_LAUNCH_OK("k_conv64");
             return 0;
         }
@@ -675,6 +712,44 @@ int lft_init_features_fwd(const void* packed, const float* lr, void* act_out, vo
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
         return init_features<T>(packed, L, lr, at<T>(workspace, W.x0), at<T>(workspace, W.xa), at<T>(workspace, W.xb), static_cast<T*>(act_out), d, st);
+    });
+}
+
+int lft_init_features_legacy_fwd(const void* packed, const float* lr, void* act_out, void* workspace, int B, int A, int h, int w, int s,
+                                 int prec, void* stream) {
+    Dims d; int rc;
+    if (!packed || !lr || !act_out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
+    const PackedLayout L = packed_layout(d, prec);
+    const WorkLayout W = work_layout(d, prec);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        return init_features_x0<T>(packed, L, lr, at<T>(workspace, W.x0), at<T>(workspace, W.xa), at<T>(workspace, W.xb), static_cast<T*>(act_out), d, st);
+    });
+}
+
+int lft_conv0_fwd(const void* packed, const float* lr, void* x0_out, int recomputed, int B, int A, int h, int w, int s, int prec, void* stream) {
+    Dims d; int rc;
+    if (!packed || !lr || !x0_out) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
+    if (recomputed && prec == LFT_PREC_F32) return fail(LFT_ERR_ARG, "conv_init0 is recomputed in the 16-bit precisions only");
+    const PackedLayout L = packed_layout(d, prec);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        const int nimg = d.B * d.V;
+        const float* w0 = at<float>(packed, L.conv0_w);
+        if constexpr (sizeof(T) == 2) {
+            if (recomputed) {
+                k_conv0_recomputed<T><<<nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv)), 64 * kNwConv, 0, st>>>(static_cast<T*>(x0_out), nimg, d.h, d.w, ConvLr{lr, w0, d.A});
+                LFT_LAUNCH_OK("k_conv0_recomputed");
+                return 0;
+            }
+        }
+        k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, st>>>(lr, w0, static_cast<T*>(x0_out), d.B, d.A, d.h, d.w);
+        LFT_LAUNCH_OK("k_conv0");
+        return 0;
     });
 }
 

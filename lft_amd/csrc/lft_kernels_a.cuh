@@ -265,9 +265,104 @@ LFT_DEV void conv3x3_tile(const char* lds_in, const char* zero_row, int tl, int 
 // packed weights are streamed into the CU once per 32*NW tokens.
 constexpr int kNwConv = 4;
 constexpr int kConv64Chunk = 12;   // 72 fragments: 6 chunks of 12, 3-slot ring = 36 KiB (bf16) so two workgroups share a CU
-template <typename T, bool RES, int NW = kNwConv>
+
+// ------------------------------------------------------------------------------------------
+// The 16-bit front end computes conv_init0 where its output is consumed, from the LR pixels, instead of writing
+// x0 to memory and reading it twice.  conv_init0 (1 -> 64) has no bias and no activation (reference LFT.py:23-25,65),
+// so with lr~ = the view's LR image, zero outside it:
+//   x0(q)[c] = sum_t0 w0[c,t0] lr~(q+t0)
+//   a(p)[o]  = sum_t1 [p+t1 inside the view] sum_c w1[o,c,t1] x0(p+t1)[c]
+//            = sum_(t1,t0) [p+t1 inside the view] W01[o,t1,t0] lr~(p+t1+t0),   W01[o,t1,t0] = sum_c w1[o,c,t1] w0[c,t0]
+// The bracket is the per-view zero padding of x0 in front of conv_init.0; it is applied to the B operand, so there are
+// no border classes.  K = 81 (k = 9 t1 + t0) padded to 96 = 6 k-steps x 2 row tiles = one kConv64Chunk of fragments.
+// Operand type of THIS product: IEEE half in both 16-bit precisions (ConvLrOp).  x0 used to be formed in fp32, so a filter
+// whose taps nearly cancel on a smooth image (what training produces) kept its small response exactly; composed, the
+// cancellation happens inside the product, on ROUNDED pixels and ROUNDED W01 entries, and 8 significant bits quantise
+// a [0, 1] image like an 8-bit file (bf16 forward on trained weights: 0.027 dB from the oracle where 0.014 dB is the level
+// of the other sites).  11 bits keep the first product at the fp16 path's level; LR pixels and W01 entries are far inside
+// the half range (|lr| > 65504 would overflow).  The result is rounded to T where ta used to be stored, as before.
+typedef f16_t ConvLrOp;
+// ------------------------------------------------------------------------------------------
+constexpr int kW01K = 96, kW01Frags = 12;
+// Row rho of the composed matrix holds output channel conv01_row_channel(rho) (bits 2 and 3 exchanged): the accumulator
+// of the W01 product, taken as fragments (acc_frags), then holds channels 16 ks + 8 h + j in element j of fragment ks
+// -- the natural order of a token row in memory, so conv_init.2 consumes the tile with the stream it always had.
+__host__ __device__ __forceinline__ int conv01_row_channel(int rho) { return (rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1); }
+// w0 [64][9], w1 [64][64][9] -> w01 [64][kW01K] fp32 (pack time; k_pack rounds it to ConvLrOp)
+__global__ void k_compose_w01(const float* __restrict__ w0, const float* __restrict__ w1, float* __restrict__ w01) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 64 * kW01K) return;
+    const int rho = idx / kW01K, k = idx - rho * kW01K;
+    float v = 0.0f;
+    if (k < 81) {
+        const int o = conv01_row_channel(rho), t1 = k / 9, t0 = k - 9 * t1;
+        for (int c = 0; c < 64; ++c) v += w1[o * 576 + c * 9 + t1] * w0[c * 9 + t0];
+    }
+    w01[idx] = v;
+}
+// View (a1, a2) of image b inside the LR mosaic [B,1,A*h,A*w]; row stride A*w (see k_conv0).
+LFT_DEV const float* lr_view(const float* __restrict__ lr, int im, int A, int h, int w) {
+    const int V = A * A, b = im / V, v = im - b * V, a1 = v / A, a2 = v - a1 * A;
+    return lr + (size_t)b * (A * h) * (A * w) + (size_t)(a1 * h) * (A * w) + a2 * w;
+}
+// LR pixels of a workgroup tile in LDS: the image rows of the tile's slots plus two rows above and below, two zero
+// columns left and right; everything outside the view is stored as zero (lr~), so a 5 x 5 patch is 25 unconditional reads.
+template <int NW> struct LrStage {
+    static __host__ __device__ int width(int w) { return w + 4; }
+    static __host__ __device__ int max_rows(int w) { return (32 * NW + 2 * w + 1) / w + 6; }    // slots span at most (TT + 2w + 1) / w + 2 rows
+    static __host__ __device__ int bytes(int w) { return (max_rows(w) * width(w) * 4 + 15) & ~15; }
+};
+// conv_init0's weights in LDS as [tap][64] (kConv0WBytes), and conv_init0 for one token in accumulator layout with the
+// arithmetic of k_conv0: the same fp32 order of additions, rounded to T and widened back -- bit-identical to the x0 it stores.
+constexpr int kConv0WBytes = 9 * 64 * 4;
+LFT_DEV void conv0_w_stage(const float* __restrict__ w0, float* wl) {       // the caller's barrier publishes it
+    float wv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) wv[k] = w0[min((int)threadIdx.x + 256 * k, 575)];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = (int)threadIdx.x + 256 * k, ch = i / 9, t = i - ch * 9;
+        if (i < 576) wl[t * 64 + ch] = wv[k];
+    }
+}
+LFT_DEV void conv0_taps_load(const float* __restrict__ img, int ldi, int y, int x, int h, int w, float (&val)[9]) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {                                           // clamped (readable) positions; masked at use
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        val[t] = img[min(max(yy, 0), h - 1) * ldi + min(max(xx, 0), w - 1)];
+    }
+}
+template <typename T>
+LFT_DEV void conv0_token_acc(const float (&tap)[9], const float* wl, int y, int x, int h, int w, int hh, f32x16 (&rr)[2]) {
+    float val[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        val[t] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? tap[t] : 0.0f;
+    }
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 wq[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) wq[t] = __builtin_bit_cast(f32x4, load_raw16(reinterpret_cast<const char*>(wl + t * 64 + 32 * nt + 8 * g + 4 * hh)));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float a = 0.0f;                                              // k_conv0's order of additions
+#pragma unroll
+                for (int t = 0; t < 9; ++t) a += wq[t][j] * val[t];
+                rr[nt][4 * g + j] = (float)(T)a;
+            }
+        }
+}
+struct ConvLr { const float* lr; const float* w0; int A; };   // RES == 2: LR mosaic, conv_init0 weights (fp32), angular resolution
+
+// RES: 0 no residual; 1 the residual tile is read from `res`; 2 the residual is conv_init0 of the LR pixels, recomputed
+// (16-bit front end: x0 is never written).
+template <typename T, int RES, int NW = kNwConv>
 __global__ __launch_bounds__(64 * NW) void k_conv64(const T* __restrict__ in, T* __restrict__ out, const T* __restrict__ res,
-                                                   const T* __restrict__ wstream, int nimg, int h, int w) {
+                                                   const T* __restrict__ wstream, int nimg, int h, int w, ConvLr cl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TT = 32 * NW;                                       // tokens per workgroup tile
     const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = threadIdx.x >> 6;
@@ -281,15 +376,21 @@ __global__ __launch_bounds__(64 * NW) void k_conv64(const T* __restrict__ in, T*
     char* lds_in = smem + WRing<T, kConv64Chunk, NW>::LDS_BYTES;
     char* scr = lds_in + ConvIn<T, NW>::bytes(w) + wave * TileIO<2, T>::BYTES;        // wave-private tile I/O scratch
     char* zero_row = lds_in + ConvIn<T, NW>::bytes(w) + NW * TileIO<2, T>::BYTES;
+    float* wl = reinterpret_cast<float*>(zero_row + kConvZeroRow);                    // RES == 2 only
+    const int pc = min(p, hw - 1), yc = pc / w, xc = pc - yc * w;
     f32x16 rr[2];
-    if (RES) load_tile<2, T>(res + tile_off, nvalid, lane, rr, scr);                  // first: its latency hides under the tile
+    float tap[9];
+    if constexpr (RES == 1) load_tile<2, T>(res + tile_off, nvalid, lane, rr, scr);   // first: its latency hides under the tile
+    if constexpr (RES == 2) conv0_taps_load(lr_view(cl.lr, im, cl.A, h, w), cl.A * w, yc, xc, h, w, tap);
     WRing<T, kConv64Chunk, NW> ring;
     ring.init(wstream, smem, 72);
     stage_conv_input<T, NW>(in + (size_t)im * hw * 64, p0, hw, w, lds_in);
     clear_zero_row(zero_row);
+    if constexpr (RES == 2) conv0_w_stage(cl.w0, wl);
     wait_staged();
     __syncthreads();                                                                 // ... and everybody else's
     LFT_NOTE_ASM_("USE", kNoteConvIn, 0);
+    if constexpr (RES == 2) conv0_token_acc<T>(tap, wl, yc, xc, h, w, hh, rr);
     f32x16 acc[2];
     zero_acc<2>(acc);
     conv3x3_tile<2, T, NW>(lds_in, zero_row, tl, p / w, p % w, ok, h, w, hh, ring, acc);
@@ -297,11 +398,128 @@ __global__ __launch_bounds__(64 * NW) void k_conv64(const T* __restrict__ in, T*
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[nt][i] = lrelu02_fast(acc[nt][i]);
-    if (RES) {
+    if constexpr (RES != 0) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) acc[nt] += rr[nt];
     }
     store_tile<2, T>(out + tile_off, nvalid, lane, acc, scr);
+}
+
+// conv_init.0 composed with conv_init0, then conv_init.2: LR mosaic -> tb (16-bit precisions).  Same tile as k_conv64; the
+// conv-input tile of conv_init.2 (ConvIn::slots(w) token rows, swizzled as conv3x3_tile reads them) is COMPUTED here
+// instead of fetched: per 32 slots one masked B operand from the staged LR pixels, 12 half-precision MFMAs against W01, LeakyReLU,
+// four 16-byte LDS stores per lane.  The column tiles of 32 slots are spread over the NW waves.  Stream: the 12 W01
+// fragments (nt-major), then conv_init.2's 72 -- W01 is the first chunk of the ring, taken into registers by every wave.
+// Slots outside the view and tokens beyond hw hold values of clamped positions; conv3x3_tile never uses them.
+template <typename T, int NW = kNwConv>
+__global__ __launch_bounds__(64 * NW) void k_conv64_lr(const float* __restrict__ lr, T* __restrict__ out, const T* __restrict__ wstream,
+                                                      int A, int nimg, int h, int w) {
+    static_assert(sizeof(T) == 2, "16-bit operand types only");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using CI = ConvIn<T, NW>;
+    constexpr int TT = 32 * NW;
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hw = h * w, tpi = (hw + TT - 1) / TT;
+    const int bid = xcd_tile(blockIdx.x, gridDim.x);
+    const int im = bid / tpi, p0 = (bid % tpi) * TT;
+    const int tl = wave * 32 + r, p = p0 + tl;
+    const bool ok = p < hw;
+    const int t0 = p0 + wave * 32, nvalid = max(0, min(32, hw - t0));
+    const size_t tile_off = ((size_t)im * hw + min(t0, hw - 1)) * 64;
+    char* lds_in = smem + WRing<T, kConv64Chunk, NW>::LDS_BYTES;
+    char* scr = lds_in + CI::bytes(w) + wave * TileIO<2, T>::BYTES;
+    char* zero_row = lds_in + CI::bytes(w) + NW * TileIO<2, T>::BYTES;
+    float* lrs = reinterpret_cast<float*>(zero_row + kConvZeroRow);
+    WRing<T, kConv64Chunk, NW> ring;
+    ring.init(wstream, smem, kW01Frags + 72);
+    // LR pixels: rows y_first - 2 .. y_last + 2 of the view, columns -2 .. w + 1
+    const int nslots = CI::slots(w), LW = LrStage<NW>::width(w);
+    const int y_first = max(p0 - w - 1, 0) / w, y_last = min(p0 + TT + w, hw - 1) / w;
+    {
+        const float* img = lr_view(lr, im, A, h, w);
+        const int n = (y_last - y_first + 5) * LW, ldi = A * w;
+        for (int i = threadIdx.x; i < n; i += 64 * NW) {
+            const int row = i / LW, yy = y_first - 2 + row, xx = i - row * LW - 2;
+            const float v = img[min(max(yy, 0), h - 1) * ldi + min(max(xx, 0), w - 1)];
+            lrs[i] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? v : 0.0f;
+        }
+    }
+    clear_zero_row(zero_row);
+    Frag<ConvLrOp> wf[kW01Frags];                                      // packed as ConvLrOp whatever T is: same 1 KiB pieces
+#pragma unroll
+    for (int i = 0; i < kW01Frags; ++i) wf[i].v = __builtin_bit_cast(H16<ConvLrOp>::v8, ring.next().v);   // the ring's first barrier also publishes the LR pixels
+    for (int ct = wave; ct * 32 < nslots; ct += NW) {
+        const int slot = ct * 32 + r;
+        const int q = min(max(p0 - w - 1 + slot, 0), hw - 1), y = q / w, x = q - y * w;
+        const float* pl = lrs + (y - y_first) * LW + x;                 // lr~(y - 2 + a, x - 2 + b) = pl[a * LW + b]
+        float P[5][5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a)
+#pragma unroll
+            for (int b = 0; b < 5; ++b) P[a][b] = pl[a * LW + b];
+        bool m[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+            m[t] = yy >= 0 && yy < h && xx >= 0 && xx < w;
+        }
+        auto masked = [&](int k) -> float {                             // B[k = 9 t1 + t0][slot]; k is a constant after unrolling
+            if (k >= 81) return 0.0f;
+            const int t1 = k / 9, t0 = k % 9;
+            return m[t1] ? P[t1 / 3 + t0 / 3][t1 % 3 + t0 % 3] : 0.0f;
+        };
+        f32x16 a01[2];
+        zero_acc<2>(a01);
+#pragma unroll
+        for (int ks = 0; ks < kW01K / 16; ++ks) {
+            Frag<ConvLrOp> b;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) b.v[j] = (ConvLrOp)(hh ? masked(16 * ks + 8 + j) : masked(16 * ks + j));
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) mma(wf[nt * (kW01K / 16) + ks], b, a01[nt]);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) a01[nt][i] = lrelu02_fast(a01[nt][i]);
+        Frag<T> of[4];
+        acc_frags<2, T>(a01, of);
+        if (slot < nslots) {
+            char* row = lds_in + slot * CI::ROW_BYTES;
+            const int sw = CI::swz(slot);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) store_raw16(row + (((2 * ks + hh) ^ sw) * 16), __builtin_bit_cast(raw16, of[ks].v));
+        }
+    }
+    wg_barrier_keep_vm();                                              // the computed tile is published (lgkmcnt(0) inside)
+    f32x16 acc[2];
+    zero_acc<2>(acc);
+    conv3x3_tile<2, T, NW>(lds_in, zero_row, tl, p / w, p % w, ok, h, w, hh, ring, acc);
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[nt][i] = lrelu02_fast(acc[nt][i]);
+    store_tile<2, T>(out + tile_off, nvalid, lane, acc, scr);
+}
+// Test hook (lft_conv0_fwd): the residual tile k_conv64<T, 2> computes, written out as tokens [ntok][64].
+template <typename T, int NW = kNwConv>
+__global__ __launch_bounds__(64 * NW) void k_conv0_recomputed(T* __restrict__ out, int nimg, int h, int w, ConvLr cl) {
+    __shared__ __attribute__((aligned(16))) char sm[kConv0WBytes + NW * TileIO<2, T>::BYTES];
+    constexpr int TT = 32 * NW;
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = threadIdx.x >> 6;
+    const int hw = h * w, tpi = (hw + TT - 1) / TT;
+    const int im = blockIdx.x / tpi, p0 = (blockIdx.x % tpi) * TT;
+    const int t0 = p0 + wave * 32, nvalid = max(0, min(32, hw - t0));
+    const size_t tile_off = ((size_t)im * hw + min(t0, hw - 1)) * 64;
+    const int pc = min(p0 + wave * 32 + r, hw - 1), yc = pc / w, xc = pc - yc * w;
+    float* wl = reinterpret_cast<float*>(sm);
+    float tap[9];
+    conv0_taps_load(lr_view(cl.lr, im, cl.A, h, w), cl.A * w, yc, xc, h, w, tap);
+    conv0_w_stage(cl.w0, wl);
+    __syncthreads();
+    f32x16 rr[2];
+    conv0_token_acc<T>(tap, wl, yc, xc, h, w, hh, rr);
+    store_tile<2, T>(out + tile_off, nvalid, lane, rr, sm + kConv0WBytes + wave * TileIO<2, T>::BYTES);
 }
 
 // ------------------------------------------------------------------------------------------
