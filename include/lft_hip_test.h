@@ -1,6 +1,6 @@
 /* lft_hip_test.h -- test-only entry points of liblft_hip.so (NOT part of the product ABI of lft_hip.h; no reference counterpart).
- * The library exports them for tests/ only: the MFMA fragment-layout self test the parity suite starts with, and the two
- * stages the composed 16-bit front end is compared against. */
+ * The library exports them for tests/ only: the MFMA fragment-layout self test the parity suite starts with, the product-policy
+ * self test of the training GEMMs, and the two stages the composed 16-bit front end is compared against. */
 #ifndef LFT_HIP_TEST_H
 #define LFT_HIP_TEST_H
 #ifdef __cplusplus
@@ -9,6 +9,11 @@ extern "C" {
 
 /* MFMA fragment-layout self test: C = Am[32x16] * Bm[16x32], D = W2[32x32] * C.  All fp32 device buffers. */
 int lft_mfma_selftest(const float* Am, const float* Bm, const float* W2, float* C, float* D, int prec, void* stream);
+
+/* Product-policy self test of the training GEMMs (math = LFT_MATH_*): W [32][16] is packed as one weight fragment, X is [32 tokens][16];
+ * Y [32 tokens][32] = X W^T, Yl / Yr = the same product with X's rows moved by one token (row t takes row t - 1 / t + 1, a zero row at
+ * the edge).  All fp32 device buffers; returns after the stream has drained. */
+int lft_prod_selftest(const float* W, const float* X, float* Y, float* Yl, float* Yr, int math, void* stream);
 
 /* lft_init_features_fwd as it ran before conv_init0 was composed into conv_init.0 (and as fp32 still runs it): conv_init0 written
  * to the workspace, then the three 64 -> 64 convolutions.  Same arguments as lft_init_features_fwd. */

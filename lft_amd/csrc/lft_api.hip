@@ -1027,6 +1027,23 @@ int lft_train_block_backward(const float* const* params, int nparams, const floa
     return train_backward(params, lr, static_cast<float*>(tape), block == LFT_BLOCK_UPSAMPLE ? d_out : nullptr, grads, d, math,
                           static_cast<hipStream_t>(stream), rq);
 }
+// Test-only (include/lft_hip_test.h): Prod<math> on one packed fragment, see k_prod_selftest.
+int lft_prod_selftest(const float* W, const float* X, float* Y, float* Yl, float* Yr, int math, void* stream) {
+    if (!W || !X || !Y || !Yl || !Yr) return fail(LFT_ERR_ARG, "null pointer");
+    if (math != LFT_MATH_F32 && math != LFT_MATH_BF16X3 && math != LFT_MATH_BF16X6) return fail(LFT_ERR_ARG, "bad math %d", math);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mm = math_mode(math);
+    float* wp = nullptr;
+    LFT_HIP_OK(hipMalloc(&wp, frag_floats(mm) * sizeof(float)));
+    std::vector<PackOp> ops{lin_op(W, 0, 32, 16, 0, 1, 0, 1.0f)};
+    int rc = mm ? run_pack_split(ops, wp, 1, st, mm) : run_pack<float>(ops, wp, 1, st);
+    if (!rc) rc = dispatch<1, 2, 0>(mm, [&](auto MM) { k_prod_selftest<MM><<<1, 64, 0, st>>>(wp, X, Y, Yl, Yr); return 0; });
+    const hipError_t e = hipStreamSynchronize(st);                    // the fragment is freed below
+    (void)hipFree(wp);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail((int)e, "k_prod_selftest: %s", hipGetErrorString(e));
+    return 0;
+}
 // ---- attention maps from the tape (lft_attn_maps.cuh) ----
 static int attn_maps_args(int block, int heads_mode) {
     if (block != LFT_BLOCK_ANG && block != LFT_BLOCK_SPA) return fail(LFT_ERR_ARG, "block must be LFT_BLOCK_ANG or LFT_BLOCK_SPA, got %d", block);

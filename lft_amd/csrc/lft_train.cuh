@@ -7,6 +7,10 @@
 //                                       transposed weight strides and flipped taps -- their input gradients
 //   k_wgrad  dW = dY^T X                split over token chunks (deterministic two-stage reduction)
 // plus the small VALU kernels around them (LayerNorm, both attentions, activations, up-sampler tail).
+// The GEMMs come in three arithmetics (LFT_MATH_F32 / _BF16X3 / _BF16X6).  The kernels are written once, over the product policy
+// Prod<MM> below: it owns the operand type of a mode, its packed fragment size, the split of fp32 values into the mode's parts,
+// the fragment loads, the lane shift and the MFMA sequence of one product.  A kernel never branches on the mode; another product
+// scheme or piece layout is a change to (or another specialisation of) Prod.
 // Weights change every step: at the start of a step both orientations (W for the forward, W^T for the input gradients)
 // are re-packed into fragment order by k_pack (9 MB, microseconds) so that every weight read is a coalesced 1 KiB piece.
 // All tensors are fp32 channels-last [token][channel]; token = ((b*V + v)*h + y)*w + x.
@@ -15,81 +19,158 @@
 #include "lft_kernels_b.cuh"   // asm-issued loads with counted waits (ld16_async_ofs, wait_vm_q)
 
 // ------------------------------------------------------------------------------------------
-// Split-bf16 products ("bf16x3").  The fp32 MFMA (v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak) is 16x slower than the
-// bf16 one, so an fp32 operand x is split into two bf16 numbers x = hi + lo (+ O(2^-17 x)) and a product is
+// Product policy.  The GEMM kernels below (k_lin, k_linr, k_wgrad, k_pack_split) are templates over the math mode MM and never
+// look at it themselves: Prod<MM> is the only place that knows how a mode represents an operand and multiplies two of them.
+//   Op                 the operand of one 16-deep k-step (8 values per lane), in the mode's representation
+//   FRAG_BYTES         bytes of one packed weight fragment: 1 KiB lane-linear pieces, one per bf16 part (two for fp32)
+//   elem / put         one float -> the mode's parts of it; such an element -> position j of an Op
+//   split              a whole fp32 fragment -> Op (elem + put eight times; the identity for fp32)
+//   store_w            an element -> the packed fragment in memory (k_pack_split; fp32 fragments are written by k_pack)
+//   load_w / load_w_lds  the packed fragment from the global stream / from an LDS ring slot
+//   shift<DIR>         lane_shift1 on every piece: the operand of the neighbouring token
+//   mul(w, x, acc)     acc += w x; the order of the MFMAs is pinned by the gradient fixtures
+//   keep               empty asm over every piece: pins the compiler's wait for the operand's loads where it stands (k_linr)
+// All members are forced inline; the mode is a template argument everywhere, never a runtime value.
+// ------------------------------------------------------------------------------------------
+// One token to the left / right inside a wave's 32-token row (lanes 0-31 and 32-63 hold the two k-halves of the same tokens):
+// DIR = +1: lane r takes lane r + 1 (v_mov_dpp wave_shl:1), DIR = -1: lane r - 1 (wave_shr:1); the row's first / last token takes 0
+// (the lane the shift would pull across the two halves, or from outside the wave).
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+template <int DIR> LFT_DEV u32x4_t lane_shift1_u(u32x4_t u, bool edge) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int s = __builtin_amdgcn_update_dpp(0, (int)u[i], DIR > 0 ? 0x130 : 0x138, 0xf, 0xf, true);
+        u[i] = edge ? 0u : (unsigned)s;
+    }
+    return u;
+}
+template <int DIR> LFT_DEV bf16x8 lane_shift1(bf16x8 v, bool edge) { return __builtin_bit_cast(bf16x8, lane_shift1_u<DIR>(__builtin_bit_cast(u32x4_t, v), edge)); }
+template <int DIR> LFT_DEV f32x4 lane_shift1(f32x4 v, bool edge) { return __builtin_bit_cast(f32x4, lane_shift1_u<DIR>(__builtin_bit_cast(u32x4_t, v), edge)); }
+LFT_DEV bf16x8 load_piece(const char* p) { return __builtin_bit_cast(bf16x8, load_raw16(p)); }
+
+template <int MM> struct Prod;          // MM: 0 exact fp32 MFMA, 1 split-bf16 (3 products), 2 bf16x6 (6 products, fp32-class)
+// P::split for the split modes: every value of the fragment through the element pair
+template <typename P> LFT_DEV typename P::Op split_elems(const Frag<float>& f) {
+    typename P::Op r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) P::put(r, j, P::elem(j < 4 ? f.lo[j] : f.hi[j - 4]));
+    return r;
+}
+
+// Exact fp32 (LFT_MATH_F32): v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak.  The operand is the fp32 fragment itself.
+template <> struct Prod<0> {
+    using Op = Frag<float>;
+    using Elem = float;
+    static constexpr int FRAG_BYTES = 2048;
+    LFT_DEV Elem elem(float x) { return x; }
+    LFT_DEV void put(Op& o, int j, Elem e) { if (j < 4) o.lo[j] = e; else o.hi[j - 4] = e; }
+    LFT_DEV const Op& split(const Frag<float>& f) { return f; }        // by reference: no copy of the operand is made
+    LFT_DEV Op load_w_lds(const char* base) {
+        Op r;
+        r.lo = __builtin_bit_cast(f32x4, load_raw16(base));
+        r.hi = __builtin_bit_cast(f32x4, load_raw16(base + 1024));
+        return r;
+    }
+    LFT_DEV Op load_w(const float* __restrict__ stream, int f, int lane) { return load_wfrag(stream, f, lane); }
+    template <int DIR> LFT_DEV Op shift(const Op& x, bool edge) {
+        Op r;
+        r.lo = lane_shift1<DIR>(x.lo, edge); r.hi = lane_shift1<DIR>(x.hi, edge);
+        return r;
+    }
+    LFT_DEV void mul(const Op& w, const Op& x, f32x16& acc) { mma(w, x, acc); }
+    LFT_DEV void keep(const Op& x) { asm volatile("" :: "v"(x.lo), "v"(x.hi)); }
+};
+
+// Split-bf16 products ("bf16x3", LFT_MATH_BF16X3).  The fp32 MFMA is 16x slower than the bf16 one, so an fp32 operand x is split
+// into two bf16 numbers x = hi + lo (+ O(2^-17 x)) and a product is
 //   a * b ~= ah*bh + ah*bl + al*bh            (3 MFMAs, fp32 accumulate; the dropped al*bl is O(2^-18 a b))
 // i.e. fp32 operands with ~2^-16 relative error per product at 3/16 of the fp32-MFMA cost.
 // Packed weights in this mode: fragment f = [1 KiB hi piece][1 KiB lo piece] (same 2 KiB as an fp32 fragment).
-// ------------------------------------------------------------------------------------------
 struct Frag2 { Frag<bf16_t> hi, lo; };
-LFT_DEV Frag2 split_frag(const Frag<float>& f) {
-    Frag2 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = j < 4 ? f.lo[j] : f.hi[j - 4];
-        const bf16_t h = (bf16_t)x;
-        r.hi.v[j] = h;
-        r.lo.v[j] = (bf16_t)(x - (float)h);
+template <> struct Prod<1> {
+    using Op = Frag2;
+    struct Elem { bf16_t hi, lo; };
+    static constexpr int FRAG_BYTES = 2048;
+    LFT_DEV Elem elem(float x) {
+        Elem e;
+        e.hi = (bf16_t)x;
+        e.lo = (bf16_t)(x - (float)e.hi);
+        return e;
     }
-    return r;
-}
-LFT_DEV void mma3(const Frag2& a, const Frag2& b, f32x16& c) {
-    mma(a.lo, b.hi, c);
-    mma(a.hi, b.lo, c);
-    mma(a.hi, b.hi, c);
-}
-// "bf16x6" (round 4): an fp32 number IS the sum of three bf16 numbers, x = a + b + c exactly (8 + 8 + 8 significant bits; each
-// remainder is exact in fp32), so a product is the sum of nine bf16 products of which the three smallest (b c', c b', c c':
+    LFT_DEV void put(Op& o, int j, const Elem& e) { o.hi.v[j] = e.hi; o.lo.v[j] = e.lo; }
+    LFT_DEV Op split(const Frag<float>& f) { return split_elems<Prod>(f); }
+    LFT_DEV void store_w(bf16_t* frag, int i, const Elem& e) { frag[i] = e.hi; frag[512 + i] = e.lo; }   // i = 8 lane + j
+    LFT_DEV Op load_w_lds(const char* base) {
+        Op r;
+        r.hi.v = load_piece(base); r.lo.v = load_piece(base + 1024);
+        return r;
+    }
+    LFT_DEV Op load_w(const float* __restrict__ stream, int f, int lane) {
+        return load_w_lds(reinterpret_cast<const char*>(stream) + (size_t)f * FRAG_BYTES + lane * 16);
+    }
+    template <int DIR> LFT_DEV Op shift(const Op& x, bool edge) {
+        Op r;
+        r.hi.v = lane_shift1<DIR>(x.hi.v, edge); r.lo.v = lane_shift1<DIR>(x.lo.v, edge);
+        return r;
+    }
+    LFT_DEV void mul(const Op& w, const Op& x, f32x16& acc) {
+        mma(w.lo, x.hi, acc);
+        mma(w.hi, x.lo, acc);
+        mma(w.hi, x.hi, acc);
+    }
+    LFT_DEV void keep(const Op& x) { asm volatile("" :: "v"(x.hi.v), "v"(x.lo.v)); }
+};
+
+// "bf16x6" (LFT_MATH_BF16X6): an fp32 number IS the sum of three bf16 numbers, x = a + b + c exactly (8 + 8 + 8 significant bits;
+// each remainder is exact in fp32), so a product is the sum of nine bf16 products of which the three smallest (b c', c b', c c':
 // <= 2^-23 |x y| together) are dropped:
 //   x * y ~= a a' + (a b' + b a') + (a c' + c a' + b b')        6 MFMAs, fp32 accumulate, smallest terms first
-// -- fp32-class products (the fp32 MFMA rounds its product to 2^-24) at 6/16 of the fp32-MFMA cost.  Used by the weight-gradient
-// kernel, whose operands are activations split in registers (no packed weights, no layout change).
+// -- fp32-class products (the fp32 MFMA rounds its product to 2^-24) at 6/16 of the fp32-MFMA cost.
+// Packed weights in this mode: fragment f = [1 KiB a][1 KiB b][1 KiB c] (3 KiB; the fp32 and split-bf16 fragments are 2 KiB).
 struct Frag3 { Frag<bf16_t> a, b, c; };
-LFT_DEV void split3(float x, bf16_t& a, bf16_t& b, bf16_t& c) {
-    a = (bf16_t)x;
-    const float r1 = x - (float)a;
-    b = (bf16_t)r1;
-    c = (bf16_t)(r1 - (float)b);
-}
-LFT_DEV Frag3 split3_frag(const Frag<float>& f) {
-    Frag3 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        bf16_t a, b, c;
-        split3(j < 4 ? f.lo[j] : f.hi[j - 4], a, b, c);
-        r.a.v[j] = a; r.b.v[j] = b; r.c.v[j] = c;
+template <> struct Prod<2> {
+    using Op = Frag3;
+    struct Elem { bf16_t a, b, c; };
+    static constexpr int FRAG_BYTES = 3072;
+    LFT_DEV Elem elem(float x) {
+        Elem e;
+        e.a = (bf16_t)x;
+        const float r1 = x - (float)e.a;
+        e.b = (bf16_t)r1;
+        e.c = (bf16_t)(r1 - (float)e.b);
+        return e;
     }
-    return r;
-}
-LFT_DEV void mma6(const Frag3& x, const Frag3& y, f32x16& c) {
-    mma(x.c, y.a, c);
-    mma(x.a, y.c, c);
-    mma(x.b, y.b, c);
-    mma(x.b, y.a, c);
-    mma(x.a, y.b, c);
-    mma(x.a, y.a, c);
-}
-LFT_DEV Frag2 load_wfrag2(const float* __restrict__ stream, int f, int lane) {
-    const char* base = reinterpret_cast<const char*>(stream) + (size_t)f * 2048 + lane * 16;
-    Frag2 r;
-    r.hi.v = __builtin_bit_cast(bf16x8, load_raw16(base));
-    r.lo.v = __builtin_bit_cast(bf16x8, load_raw16(base + 1024));
-    return r;
-}
-// bf16x6: packed weight fragment f = [1 KiB a][1 KiB b][1 KiB c] (3 KiB; the fp32 and split-bf16 fragments are 2 KiB)
-constexpr int kFragBytes2 = 2048, kFragBytes3 = 3072;
-LFT_DEV Frag3 load_wfrag3(const float* __restrict__ stream, int f, int lane) {
-    const char* base = reinterpret_cast<const char*>(stream) + (size_t)f * kFragBytes3 + lane * 16;
-    Frag3 r;
-    r.a.v = __builtin_bit_cast(bf16x8, load_raw16(base));
-    r.b.v = __builtin_bit_cast(bf16x8, load_raw16(base + 1024));
-    r.c.v = __builtin_bit_cast(bf16x8, load_raw16(base + 2048));
-    return r;
-}
-// k_pack's twin for the split modes: same PackOp description (natural k order), writes hi / lo pieces (THREE = false) or the
-// three exact bf16 parts a / b / c (THREE = true, 3 KiB per fragment).
-template <bool THREE>
+    LFT_DEV void put(Op& o, int j, const Elem& e) { o.a.v[j] = e.a; o.b.v[j] = e.b; o.c.v[j] = e.c; }
+    LFT_DEV Op split(const Frag<float>& f) { return split_elems<Prod>(f); }
+    LFT_DEV void store_w(bf16_t* frag, int i, const Elem& e) { frag[i] = e.a; frag[512 + i] = e.b; frag[1024 + i] = e.c; }
+    LFT_DEV Op load_w_lds(const char* base) {
+        Op r;
+        r.a.v = load_piece(base); r.b.v = load_piece(base + 1024); r.c.v = load_piece(base + 2048);
+        return r;
+    }
+    LFT_DEV Op load_w(const float* __restrict__ stream, int f, int lane) {
+        return load_w_lds(reinterpret_cast<const char*>(stream) + (size_t)f * FRAG_BYTES + lane * 16);
+    }
+    template <int DIR> LFT_DEV Op shift(const Op& x, bool edge) {
+        Op r;
+        r.a.v = lane_shift1<DIR>(x.a.v, edge); r.b.v = lane_shift1<DIR>(x.b.v, edge); r.c.v = lane_shift1<DIR>(x.c.v, edge);
+        return r;
+    }
+    LFT_DEV void mul(const Op& w, const Op& x, f32x16& acc) {
+        mma(w.c, x.a, acc);
+        mma(w.a, x.c, acc);
+        mma(w.b, x.b, acc);
+        mma(w.b, x.a, acc);
+        mma(w.a, x.b, acc);
+        mma(w.a, x.a, acc);
+    }
+    LFT_DEV void keep(const Op& x) { asm volatile("" :: "v"(x.a.v), "v"(x.b.v), "v"(x.c.v)); }
+};
+
+// k_pack's twin for the split modes (MM = 1, 2): same PackOp description (natural k order), every value written as the mode's parts.
+template <int MM>
 __global__ __launch_bounds__(64) void k_pack_split(PackArgs args, float* __restrict__ dst) {
+    using P = Prod<MM>;
     const int f = blockIdx.x, lane = threadIdx.x, r = lane & 31, h = lane >> 5;
     int oi = 0;
     for (int i = 0; i < args.nops; ++i)
@@ -98,7 +179,7 @@ __global__ __launch_bounds__(64) void k_pack_split(PackArgs args, float* __restr
     int nt, ks;
     wfrag_coords(op.ntiles, op.ksteps, f - op.frag0, op.order, nt, ks);
     const int n = 32 * nt + r;
-    bf16_t* d = reinterpret_cast<bf16_t*>(dst) + (size_t)f * (THREE ? 1536 : 1024);   // 2 KiB = 1024 bf16 (3 KiB = 1536) per fragment
+    bf16_t* d = reinterpret_cast<bf16_t*>(dst) + (size_t)f * (P::FRAG_BYTES / 2);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int kk = op.k0 + 16 * ks + 8 * h + j;
@@ -108,16 +189,30 @@ __global__ __launch_bounds__(64) void k_pack_split(PackArgs args, float* __restr
             else if (op.kind == 1) v = upm_entry(op.src, n, kk, op.s);
             else v = kk < (op.s + 2) * (op.s + 2) ? upm_entry(op.src, kk, n, op.s) : 0.0f;
         }
-        if constexpr (THREE) {
-            bf16_t a, b, c;
-            split3(v, a, b, c);
-            d[lane * 8 + j] = a; d[512 + lane * 8 + j] = b; d[1024 + lane * 8 + j] = c;
-        } else {
-            const bf16_t hi = (bf16_t)v;
-            d[lane * 8 + j] = hi;
-            d[512 + lane * 8 + j] = (bf16_t)(v - (float)hi);
-        }
+        P::store_w(d, lane * 8 + j, P::elem(v));
     }
+}
+
+// Test-only (lft_prod_selftest): the policy in isolation, one wave.  Wp = one packed fragment of W [32][16] (k_pack / k_pack_split),
+// X [32 tokens][16]; Y [token][o] = X W^T, Yr / Yl the same product with the operand of the token to the right / left (zero at the edge).
+template <int MM>
+__global__ __launch_bounds__(64) void k_prod_selftest(const float* __restrict__ Wp, const float* __restrict__ X,
+                                                      float* __restrict__ Y, float* __restrict__ Yl, float* __restrict__ Yr) {
+    using P = Prod<MM>;
+    const int lane = threadIdx.x, r = lane & 31, kh = lane >> 5;
+    const Frag<float> xf = load_row8(X + r * 16 + 8 * kh, true, 0.0f);
+    const auto& x = P::split(xf);
+    const typename P::Op w = P::load_w(Wp, 0, lane), xr = P::template shift<1>(x, r == 31), xl = P::template shift<-1>(x, r == 0);
+    f32x16 acc[3];
+    zero_acc<3>(acc);
+    P::mul(w, x, acc[0]);
+    P::mul(w, xl, acc[1]);
+    P::mul(w, xr, acc[2]);
+    float* const out[3] = {Y, Yl, Yr};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) out[k][r * 32 + acc_row(i, kh)] = acc[k][i];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -143,9 +238,9 @@ struct LinP {
 // TILED (plain Linears at small batch): the 32 input rows of a wave, consecutive in memory, are fetched in coalesced
 // 64-channel chunks through the scratch instead of one 32-byte piece per lane and k-step -- fewer, fuller memory
 // requests when there are too few waves to hide latency; at large batch the direct form's higher occupancy wins.
-template <int NT, int MM, bool TILED>      // MM: 0 exact fp32 MFMA, 1 split-bf16 (3 products), 2 bf16x6 (6 products, fp32-class)
+template <int NT, int MM, bool TILED>      // MM: the math mode, see Prod
 __global__ __launch_bounds__(256, 3) void k_lin(const LinP p) {
-    constexpr bool M3 = MM == 1;
+    using P = Prod<MM>;
     constexpr int SCR = TileIO<(NT > 2 ? NT : 2), float>::BYTES;          // output tile or a 64-channel input chunk
     __shared__ __attribute__((aligned(16))) char scr_all[4 * SCR];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, kh = lane >> 5;
@@ -167,18 +262,9 @@ __global__ __launch_bounds__(256, 3) void k_lin(const LinP p) {
             load_tile_frags_s<4, float>(p.X + t0 * p.ldx + 16 * k0, (size_t)p.ldx * 4, nvalid, lane, b, scr);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                if constexpr (MM == 2) {
-                    const Frag3 b3 = split3_frag(b[ks]);
+                const auto& x = P::split(b[ks]);
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) mma6(load_wfrag3(p.Wp, wfrag_index(p.OT, p.KS, ot0 + nt, k0 + ks), lane), b3, acc[nt]);
-                } else if constexpr (M3) {
-                    const Frag2 b2 = split_frag(b[ks]);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) mma3(load_wfrag2(p.Wp, wfrag_index(p.OT, p.KS, ot0 + nt, k0 + ks), lane), b2, acc[nt]);
-                } else {
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) mma(load_wfrag(p.Wp, wfrag_index(p.OT, p.KS, ot0 + nt, k0 + ks), lane), b[ks], acc[nt]);
-                }
+                for (int nt = 0; nt < NT; ++nt) P::mul(P::load_w(p.Wp, wfrag_index(p.OT, p.KS, ot0 + nt, k0 + ks), lane), x, acc[nt]);
             }
         }
     } else
@@ -190,20 +276,14 @@ __global__ __launch_bounds__(256, 3) void k_lin(const LinP p) {
         const int fbase = tap * p.OT * p.KS;
         for (int ks = 0; ks < p.KS; ++ks) {
             const Frag<float> b = load_row8(row + 16 * ks, ok, 0.0f);
-            if constexpr (MM == 2) {
-                const Frag3 b3 = split3_frag(b);
+            const auto& x = P::split(b);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) mma6(load_wfrag3(p.Wp, fbase + wfrag_index(p.OT, p.KS, ot0 + nt, ks), lane), b3, acc[nt]);
-            } else if constexpr (M3) {
-                const Frag2 b2 = split_frag(b);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) mma3(load_wfrag2(p.Wp, fbase + wfrag_index(p.OT, p.KS, ot0 + nt, ks), lane), b2, acc[nt]);
-            } else {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) mma(load_wfrag(p.Wp, fbase + wfrag_index(p.OT, p.KS, ot0 + nt, ks), lane), b, acc[nt]);
-            }
+            for (int nt = 0; nt < NT; ++nt) P::mul(P::load_w(p.Wp, fbase + wfrag_index(p.OT, p.KS, ot0 + nt, ks), lane), x, acc[nt]);
         }
     }
+    // The epilogue (activation, derivative mask, output tile) is the same in k_lin and k_linr and is written out in both: as a
+    // shared inlined helper its blocks land in front of the main loop in the function's layout and hipcc allocates differently
+    // (VGPR counts moved in 21 of the 33 instantiations, the 3x3 row kernels gained up to 93 register moves).
     if (p.act) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -241,30 +321,21 @@ __global__ __launch_bounds__(256, 3) void k_lin(const LinP p) {
 // and after the last k-step (activation-derivative tile, output tile); slot 2 is first written by the DMA behind barrier 0.
 // Requires: the call's output block is one packed group (NT == its tile count, first tile a multiple of 4); taps == 9: OT == NT.
 // ------------------------------------------------------------------------------------------
-// One token to the left / right inside a wave's 32-token row (lanes 0-31 and 32-63 hold the two k-halves of the same tokens):
-// DIR = +1: lane r takes lane r + 1 (v_mov_dpp wave_shl:1), DIR = -1: lane r - 1 (wave_shr:1); the row's first / last token takes 0
-// (the lane the shift would pull across the two halves, or from outside the wave).
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-template <int DIR> LFT_DEV u32x4_t lane_shift1_u(u32x4_t u, bool edge) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int s = __builtin_amdgcn_update_dpp(0, (int)u[i], DIR > 0 ? 0x130 : 0x138, 0xf, 0xf, true);
-        u[i] = edge ? 0u : (unsigned)s;
-    }
-    return u;
-}
-template <int DIR> LFT_DEV bf16x8 lane_shift1(bf16x8 v, bool edge) { return __builtin_bit_cast(bf16x8, lane_shift1_u<DIR>(__builtin_bit_cast(u32x4_t, v), edge)); }
-template <int DIR> LFT_DEV f32x4 lane_shift1(f32x4 v, bool edge) { return __builtin_bit_cast(f32x4, lane_shift1_u<DIR>(__builtin_bit_cast(u32x4_t, v), edge)); }
-
 // KS3 > 0 (= KS, 4 or 8): a per-view 3x3 convolution on 32-wide views, where a wave's 32 tokens are ONE image row.  The KS row
 // fragments of an input row (dy) are loaded ONCE and serve its three taps: the neighbours to the left and right are the same
-// registers one lane over (lane_shift1), the image's left / right border is the shift's zero.  Input rows come from L2 three
+// registers one lane over (Prod::shift), the image's left / right border is the shift's zero.  Input rows come from L2 three
 // times instead of nine and the split into bf16 pairs is done once per row fragment instead of once per tap -- in the SAME step
 // order (tap row, tap column, k-step) and with the same operand values as the generic form, so the results are bit-identical.
+// acc += (the NT packed fragments of one published chunk of k_linr's LDS ring; base = the chunk's slot + this lane's 16 bytes) x
+template <typename P, int NT>
+LFT_DEV void mul_chunk(const char* base, const typename P::Op& x, f32x16 (&acc)[NT]) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) P::mul(P::load_w_lds(base + nt * P::FRAG_BYTES), x, acc[nt]);
+}
 template <int NT, int MM, int KS3 = 0>     // MM as k_lin
 __global__ __launch_bounds__(256, 3) void k_linr(const LinP p) {
-    constexpr bool M3 = MM == 1;
-    constexpr int FB = MM == 2 ? kFragBytes3 : kFragBytes2;               // bytes per packed fragment
+    using P = Prod<MM>;
+    constexpr int FB = P::FRAG_BYTES;                                     // bytes per packed fragment
     constexpr int CHUNK = NT * FB, NPIECE = CHUNK / 1024;                 // bytes / 1 KiB pieces of weights per k-step
     // pieces per wave and chunk: NPIECE / 4, except bf16x6 with two output tiles (6 pieces): waves 0, 1 move two, waves 2, 3 one
     constexpr bool EVEN = NPIECE % 4 == 0;
@@ -316,14 +387,9 @@ __global__ __launch_bounds__(256, 3) void k_linr(const LinP p) {
             Frag<float> xr[KS3];
 #pragma unroll
             for (int ks = 0; ks < KS3; ++ks) xr[ks] = load_row8(row + 16 * ks, true, 0.0f);
-            Frag<float> xf[MM == 0 ? KS3 : 1];
-            Frag2 x2[M3 ? KS3 : 1];
-            Frag3 x3[MM == 2 ? KS3 : 1];
+            typename P::Op xs[KS3];
 #pragma unroll
-            for (int ks = 0; ks < KS3; ++ks) {
-                const Frag<float> z = okr ? xr[ks] : frag_zero(0.0f);
-                if constexpr (MM == 2) x3[ks] = split3_frag(z); else if constexpr (M3) x2[ks] = split_frag(z); else xf[ks] = z;
-            }
+            for (int ks = 0; ks < KS3; ++ks) xs[ks] = P::split(okr ? xr[ks] : frag_zero(0.0f));
             for (int dxi = 0; dxi < 3; ++dxi) {
                 const int dx = p.flip ? 1 - dxi : dxi - 1;               // uniform
 #pragma unroll
@@ -333,43 +399,8 @@ __global__ __launch_bounds__(256, 3) void k_linr(const LinP p) {
                     wait_vmcnt(cs + 1 < S ? my_count : 0);
                     wg_barrier_keep_vm();
                     issue_w(cs + 2, slot == 0 ? 2 : slot - 1);
-                    const char* base = lds + slot * CHUNK + lane * 16;
-                    Frag2 b2;
-                    Frag3 b3;
-                    Frag<float> b;
-                    if constexpr (MM == 2) {
-                        b3 = x3[ks];
-                        if (dx > 0) { b3.a.v = lane_shift1<1>(x3[ks].a.v, e_hi); b3.b.v = lane_shift1<1>(x3[ks].b.v, e_hi); b3.c.v = lane_shift1<1>(x3[ks].c.v, e_hi); }
-                        else if (dx < 0) { b3.a.v = lane_shift1<-1>(x3[ks].a.v, e_lo); b3.b.v = lane_shift1<-1>(x3[ks].b.v, e_lo); b3.c.v = lane_shift1<-1>(x3[ks].c.v, e_lo); }
-                    } else if constexpr (M3) {
-                        b2 = x2[ks];
-                        if (dx > 0) { b2.hi.v = lane_shift1<1>(x2[ks].hi.v, e_hi); b2.lo.v = lane_shift1<1>(x2[ks].lo.v, e_hi); }
-                        else if (dx < 0) { b2.hi.v = lane_shift1<-1>(x2[ks].hi.v, e_lo); b2.lo.v = lane_shift1<-1>(x2[ks].lo.v, e_lo); }
-                    } else {
-                        b = xf[ks];
-                        if (dx > 0) { b.lo = lane_shift1<1>(xf[ks].lo, e_hi); b.hi = lane_shift1<1>(xf[ks].hi, e_hi); }
-                        else if (dx < 0) { b.lo = lane_shift1<-1>(xf[ks].lo, e_lo); b.hi = lane_shift1<-1>(xf[ks].hi, e_lo); }
-                    }
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        if constexpr (MM == 2) {
-                            Frag3 w3;
-                            w3.a.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * FB));
-                            w3.b.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * FB + 1024));
-                            w3.c.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * FB + 2048));
-                            mma6(w3, b3, acc[nt]);
-                        } else if constexpr (M3) {
-                            Frag2 w2;
-                            w2.hi.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * 2048));
-                            w2.lo.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * 2048 + 1024));
-                            mma3(w2, b2, acc[nt]);
-                        } else {
-                            Frag<float> wf;
-                            wf.lo = __builtin_bit_cast(f32x4, load_raw16(base + nt * 2048));
-                            wf.hi = __builtin_bit_cast(f32x4, load_raw16(base + nt * 2048 + 1024));
-                            mma(wf, b, acc[nt]);
-                        }
-                    }
+                    const typename P::Op b = dx > 0 ? P::template shift<1>(xs[ks], e_hi) : dx < 0 ? P::template shift<-1>(xs[ks], e_lo) : xs[ks];
+                    mul_chunk<P>(lds + slot * CHUNK + lane * 16, b, acc);
                     ++cs;
                     slot = slot == 2 ? 0 : slot + 1;
                 }
@@ -388,41 +419,12 @@ __global__ __launch_bounds__(256, 3) void k_linr(const LinP p) {
     };
     int cs = 0, slot = 0;                                                // current k-step and its ring slot
     auto step = [&](const Frag<float>& xraw, bool ok) {
-        const Frag<float> xs = ok ? xraw : frag_zero(0.0f);
-        Frag2 b2;
-        Frag3 b3;
-        if constexpr (MM == 2) {
-            b3 = split3_frag(xs);
-            asm volatile("" :: "v"(b3.a.v), "v"(b3.b.v), "v"(b3.c.v));
-        } else if constexpr (M3) {
-            b2 = split_frag(xs);                                         // (the compiler's wait for the rows sits here, in front of the barrier)
-            asm volatile("" :: "v"(b2.hi.v), "v"(b2.lo.v));
-        } else {
-            asm volatile("" :: "v"(xs.lo), "v"(xs.hi));
-        }
+        const Frag<float> xz = ok ? xraw : frag_zero(0.0f);
+        const auto& xs = P::split(xz);
+        P::keep(xs);                                                     // (the compiler's wait for the rows sits here, in front of the barrier)
         wg_barrier_keep_vm();                                            // chunk cs published by every wave, chunk cs - 1 retired
         issue_w(cs + 2, slot == 0 ? 2 : slot - 1);                       // into the slot chunk cs - 1 vacated
-        const char* base = lds + slot * CHUNK + lane * 16;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            if constexpr (MM == 2) {
-                Frag3 w3;
-                w3.a.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * FB));
-                w3.b.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * FB + 1024));
-                w3.c.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * FB + 2048));
-                mma6(w3, b3, acc[nt]);
-            } else if constexpr (M3) {
-                Frag2 w2;
-                w2.hi.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * 2048));
-                w2.lo.v = __builtin_bit_cast(bf16x8, load_raw16(base + nt * 2048 + 1024));
-                mma3(w2, b2, acc[nt]);
-            } else {
-                Frag<float> wf;
-                wf.lo = __builtin_bit_cast(f32x4, load_raw16(base + nt * 2048));
-                wf.hi = __builtin_bit_cast(f32x4, load_raw16(base + nt * 2048 + 1024));
-                mma(wf, xs, acc[nt]);
-            }
-        }
+        mul_chunk<P>(lds + slot * CHUNK + lane * 16, xs, acc);
         ++cs;
         slot = slot == 2 ? 0 : slot + 1;
     };
@@ -445,9 +447,9 @@ __global__ __launch_bounds__(256, 3) void k_linr(const LinP p) {
                 acc[nt][i] = v > 0.0f ? v : (p.act == 1 ? 0.0f : 0.2f * v);
             }
     }
-    if (p.M) {
+    if (p.M) {                                                           // dZ = dY * act'(Z), sign(Z) read off the saved act(Z)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
+        for (int nt = 0; nt < NT; ++nt) {                                // one 32-channel tile at a time: 16 live registers, not 16 NT
             f32x16 mk[1];
             load_tile<1, float>(p.M + t0 * p.ldm + o0 + 32 * nt, nvalid, lane, mk, scr, (size_t)p.ldm * 4);
 #pragma unroll
@@ -480,9 +482,9 @@ struct WgP {
 // split) once for three products and the three shifted X rows are neighbours in memory.
 // The 4 waves of a workgroup split the chunk's tokens and add their accumulators through LDS, in a fixed order:
 // one partial image per workgroup (a quarter of the partial-sum traffic for the same number of waves in flight).
-template <int NI, int MM, int TX>      // MM: 0 exact fp32 MFMA, 1 split-bf16 (3 products), 2 bf16x6 (6 products, fp32-class)
+template <int NI, int MM, int TX>      // MM: the math mode, see Prod
 __global__ __launch_bounds__(256, TX == 3 ? 2 : 3) void k_wgrad(const WgP p) {
-    constexpr bool M3 = MM == 1;
+    using P = Prod<MM>;
     extern __shared__ __attribute__((aligned(16))) float wred[];        // [3 waves][TX * NI tiles][16][64]
     const int lane = threadIdx.x & 63, r = lane & 31, kh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -517,9 +519,9 @@ __global__ __launch_bounds__(256, TX == 3 ? 2 : 3) void k_wgrad(const WgP p) {
     if constexpr (TX == 3) { const int pix = (int)((ta + 8 * kh) % hw); ys = pix / p.w; xs = pix - ys * p.w; }
     // 3x3 on 32-wide views: a 16-token step lies in one half of ONE image row, every step is full (N, the chunk and the wave's
     // share are multiples of 16).  A lane's three tap fragments X[t + j - 1], X[t + j], X[t + j + 1] (j = 0..7) are ten values:
-    // eight centre ones, a left and a right neighbour -- 10 loads instead of 24, and in split mode each value is split ONCE and
-    // the three fragments are two packings of the same bf16 pairs (even pairs (c0,c1).. for the centre tap, odd pairs
-    // (L,c0),(c1,c2)..,(c7,R) for the other two).  Same values, same MFMA order as the general form below: bit-identical.
+    // eight centre ones, a left and a right neighbour -- 10 loads instead of 24, each value is split ONCE into the mode's element
+    // (Prod::elem) and the three fragments are gathered from the ten elements (in the bf16 modes: two packings of the same bf16
+    // pairs, even pairs (c0,c1).. for the centre tap, odd pairs (L,c0),(c1,c2)..,(c7,R) for the other two).  Same values, same MFMA order as the general form below: bit-identical.
     bool fast3 = false;
     if constexpr (TX == 3) fast3 = p.w == 32 && nsub % 16 == 0 && ta % 16 == 0;
     if (fast3) {
@@ -546,49 +548,21 @@ __global__ __launch_bounds__(256, TX == 3 ? 2 : 3) void k_wgrad(const WgP p) {
                 vy += 16u * p.ldy * 4u; vx += 16u * p.ldx * 4u;
                 xb += 16;
                 if (xb == 32) { xb = 0; if (++yw == p.h) yw = 0; }
-                if constexpr (MM == 2) {
-                    const Frag3 a3 = split3_frag(a);
-                    bf16_t sa[NI][10], sb[NI][10], sc[NI][10];
+                const auto& a_op = P::split(a);
+                typename P::Elem el[NI][10];
 #pragma unroll
-                    for (int ni = 0; ni < NI; ++ni)
+                for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-                        for (int e = 0; e < 10; ++e) split3(v[ni][e], sa[ni][e], sb[ni][e], sc[ni][e]);
+                    for (int e = 0; e < 10; ++e) el[ni][e] = P::elem(v[ni][e]);
 #pragma unroll
-                    for (int tx = 0; tx < 3; ++tx)
+                for (int tx = 0; tx < 3; ++tx)
 #pragma unroll
-                        for (int ni = 0; ni < NI; ++ni) {
-                            Frag3 b3;
+                    for (int ni = 0; ni < NI; ++ni) {
+                        typename P::Op b;
 #pragma unroll
-                            for (int j = 0; j < 8; ++j) { b3.a.v[j] = sa[ni][j + tx]; b3.b.v[j] = sb[ni][j + tx]; b3.c.v[j] = sc[ni][j + tx]; }
-                            mma6(a3, b3, acc[tx][ni]);
-                        }
-                } else if constexpr (M3) {
-                    const Frag2 a2 = split_frag(a);
-                    bf16_t hi[NI][10], lo[NI][10];
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                        for (int e = 0; e < 10; ++e) { hi[ni][e] = (bf16_t)v[ni][e]; lo[ni][e] = (bf16_t)(v[ni][e] - (float)hi[ni][e]); }
-#pragma unroll
-                    for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-                        for (int ni = 0; ni < NI; ++ni) {
-                            Frag2 b2;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) { b2.hi.v[j] = hi[ni][j + tx]; b2.lo.v[j] = lo[ni][j + tx]; }
-                            mma3(a2, b2, acc[tx][ni]);
-                        }
-                } else {
-#pragma unroll
-                    for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-                        for (int ni = 0; ni < NI; ++ni) {
-                            Frag<float> b;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) { if (j < 4) b.lo[j] = v[ni][j + tx]; else b.hi[j - 4] = v[ni][j + tx]; }
-                            mma(a, b, acc[tx][ni]);
-                        }
-                }
+                        for (int j = 0; j < 8; ++j) P::put(b, j, el[ni][j + tx]);
+                        P::mul(a_op, b, acc[tx][ni]);
+                    }
             }
         }
     } else
@@ -620,24 +594,11 @@ __global__ __launch_bounds__(256, TX == 3 ? 2 : 3) void k_wgrad(const WgP p) {
             xs += 16;
             while (xs >= p.w) { xs -= p.w; if (++ys == p.h) ys = 0; }
         }
-        if constexpr (MM == 2) {
-            const Frag3 a3 = split3_frag(a);
+        const auto& a_op = P::split(a);
 #pragma unroll
-            for (int tx = 0; tx < TX; ++tx)
+        for (int tx = 0; tx < TX; ++tx)
 #pragma unroll
-                for (int ni = 0; ni < NI; ++ni) mma6(a3, split3_frag(b[tx][ni]), acc[tx][ni]);
-        } else if constexpr (M3) {
-            const Frag2 a2 = split_frag(a);
-#pragma unroll
-            for (int tx = 0; tx < TX; ++tx)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) mma3(a2, split_frag(b[tx][ni]), acc[tx][ni]);
-        } else {
-#pragma unroll
-            for (int tx = 0; tx < TX; ++tx)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) mma(a, b[tx][ni], acc[tx][ni]);
-        }
+            for (int ni = 0; ni < NI; ++ni) P::mul(a_op, P::split(b[tx][ni]), acc[tx][ni]);
     }
     if (wave) {
 #pragma unroll

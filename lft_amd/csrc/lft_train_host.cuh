@@ -99,11 +99,16 @@ WViews build_views(const float* const* P, int s, std::vector<PackOp>* ops) {
     return W;
 }
 
+// The template mode of the GEMM kernels (Prod<MM>) for a LFT_MATH_* value (validated at the C ABI), and the floats one packed
+// weight fragment takes in it.
+inline int math_mode(int math) { return math == LFT_MATH_BF16X3 ? 1 : math == LFT_MATH_BF16X6 ? 2 : 0; }
+inline size_t frag_floats(int mm) { return (mm == 2 ? Prod<2>::FRAG_BYTES : mm == 1 ? Prod<1>::FRAG_BYTES : Prod<0>::FRAG_BYTES) / sizeof(float); }
+
 // ---- tape: everything the backward pass re-reads (floats, offsets in floats) ----
 struct AngTape { size_t n, qk, v, o, t1, m, hdn, y; };
 struct SpaTape { size_t petok, tok, n, qk, v, o, t1, m, hdn, t2, y; };      // qk = [N][256]: Q | K
 struct TrainLayout {
-    size_t wp;                                   // packed weight views (build_views order), 512 floats per fragment
+    size_t wp;                                   // packed weight views (build_views order), frag_floats(mode) per fragment
     size_t pe_ang, pe_spa, x0, c1, c2, c3, feat;
     AngTape ang[kLayers];
     SpaTape spa[kLayers];
@@ -126,7 +131,7 @@ TrainLayout train_layout(const Dims& d) {
     size_t o = 0;
     auto take = [&](size_t floats) { size_t r = o; o += (floats + 63) & ~(size_t)63; return r; };
     const size_t n = (size_t)d.ntok, ss = (size_t)d.s * d.s;
-    T.wp = take(build_views(nullptr, d.s, nullptr).nfrags * 768);     // 3 KiB per fragment in the bf16x6 mode (2 KiB in the others)
+    T.wp = take(build_views(nullptr, d.s, nullptr).nfrags * frag_floats(2));     // the largest of the modes: 3 KiB per fragment (bf16x6)
     T.pe_ang = take((size_t)d.V * 64); T.pe_spa = take((size_t)d.hw * 64);
     T.x0 = take(n * 64); T.c1 = take(n * 64); T.c2 = take(n * 64); T.c3 = take(n * 64); T.feat = take(n * 64);
     for (int l = 0; l < kLayers; ++l) {
@@ -163,7 +168,7 @@ TrainLayout train_layout(const Dims& d) {
     return T;
 }
 
-int run_pack_split(std::vector<PackOp>& ops, float* dst, int expect_frags, hipStream_t st, bool three = false) {
+int run_pack_split(std::vector<PackOp>& ops, float* dst, int expect_frags, hipStream_t st, int mm) {      // mm = 1, 2
     int total = 0;
     size_t i = 0;
     while (i < ops.size()) {
@@ -175,8 +180,7 @@ int run_pack_split(std::vector<PackOp>& ops, float* dst, int expect_frags, hipSt
             nf += ops[i].ntiles * ops[i].ksteps;
             ++a.nops; ++i;
         }
-        if (three) k_pack_split<true><<<nf, 64, 0, st>>>(a, dst + (size_t)total * 768);
-        else k_pack_split<false><<<nf, 64, 0, st>>>(a, dst + (size_t)total * 512);
+        if (int rc = dispatch<1, 2>(mm, [&](auto MM) { k_pack_split<MM><<<nf, 64, 0, st>>>(a, dst + (size_t)total * frag_floats(MM)); return 0; })) return rc;
         LFT_LAUNCH_OK("k_pack_split");
         total += nf;
     }
@@ -197,6 +201,7 @@ struct TrainCtx {
     const WViews& W;
     hipStream_t st;
     int math;                  // LFT_MATH_F32, LFT_MATH_BF16X3 or LFT_MATH_BF16X6
+    int mm() const { return math_mode(math); }
     RedTab* red = nullptr;     // backward only: pending reductions (k_reduce_all) ...
     size_t* part_used = nullptr;   // ... and the next free float of the partial buffer
     size_t* part_peak = nullptr;   // its high-water mark (the sizing run sizes the buffer with it)
@@ -230,8 +235,8 @@ int run_lin(const TrainCtx& c, int view, int ot0, int nOT, const float* X, int l
     const WView& v = c.W.v[view];
     if (nOT <= 0) nOT = v.OT;
     if ((v.taps != 1 && (ot0 || nOT != v.OT))) return fail(LFT_ERR_ARG, "run_lin: bad tile block (view %d)", view);
-    const int mm = c.math == LFT_MATH_BF16X3 ? 1 : c.math == LFT_MATH_BF16X6 ? 2 : 0;
-    LinP p{X, ldx, c.F(c.T.wp) + v.frag0 * (mm == 2 ? 768 : 512), v.OT, v.KS, ot0, R, ldr, Y, ldy, M, ldy, mact, v.taps, flip, act, c.d.h, c.d.w, N, 1};
+    const int mm = c.mm();
+    LinP p{X, ldx, c.F(c.T.wp) + v.frag0 * frag_floats(mm), v.OT, v.KS, ot0, R, ldr, Y, ldy, M, ldy, mact, v.taps, flip, act, c.d.h, c.d.w, N, 1};
     const unsigned gx = (unsigned)((N + 127) / 128);
     // output tiles per wave: 4 when that still gives the chip >= 2 waves per SIMD, fewer (more, thinner waves) for small N
     const long long tiles = (N + 31) / 32;
@@ -309,11 +314,10 @@ int wgrad(const TrainCtx& c, const float* dY, int Co, const float* X, int Ci, in
     if ((rc = part_take(c, (size_t)nch * wsize, &poff))) return rc;
     return c.enqueue([&] {
         WgP p{dY, Co, X, Ci, c.F(c.T.part + poff), wsize, Ci * taps, taps, 1, Co, Ci, taps, c.d.h, c.d.w, N, len, 1, nch, 1};
-        const int mm = c.math == LFT_MATH_BF16X3 ? 1 : c.math == LFT_MATH_BF16X6 ? 2 : 0;
         auto launch = [&](auto NI, auto TX) {
             const size_t lds = (size_t)3 * TX * NI * 16 * 64 * sizeof(float);
             const dim3 g((unsigned)((nch + 7) / 8 * 8 * p.gy * TX));
-            return dispatch<1, 2, 0>(mm, [&](auto MM) {
+            return dispatch<1, 2, 0>(c.mm(), [&](auto MM) {
                 if (int r = allow_lds(k_wgrad<NI, MM, TX>, lds, "k_wgrad")) return r;
                 k_wgrad<NI, MM, TX><<<g, 256, lds, c.st>>>(p);
                 return 0;
@@ -456,7 +460,7 @@ int train_forward(const float* const* P, const float* lr, float* out, float* tap
     const int nimg = d.B * d.V;
     int rc;
 #define TRY(x) do { if ((rc = (x))) return rc; } while (0)
-    if (math == LFT_MATH_BF16X3 || math == LFT_MATH_BF16X6) TRY(run_pack_split(ops, c.F(T.wp), (int)WV.nfrags, st, math == LFT_MATH_BF16X6));
+    if (c.mm()) TRY(run_pack_split(ops, c.F(T.wp), (int)WV.nfrags, st, c.mm()));
     else TRY(run_pack<float>(ops, c.F(T.wp), (int)WV.nfrags, st));   // both orientations of every matrix, for this step's weights
     k_pe_plain<<<blocks_for(std::max(d.V, d.hw) * 64, 256), 256, 0, st>>>(c.F(T.pe_ang), c.F(T.pe_spa), d.V, d.h, d.w);
     LFT_LAUNCH_OK("k_pe_plain");

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compile lft_api.hip for gfx950 and print per-kernel register / spill / occupancy figures."""
+"""Compile lft_api.hip for gfx950 and print per-kernel register / spill / occupancy / static LDS figures (extra arguments go to hipcc)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
@@ -14,8 +14,8 @@ for line in out.splitlines():
     for key in ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill", "LDS Size [bytes/block]"):
         m = re.search(re.escape(key) + r": (\d+)", line)
         if m and cur: rows[cur][key] = int(m.group(1))
-print(f"{'kernel':58s} VGPR AGPR spill scratch occ")
+print(f"{'kernel':58s} VGPR AGPR spill scratch occ    lds")
 for k, r in rows.items():
     if "k_" not in k: continue
     name = k[:56]
-    print(f"{name:58s} {r.get('VGPRs',0):4d} {r.get('AGPRs',0):4d} {r.get('VGPRs Spill',0):5d} {r.get('ScratchSize [bytes/lane]',0):7d} {r.get('Occupancy [waves/SIMD]',0):3d}")
+    print(f"{name:58s} {r.get('VGPRs',0):4d} {r.get('AGPRs',0):4d} {r.get('VGPRs Spill',0):5d} {r.get('ScratchSize [bytes/lane]',0):7d} {r.get('Occupancy [waves/SIMD]',0):3d} {r.get('LDS Size [bytes/block]',0):6d}")
