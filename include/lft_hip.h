@@ -21,7 +21,8 @@
  *    inf / NaN, where the kernels set a sticky flag in the workspace that lft_status_read reports: an overflow is a loud error,
  *    not a silently wrong image).
  *    Activations between kernels are stored in the same type (float, __bf16 or _Float16, channels-last [B, A*A, h, w, C]).
- *  - Shapes: A = angRes (A*A <= 128 views; 5x5 and 9x9 are the tested ones), h x w = LR view size, s = scale factor (2 or 4),
+ *  - Shapes: A = angRes (A*A <= 128 views, i.e. A = 1 .. 11: every A is tested against the oracle, 2, 3, 5 and 9 at BASELINE's
+ *    view sizes, the others at small views -- tests/test_gpu_parity.py), h x w = LR view size, s = scale factor (2 or 4),
  *    channels fixed to 64 (reference option.py --channels default, LFT.py:11).
  */
 #ifndef LFT_HIP_H

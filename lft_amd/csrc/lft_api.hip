@@ -445,6 +445,15 @@ int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* 
     LFT_LAUNCH_OK("k_ang");
     return 0;
 }
+// One kernel instantiation per class of view count, each in the three precisions.  tests/test_gpu_parity.py runs every one of
+// them against the oracle: test_ang_block[<case>-<layer>-<prec>] on a few dozen positions, test_ang_block_many_positions[<A>-<prec>]
+// on more positions than the grid covers in one sweep (1155 or 2205, odd), where the workgroups loop:
+//   V <= 25  (A 1 .. 5)  k_ang<T, 13>              cases A5_s2_B2_6x6, A3_s2_B1_9x7, A2_*, A1_s2_B2_6x7, A4_s2_B1_5x5;  many_positions[1-*], [4-*]
+//   V 36, 49 (A 6, 7)    k_ang_multi<T, 2, LL 9>   cases A6_s2_B1_6x5, A7_s2_B1_3x5;                                  many_positions[6-*], [7-*]
+//   V 64     (A 8)       k_ang_multi<T, 2, LL 16>  case  A8_s2_B1_5x3;                                                many_positions[8-*]
+//   V 81     (A 9)       k_ang_multi<T, 3, LL 9>   case  A9_s4_B1_8x8;                                                many_positions[9-*]
+//   V 100    (A 10)      k_ang_multi<T, 4, LL 9>   case  A10_s4_B1_3x5;                                               many_positions[10-*]
+//   V 121    (A 11)      k_ang_multi<T, 4, LL 13>  case  A11_s2_B1_4x3;                                               many_positions[11-*]
 template <typename T>
 int ang_block(const void* packed, const PackedLayout& L, int l, const T* in, T* out, const Dims& d, hipStream_t st, unsigned* status = nullptr) {
     // V = A*A (make_dims): above 32 views only 36, 49 | 64 | 81 | 100 | 121 occur, with 4, 17 | 32 | 17 | 4 | 25 rows in the last key tile

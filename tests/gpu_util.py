@@ -20,7 +20,7 @@ def stream():
 class Packed:
     """Packed weights + workspace for one (state dict, A, h, w, s, prec, B)."""
 
-    def __init__(self, sd_np, A, h, w, s, prec, B):
+    def __init__(self, sd_np, A, h, w, s, prec, B, work=True):
         self.A, self.h, self.w, self.s, self.B = A, h, w, s, B
         self.prec_name, self.prec = prec, PRECS[prec]
         names = [n for n, _, _ in param_table(64, s)]
@@ -29,7 +29,8 @@ class Packed:
         arr = (ctypes.c_void_p * len(self.params))(*[p.data_ptr() for p in self.params])
         _lib.check(_lib.lib().lft_pack_weights(arr, len(self.params), self.buf.data_ptr(), A, h, w, s, self.prec, stream()),
                    "lft_pack_weights")
-        self.work = torch.empty(_lib.workspace_bytes(B, A, h, w, s, self.prec), dtype=torch.uint8, device=DEV)
+        # work=False: for the entry points that take no workspace (lft_ang_block_fwd) at sizes where it would be hundreds of MiB
+        self.work = torch.empty(_lib.workspace_bytes(B, A, h, w, s, self.prec), dtype=torch.uint8, device=DEV) if work else None
         torch.cuda.synchronize()
 
     def dims(self):

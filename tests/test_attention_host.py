@@ -137,3 +137,16 @@ def test_fixtures_match_the_functional_attention_on_oracle_taps(name):
                 print(f"{name} {kind}{l} {key}: max {float(ref.max()):.3f} abs err {float((g - ref).abs().max()):.2e} rel_max {rel:.2e}")
                 assert rel <= U.FP32_STAGE_TOL, (kind, l, key, rel)
     assert all(f"{kind}{l}_heads" in z.files for kind in ("ang", "spa") for l in (0, 3))
+
+
+@pytest.mark.parametrize("A", range(1, 12))
+def test_am_div_is_exact_for_every_view_count(A):
+    """k_ang_maps (lft_attn_maps.cuh) splits a flat element e of a [V][V] map into (e / V, e % V) with a float product,
+    (int)(((float)e + 0.5f) * (1.0f / (float)V)): the same expression in fp32 numpy equals e // V for every e < V*V."""
+    import numpy as np
+    V = A * A
+    e = np.arange(V * V, dtype=np.int64)
+    inv = np.float32(1.0) / np.float32(V)
+    i = ((e.astype(np.float32) + np.float32(0.5)) * inv).astype(np.int64)
+    assert i.dtype == np.int64 and ((e.astype(np.float32) + np.float32(0.5)) * inv).dtype == np.float32
+    assert np.array_equal(i, e // V)

@@ -78,7 +78,9 @@ def test_maps_match_the_reference(name):
     print(f"{name}: worst rel_max {worst:.3e}")
 
 
-SHAPES = [(5, 2, 2, 6, 6), (3, 2, 1, 9, 7), (9, 4, 1, 8, 8), (5, 2, 1, 32, 32), (2, 2, 1, 64, 64), (2, 2, 1, 6, 12)]
+SHAPES = [(5, 2, 2, 6, 6), (3, 2, 1, 9, 7), (9, 4, 1, 8, 8), (5, 2, 1, 32, 32), (2, 2, 1, 64, 64), (2, 2, 1, 6, 12),
+          # every other view count class: V = 1, 16 (k_ang_attn<32>), 49, 64, 100, 121 (k_ang_attn<128>; k_ang_maps sizes its LDS from V)
+          (1, 2, 2, 6, 7), (4, 2, 1, 5, 5), (7, 2, 1, 3, 5), (8, 2, 1, 5, 3), (10, 4, 1, 3, 5), (11, 2, 1, 4, 3)]
 
 
 @pytest.mark.parametrize("A,s,B,h,w", SHAPES)
@@ -106,7 +108,7 @@ def test_shape_coverage_against_functional_attention(A, s, B, h, w):
         assert rel <= 1e-6, (b, rel)
 
 
-@pytest.mark.parametrize("A,s,B,h,w", [(5, 2, 2, 6, 6), (2, 2, 1, 6, 12), (9, 4, 1, 8, 8)])
+@pytest.mark.parametrize("A,s,B,h,w", [(5, 2, 2, 6, 6), (2, 2, 1, 6, 12), (9, 4, 1, 8, 8), (11, 2, 1, 4, 3)])
 def test_maps_are_the_weights_the_network_used(A, s, B, h, w):
     """Per-head maps times the tape's V give the tape's attention output o (angular layer 1, spatial layer 2)."""
     sd = deterministic_state(64, s, seed=1, flavor="stress")

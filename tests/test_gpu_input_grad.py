@@ -94,12 +94,13 @@ def run_input_backward(A, s, B, h, w, math, dseed=3, iseed=0):
 
 # ---------------------------------------------------------------------------------------------------- 1. stage kernel
 STAGE_VIEWS = [(4, 4), (5, 9), (8, 5), (6, 12), (16, 16), (20, 33)]      # (20, 33): several 16 x 16 tiles per view, ragged ones
+STAGE_EDGE_A = [1, 8, 11]             # one view, 64 and 121 views (the C ABI takes A*A <= 128): on the two smallest views only, to bound the count
 
 
 @pytest.mark.parametrize("with_dout", [True, False], ids=["both_terms", "conv_only"])
 @pytest.mark.parametrize("s", [2, 4])
-@pytest.mark.parametrize("A", [2, 3, 5, 9])
-@pytest.mark.parametrize("hw", STAGE_VIEWS, ids=lambda v: "%dx%d" % v)
+@pytest.mark.parametrize("hw,A", [(hw, A) for hw in STAGE_VIEWS for A in [2, 3, 5, 9]] + [(hw, A) for hw in STAGE_VIEWS[:2] for A in STAGE_EDGE_A],
+                         ids=lambda v: "%dx%d" % v if isinstance(v, tuple) else str(v))
 def test_stage_kernel_matches_autograd(hw, A, s, with_dout):
     h, w = hw
     B = 2 if A <= 3 else 1

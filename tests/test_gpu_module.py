@@ -13,7 +13,9 @@ from oracle import lft_oracle as O
 
 pytestmark = pytest.mark.gpu
 BF16_END_TO_END = 2.5e-3      # max|err| / max|ref| of the bf16 throughput path (operand rounding; see tests/diag_precision_study.py)
-GOLDEN = ["tiny_a5_s2_b2_6x6", "small_a5_s4_b1_8x8", "small_a9_s4_b1_8x8", "rect_a5_s2_b1_8x6", "wide_a2_s2_b1_6x12", "cfg1_a5_s2_b1_32x32", "cfg2_a5_s4_b1_32x32"]
+GOLDEN = ["tiny_a5_s2_b2_6x6", "small_a5_s4_b1_8x8", "small_a9_s4_b1_8x8", "rect_a5_s2_b1_8x6", "wide_a2_s2_b1_6x12", "cfg1_a5_s2_b1_32x32", "cfg2_a5_s4_b1_32x32",
+          # one per angular-attention code path (V = 1, 16, 49, 64, 100, 121)
+          "views_a1_s2_b2_6x7", "views_a4_s2_b1_5x5", "views_a7_s2_b1_3x5", "views_a8_s2_b1_5x3", "views_a10_s4_b1_3x5", "views_a11_s2_b1_4x3"]
 
 
 def make_net(A, s, wseed, flavor, precision):

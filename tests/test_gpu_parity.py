@@ -12,6 +12,9 @@ Tolerances (BASELINE.json north_star: 1e-3 relative fp32):
               model of that precision (oracle/lft_oracle_lp.py) on the same input, in max norm, per token, image position, view, channel
               and batch element, each within M = 2 of the model.  A global rms cannot see one wrong token or column; these can
               (tests/test_parity_gates.py).  Every stage test prints its six ratios.
+  VIEW_CASES (one shape per angular-attention code path: V = 1, 16, 49, 64, 100, 121) and test_ang_block_many_positions, fp32
+              additionally: max|err| <= 1e-4 * max|ref| VIEW BY VIEW, over each view's own maximum -- a wrong view of the last key
+              tile cannot hide behind a larger one.
 """
 import os
 
@@ -36,12 +39,26 @@ END_TO_END = {"fp32": 1e-3, "fp16": 1e-3, "bf16": 2.5e-3}
 ALL_PRECS = ["fp32", "fp16", "bf16"]
 
 
-def check(got, ref, prec, what, model=None, layout="act", A=None, s=None):
-    """`model` (16-bit precisions): () -> the rounding model's output for the input the kernel saw."""
+def per_view_rel_max(got, ref, layout="act", A=None, s=None):
+    """(worst max|err| / max|ref| over the views, each over its own maximum; that view's index)."""
+    keep = PG._dims(layout)["view"]
+    e, r = PG._shape(got - ref, layout, A, s).abs(), PG._shape(ref, layout, A, s).abs()
+    red = tuple(d for d in range(e.dim()) if d not in keep)
+    rel = (e.amax(dim=red) / r.amax(dim=red)).reshape(-1)
+    return float(rel.max()), int(rel.argmax())
+
+
+def check(got, ref, prec, what, model=None, layout="act", A=None, s=None, per_view=False):
+    """`model` (16-bit precisions): () -> the rounding model's output for the input the kernel saw.
+    `per_view` (fp32): the 1e-4 of the stage also view by view."""
     msg = f"{what} [{prec}]: " + G.err_report(got, ref)
     assert not torch.isnan(got).any(), msg
     if prec == "fp32":
         assert G.rel_max(got, ref) <= FP32_STAGE_TOL, msg
+        if per_view:
+            worst, view = per_view_rel_max(got, ref, layout, A, s)
+            msg += f" per-view rel_max {worst:.3e} (view {view})"
+            assert worst <= FP32_STAGE_TOL, msg
     else:
         assert G.rel_rms(got, ref) <= (FP16_STAGE_RMS if prec == "fp16" else BF16_STAGE_RMS), msg
         with torch.no_grad():
@@ -88,6 +105,11 @@ def test_bicubic(A, h, w, s):
 CASES = [(5, 2, 2, 6, 6), (5, 4, 1, 8, 8), (3, 2, 1, 9, 7), (5, 2, 1, 32, 32), (9, 4, 1, 8, 8), (6, 2, 1, 6, 5),   # 81 views: 3 column tiles; 36: 2
          (2, 2, 1, 64, 64),                   # 64-wide views: two column tiles per row, wide-tile LDS path
          (2, 2, 1, 6, 12), (2, 2, 1, 36, 64)]  # h < w: queries with x - 2 >= h have an EMPTY window (LFT.py:155) -> attention output 0
+# One shape per angular-attention code path that the cases above leave out, at the smallest views where every kernel still has work
+# (12 .. 42 positions per batch element; four of the six with an odd B*h*w: the last two-position group of the 16-bit k_ang_multi is
+# half empty): V = 1 and 16 (k_ang), 49 (17 rows in the last key tile), 64 (a full last tile), 100 and 121 (four key tiles).
+VIEW_CASES = [(1, 2, 2, 6, 7), (4, 2, 1, 5, 5), (7, 2, 1, 3, 5), (8, 2, 1, 5, 3), (10, 4, 1, 3, 5), (11, 2, 1, 4, 3)]
+CASES += VIEW_CASES
 
 
 @pytest.fixture(scope="module", params=CASES, ids=lambda c: "A%d_s%d_B%d_%dx%d" % c)
@@ -99,7 +121,8 @@ def case(request):
     taps = {}
     out = O.forward(sd, lr, A, s, taps)
     packs = {p: G.Packed(sd_np, A, h, w, s, p, B) for p in ALL_PRECS}
-    return dict(A=A, s=s, B=B, h=h, w=w, sd=sd, lr=lr, taps=taps, out=out, packs=packs, mask=O.window_mask(h, w))
+    return dict(A=A, s=s, B=B, h=h, w=w, sd=sd, lr=lr, taps=taps, out=out, packs=packs, mask=O.window_mask(h, w),
+                per_view=request.param in VIEW_CASES)
 
 
 @pytest.mark.parametrize("prec", ALL_PRECS)
@@ -111,7 +134,7 @@ def test_init_features(case, prec):
                                                 *pk.dims(), G.stream()), "init_features")
     torch.cuda.synchronize()
     check(G.from_act(act), case["taps"]["feat"], prec, "init_features",
-          lambda: LP.init_features(case["sd"], O.mosaic_to_views(case["lr"], case["A"]), prec))
+          lambda: LP.init_features(case["sd"], O.mosaic_to_views(case["lr"], case["A"]), prec), per_view=case["per_view"])
 
 
 @pytest.mark.parametrize("prec", ALL_PRECS)
@@ -125,7 +148,8 @@ def test_ang_block(case, prec, layer):
     _lib.check(_lib.lib().lft_ang_block_fwd(pk.buf.data_ptr(), layer, xin.data_ptr(), act.data_ptr(), *pk.dims(), G.stream()),
                "ang_block")
     torch.cuda.synchronize()
-    check(G.from_act(act), ref, prec, f"ang_block{layer}", lambda: LP.ang_block(case["sd"], layer, G.from_act(xin), prec))
+    check(G.from_act(act), ref, prec, f"ang_block{layer}", lambda: LP.ang_block(case["sd"], layer, G.from_act(xin), prec),
+          per_view=case["per_view"])
 
 
 @pytest.mark.parametrize("prec", ALL_PRECS)
@@ -142,7 +166,8 @@ def test_spa_block(case, prec, layer, with_skip):
                                             act.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream()), "spa_block")
     torch.cuda.synchronize()
     check(G.from_act(act), ref, prec, f"spa_block{layer}",
-          lambda: LP.spa_block(case["sd"], layer, G.from_act(xin), prec, case["mask"], G.from_act(skip) if with_skip else None))
+          lambda: LP.spa_block(case["sd"], layer, G.from_act(xin), prec, case["mask"], G.from_act(skip) if with_skip else None),
+          per_view=case["per_view"])
 
 
 @pytest.mark.parametrize("prec", ALL_PRECS)
@@ -158,7 +183,7 @@ def test_upsample(case, prec):
     ref = O.upsample(case["sd"], O.views_to_mosaic(G.from_act(xin), A), s)
     skip = case["taps"]["skip"]
     check(out.cpu() - skip, ref, prec, "upsample(residual branch)",
-          lambda: LP.upsample(case["sd"], O.views_to_mosaic(G.from_act(xin), A), s, prec), "image", A, s)
+          lambda: LP.upsample(case["sd"], O.views_to_mosaic(G.from_act(xin), A), s, prec), "image", A, s, per_view=case["per_view"])
 
 
 @pytest.mark.parametrize("prec", ALL_PRECS)
@@ -176,3 +201,75 @@ def test_forward_vs_oracle(case, prec):
     assert G.rel_max(got, ref) <= END_TO_END[prec], msg
     res_got, res_ref = got - case["taps"]["skip"], case["taps"]["res"]
     assert G.rel_rms(res_got, res_ref) <= {"fp32": 1e-4, "fp16": 4e-3, "bf16": 2e-2}[prec], "residual branch: " + G.err_report(res_got, res_ref)
+
+
+# ---------------------------------------------------------------------------------------------------- beyond the grid cap
+def ang_positions_per_sweep(V, prec):
+    """Positions one launch of the angular block covers before its workgroups loop: lft_api.hip, ang_block / ang_multi and lds_ang
+    re-derived -- grid = min(ceil(positions / per workgroup), 256 * max(1, 160 KiB / LDS per workgroup))."""
+    esz = 4 if prec == "fp32" else 2
+    fb = 1024 * (2 if prec == "fp32" else 1)                 # bytes of one weight / K / V fragment
+    tile_io = 16 * (64 * esz + 16)                           # TileIO<2, T>::BYTES
+    if V <= 32:                                              # k_ang: 4 waves = 4 positions, the 64 weight fragments in LDS
+        lds, per_wg = 64 * fb + 1024 + 4 * tile_io, 4
+    else:                                                    # k_ang_multi<CT, NG>
+        ct = 4 if V > 96 else 3 if V > 64 else 2
+        per_wg = 2 if esz == 2 and ct <= 3 else 1            # NG
+        lds = (64 * fb if esz == 2 else 0) + 1024 + per_wg * ct * 8 * fb + per_wg * ct * tile_io
+    assert lds <= 160 * 1024
+    return 256 * max(1, 160 * 1024 // lds) * per_wg
+
+
+MANY_B, MANY_W = 3, 35
+
+
+def many_positions_h(V, prec):
+    h = 11
+    while MANY_B * h * MANY_W <= ang_positions_per_sweep(V, prec):
+        h += 2                                               # stays odd
+    return h
+
+
+_MANY_X = {}
+
+
+@pytest.mark.parametrize("prec", ALL_PRECS)
+@pytest.mark.parametrize("A", [1, 4, 6, 7, 8, 9, 10, 11])
+def test_ang_block_many_positions(A, prec):
+    """lft_ang_block_fwd alone (layer 0) on more positions than one sweep of the grid covers, so that workgroups take the
+    grid-stride loop, with an odd position count: B 3, w 35, h 11 -> 1155 positions (h*w = 385 is odd too: groups of 2 or 4
+    positions straddle batch elements, and the last two-position group of the 16-bit k_ang_multi is half empty).
+
+    Positions per sweep (ang_positions_per_sweep):
+        A (V)           kernel                  fp32    fp16 / bf16
+        1, 4 (1, 16)    k_ang<13>               1024    2048  -> h = 21 there: 2205 positions
+        6, 7 (36, 49)   k_ang_multi<2, LL 9>     768     512
+        8 (64)          k_ang_multi<2, LL 16>    768     512
+        9 (81)          k_ang_multi<3, LL 9>     512     512
+        10 (100)        k_ang_multi<4, LL 9>     256     256
+        11 (121)        k_ang_multi<4, LL 13>    256     256
+    The input is a seeded normal tensor rounded to the activation type (no network in front: the oracle's other stages at
+    140 k tokens are the slow part).  The output buffer is pre-filled with NaN, so check() also proves that every token was
+    stored, and 64 elements behind it must stay as they were."""
+    V, B, w, s = A * A, MANY_B, MANY_W, 2
+    h = many_positions_h(V, prec)
+    cap = ang_positions_per_sweep(V, prec)
+    assert cap == {("k_ang", True): 1024, ("k_ang", False): 2048, (2, True): 768, (2, False): 512, (3, True): 512, (3, False): 512,
+                   (4, True): 256, (4, False): 256}[("k_ang" if V <= 32 else (V + 31) // 32, prec == "fp32")]
+    assert B * h * w > cap and (B * h * w) % 2 == 1 and h == (21 if V <= 32 and prec != "fp32" else 11)
+    sd_np = deterministic_state(64, s, seed=1, flavor="stress")
+    sd = O.state_from_numpy(sd_np)
+    if (A, h) not in _MANY_X:
+        _MANY_X[(A, h)] = torch.randn(B, 64, V, h, w, generator=torch.Generator().manual_seed(1000 + A))
+    xin = G.to_act(_MANY_X[(A, h)], prec)
+    pk = G.Packed(sd_np, A, h, w, s, prec, B, work=False)
+    n = B * V * h * w * 64
+    buf = torch.full((n + 64,), float("nan"), dtype=G.ACT_DTYPE[prec], device=G.DEV)
+    buf[n:] = -7.0
+    act = buf[:n].view(B, V, h, w, 64)
+    with torch.no_grad():
+        ref = O.ang_block(sd, 0, G.from_act(xin))
+    _lib.check(_lib.lib().lft_ang_block_fwd(pk.buf.data_ptr(), 0, xin.data_ptr(), act.data_ptr(), *pk.dims(), G.stream()), "ang_block")
+    torch.cuda.synchronize()
+    assert bool((buf[n:].float() == -7.0).all()), "the 64 elements behind the output were written"
+    check(G.from_act(act), ref, prec, f"ang_block0 A{A} {B}x{h}x{w}", lambda: LP.ang_block(sd, 0, G.from_act(xin), prec), per_view=True)

@@ -22,7 +22,10 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-3
 
 CASES = [(3, 2, 2, 6, 6), (2, 4, 1, 8, 5), (5, 2, 1, 8, 8), (2, 2, 1, 5, 9),      # h < w: empty windows pass no gradient
-         (9, 2, 1, 4, 4), (3, 2, 1, 7, 5), (5, 2, 1, 16, 16)]                    # 81 views; ragged 32-token tiles (315 tokens); 6400 tokens
+         (9, 2, 1, 4, 4), (3, 2, 1, 7, 5), (5, 2, 1, 16, 16),                    # 81 views; ragged 32-token tiles (315 tokens); 6400 tokens
+         # the other view counts: k_ang_attn<32> at V = 1 and 16; k_ang_attn<128> at V = 36 (just above the switch), 64 and 121 (968 of
+         # its 1024 threads live)
+         (1, 2, 2, 6, 7), (4, 2, 1, 5, 5), (6, 2, 1, 4, 4), (8, 2, 1, 5, 3), (11, 2, 1, 4, 3)]
 # The network is piecewise linear (ReLU, LeakyReLU, |.|): when a pre-activation lies within fp32 rounding of 0, two
 # correct fp32 implementations take different branches and -- at small token counts, where one token is 1/300 of the
 # batch -- whole gradient tensors move by ~1e-3 (torch-fp32 against torch-fp64 shows the same; tests/diag_train_grad_report.py).
@@ -77,8 +80,9 @@ def case(request):
     return build_case(request.param)
 
 
-# the per-block backward tests: three shapes (2x, 4x with h != w, 5 x 5 views) x the three math modes -- every backward kernel runs in each
-BLOCK_CASES = [(3, 2, 2, 6, 6), (2, 4, 1, 8, 5), (5, 2, 1, 8, 8)]
+# the per-block backward tests: three shapes (2x, 4x with h != w, 5 x 5 views) x the three math modes -- every backward kernel runs in each;
+# 64 and 121 views: the one-workgroup-per-position angular attention (k_ang_attn<128>) with every thread / 968 of 1024 threads live
+BLOCK_CASES = [(3, 2, 2, 6, 6), (2, 4, 1, 8, 5), (5, 2, 1, 8, 8), (8, 2, 1, 5, 3), (11, 2, 1, 4, 3)]
 
 
 @pytest.fixture(scope="module", params=[(c, m) for c in BLOCK_CASES for m in MATHS], ids=_CASE_ID)

@@ -12,7 +12,10 @@ from oracle import lft_oracle as O
 from fixture_util import stats, sub_indices
 
 CASES = ["tiny_a5_s2_b2_6x6", "small_a5_s4_b1_8x8", "small_a9_s4_b1_8x8", "rect_a5_s2_b1_8x6", "wide_a2_s2_b1_6x12",
-         "cfg1_a5_s2_b1_32x32", "cfg2_a5_s4_b1_32x32"]
+         "cfg1_a5_s2_b1_32x32", "cfg2_a5_s4_b1_32x32",
+         # one per angular-attention code path (V = 1, 16, 49, 64, 100, 121): tools/gen_golden.py --views-only
+         "views_a1_s2_b2_6x7", "views_a4_s2_b1_5x5", "views_a7_s2_b1_3x5", "views_a8_s2_b1_5x3", "views_a10_s4_b1_3x5",
+         "views_a11_s2_b1_4x3"]
 TOL = 2e-6   # fp32 re-association between two stock-op formulations of the same maths
 
 

@@ -108,6 +108,29 @@ def test_gates_pass_a_second_implementation_and_catch_local_corruptions(setup, s
                 assert old <= OLD_RMS_GATE[prec], f"{corrupt.__name__}: the rms assertion was expected to miss this ({old:.2e})"
 
 
+def test_gates_catch_a_wrong_last_view_at_121_views():
+    """A 11, 2x, 4x3 views (121 views, 12 positions -- the smallest of the view-count cases of tests/test_gpu_parity.py): view
+    V - 1, the last row of the last key tile of the angular attention, x1.02.  Global rel_max of that corruption: 1.5e-2.  Found:
+    the healthy candidate <= 1.11 in every gate; the `view` gate reads 4.7 / 7.1 in bf16 and 36 / 57 in fp16 (spa / ang block)."""
+    A_, B, h, w = 11, 1, 4, 3
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    sd = O.state_from_numpy(deterministic_state(64, S, seed=1, flavor="stress"))
+    taps = {}
+    O.forward(sd, torch.from_numpy(synthetic_lr(B, A_, h, w, seed=0)), A_, S, taps)
+    setup = (sd, {k: v.double() for k, v in sd.items()}, taps)
+    for stage in ("spa", "ang"):
+        for prec in ("bf16", "fp16"):
+            ref, model, healthy = block_outputs(setup, stage, prec, B)
+            ratios, text = PG.gate_report(healthy, ref, model)
+            print(f"A11 {stage} {prec} healthy: {text}")
+            assert max(ratios.values()) <= HEALTHY, text
+            cand = healthy.clone()
+            cand[:, :, A_ * A_ - 1] *= 1.02
+            ratios, text = PG.gate_report(cand, ref, model)
+            print(f"A11 {stage} {prec} last view x1.02: {text} | old rms {rel_rms(cand, ref):.2e}")
+            assert "view" in PG.failed(ratios), f"a wrong last view passes the view gate: {text}"
+
+
 def test_image_layout_slices():
     """The up-sampler's layout: a corruption of one sub-pixel phase, one view, one LR pixel's block lands in its own gate."""
     g = torch.Generator().manual_seed(0)

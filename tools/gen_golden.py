@@ -255,6 +255,12 @@ KINK_SHAPE_CASES = [("train_kink_a5_s4_b1_16x16_seed0", 5, 4, 1, 16, 16),
                     ("train_kink_a3_s2_b1_16x40_seed0", 3, 2, 1, 16, 40)]
 
 
+# One shape per angular-attention code path that no other fixture reaches (the view count V = A*A picks the kernel: V <= 25,
+# 36/49, 64, 81, 100, 121), at the smallest views where every kernel still has work; four of the six have an odd B*h*w.
+VIEW_CASES = [("views_a1_s2_b2_6x7", 1, 2, 2, 6, 7), ("views_a4_s2_b1_5x5", 4, 2, 1, 5, 5), ("views_a7_s2_b1_3x5", 7, 2, 1, 3, 5),
+              ("views_a8_s2_b1_5x3", 8, 2, 1, 5, 3), ("views_a10_s4_b1_3x5", 10, 4, 1, 3, 5), ("views_a11_s2_b1_4x3", 11, 2, 1, 4, 3)]
+
+
 def main():
     torch.set_num_threads(8)
     ref = load_reference()
@@ -281,6 +287,10 @@ def main():
         return
     if "--wide-only" in sys.argv:      # add the h < w fixture without rewriting the others
         run_case(ref, "wide_a2_s2_b1_6x12", 2, 2, 1, 6, 12, full_taps=True)
+        return
+    if "--views-only" in sys.argv:     # add the view-count fixtures without rewriting the others
+        for args in VIEW_CASES:
+            run_case(ref, *args)
         return
     misc(ref)
     tiling(load_reference_tiling())
