@@ -1,6 +1,7 @@
 /* lft_hip_test.h -- test-only entry points of liblft_hip.so (NOT part of the product ABI of lft_hip.h; no reference counterpart).
  * The library exports them for tests/ only: the MFMA fragment-layout self test the parity suite starts with, the product-policy
- * self test of the training GEMMs, and the two stages the composed 16-bit front end is compared against. */
+ * self test of the training GEMMs, the two stages the composed 16-bit front end is compared against, and the tail of the forward
+ * (last SpaTrans + up-sampler) with either hand-off between the two. */
 #ifndef LFT_HIP_TEST_H
 #define LFT_HIP_TEST_H
 #ifdef __cplusplus
@@ -23,6 +24,12 @@ int lft_init_features_legacy_fwd(const void* packed, const float* lr, void* act_
 /* conv_init0 alone, tokens [B*A*A*h*w][64] in the activation type: recomputed == 0 -- the stand-alone kernel; recomputed != 0 (16-bit
  * only) -- the residual tile the last convolution of the front end computes from the LR pixels.  The two must be bit-identical. */
 int lft_conv0_fwd(const void* packed, const float* lr, void* x0_out, int recomputed, int B, int A, int h, int w, int s, int prec, void* stream);
+
+/* SpaTrans of layer 3 with the global skip, then the up-sampler, as lft_forward chains them (act_in / skip: tokens in the activation
+ * type, out: the fp32 HR mosaic).  handoff != 0: the block writes lane-major tiles and k_up reads them (requires the lane-major
+ * property of the view size in this precision, else LFT_ERR_SHAPE and nothing is launched).  handoff == 0: row-major. */
+int lft_tail_fwd(const void* packed, const void* act_in, const void* skip, const float* lr, float* out, void* workspace,
+                 int B, int A, int h, int w, int s, int prec, int handoff, void* stream);
 
 #ifdef __cplusplus
 }

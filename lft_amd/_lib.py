@@ -155,9 +155,10 @@ _SIGS = {
     "lft_prod_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lft_init_features_legacy_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "lft_conv0_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lft_tail_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
-TEST_EXPORTS = ("lft_mfma_selftest", "lft_prod_selftest", "lft_init_features_legacy_fwd", "lft_conv0_fwd")   # declared in include/lft_hip_test.h, not in the product header
+TEST_EXPORTS = ("lft_mfma_selftest", "lft_prod_selftest", "lft_init_features_legacy_fwd", "lft_conv0_fwd", "lft_tail_fwd")   # declared in include/lft_hip_test.h, not in the product header
 BLOCK_UPSAMPLE, BLOCK_SPA, BLOCK_ANG, BLOCK_INIT = 0, 1, 2, 3    # LFT_BLOCK_* of include/lft_hip.h
 LF_UINT8, LF_FLOAT32, LF_FLOAT64 = 0, 1, 2                      # LFT_LF_* of include/lft_hip.h
 MAPS_MEAN, MAPS_HEADS = 0, 1                                    # LFT_MAPS_* of include/lft_hip.h

@@ -282,6 +282,29 @@ template <typename T> bool tok_lane_major(const Dims& d) {
 }
 // k_spa1 launch with the ring chunk size that fits best: 16-fragment chunks if two workgroups then still share a CU
 // (<= 80 KiB each) or if they are the only ones fitting at all... else 8-fragment chunks (wide views, fp32).
+//
+// The spatial path takes a different route per class of view size h x w.  tests/test_gpu_parity.py runs one case per class against
+// the oracle and asserts the class itself from tests/spa_classes.py, a restatement of the two functions here and of the LDS sizes
+// above (cases are named A<angRes>_s<scale>_B<batch>_<h>x<w>; "tail" = tests/test_gpu_tail.py, lft_tail_fwd):
+//   128-token tiles of a view image (front-end convs, k_spa1)
+//     one partial tile, starting at token 0              6x6, 8x8, 9x7, 6x5, 6x12 and the view-count cases
+//     every tile full, starting at column 0 of a row     32x32, 64x64, 36x64
+//     a later tile starting mid-row, partial last tile   13x11 (15 tokens, waves 1..3 empty), 17x19 (a middle tile; 32 32 3 0),
+//                                                        35x37 (11 tiles), 31x32 (32 32 32 0), 53x55 .. 58x60
+//     full tiles starting mid-row                        16x24;  row-aligned with w < 32: 24x16
+//   hand-off k_spa1 -> part B, and last block -> k_up inside lft_forward
+//     lane-major in every precision                      32x32, 64x64, 36x64;  partial last row tile of k_spa_b (h % 4 = 2): 62x64
+//     lane-major in fp32, row-major in 16 bit            16x24, 24x16 (4x: GT = 2 in k_up)
+//     row-major                                          every other case
+//     lane-major tail (YLM store, k_up<.., LM> load) against the row-major one, bit for bit: tail 8x32, 32x32 (4x), 62x64; fp32 16x24, 24x16
+//   k_spa_b's 4 x 32 query tiles, row-major
+//     one column tile, partial                           every case with w < 32;  full with a 3-row last tile: 31x32
+//     two column tiles, the second partial               35x37 (5 columns, 3-row last tile), 53x55 .. 58x60
+//   k_spa1's ring chunk (launch_spa1 below)
+//     16 bit: CH 16 up to w = 55, CH 8 from w = 56       53x55 | 54x56 (row-major), 62x64, 64x64 (lane-major);  CH 16 again from w = 152: not run
+//     fp32:   CH 16 up to w = 59, CH 8 from w = 60       57x59 (163 072 B of LDS, with k_conv64 at w = 75 the largest allocation) | 58x60, 62x64, 64x64
+//   widest view: fp32 75 columns (k_conv64), 16 bit 347 (k_conv64_lr); k_spa1 would take 155 / 471.  test_init_features_widest_view runs
+//   3x75 / 3x347, test_too_wide_view_is_refused one column more (LFT_ERR_SHAPE from allow_lds, nothing launched).
 template <typename T, bool PE_ONLY>
 int launch_spa1(unsigned nwg, const T* in, const T* ws, const float* ln, const T* petok, T* tok, T* q, T* k, T* v, T* pe_out,
                 int nimg, const Dims& d, hipStream_t st, unsigned* status) {
@@ -802,6 +825,27 @@ int lft_upsample_fwd(const void* packed, const void* act_in, const float* lr, fl
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
         return upsample<T>(packed, L, static_cast<const T*>(act_in), lr, out, workspace, W, d, st);
+    });
+}
+
+// Test-only (include/lft_hip_test.h): the tail of lft_forward -- SpaTrans of layer 3 with the global skip into the workspace's xb,
+// then the up-sampler -- with the hand-off between the two chosen by the caller.
+int lft_tail_fwd(const void* packed, const void* act_in, const void* skip, const float* lr, float* out, void* workspace,
+                 int B, int A, int h, int w, int s, int prec, int handoff, void* stream) {
+    Dims d; int rc;
+    if (!packed || !act_in || !skip || !lr || !out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
+    const PackedLayout L = packed_layout(d, prec);
+    const WorkLayout W = work_layout(d, prec);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_prec(prec, [&](auto t) {
+        using T = decltype(t);
+        const bool lm = handoff != 0;
+        if (lm && !tok_lane_major<T>(d))
+            return fail(LFT_ERR_SHAPE, "lft_tail_fwd: views of %dx%d have no lane-major hand-off in this precision", d.h, d.w);
+        T* xb = at<T>(workspace, W.xb);
+        if (int r = spa_block<T>(packed, L, kLayers - 1, static_cast<const T*>(act_in), static_cast<const T*>(skip), xb, workspace, W, d, st, lm)) return r;
+        return upsample<T>(packed, L, xb, lr, out, workspace, W, d, st, lm);
     });
 }
 
