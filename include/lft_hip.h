@@ -133,6 +133,30 @@ int lft_scene_counts(int h0, int w0, int patch, int stride, int* num_u, int* num
 int lft_scene_divide(const float* scene, float* patches, int A, int h0, int w0, int patch, int stride, void* stream);
 int lft_scene_integrate(const float* sr_patches, float* sr_scene, int A, int h0, int w0, int patch, int stride, int s, void* stream);
 
+/* ---- dihedral light-field transforms: geometric self-ensemble at inference, per-sample augmentation in training ----
+ * A code t in 0..7 has three bits, applied in this order (the three coin flips of the reference's augmentation,
+ * utils/utils_datasets.py:114-124): bit 0 mirrors the mosaic left-right, bit 1 up-down, bit 2 transposes it.  For x[H, W]
+ *     T_t(x)[i, j] = x[fi(p), fj(q)],  (p, q) = (j, i) if bit 2 else (i, j),  fi(p) = H-1-p if bit 1 else p,  fj(q) = W-1-q if bit 0 else q;
+ * T_t(x) is [W, H] when bit 2 is set.  T_t^-1 undoes the transpose first, then the mirrors (for t = 5, 6 it is not T_t).
+ * A set of variants is an 8-bit mask (bit t = code t takes part, E = popcount, variants in ascending code order):
+ * 0xFF = all eight, 0x0F = the four mirrors (valid for H != W), 0x01 = the identity.
+ * lft_dihedral_batch : out[b] = T_(codes[b] & 7)(in[b]) -- codes: DEVICE int32 [B]; out holds B images of H*W floats each,
+ *                      image b laid out [W, H] when its code transposes.
+ * lft_dihedral_expand: out[b*E + k] = T_code_k(in[b]); out holds B*E images.
+ * lft_dihedral_merge : out[b] = (1/E) sum_k T^-1_code_k(in[b*E + k]); H, W are those of the OUTPUT, variant k is stored [W, H]
+ *                      when its code transposes.  fp32: acc = first variant, += the others in ascending code order, one
+ *                      multiplication by 1.0f / E -- the same operations in torch give the same bits.
+ * lft_scene_integrate_ens: lft_scene_integrate and the merge in one pass over sr_variants [N*E, 1, A*patch*s, A*patch*s] (the
+ *                      E variants of patch n adjacent at n*E + k); reads only the central stride*s region of every variant.
+ * in == out is refused (LFT_ERR_ARG), as are mask == 0 and mask > 0xFF; non-positive sizes give LFT_ERR_SHAPE.  H != W is valid
+ * for the three lft_dihedral_* calls (a transposed image is only laid out differently); the variants of
+ * lft_scene_integrate_ens are square by construction. */
+int lft_dihedral_batch(const float* in, float* out, const int* codes, int B, int H, int W, void* stream);
+int lft_dihedral_expand(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream);
+int lft_dihedral_merge(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream);
+int lft_scene_integrate_ens(const float* sr_variants, float* sr_scene, unsigned mask, int A, int h0, int w0, int patch, int stride, int s,
+                            void* stream);
+
 /* ---- fp32 training step (what PyTorch autograd records / replays for reference LFT.py:52-83 under train.py:89-107) ----
  * The 78 parameters are read IN PLACE (device pointers in state_dict order, HOST array), nothing is packed.
  * `tape` (lft_train_tape_bytes) holds every activation the backward pass re-reads plus its scratch; it must stay

@@ -13,7 +13,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_vo
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LFT_LIB_PATH") or os.path.join(HERE, "liblft_hip.so")   # LFT_LIB_PATH: experiment builds (tools/ab_build.py)
-SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_metrics.cuh", "lft_prepare.cuh"]
+SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh"]
 ABI_VERSION = 5                      # LFT_ABI_VERSION of include/lft_hip.h: lib() refuses a library that reports another one
 STATUS_NONFINITE = 1001              # LFT_STATUS_NONFINITE
 
@@ -126,6 +126,10 @@ _SIGS = {
     "lft_scene_counts": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "lft_scene_divide": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "lft_scene_integrate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lft_dihedral_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "lft_dihedral_expand": (c_int, [c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_int, c_void_p]),
+    "lft_dihedral_merge": (c_int, [c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_int, c_void_p]),
+    "lft_scene_integrate_ens": (c_int, [c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "lft_train_tape_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "lft_train_grad_floats": (c_int, [c_int, POINTER(c_size_t)]),
     "lft_train_tape_offset": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),

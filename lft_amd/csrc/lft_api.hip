@@ -37,6 +37,9 @@ namespace {
 #if LFT_TU != 1
 #include "lft_attn_maps.cuh" // attention weights from the tape's Q | K (lft_train_attn_maps)
 #endif
+#if LFT_TU != 2
+#include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
+#endif
 }  // namespace
 
 #if LFT_TU == 2
@@ -891,6 +894,58 @@ int lft_scene_integrate(const float* sr_patches, float* sr_scene, int A, int h0,
     const dim3 grid((unsigned)((A * w0 * s + 255) / 256), (unsigned)(A * h0 * s));
     k_scene_integrate<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_patches, sr_scene, A, patch * s, stride * s, h0 * s, w0 * s, nv);
     LFT_LAUNCH_OK("k_scene_integrate");
+    return 0;
+}
+
+// ---- dihedral transforms (lft_ensemble.cuh) ----
+static int dihedral_args(const void* in, const void* out, unsigned mask, int B, int H, int W, int* E, unsigned* blocks) {
+    if (!in || !out) return fail(LFT_ERR_ARG, "null pointer");
+    if (in == out) return fail(LFT_ERR_ARG, "the transforms do not work in place (in == out)");
+    if (mask == 0 || mask > 0xFFu) return fail(LFT_ERR_ARG, "mask 0x%x: one bit per dihedral code 0..7, at least one set", mask);
+    if (B < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "bad image batch (B=%d H=%d W=%d)", B, H, W);
+    *E = __builtin_popcount(mask);
+    const unsigned long long n = (unsigned long long)B * (unsigned long long)((H + DH_TILE - 1) / DH_TILE) * (unsigned long long)((W + DH_TILE - 1) / DH_TILE);
+    if (n * 8ull > 0x7fffffffull) return fail(LFT_ERR_SHAPE, "batch of %d images of %dx%d needs more than 2^31 blocks", B, H, W);
+    *blocks = (unsigned)n;
+    return 0;
+}
+int lft_dihedral_batch(const float* in, float* out, const int* codes, int B, int H, int W, void* stream) {
+    int E, rc; unsigned blocks;
+    if (!codes) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = dihedral_args(in, out, 1u, B, H, W, &E, &blocks))) return rc;
+    k_dihedral<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, codes, 1u, 1, H, W);
+    LFT_LAUNCH_OK("k_dihedral");
+    return 0;
+}
+int lft_dihedral_expand(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream) {
+    int E, rc; unsigned blocks;
+    if ((rc = dihedral_args(in, out, mask, B, H, W, &E, &blocks))) return rc;
+    k_dihedral<<<blocks * (unsigned)E, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, nullptr, mask, E, H, W);
+    LFT_LAUNCH_OK("k_dihedral");
+    return 0;
+}
+int lft_dihedral_merge(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream) {
+    int E, rc; unsigned blocks;
+    if ((rc = dihedral_args(in, out, mask, B, H, W, &E, &blocks))) return rc;
+    k_dihedral_merge<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, mask, E, H, W);
+    LFT_LAUNCH_OK("k_dihedral_merge");
+    return 0;
+}
+int lft_scene_integrate_ens(const float* sr_variants, float* sr_scene, unsigned mask, int A, int h0, int w0, int patch, int stride, int s,
+                            void* stream) {
+    int nu, nv, rc;
+    if (!sr_variants || !sr_scene) return fail(LFT_ERR_ARG, "null pointer");
+    if (sr_variants == sr_scene) return fail(LFT_ERR_ARG, "the merge does not work in place (in == out)");
+    if (mask == 0 || mask > 0xFFu) return fail(LFT_ERR_ARG, "mask 0x%x: one bit per dihedral code 0..7, at least one set", mask);
+    if (A < 1 || s < 1) return fail(LFT_ERR_SHAPE, "bad scene (A=%d s=%d)", A, s);
+    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
+    // the variants are A*patch*s square mosaics by construction, so a transposing code needs no further shape check
+    const int S = stride * s, ts = (S + DH_TILE - 1) / DH_TILE;
+    const unsigned long long n = (unsigned long long)nu * nv * A * A * ts * ts;
+    if (n > 0x7fffffffull) return fail(LFT_ERR_SHAPE, "scene needs more than 2^31 blocks");
+    k_scene_integrate_ens<<<(unsigned)n, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_variants, sr_scene, mask, __builtin_popcount(mask),
+                                                                                    A, patch * s, S, h0 * s, w0 * s, nv);
+    LFT_LAUNCH_OK("k_scene_integrate_ens");
     return 0;
 }
 

@@ -202,6 +202,12 @@ class get_model(nn.Module):
                 self.check_status()                     # fp16 by default: an overflow raises here (synchronises, like the .cpu() that follows in test.py)
         return out
 
+    def self_ensemble(self, lr: torch.Tensor, mode="dihedral", max_batch: int = 64) -> torch.Tensor:
+        """Geometric self-ensemble: the average over the dihedral variants of ``mode`` ("dihedral" x8, "flips" x4 for h != w, "none")
+        of the back-transformed forwards, lft_amd.ensemble.self_ensemble(self, lr, mode, max_batch).  Inference only."""
+        from .ensemble import self_ensemble
+        return self_ensemble(self, lr, mode=mode, max_batch=max_batch)
+
     def attention_maps(self, lr: torch.Tensor, **kw):
         """The softmax weights of the eight attention blocks for ``lr`` (what ``need_weights=True`` at reference LFT.py:183-187 and
         :230-233 returns), as ``{"ang0": t, "spa0": t, ...}`` of device tensors: lft_amd.attention.attention_maps(self, lr, **kw)."""

@@ -42,11 +42,32 @@ def integrate(sr_patches: torch.Tensor, ang: int, h0: int, w0: int, scale: int, 
     return out
 
 
+def integrate_ensemble(sr_variants: torch.Tensor, mask: int, ang: int, h0: int, w0: int, scale: int, patch: int = 32,
+                       stride: int = 16) -> torch.Tensor:
+    """`integrate` and lft_amd.ensemble.merge in one pass: sr_variants float32 [numU*numV*E, 1, A*patch*s, A*patch*s] (the E
+    variants of a patch adjacent, as lft_amd.ensemble.expand lays them out) -> SR scene mosaic [A*h0*s, A*w0*s]."""
+    x = sr_variants.contiguous().float()
+    out = torch.empty((ang * h0 * scale, ang * w0 * scale), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().lft_scene_integrate_ens(x.data_ptr(), out.data_ptr(), mask, ang, h0, w0, patch, stride, scale,
+                                                      torch.cuda.current_stream(x.device).cuda_stream), "lft_scene_integrate_ens")
+    return out
+
+
 @torch.no_grad()
-def super_resolve_scene(net, scene: torch.Tensor, patch: int = 32, stride: int = 16, max_batch: int = 64) -> torch.Tensor:
-    """Equivalent of the body of the reference's test() for one scene (test.py:79-101), batched."""
+def super_resolve_scene(net, scene: torch.Tensor, patch: int = 32, stride: int = 16, max_batch: int = 64, ensemble=None) -> torch.Tensor:
+    """Equivalent of the body of the reference's test() for one scene (test.py:79-101), batched.
+    ensemble: None, or a mode of lft_amd.ensemble.MASKS ("dihedral", "flips", "none") / an 8-bit mask -- geometric self-ensemble:
+    every patch goes through the network in its E dihedral variants (chunks of max(1, max_batch // E) patches) and
+    lft_scene_integrate_ens averages the back-transformed central regions straight into the scene; no merged patch is stored."""
     A, s = net.angRes, net.factor
     h0, w0 = scene.shape[0] // A, scene.shape[1] // A
     patches = divide(scene, A, patch, stride)
+    if ensemble is not None:
+        from . import ensemble as ens
+        mask = ens.mask_of(ensemble)
+        per = max(1, max_batch // len(ens.codes_of(mask)))
+        outs = [net(ens.expand(patches[i:i + per], mask)) for i in range(0, patches.shape[0], per)]
+        return integrate_ensemble(torch.cat(outs, dim=0), mask, A, h0, w0, s, patch, stride)
     outs = [net(patches[i:i + max_batch]) for i in range(0, patches.shape[0], max_batch)]
     return integrate(torch.cat(outs, dim=0), A, h0, w0, s, patch, stride)

@@ -92,6 +92,21 @@ def augment(lr: torch.Tensor, hr: torch.Tensor, rng: np.random.Generator) -> Tup
     return torch.stack(lo).contiguous(), torch.stack(ho).contiguous()
 
 
+def augment_gpu(lr: torch.Tensor, hr: torch.Tensor, rng: np.random.Generator) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`augment` as two kernel launches: the same three rng.random() draws per sample, in the same order, become one dihedral code
+    per sample (bit 0 left-right, bit 1 up-down, bit 2 transpose) and lft_dihedral_batch moves lr and hr; bit-identical to
+    `augment` for equally seeded generators."""
+    from . import ensemble
+    codes = np.empty(lr.shape[0], dtype=np.int32)
+    for i in range(lr.shape[0]):
+        c = 1 if rng.random() < 0.5 else 0
+        c |= 2 if rng.random() < 0.5 else 0
+        c |= 4 if rng.random() < 0.5 else 0
+        codes[i] = c
+    codes_dev = torch.from_numpy(codes).to(lr.device)
+    return ensemble.dihedral_batch(lr, codes_dev), ensemble.dihedral_batch(hr, codes_dev)
+
+
 # ---------------------------------------------------------------------------------------------- patch sources
 class TensorPatchSource:
     def __init__(self, lr: torch.Tensor, hr: torch.Tensor):
@@ -142,13 +157,15 @@ def psnr_gpu(sr: torch.Tensor, hr: torch.Tensor) -> float:
 def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: int = 15, gamma: float = 0.5,
         start_epoch: int = 0, ckpt_dir: Optional[str] = None, model_name: str = "LFT", seed: int = 0,
         use_augmentation: bool = True, log=print, max_batches_per_epoch: Optional[int] = None, decay_rate: float = 0.0,
-        batch_metrics: bool = False, ssim_range: float = 2.0):
+        batch_metrics: bool = False, ssim_range: float = 2.0, gpu_augment: bool = False):
     """Train ``net`` (lft_amd.module.get_model on this rank's GPU) like reference train.py:86-110.  ``batch_size`` is
     the GLOBAL batch (reference --batch_size).  Returns the list of per-epoch mean losses (global).
     batch_metrics: also compute the reference's per-batch ``cal_metrics(args, label, out)`` (train.py:121-124: per-view PSNR / SSIM of
     the step's own output, means over positive views, then the mean over the epoch's batches) -- on the GPU (lft_view_metrics), with
     no host synchronisation inside the epoch -- and log the reference's line ('... loss is: %.5f, psnr is %.5f, ssim is %.5f');
-    ``fit.last_metrics`` then holds the per-epoch (psnr, ssim) pairs."""
+    ``fit.last_metrics`` then holds the per-epoch (psnr, ssim) pairs.
+    gpu_augment: augment with `augment_gpu` (one lft_dihedral_batch launch per tensor) instead of `augment`'s per-sample torch ops;
+    the batches are bit-identical."""
     import torch.distributed as dist
     from .train import TrainStep
     rank, _, world = dp.env_world()
@@ -170,7 +187,7 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
             a, b = source.get(ix)
             a, b = a.to(dev, non_blocking=True), b.to(dev, non_blocking=True)
             if use_augmentation:
-                a, b = augment(a, b, rng)
+                a, b = (augment_gpu if gpu_augment else augment)(a, b, rng)
             loss = ts.step(a, b)
             if batch_metrics:
                 from . import metrics
