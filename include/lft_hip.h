@@ -279,6 +279,28 @@ int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int
                    const int* crops, int n_crops, int crop_h, int crop_w, const double* weights_h, const int* indices_h, int taps_h,
                    const double* weights_w, const int* indices_w, int taps_w, float* hr, float* lr, void* stream);
 
+/* ---- colour path: a raw RGB light field in, super-resolved RGB views out ----
+ * lf, lf_class, U, V, H, W, C, strides, A: the light field and its centre A x A views, as for lft_lf_prepare (any strides, a
+ *     v7.3 .mat's reversed array read in place), with ONE difference: the values are scaled to [0, 1] first, x = double(LF) / 255
+ *     for LFT_LF_UINT8 and x = double(LF) for the float classes (stored in [0, 1]); lft_lf_prepare takes them as stored.
+ * Per view, in fp64: ycc = rgb2ycbcr(x) (reference utils/utils.py:160-168).
+ * lft_lf_luma: y_out = single(ycc[..., 0]) as the network's input mosaic [A*H, A*W] (row u*H + h, column v*W + w).
+ * lft_colour_merge: Cb and Cr are up-scaled by imresize(., s) (reference utils/imresize.py: Keys cubic a = -0.5, no antialiasing,
+ *     symmetric border, rows first) with the caller's contribution tables, weights_* fp64 [s*L, taps] and indices_* int32
+ *     [s*L, taps] on the device (lft_amd/colour.py:up_contributions; L = H for _h, W for _w; 1 <= taps <= 6).
+ *     Y is sr_y, the fp32 mosaic [A*s*H, A*s*W] of the super-resolved luma, or with sr_y == NULL the up-scaled ycc[..., 0]: the
+ *     bicubic baseline.  rgb = Minv * (255 * [Y, Cb, Cr] - [16, 128, 128]), minv: HOST array of 9 doubles, the row-major inverse
+ *     of rgb2ycbcr's 3 x 3 matrix (evaluated by the caller in fp64; read before the call returns).
+ *     out: [A, A, s*H, s*W, 3] interleaved RGB; out_class LFT_LF_UINT8 stores convertDouble2Byte(rgb) (clip to [0, 1], * 255,
+ *     round half to even), LFT_LF_FLOAT32 stores single(rgb), unclipped.  s is 2 or 4.
+ * Both calls only enqueue on `stream` (graph-capturable), allocate nothing, and refuse bad arguments with LFT_ERR_ARG or
+ * LFT_ERR_SHAPE before anything is launched. */
+int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, float* y_out,
+                void* stream);
+int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
+                     const float* sr_y, const double* weights_h, const int* indices_h, int taps_h, const double* weights_w,
+                     const int* indices_w, int taps_w, const double* minv, void* out, int out_class, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_vo
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LFT_LIB_PATH") or os.path.join(HERE, "liblft_hip.so")   # LFT_LIB_PATH: experiment builds (tools/ab_build.py)
-SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh"]
+SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh", "lft_colour.cuh"]
 ABI_VERSION = 5                      # LFT_ABI_VERSION of include/lft_hip.h: lib() refuses a library that reports another one
 STATUS_NONFINITE = 1001              # LFT_STATUS_NONFINITE
 
@@ -154,6 +154,10 @@ _SIGS = {
     "lft_lf_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_int,
                                POINTER(c_int), c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p]),
+    "lft_lf_luma": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_void_p, c_void_p]),
+    "lft_colour_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), c_void_p, c_int,
+                                 c_void_p]),
     # test-only entry point (include/lft_hip_test.h)
     "lft_mfma_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lft_prod_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -39,6 +39,7 @@ namespace {
 #endif
 #if LFT_TU != 2
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
+#include "lft_colour.cuh"    // colour path: RGB light field -> Y mosaic; SR Y + up-scaled chroma -> RGB views
 #endif
 }  // namespace
 
@@ -1025,6 +1026,73 @@ int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int
         else k_lf_prepare<double><<<grid, 256, 0, st>>>(a, c);
         LFT_LAUNCH_OK("k_lf_prepare");
     }
+    return 0;
+}
+
+// ---- colour path (lft_colour.cuh) ----
+namespace {
+// what lft_lf_luma and lft_colour_merge ask of the light field; nothing is launched when this fails
+int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A) {
+    if (!lf || !strides) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
+        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", who, lf_class);
+    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
+        return fail(LFT_ERR_SHAPE, "%s: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", who, U, V, H, W, C);
+    for (int i = 0; i < 5; ++i)
+        if (strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, strides[i]);
+    if (A < 1 || A > U || A > V) return fail(LFT_ERR_SHAPE, "%s: angRes %d outside the %d x %d views", who, A, U, V);
+    if ((U - A) % 2 || (V - A) % 2)
+        return fail(LFT_ERR_SHAPE, "%s: U-A = %d and V-A = %d must be even (the centre-view index 0.5*(U-A+2) is not an integer)", who, U - A, V - A);
+    if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
+    return 0;
+}
+}  // namespace
+
+int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, float* y_out,
+                void* stream) {
+    if (!y_out) return fail(LFT_ERR_ARG, "lft_lf_luma: null pointer");
+    if (int rc = colour_lf_ok("lft_lf_luma", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
+    const long long blocks = ((long long)H * W + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "lft_lf_luma: views of %d x %d need more than 2^31 blocks", H, W);
+    LumaArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.H = H; a.W = W; a.y = y_out;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)blocks, (unsigned)(A * A));
+    if (lf_class == LFT_LF_UINT8) k_lf_luma<uint8_t><<<grid, 256, 0, st>>>(a);
+    else if (lf_class == LFT_LF_FLOAT32) k_lf_luma<float><<<grid, 256, 0, st>>>(a);
+    else k_lf_luma<double><<<grid, 256, 0, st>>>(a);
+    LFT_LAUNCH_OK("k_lf_luma");
+    return 0;
+}
+
+int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
+                     const float* sr_y, const double* weights_h, const int* indices_h, int taps_h, const double* weights_w,
+                     const int* indices_w, int taps_w, const double* minv, void* out, int out_class, void* stream) {
+    if (!weights_h || !indices_h || !weights_w || !indices_w || !minv || !out) return fail(LFT_ERR_ARG, "lft_colour_merge: null pointer");
+    if (int rc = colour_lf_ok("lft_colour_merge", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
+    if (s != 2 && s != 4) return fail(LFT_ERR_SHAPE, "lft_colour_merge: scale factor must be 2 or 4, got %d", s);
+    if (taps_h < 1 || taps_w < 1 || taps_h > kColMaxTaps || taps_w > kColMaxTaps)
+        return fail(LFT_ERR_ARG, "lft_colour_merge: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kColMaxTaps);
+    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_colour_merge: output class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", out_class);
+    const long long tiles = (((long long)s * H + kColTile - 1) / kColTile) * (((long long)s * W + kColTile - 1) / kColTile);
+    if ((long long)s * H > 0x7fffffffLL || (long long)s * W > 0x7fffffffLL || tiles > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "lft_colour_merge: views of %d x %d at %dx need more than 2^31 blocks", H, W, s);
+    ColourArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s; a.H = H; a.W = W; a.ph = taps_h; a.pw = taps_w;
+    a.sr_y = sr_y; a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w;
+    for (int i = 0; i < 9; ++i) a.minv[i] = minv[i];
+    a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)tiles, (unsigned)(A * A));
+    if (lf_class == LFT_LF_UINT8) k_colour_merge<uint8_t><<<grid, 256, 0, st>>>(a);
+    else if (lf_class == LFT_LF_FLOAT32) k_colour_merge<float><<<grid, 256, 0, st>>>(a);
+    else k_colour_merge<double><<<grid, 256, 0, st>>>(a);
+    LFT_LAUNCH_OK("k_colour_merge");
     return 0;
 }
 

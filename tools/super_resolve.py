@@ -1,0 +1,70 @@
+"""Super-resolve one raw RGB light field and write its views as PNG files (GPU box).
+
+  python tools/super_resolve.py --angRes 5 --scale_factor 4 --path_pre_pth LFT_5x5_4x.pth.tar --lf scene.mat --out_dir out/
+                                [--self_ensemble dihedral|flips|none] [--precision fp32|bf16|fp16] [--bicubic] [--mosaic]
+
+The scene is a light-field .mat with the variable LF [U, V, H, W, C] (uint8, or single / double in [0, 1]); its centre angRes x angRes
+views are the LOW-resolution input.  Writes <out_dir>/view_<u>_<v>.png, 8-bit RGB, one per view (lft_amd.colour.super_resolve_lf:
+the network super-resolves the luma, the chroma is up-scaled bicubically).  --bicubic adds bicubic_<u>_<v>.png, the bicubic
+up-scaling of every channel that comparison figures show beside the result; --mosaic adds mosaic.png (and bicubic_mosaic.png), the
+whole array of views in one image."""
+import argparse
+import os
+import sys
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from lft_amd import colour, png, prepare, trainer  # noqa: E402
+
+
+def write_views(out_dir: str, views: torch.Tensor, prefix: str, mosaic_name=None):
+    """views: uint8 [A, A, H, W, 3] on any device.  Returns the paths written."""
+    v = views.cpu().numpy()
+    A = v.shape[0]
+    paths = []
+    for u in range(A):
+        for w in range(A):
+            paths.append(os.path.join(out_dir, f"{prefix}_{u}_{w}.png"))
+            png.write_png(paths[-1], v[u, w])
+    if mosaic_name:
+        paths.append(os.path.join(out_dir, mosaic_name))
+        png.write_png(paths[-1], v.transpose(0, 2, 1, 3, 4).reshape(A * v.shape[2], A * v.shape[3], 3))
+    return paths
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--angRes", type=int, default=5)
+    ap.add_argument("--scale_factor", type=int, default=4)
+    ap.add_argument("--path_pre_pth", required=True, help="checkpoint in the reference's format")
+    ap.add_argument("--lf", required=True, help="light-field .mat (variable LF)")
+    ap.add_argument("--out_dir", required=True)
+    ap.add_argument("--self_ensemble", default=None, help="dihedral, flips or none (lft_amd.ensemble.MASKS); default: one pass")
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "fp16"))
+    ap.add_argument("--bicubic", action="store_true", help="also write the bicubic baseline")
+    ap.add_argument("--mosaic", action="store_true", help="also write the whole array of views as one PNG")
+    ap.add_argument("--patch_size_for_test", type=int, default=32)
+    ap.add_argument("--stride_for_test", type=int, default=16)
+    args = ap.parse_args(argv)
+
+    from model import LFT
+    dev = torch.device("cuda", 0)
+    net = LFT.get_model(SimpleNamespace(channels=64, angRes=args.angRes, scale_factor=args.scale_factor),
+                        precision=args.precision).to(dev).eval()
+    trainer.load_checkpoint(net, args.path_pre_pth)
+    lf = prepare.to_device(prepare.load_lf(args.lf), args.angRes, dev)
+    os.makedirs(args.out_dir, exist_ok=True)
+    sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble)
+    paths = write_views(args.out_dir, sr, "view", "mosaic.png" if args.mosaic else None)
+    if args.bicubic:
+        paths += write_views(args.out_dir, colour.bicubic_lf(lf, args.angRes, args.scale_factor), "bicubic",
+                             "bicubic_mosaic.png" if args.mosaic else None)
+    print(f"{args.out_dir}: {len(paths)} PNG files, views of {sr.shape[3]} x {sr.shape[2]}")
+    return paths
+
+
+if __name__ == "__main__":
+    main()
