@@ -30,6 +30,12 @@
  *    lft_amd/csrc/lft_api.hip): views below 128 pixels, 32- and 64-wide views with h*w % 128 == 0, ragged sizes (13x11, 17x19,
  *    35x37, 31x32), sizes that are lane-major in fp32 only (16x24, 24x16), 62x64, both sides of the k_spa1 chunk switch (53x55 |
  *    54x56 in 16 bit, 57x59 | 58x60 in fp32), and the widest views (3x75, 3x347; init_features only).
+ *    Training (lft_train_*): the GEMM and weight-gradient kernels are chosen by the token count N = B*A*A*h*w and the view width;
+ *    gradients are compared with float64 autograd over the oracle in every class of that dispatch (tests/train_classes.py,
+ *    tests/test_gpu_train_classes.py), block by block in the three math modes: 4 096 tokens of 32-wide views (A2 2x B1 32x32),
+ *    40 000 (A5 2x B16 10x10), 65 536 = the last size before the ring-fed GEMM (A8 4x B16 8x8), 72 600 (A11 2x B6 10x10; also the
+ *    whole network, all 78 gradients), 76 800 = three 5x5 patches of 32x32 (A5 2x B3 32x32) and 69 192 at 4x (A6 4x B2 31x31:
+ *    up-sampler and feature extractor); besides the small shapes and fixtures (<= 12 800 tokens) of tests/test_gpu_train.py.
  */
 #ifndef LFT_HIP_H
 #define LFT_HIP_H

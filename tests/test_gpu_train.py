@@ -530,8 +530,10 @@ def test_fit_batch_metrics_are_the_reference_loops_cal_metrics(tmp_path):
 @pytest.mark.parametrize("hw", [(32, 32), (33, 35), (26, 32)], ids=["32x32", "33x35_ragged", "26x32_rows_across_workgroups"])
 @pytest.mark.parametrize("math", MATHS)
 def test_full_size_backward_properties_cfg3(math, hw):
-    """BASELINE configs[2] shape (A5, 2x, 32x32 LR views), where autograd over the CPU oracle takes minutes: properties
-    that hold at any size instead.  For a fixed forward the backward pass is linear in d loss / d out, and patches never
+    """BASELINE configs[2] shape (A5, 2x, 32x32 LR views): properties that hold at any size.  (Autograd over the WHOLE CPU oracle
+    takes minutes at 32x32 views, because of its dense [hw, hw] window mask; block by block it takes seconds, and
+    tests/test_gpu_train_classes.py compares every block of this shape with fp64 autograd -- a backward kernel that is consistently
+    wrong passes the properties here, which hold for any linear map.)  For a fixed forward the backward pass is linear in d loss / d out, and patches never
     interact, so (i) grads(a*g1 + g2) = a*grads(g1) + grads(g2), (ii) the gradient of a 3-patch batch is the sum of the
     per-patch gradients; and the forward-with-tape must agree with the fused inference kernels.  Three patches are 76 800 tokens:
     the batch runs the ring-fed GEMM kernel (k_linr, above 65 536 tokens), the single patches the direct one (k_lin) -- (ii) and
