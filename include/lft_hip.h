@@ -257,6 +257,42 @@ int lft_l1_loss(const float* sr, const float* hr, long long n, float* dsr, float
  * then weight_decay * p is added (torch's L2 form); bias corrections are computed in double, as torch does. */
 int lft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                   int step, float gscale, float weight_decay, void* stream);
+/* ---- guarded Adam step: gradient-norm clipping, non-finite gradients skipped, frozen tensors, all decided on the device ----
+ * lft_adam_step applies whatever the gradient buffer holds.  lft_adam_step_guarded first measures it (one pass, fp64 sums folded
+ * in a fixed order: bit-reproducible), then
+ *   - a NaN / inf anywhere in a TRAINABLE segment: p, m and v keep their bits, steps_skipped += 1, Adam's step counter does not
+ *     advance (the next clean call uses the same bias corrections as if the bad call had not happened);
+ *   - otherwise coef = min(1, max_norm / (norm + 1e-6)) with norm = gscale * sqrt(sum of g^2 over the trainable segments), in
+ *     double -- torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False)'s formula; coef = 1 when max_norm <= 0 or +inf (no
+ *     clipping) --, steps_applied += 1 =: t, and lft_adam_step's update with g * gscale * coef in place of g * gscale and bias
+ *     corrections 1 - beta^t formed in double, on the trainable segments only.
+ * Unlike torch, which scales .grad in place, the gradient buffer is NEVER written: the clip is folded into the update.
+ * Guard block: a caller-owned DEVICE buffer of lft_guard_bytes(nseg) bytes, 16-byte aligned, that lives across steps.  It holds the
+ * segment table (one segment per tensor of the flat buffer: ascending, tiling [0, n) exactly; trainable = 0 freezes a tensor --
+ * its p, m, v are never touched and its gradient, NaN included, takes no part in the norm or the decision, as torch ignores a
+ * parameter without .grad), the counters and the report of the last step.
+ *   lft_guard_init        : enqueue the writing of the block.  segs is a HOST array read before the call returns.  steps_applied0:
+ *                           Adam steps already taken (0 for a fresh optimizer; resuming at step t + 1 passes t).  The library
+ *                           remembers (guard address -> n, block count) on the host, so that lft_adam_step_guarded can refuse
+ *                           a block it did not initialise, or another n, before anything is launched; the newest 256 blocks
+ *                           are remembered.
+ *   lft_adam_step_guarded : three launches on `stream`; no allocation, no synchronisation, graph-capturable -- the step number is
+ *                           read from the block, so a captured call replays correctly.
+ *   lft_guard_read        : copy the report to *host; SYNCHRONISES `stream`.  grad_norm, clip_coef (0 on a skipped step),
+ *                           skipped_last, nonfinite_last (trainable segments) and bad_segment (first trainable segment holding a
+ *                           non-finite element, -1 if none) describe the LAST call; seg_norm[i] = gscale * sqrt(sum of the finite
+ *                           g^2 of segment i), frozen segments included; the three counters run since lft_guard_init.
+ * LFT_ERR_ARG / LFT_ERR_SHAPE before anything is launched: null or misaligned pointers, nseg outside 1..128, a table that does not
+ * tile [0, n) in ascending order with counts >= 1, a block that was not initialised, n other than lft_guard_init's, NaN max_norm. */
+#define LFT_GUARD_MAX_SEGMENTS 128
+typedef struct { long long first, count; int trainable; } lft_segment;
+typedef struct { float grad_norm, clip_coef; int skipped_last, bad_segment; long long nonfinite_last,
+                 steps_applied, steps_skipped, steps_clipped; float seg_norm[LFT_GUARD_MAX_SEGMENTS]; } lft_guard_report;
+int lft_guard_bytes(int nseg, size_t* out_bytes);
+int lft_guard_init(void* guard, const lft_segment* segs, int nseg, long long n, long long steps_applied0, void* stream);
+int lft_adam_step_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                          float gscale, float weight_decay, float max_norm, void* guard, void* stream);
+int lft_guard_read(const void* guard, void* stream, lft_guard_report* host);
 
 /* ---- per-view quality metrics (reference utils/utils.py:56-88 cal_metrics, which calls scikit-image) ----
  * label, out: fp32 mosaics [B,1,A*h,A*w]; psnr, ssim: fp32 [B*A*A] in (b, u, v) order.  PSNR = 10 log10(R^2 / MSE) with

@@ -17,6 +17,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cmath>
+#include <map>
+#include <mutex>
 #include <set>
 #include <string>
 #include <algorithm>
@@ -36,6 +38,7 @@ namespace {
 #include "lft_train.cuh"     // training kernels; the fp32 inference path shares their LDS-tiled window attention
 #if LFT_TU != 1
 #include "lft_attn_maps.cuh" // attention weights from the tape's Q | K (lft_train_attn_maps)
+#include "lft_optim.cuh"     // guarded Adam step: gradient statistics, skip / clip decision, update (lft_adam_step_guarded)
 #endif
 #if LFT_TU != 2
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
@@ -1300,6 +1303,96 @@ int lft_adam_step(float* p, const float* g, float* m, float* v, long long n, flo
     const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step)), bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));   // in double, as torch.optim.Adam
     k_adam<<<blocks_for(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2, gscale, weight_decay);
     LFT_LAUNCH_OK("k_adam");
+    return 0;
+}
+
+// ---- guarded Adam step (lft_optim.cuh) ----
+namespace {
+// Host memory of the guard blocks lft_guard_init wrote: what lft_adam_step_guarded needs to size its launches and to refuse a
+// foreign block or another n without reading device memory.  Bounded: the oldest entry goes when a 257th block is initialised.
+struct GuardHost { long long n; int nseg, nblocks; unsigned long long seq; };
+constexpr size_t kGuardHostMax = 256;
+std::mutex g_guard_mu;
+std::map<const void*, GuardHost> g_guards;
+unsigned long long g_guard_seq = 0;
+
+}  // namespace
+
+int lft_guard_bytes(int nseg, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
+    if (nseg < 1 || nseg > kGuardMaxSeg) return fail(LFT_ERR_ARG, "nseg %d outside 1..%d", nseg, kGuardMaxSeg);
+    *out_bytes = sizeof(GuardBlock) + (size_t)(kGuardMaxChunks + nseg) * sizeof(GuardPart);
+    return 0;
+}
+int lft_guard_init(void* guard, const lft_segment* segs, int nseg, long long n, long long steps_applied0, void* stream) {
+    if (!guard || !segs) return fail(LFT_ERR_ARG, "null pointer");
+    if ((uintptr_t)guard & 15) return fail(LFT_ERR_ARG, "the guard block must be 16-byte aligned");
+    if (nseg < 1 || nseg > kGuardMaxSeg) return fail(LFT_ERR_ARG, "nseg %d outside 1..%d", nseg, kGuardMaxSeg);
+    if (n < 1) return fail(LFT_ERR_SHAPE, "n must be positive, got %lld", n);
+    if (steps_applied0 < 0) return fail(LFT_ERR_ARG, "steps_applied0 must not be negative, got %lld", steps_applied0);
+    GuardInitArgs a = {};
+    long long off = 0;
+    for (int i = 0; i < nseg; ++i) {
+        if (segs[i].first != off || segs[i].count < 1 || segs[i].count > n - off)
+            return fail(LFT_ERR_SHAPE, "segment %d (first %lld, count %lld) does not continue the tiling of [0, %lld) at %lld", i,
+                        segs[i].first, segs[i].count, n, off);
+        a.count[i] = segs[i].count;
+        if (segs[i].trainable) a.trainable[i >> 5] |= 1u << (i & 31);
+        off += segs[i].count;
+    }
+    if (off != n) return fail(LFT_ERR_SHAPE, "the %d segments cover [0, %lld), not [0, %lld)", nseg, off, n);
+    a.n = n; a.steps0 = steps_applied0; a.nseg = nseg;
+    a.per = kGuardChunk;                                            // floats per block; larger only to bound the number of partials
+    if ((n + a.per - 1) / a.per > kGuardMaxChunks) a.per = ((n + kGuardMaxChunks - 1) / kGuardMaxChunks + 1023) / 1024 * 1024;
+    int nblocks = 0;
+    for (int i = 0; i < nseg; ++i) nblocks += (int)((a.count[i] + a.per - 1) / a.per);
+    if (nblocks > kGuardMaxChunks + nseg) return fail(LFT_ERR_SHAPE, "internal: %d blocks for %d segments", nblocks, nseg);
+    k_guard_init<<<1, kGuardMaxSeg, 0, static_cast<hipStream_t>(stream)>>>(static_cast<GuardBlock*>(guard), a);
+    LFT_LAUNCH_OK("k_guard_init");
+    std::lock_guard<std::mutex> lock(g_guard_mu);
+    g_guards[guard] = GuardHost{n, nseg, nblocks, ++g_guard_seq};
+    if (g_guards.size() > kGuardHostMax) {
+        auto oldest = g_guards.begin();
+        for (auto it = g_guards.begin(); it != g_guards.end(); ++it)
+            if (it->second.seq < oldest->second.seq) oldest = it;
+        g_guards.erase(oldest);
+    }
+    return 0;
+}
+int lft_adam_step_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                          float gscale, float weight_decay, float max_norm, void* guard, void* stream) {
+    if (!p || !g || !m || !v || !guard) return fail(LFT_ERR_ARG, "null pointer");
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) return fail(LFT_ERR_ARG, "p, g, m, v must be 4-byte aligned");
+    if (weight_decay < 0.0f) return fail(LFT_ERR_ARG, "weight decay must not be negative");
+    if (std::isnan(max_norm)) return fail(LFT_ERR_ARG, "max_norm is NaN (<= 0 or +inf switches clipping off)");
+    GuardHost h;
+    {
+        std::lock_guard<std::mutex> lock(g_guard_mu);
+        auto it = g_guards.find(guard);
+        if (it == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
+        h = it->second;
+    }
+    if (n != h.n) return fail(LFT_ERR_SHAPE, "n = %lld, but the guard block was initialised for %lld", n, h.n);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GuardBlock* gb = static_cast<GuardBlock*>(guard);
+    const int clip = max_norm > 0.0f && !std::isinf(max_norm);
+    k_grad_stats<<<h.nblocks, kGuardThreads, 0, st>>>(g, gb);
+    LFT_LAUNCH_OK("k_grad_stats");
+    k_guard_final<<<1, kGuardThreads, 0, st>>>(gb, gscale, max_norm, clip, beta1, beta2);
+    LFT_LAUNCH_OK("k_guard_final");
+    k_adam_guarded<<<h.nblocks, kGuardThreads, 0, st>>>(p, g, m, v, gb, lr, beta1, beta2, eps, gscale, weight_decay);
+    LFT_LAUNCH_OK("k_adam_guarded");
+    return 0;
+}
+int lft_guard_read(const void* guard, void* stream, lft_guard_report* host) {
+    if (!guard || !host) return fail(LFT_ERR_ARG, "null pointer");
+    {
+        std::lock_guard<std::mutex> lock(g_guard_mu);
+        if (g_guards.find(guard) == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LFT_HIP_OK(hipMemcpyAsync(host, guard, sizeof(lft_guard_report), hipMemcpyDeviceToHost, st));   // the report is the block's first member
+    LFT_HIP_OK(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -1,0 +1,233 @@
+// lft_optim.cuh -- the guarded Adam step (lft_adam_step_guarded): gradient statistics, the skip / clip decision and the update,
+// three launches on one stream with no host round trip, so that a non-finite gradient or an exploding norm is dealt with on the
+// device and the call is graph-capturable (Adam's step counter lives in the guard block, not in a host scalar).
+//
+//   k_guard_init    writes the guard block: the segment table (one segment per parameter tensor of the flat buffer), the block
+//                   map derived from it, the counters, an empty report.
+//   k_grad_stats    ONE pass over the flat fp32 gradient buffer: per block the sum of squares (fp64: the square of an fp32 number
+//                   is exact in fp64, nothing rounds before it is added) and the number of non-finite elements, which are left
+//                   out of the sum.  No floating-point atomics: every block writes one partial.
+//   k_guard_final   one workgroup folds the partials in a fixed order (bit-reproducible run to run), per segment and over the
+//                   trainable segments, and decides: a non-finite element in a trainable segment -> skip (only steps_skipped
+//                   advances); otherwise coef = min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s formula, in
+//                   double --, steps_applied += 1 =: t, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in double as lft_adam_step forms them.
+//   k_adam_guarded  k_adam's arithmetic with gi = g * gscale * coef + wd * p over the trainable segments only; on skip p, m and v
+//                   keep their bits.
+//
+// DIFFERENCE FROM TORCH: clip_grad_norm_ scales .grad in place, so a later reader of .grad sees the clipped gradient.  Here the
+// gradient buffer is NEVER written: the coefficient is folded into the update, and g after the call is what the backward pass (and
+// the all-reduce) left there.  The report carries the norm and the coefficient for whoever wants the clipped values.
+//
+// Block map: a block works on at most `per` consecutive floats of ONE segment (per = kGuardChunk, larger only for buffers beyond
+// kGuardChunk * kGuardMaxChunks floats, so that the number of partials is bounded by the segment count alone); segment i owns
+// blocks bstart[i] .. bstart[i + 1] - 1.  Segments begin at arbitrary float offsets: a block's range is split into a scalar head
+// up to the first 16-byte boundary, 16-byte loads / stores, and a scalar tail.
+
+constexpr int kGuardMaxSeg = 128;          // seg_norm[128] of lft_guard_report
+constexpr int kGuardChunk = 2048;          // floats per block: 256 threads x two 16-byte accesses per array
+constexpr int kGuardMaxChunks = 2048;      // n / per never exceeds this; the map has at most kGuardMaxChunks + nseg blocks
+constexpr int kGuardThreads = 256;
+
+struct GuardPart { double sumsq; unsigned long long bad; };
+struct GuardBlock {
+    lft_guard_report rep;                  // first: lft_guard_read copies exactly this
+    long long n, per;
+    int nseg, nblocks;
+    float bc1, bc2;                        // Adam's bias corrections of the step k_guard_final admitted last
+    long long first[kGuardMaxSeg], count[kGuardMaxSeg];
+    int trainable[kGuardMaxSeg];
+    int bstart[kGuardMaxSeg + 1];
+    int pad_[3];                           // the partials that follow the block start on a 16-byte boundary
+};
+static_assert(sizeof(GuardBlock) % 16 == 0, "GuardPart array behind the block must be 16-byte aligned");
+static_assert(sizeof(lft_guard_report) == 48 + 4 * kGuardMaxSeg, "lft_guard_report has no padding");
+
+__device__ __host__ inline GuardPart* guard_parts(GuardBlock* gb) { return reinterpret_cast<GuardPart*>(gb + 1); }
+__device__ __host__ inline const GuardPart* guard_parts(const GuardBlock* gb) { return reinterpret_cast<const GuardPart*>(gb + 1); }
+
+// Passed BY VALUE as the kernel's argument: the host table is read when the launch is enqueued, no copy from caller memory is
+// left in flight when lft_guard_init returns.  first[] is implied by the counts (the table tiles [0, n)).
+struct GuardInitArgs {
+    long long count[kGuardMaxSeg];
+    unsigned trainable[kGuardMaxSeg / 32];
+    long long n, per, steps0;
+    int nseg;
+};
+
+__global__ void k_guard_init(GuardBlock* __restrict__ gb, const GuardInitArgs a) {
+    if (blockIdx.x != 0) return;
+    for (int i = threadIdx.x; i < kGuardMaxSeg; i += blockDim.x) {
+        const bool in = i < a.nseg;
+        gb->count[i] = in ? a.count[i] : 0;
+        gb->trainable[i] = in ? (int)((a.trainable[i >> 5] >> (i & 31)) & 1u) : 0;
+        gb->rep.seg_norm[i] = 0.0f;
+    }
+    if (threadIdx.x != 0) return;
+    long long off = 0;
+    int b = 0;
+    for (int i = 0; i < kGuardMaxSeg; ++i) {
+        gb->first[i] = off;
+        gb->bstart[i] = b;
+        if (i < a.nseg) {
+            off += a.count[i];
+            b += (int)((a.count[i] + a.per - 1) / a.per);
+        }
+    }
+    gb->bstart[kGuardMaxSeg] = b;
+    gb->n = a.n; gb->per = a.per; gb->nseg = a.nseg; gb->nblocks = b;
+    gb->bc1 = 1.0f; gb->bc2 = 1.0f;
+    gb->rep.grad_norm = 0.0f; gb->rep.clip_coef = 1.0f;
+    gb->rep.skipped_last = 0; gb->rep.bad_segment = -1;
+    gb->rep.nonfinite_last = 0;
+    gb->rep.steps_applied = a.steps0; gb->rep.steps_skipped = 0; gb->rep.steps_clipped = 0;
+}
+
+// Segment and float range [lo, hi) of block b (b < gb->nblocks): the last segment whose first block is <= b.
+__device__ inline int guard_range(const GuardBlock* __restrict__ gb, int b, long long* lo, long long* hi) {
+    int s0 = 0, s1 = gb->nseg;             // bstart[s0] <= b < bstart[s1]
+    while (s1 - s0 > 1) {
+        const int mid = (s0 + s1) >> 1;
+        if (gb->bstart[mid] <= b) s0 = mid; else s1 = mid;
+    }
+    const long long first = gb->first[s0], end = first + gb->count[s0];
+    *lo = first + (long long)(b - gb->bstart[s0]) * gb->per;
+    *hi = *lo + gb->per < end ? *lo + gb->per : end;
+    return s0;
+}
+// Floats of [lo, hi) in front of the first 16-byte boundary of base + lo (base: a float pointer's address).
+__device__ inline long long guard_head(uintptr_t base, long long lo, long long hi) {
+    const long long head = (long long)((4 - (((base >> 2) + (unsigned long long)lo) & 3)) & 3);
+    return head < hi - lo ? head : hi - lo;
+}
+
+__device__ inline void stats_add(float x, double& sum, unsigned long long& bad) {
+    if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) { ++bad; return; }      // inf or NaN: counted, not summed
+    const double d = (double)x;
+    sum += d * d;
+}
+
+__global__ __launch_bounds__(kGuardThreads) void k_grad_stats(const float* __restrict__ g, GuardBlock* __restrict__ gb) {
+    __shared__ double s_sum[kGuardThreads / 64];
+    __shared__ unsigned long long s_bad[kGuardThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= gb->nblocks) return;
+    long long lo, hi;
+    guard_range(gb, b, &lo, &hi);
+    const long long a = lo + guard_head((uintptr_t)g, lo, hi);
+    const long long nvec = (hi - a) >> 2, vend = a + 4 * nvec;
+    double sum = 0.0;
+    unsigned long long bad = 0;
+    if (lo + tid < a) stats_add(g[lo + tid], sum, bad);                             // head: at most 3 floats
+    for (long long q = tid; q < nvec; q += kGuardThreads) {
+        const float4 x = *reinterpret_cast<const float4*>(g + a + 4 * q);
+        stats_add(x.x, sum, bad); stats_add(x.y, sum, bad); stats_add(x.z, sum, bad); stats_add(x.w, sum, bad);
+    }
+    if (vend + tid < hi) stats_add(g[vend + tid], sum, bad);                        // tail: at most 3 floats
+    for (int off = 32; off > 0; off >>= 1) {                                        // wave64 butterfly: the same order every run
+        sum += __shfl_xor(sum, off);
+        bad += __shfl_xor(bad, off);
+    }
+    if ((tid & 63) == 0) { s_sum[tid >> 6] = sum; s_bad[tid >> 6] = bad; }
+    __syncthreads();
+    if (tid == 0) {
+        GuardPart r = {0.0, 0};
+        for (int w = 0; w < kGuardThreads / 64; ++w) { r.sumsq += s_sum[w]; r.bad += s_bad[w]; }
+        guard_parts(gb)[b] = r;
+    }
+}
+
+__global__ __launch_bounds__(kGuardThreads) void k_guard_final(GuardBlock* __restrict__ gb, float gscale, float max_norm, int clip,
+                                                               float beta1, float beta2) {
+    __shared__ double s_sum[kGuardMaxSeg];
+    __shared__ unsigned long long s_bad[kGuardMaxSeg];
+    if (blockIdx.x != 0) return;
+    const int tid = threadIdx.x, lane = tid & 63, nseg = gb->nseg;
+    const GuardPart* part = guard_parts(gb);
+    for (int s = tid >> 6; s < nseg; s += kGuardThreads / 64) {                     // one wave per segment, lanes stride its partials
+        double sum = 0.0;
+        unsigned long long bad = 0;
+        for (int j = gb->bstart[s] + lane; j < gb->bstart[s + 1]; j += 64) { sum += part[j].sumsq; bad += part[j].bad; }
+        for (int off = 32; off > 0; off >>= 1) {
+            sum += __shfl_xor(sum, off);
+            bad += __shfl_xor(bad, off);
+        }
+        if (lane == 0) {
+            s_sum[s] = sum; s_bad[s] = bad;
+            gb->rep.seg_norm[s] = (float)((double)gscale * sqrt(sum));
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double tot = 0.0;
+    unsigned long long bad = 0;
+    int bad_seg = -1;
+    for (int s = 0; s < nseg; ++s) {                                                // a frozen segment's gradient is ignored
+        if (!gb->trainable[s]) continue;
+        tot += s_sum[s];
+        if (s_bad[s] && bad_seg < 0) bad_seg = s;
+        bad += s_bad[s];
+    }
+    const double norm = (double)gscale * sqrt(tot);
+    gb->rep.grad_norm = (float)norm;
+    gb->rep.nonfinite_last = (long long)bad;
+    gb->rep.bad_segment = bad_seg;
+    if (bad) {                                                                      // nothing else advances
+        gb->rep.skipped_last = 1;
+        gb->rep.clip_coef = 0.0f;
+        gb->rep.steps_skipped += 1;
+        return;
+    }
+    double coef = 1.0;
+    if (clip) {
+        coef = (double)max_norm / (norm + 1e-6);
+        if (coef > 1.0) coef = 1.0;
+    }
+    const float cf = (float)coef;
+    gb->rep.skipped_last = 0;
+    gb->rep.clip_coef = cf;
+    if (cf < 1.0f) gb->rep.steps_clipped += 1;
+    const long long t = gb->rep.steps_applied + 1;
+    gb->rep.steps_applied = t;
+    gb->bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+    gb->bc2 = (float)(1.0 - pow((double)beta2, (double)t));
+}
+
+struct AdamHyper { float lr, b1, b2, eps, bc1, bc2, gscale, coef, wd; };
+__device__ inline void adam_guarded_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
+    const float gi = g * h.gscale * h.coef + h.wd * p;                              // the clip is folded in here; g is not written
+    const float mi = h.b1 * m + (1.0f - h.b1) * gi;
+    const float vi = h.b2 * v + (1.0f - h.b2) * gi * gi;
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / sqrtf(h.bc2) + h.eps;
+    p -= (h.lr / h.bc1) * (mi / denom);
+}
+
+__global__ __launch_bounds__(kGuardThreads) void k_adam_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, const GuardBlock* __restrict__ gb, float lr,
+                                                                float b1, float b2, float eps, float gscale, float wd) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= gb->nblocks || gb->rep.skipped_last) return;
+    long long lo, hi;
+    const int s = guard_range(gb, b, &lo, &hi);
+    if (!gb->trainable[s]) return;
+    const AdamHyper h = {lr, b1, b2, eps, gb->bc1, gb->bc2, gscale, gb->rep.clip_coef, wd};
+    // 16-byte accesses need the four arrays to share their alignment; otherwise the whole range takes the scalar path
+    const unsigned ph = (unsigned)(((uintptr_t)p >> 2) & 3);
+    const bool same = ph == (((uintptr_t)g >> 2) & 3) && ph == (((uintptr_t)m >> 2) & 3) && ph == (((uintptr_t)v >> 2) & 3);
+    const long long a = same ? lo + guard_head((uintptr_t)p, lo, hi) : hi;
+    const long long nvec = (hi - a) >> 2, vend = a + 4 * nvec;
+    for (long long i = lo + tid; i < a; i += kGuardThreads) adam_guarded_one(p[i], g[i], m[i], v[i], h);
+    for (long long q = tid; q < nvec; q += kGuardThreads) {
+        const long long i = a + 4 * q;
+        float4 pp = *reinterpret_cast<float4*>(p + i), mm = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);
+        const float4 gg = *reinterpret_cast<const float4*>(g + i);
+        adam_guarded_one(pp.x, gg.x, mm.x, vv.x, h);
+        adam_guarded_one(pp.y, gg.y, mm.y, vv.y, h);
+        adam_guarded_one(pp.z, gg.z, mm.z, vv.z, h);
+        adam_guarded_one(pp.w, gg.w, mm.w, vv.w, h);
+        *reinterpret_cast<float4*>(p + i) = pp;
+        *reinterpret_cast<float4*>(m + i) = mm;
+        *reinterpret_cast<float4*>(v + i) = vv;
+    }
+    if (vend + tid < hi) adam_guarded_one(p[vend + tid], g[vend + tid], m[vend + tid], v[vend + tid], h);
+}

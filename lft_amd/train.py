@@ -7,7 +7,9 @@ Two ways in:
     fills ``p.grad`` of the 78 parameters, so the reference's ``torch.optim.Adam`` loop works unchanged.
   * :class:`TrainStep` is the MI355X-first loop: parameters, gradients and Adam moments live in three flat fp32
     buffers (the module's parameters become views), the loss gradient, backward, ONE all-reduce over RCCL and the
-    fused Adam update are five enqueues per step.
+    fused Adam update are five enqueues per step.  ``TrainStep(..., max_grad_norm=..., guard=True)`` swaps the update for
+    the guarded one (lft_adam_step_guarded): gradient-norm clipping, a step with a non-finite gradient skipped, frozen
+    (``requires_grad = False``) tensors left alone -- all decided on the device, no host round trip inside the step.
 """
 from __future__ import annotations
 
@@ -161,6 +163,38 @@ def train_backward_buckets(ps, lr, tape, dout, A, s, grads, on_bucket, math="fp3
     return grads
 
 
+# ---------------------------------------------------------------------------------------------- guarded Adam step
+def guard_bytes(nseg: int) -> int:
+    n = ctypes.c_size_t(0)
+    _lib.check(_lib.lib().lft_guard_bytes(nseg, ctypes.byref(n)), "lft_guard_bytes")
+    return n.value
+
+
+def guard_new(segments, n: int, device, steps_applied0: int = 0) -> torch.Tensor:
+    """A guard block (include/lft_hip.h: lft_guard_init) for a flat buffer of n floats; segments: (first, count, trainable) triples
+    that tile [0, n) in ascending order.  Enqueued on the current stream of `device`."""
+    segs = (_lib.GuardSegment * len(segments))(*[_lib.GuardSegment(int(f), int(c), int(bool(t))) for f, c, t in segments])
+    guard = torch.empty(guard_bytes(len(segments)), dtype=torch.uint8, device=device)
+    _lib.check(_lib.lib().lft_guard_init(guard.data_ptr(), segs, len(segments), n, steps_applied0,
+                                         torch.cuda.current_stream(guard.device).cuda_stream), "lft_guard_init")
+    return guard
+
+
+def adam_step_guarded(p, g, m, v, guard, lr, beta1=0.9, beta2=0.999, eps=1e-8, gscale=1.0, weight_decay=0.0, max_norm=None):
+    """lft_adam_step_guarded on flat fp32 tensors; max_norm None (or <= 0, or inf): no clipping.  Only enqueues."""
+    _lib.check(_lib.lib().lft_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
+                                                gscale, weight_decay, 0.0 if max_norm is None else max_norm, guard.data_ptr(),
+                                                torch.cuda.current_stream(p.device).cuda_stream), "lft_adam_step_guarded")
+
+
+def guard_read(guard: torch.Tensor) -> _lib.GuardReport:
+    """lft_guard_read: the report of the last guarded step and the counters.  SYNCHRONISES the current stream."""
+    rep = _lib.GuardReport()
+    _lib.check(_lib.lib().lft_guard_read(guard.data_ptr(), torch.cuda.current_stream(guard.device).cuda_stream, ctypes.byref(rep)),
+               "lft_guard_read")
+    return rep
+
+
 class LFTFunction(torch.autograd.Function):
     """autograd node of the whole network: forward saves the tape, backward returns the 78 parameter gradients (None for a
     parameter that does not need one) and, when the input needs one, the gradient of lr (lft_train_backward_input)."""
@@ -197,11 +231,23 @@ class TrainStep:
     contiguous buckets in which the backward pass finishes it -- each bucket's all-reduce starts as soon as its last
     kernel is enqueued and runs beside the rest of the backward pass -- and averaged inside the Adam kernel (L1Loss is a
     mean over the local shard, shards are equal: SURVEY 8e).
+
+    guard=True (implied by a finite max_grad_norm): the update is lft_adam_step_guarded.  The global gradient norm -- after the
+    all-reduce and the 1/world scale, so every rank decides alike -- is clipped to max_grad_norm as torch.nn.utils.clip_grad_norm_
+    would (the flat gradient buffer itself is NOT scaled: the clip is folded into the update); a step whose gradient holds a NaN or
+    an inf leaves weights and moments untouched and does not advance Adam's step counter; parameters with
+    ``requires_grad == False`` AT CONSTRUCTION are neither updated nor counted, as in the reference's
+    ``[p for p in net.parameters() if p.requires_grad]``.  ``guard_report()`` reads what happened.
     """
 
     def __init__(self, net, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, math: Optional[str] = None,
-                 graph: bool = True, weight_decay: float = 0.0):
+                 graph: bool = True, weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, guard: bool = False):
         self.net, self.lr, self.betas, self.eps = net, float(lr), betas, float(eps)
+        if max_grad_norm is not None and max_grad_norm != max_grad_norm:
+            raise ValueError("max_grad_norm is NaN")
+        clip = max_grad_norm is not None and 0.0 < max_grad_norm < float("inf")
+        self.max_grad_norm = float(max_grad_norm) if clip else None
+        self.guard = bool(guard) or clip
         self.weight_decay = float(weight_decay)                        # reference train.py:82 weight_decay=args.decay_rate (option.py default 0)
         self.math = math or getattr(net, "train_math", "fp32")
         # forward + loss + backward are ~450 kernel launches; for a fixed batch shape they are captured once into a HIP
@@ -230,6 +276,17 @@ class TrainStep:
                 p.grad = self.flat_grads[off:off + k].view(p.shape)
                 off += k
         self.params = ps
+        self._guard = None
+        if self.guard:                     # one segment per parameter tensor, state-dict order; trainable as of now
+            table = param_table(net.channels, self.s)
+            assert [tuple(p.shape) for p in ps] == [tuple(sh) for _, sh, _ in table]
+            self.segment_names = [name for name, _, _ in table]
+            segs, off = [], 0
+            for p in ps:
+                segs.append((off, p.numel(), p.requires_grad))
+                off += p.numel()
+            with torch.cuda.device(dev):
+                self._guard = guard_new(segs, n, dev)
         # Replicas must start from the same weights (the reference has no DP; torch's DDP broadcasts rank 0's
         # parameters at construction): a network built from scratch draws its weights from this process's own RNG.
         from .dp import broadcast_
@@ -341,12 +398,31 @@ class TrainStep:
             dp.sum_gradients_finish(handles)                   # the Adam kernel is ordered after the collectives
             gscale = dp.grad_scale(self.group) if exchange else 1.0
             stream = torch.cuda.current_stream(dev).cuda_stream
-            self.t += 1
-            _lib.check(L.lft_adam_step(self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                       self.flat_params.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.t,
-                                       gscale, self.weight_decay, stream), "lft_adam_step")
+            self.t += 1                    # calls of step(); with the guard Adam's own counter is steps_applied in the guard block
+            if self._guard is None:
+                _lib.check(L.lft_adam_step(self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                           self.flat_params.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.t,
+                                           gscale, self.weight_decay, stream), "lft_adam_step")
+            else:
+                adam_step_guarded(self.flat_params, self.flat_grads, self.m, self.v, self._guard, self.lr, self.betas[0], self.betas[1],
+                                  self.eps, gscale, self.weight_decay, self.max_grad_norm)
         self.net._packed = None            # the inference path must re-pack the new weights
         return loss.clone()
+
+    def guard_report(self) -> dict:
+        """What the guarded update saw and did: ONE synchronising read of the guard block (never called from step()).
+        grad_norm / clip_coef / skipped / nonfinite / bad_parameter describe the last step (bad_parameter: the first trainable
+        parameter, in state-dict order, whose gradient held a NaN or an inf; None if none did); steps_applied / steps_skipped /
+        steps_clipped count since construction; param_norms maps every parameter name, frozen ones included, to the norm of its
+        gradient in the last step (non-finite elements left out)."""
+        if self._guard is None:
+            raise _lib.LftError("guard_report() needs TrainStep(..., guard=True) or a max_grad_norm")
+        with torch.cuda.device(self._guard.device):
+            r = guard_read(self._guard)
+        return {"grad_norm": float(r.grad_norm), "clip_coef": float(r.clip_coef), "skipped": bool(r.skipped_last),
+                "nonfinite": int(r.nonfinite_last), "bad_parameter": self.segment_names[r.bad_segment] if r.bad_segment >= 0 else None,
+                "steps_applied": int(r.steps_applied), "steps_skipped": int(r.steps_skipped), "steps_clipped": int(r.steps_clipped),
+                "param_norms": {name: float(r.seg_norm[i]) for i, name in enumerate(self.segment_names)}}
 
 
 def names(channels: int = 64, scale: int = 2):

@@ -157,7 +157,8 @@ def psnr_gpu(sr: torch.Tensor, hr: torch.Tensor) -> float:
 def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: int = 15, gamma: float = 0.5,
         start_epoch: int = 0, ckpt_dir: Optional[str] = None, model_name: str = "LFT", seed: int = 0,
         use_augmentation: bool = True, log=print, max_batches_per_epoch: Optional[int] = None, decay_rate: float = 0.0,
-        batch_metrics: bool = False, ssim_range: float = 2.0, gpu_augment: bool = False):
+        batch_metrics: bool = False, ssim_range: float = 2.0, gpu_augment: bool = False, max_grad_norm: Optional[float] = None,
+        guard: bool = False):
     """Train ``net`` (lft_amd.module.get_model on this rank's GPU) like reference train.py:86-110.  ``batch_size`` is
     the GLOBAL batch (reference --batch_size).  Returns the list of per-epoch mean losses (global).
     batch_metrics: also compute the reference's per-batch ``cal_metrics(args, label, out)`` (train.py:121-124: per-view PSNR / SSIM of
@@ -165,16 +166,23 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
     no host synchronisation inside the epoch -- and log the reference's line ('... loss is: %.5f, psnr is %.5f, ssim is %.5f');
     ``fit.last_metrics`` then holds the per-epoch (psnr, ssim) pairs.
     gpu_augment: augment with `augment_gpu` (one lft_dihedral_batch launch per tensor) instead of `augment`'s per-sample torch ops;
-    the batches are bit-identical."""
+    the batches are bit-identical.
+    max_grad_norm / guard: the guarded update of TrainStep (gradient-norm clipping; a step with a non-finite gradient is skipped
+    instead of destroying the weights).  The guard block is read ONCE per epoch and the epoch line gains
+    'grad norm %.3g, clipped %d, skipped %d (first bad: <parameter>)' -- norm and parameter of the epoch's last step, counts of the
+    epoch; an epoch in which every step was skipped is reported with a warning.  ``fit.last_guard`` holds the per-epoch reports."""
     import torch.distributed as dist
     from .train import TrainStep
     rank, _, world = dp.env_world()
     if not (dist.is_available() and dist.is_initialized()):
         rank, world = 0, 1
     dev = next(net.parameters()).device
-    ts = TrainStep(net, lr=lr, weight_decay=decay_rate)            # reference train.py:82 weight_decay=args.decay_rate
+    ts = TrainStep(net, lr=lr, weight_decay=decay_rate,            # reference train.py:82 weight_decay=args.decay_rate
+                   max_grad_norm=max_grad_norm, guard=guard)
     history = []
     fit.last_metrics = []
+    fit.last_guard = []
+    seen = {"steps_clipped": 0, "steps_skipped": 0}
     for epoch in range(start_epoch, epochs):
         ts.lr = step_lr(lr, epoch, n_steps, gamma)
         rng = np.random.Generator(np.random.PCG64([seed, epoch, rank, 17]))
@@ -210,8 +218,20 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         if last is not None and not batch_metrics:
             with torch.no_grad():
                 msg += ", psnr(last batch) %.3f" % psnr_gpu(net(last[0]), last[1])
+        warn = None
+        if ts.guard:
+            rep = ts.guard_report()                                # the epoch's one synchronising read (every rank holds the same figures)
+            clipped, skipped = (rep[k] - seen[k] for k in ("steps_clipped", "steps_skipped"))
+            seen = {k: rep[k] for k in seen}
+            fit.last_guard.append(rep)
+            msg += ", grad norm %.3g, clipped %d, skipped %d (first bad: %s)" % (rep["grad_norm"], clipped, skipped, rep["bad_parameter"] or "-")
+            if batches and skipped == len(batches):
+                warn = ("WARNING: every step of epoch %d was skipped for non-finite gradients (last seen in %s): the weights did not move"
+                        % (epoch + 1, rep["bad_parameter"]))
         if rank == 0:
             log(msg)
+            if warn:
+                log(warn)
             if ckpt_dir:
                 save_checkpoint(net, os.path.join(ckpt_dir, checkpoint_name(model_name, net.angRes, net.factor, epoch + 1)), epoch + 1)
     return history

@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--math", default="bf16x3", choices=["fp32", "bf16x3", "bf16x6"])
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--guard", action="store_true", help="the guarded Adam step (lft_adam_step_guarded, no clipping) in place of lft_adam_step")
     args = ap.parse_args()
     from lft_amd import dp, train as T
     from lft_amd.params import deterministic_state, synthetic_lr
@@ -46,7 +47,7 @@ def main():
     net = net.to(dev).train()
     lr = torch.from_numpy(synthetic_lr(args.batch, A, H, H, seed=rank)).to(dev)
     hr = torch.from_numpy(np.random.Generator(np.random.PCG64([2, rank])).random((args.batch, 1, A * H * S, A * H * S), dtype=np.float32)).to(dev)
-    ts = T.TrainStep(net, lr=2e-4, math=args.math, graph=not args.no_graph)
+    ts = T.TrainStep(net, lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard)
 
     def sync():
         if dist is not None:
@@ -74,7 +75,10 @@ def main():
                           "global_batch": args.batch * world, "parallelism": f"dp{world} (one flat-gradient all-reduce per step)"},
                "loss_first_last": [lv[0], lv[-1]],
                "tflops_algorithmic": 3 * flops_fwd * args.batch * world * args.steps / dt / 1e12,
-               "tape_gib": T.tape_bytes(args.batch, A, H, H, S) / 2**30}
+               "tape_gib": T.tape_bytes(args.batch, A, H, H, S) / 2**30, "guard": bool(args.guard)}
+        if args.guard:
+            rep = ts.guard_report()
+            out["guard_report"] = {k: rep[k] for k in ("grad_norm", "steps_applied", "steps_skipped", "steps_clipped")}
         print(json.dumps(out), flush=True)
 
 

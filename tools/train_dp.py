@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--max_batches", type=int, default=0)
     ap.add_argument("--batch_metrics", action="store_true", help="per-batch PSNR / SSIM of train.py:121-124 (on the GPU) and the reference's epoch line")
     ap.add_argument("--gpu_augment", action="store_true", help="augment with one lft_dihedral_batch launch per tensor (same batches, bit for bit)")
+    ap.add_argument("--max_grad_norm", type=float, default=None, help="clip the global gradient norm (as torch's clip_grad_norm_); implies --guard")
+    ap.add_argument("--guard", action="store_true", help="guarded Adam step: a step with a NaN / inf gradient is skipped and reported, frozen tensors stay put")
     args = ap.parse_args()
     import importlib
     from lft_amd import dp, trainer
@@ -66,7 +68,8 @@ def main():
     ckpt_dir = os.path.join(args.path_log, "SR_%dx%d_%dx" % (args.angRes, args.angRes, args.scale_factor), args.model_name, "checkpoints")
     trainer.fit(net, src, args.epoch, args.batch_size, lr=args.lr, n_steps=args.n_steps, gamma=args.gamma, start_epoch=start,
                 ckpt_dir=ckpt_dir, model_name=args.model_name, max_batches_per_epoch=args.max_batches or None,
-                decay_rate=args.decay_rate, batch_metrics=args.batch_metrics, gpu_augment=args.gpu_augment)
+                decay_rate=args.decay_rate, batch_metrics=args.batch_metrics, gpu_augment=args.gpu_augment,
+                max_grad_norm=args.max_grad_norm, guard=args.guard)
 
 
 if __name__ == "__main__":
