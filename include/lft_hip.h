@@ -293,6 +293,17 @@ int lft_guard_init(void* guard, const lft_segment* segs, int nseg, long long n, 
 int lft_adam_step_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                           float gscale, float weight_decay, float max_norm, void* guard, void* stream);
 int lft_guard_read(const void* guard, void* stream, lft_guard_report* host);
+/* Exponential moving average of the weights, kept beside them as one more flat fp32 buffer: ema += a * (p - ema) per element in
+ * fp32, a = (float)(1 - d_t), d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay formed in double, t = Adam steps applied so
+ * far, this one included.  Call it after the Adam step, on the same stream.
+ *   guard != NULL : t is the block's steps_applied, read on the device (`step` is ignored; a captured call replays correctly); after
+ *                   a skipped step ema keeps its bits; frozen segments are never written.  The block must have been initialised for
+ *                   this n.
+ *   guard == NULL : t = step (>= 1), every element of [0, n) is updated.
+ * One launch; no allocation, no synchronisation, no atomics (bit-reproducible), graph-capturable.  16-byte accesses where ema and p
+ * share their alignment, scalar ones otherwise.  LFT_ERR_ARG before anything is launched: null or misaligned pointers, n < 1, ema
+ * and p overlapping, decay outside [0, 1) or NaN, step < 1 without a guard, a block that was not initialised or another n. */
+int lft_ema_update(float* ema, const float* p, long long n, float decay, int warmup, long long step, const void* guard, void* stream);
 
 /* ---- per-view quality metrics (reference utils/utils.py:56-88 cal_metrics, which calls scikit-image) ----
  * label, out: fp32 mosaics [B,1,A*h,A*w]; psnr, ssim: fp32 [B*A*A] in (b, u, v) order.  PSNR = 10 log10(R^2 / MSE) with

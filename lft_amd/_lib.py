@@ -167,6 +167,7 @@ _SIGS = {
     "lft_adam_step_guarded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float,
                                       c_float, c_float, c_float, c_void_p, c_void_p]),
     "lft_guard_read": (c_int, [c_void_p, c_void_p, POINTER(GuardReport)]),
+    "lft_ema_update": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_int, c_longlong, c_void_p, c_void_p]),
     "lft_view_metrics_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "lft_view_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lft_lf_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_int,
@@ -186,6 +187,7 @@ _SIGS = {
 EXPORTS = tuple(_SIGS)
 TEST_EXPORTS = ("lft_mfma_selftest", "lft_prod_selftest", "lft_init_features_legacy_fwd", "lft_conv0_fwd", "lft_tail_fwd")   # declared in include/lft_hip_test.h, not in the product header
 GUARD_EXPORTS = ("lft_guard_bytes", "lft_guard_init", "lft_adam_step_guarded", "lft_guard_read")   # added to ABI 5 without a new version number
+EMA_EXPORTS = ("lft_ema_update",)                                                                  # likewise
 BLOCK_UPSAMPLE, BLOCK_SPA, BLOCK_ANG, BLOCK_INIT = 0, 1, 2, 3    # LFT_BLOCK_* of include/lft_hip.h
 LF_UINT8, LF_FLOAT32, LF_FLOAT64 = 0, 1, 2                      # LFT_LF_* of include/lft_hip.h
 MAPS_MEAN, MAPS_HEADS = 0, 1                                    # LFT_MAPS_* of include/lft_hip.h
@@ -206,7 +208,7 @@ def lib() -> ctypes.CDLL:
         if got != ABI_VERSION:              # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
             raise LftError(f"{LIB_PATH} reports ABI version {got}, this binding needs {ABI_VERSION}: rebuild it (__graft_entry__.build())")
         for name, (res, args) in _SIGS.items():
-            if name in TEST_EXPORTS + GUARD_EXPORTS and not hasattr(L, name):
+            if name in TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS and not hasattr(L, name):
                 continue        # an older LFT_LIB_PATH build of the same ABI version (A/B runs): everything else is there, and asking it for a missing entry point raises
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args

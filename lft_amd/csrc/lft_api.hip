@@ -1395,6 +1395,32 @@ int lft_guard_read(const void* guard, void* stream, lft_guard_report* host) {
     LFT_HIP_OK(hipStreamSynchronize(st));
     return 0;
 }
+int lft_ema_update(float* ema, const float* p, long long n, float decay, int warmup, long long step, const void* guard, void* stream) {
+    if (!ema || !p) return fail(LFT_ERR_ARG, "null pointer");
+    if (((uintptr_t)ema | (uintptr_t)p) & 3) return fail(LFT_ERR_ARG, "ema and p must be 4-byte aligned");
+    if (n < 1) return fail(LFT_ERR_ARG, "n must be positive, got %lld", n);
+    if ((uintptr_t)ema < (uintptr_t)(p + n) && (uintptr_t)p < (uintptr_t)(ema + n)) return fail(LFT_ERR_ARG, "ema and p overlap");
+    if (!(decay >= 0.0f && decay < 1.0f)) return fail(LFT_ERR_ARG, "decay %g outside [0, 1)", (double)decay);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!guard) {
+        if (step < 1) return fail(LFT_ERR_ARG, "step counts from 1, got %lld", step);
+        const long long nchunks = (n + kGuardChunk - 1) / kGuardChunk;
+        k_ema_plain<<<(int)std::min<long long>(nchunks, 65536), kGuardThreads, 0, st>>>(ema, p, n, decay, warmup != 0, step);
+        LFT_LAUNCH_OK("k_ema_plain");
+        return 0;
+    }
+    GuardHost h;
+    {
+        std::lock_guard<std::mutex> lock(g_guard_mu);
+        auto it = g_guards.find(guard);
+        if (it == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
+        h = it->second;
+    }
+    if (n != h.n) return fail(LFT_ERR_ARG, "n = %lld, but the guard block was initialised for %lld", n, h.n);
+    k_ema_guarded<<<h.nblocks, kGuardThreads, 0, st>>>(ema, p, static_cast<const GuardBlock*>(guard), decay, warmup != 0);
+    LFT_LAUNCH_OK("k_ema_guarded");
+    return 0;
+}
 
 #endif  // LFT_TU != 1
 }  // extern "C"

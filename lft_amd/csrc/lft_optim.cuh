@@ -13,6 +13,9 @@
 //                   double --, steps_applied += 1 =: t, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in double as lft_adam_step forms them.
 //   k_adam_guarded  k_adam's arithmetic with gi = g * gscale * coef + wd * p over the trainable segments only; on skip p, m and v
 //                   keep their bits.
+//   k_ema_guarded   (lft_ema_update) ema += a * (p - ema) over the same block map, after the update: a step the guard skipped and a
+//   k_ema_plain     frozen segment leave ema alone, and the step number of the warm-up comes from the block.  k_ema_plain is the
+//                   form without a guard block: chunks of kGuardChunk floats over [0, n), the step number from the caller.
 //
 // DIFFERENCE FROM TORCH: clip_grad_norm_ scales .grad in place, so a later reader of .grad sees the clipped gradient.  Here the
 // gradient buffer is NEVER written: the coefficient is folded into the update, and g after the call is what the backward pass (and
@@ -230,4 +233,53 @@ __global__ __launch_bounds__(kGuardThreads) void k_adam_guarded(float* __restric
         *reinterpret_cast<float4*>(v + i) = vv;
     }
     if (vend + tid < hi) adam_guarded_one(p[vend + tid], g[vend + tid], m[vend + tid], v[vend + tid], h);
+}
+
+// ---- exponential moving average of the weights (lft_ema_update) ----
+// a = (float)(1 - d_t), d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay, in double (IEEE division and subtraction: the host
+// restatement lft_amd.train.ema_decay_at gives the same float).
+__device__ inline float ema_alpha(float decay, int warmup, long long t) {
+    double d = (double)decay;
+    if (warmup) {
+        const double w = (1.0 + (double)t) / (10.0 + (double)t);
+        if (w < d) d = w;
+    }
+    return (float)(1.0 - d);
+}
+__device__ inline void ema_one(float& e, float p, float a) { e += a * (p - e); }
+// [lo, hi) of one block: scalar head up to ema's first 16-byte boundary, 16-byte accesses, scalar tail; all scalar when ema and p
+// do not share their alignment.
+__device__ inline void ema_range(float* __restrict__ ema, const float* __restrict__ p, long long lo, long long hi, float a, int tid) {
+    const bool same = (((uintptr_t)ema >> 2) & 3) == (((uintptr_t)p >> 2) & 3);
+    const long long h = same ? lo + guard_head((uintptr_t)ema, lo, hi) : hi;
+    const long long nvec = (hi - h) >> 2, vend = h + 4 * nvec;
+    for (long long i = lo + tid; i < h; i += kGuardThreads) ema_one(ema[i], p[i], a);
+    for (long long q = tid; q < nvec; q += kGuardThreads) {
+        const long long i = h + 4 * q;
+        float4 ee = *reinterpret_cast<float4*>(ema + i);
+        const float4 pp = *reinterpret_cast<const float4*>(p + i);
+        ema_one(ee.x, pp.x, a); ema_one(ee.y, pp.y, a); ema_one(ee.z, pp.z, a); ema_one(ee.w, pp.w, a);
+        *reinterpret_cast<float4*>(ema + i) = ee;
+    }
+    if (vend + tid < hi) ema_one(ema[vend + tid], p[vend + tid], a);
+}
+
+__global__ __launch_bounds__(kGuardThreads) void k_ema_guarded(float* __restrict__ ema, const float* __restrict__ p,
+                                                               const GuardBlock* __restrict__ gb, float decay, int warmup) {
+    const int b = blockIdx.x;
+    if (b >= gb->nblocks || gb->rep.skipped_last) return;
+    long long lo, hi;
+    const int s = guard_range(gb, b, &lo, &hi);
+    if (!gb->trainable[s]) return;
+    ema_range(ema, p, lo, hi, ema_alpha(decay, warmup, gb->rep.steps_applied), threadIdx.x);
+}
+
+__global__ __launch_bounds__(kGuardThreads) void k_ema_plain(float* __restrict__ ema, const float* __restrict__ p, long long n,
+                                                             float decay, int warmup, long long step) {
+    const float a = ema_alpha(decay, warmup, step);
+    const long long nchunks = (n + kGuardChunk - 1) / kGuardChunk;
+    for (long long c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const long long lo = c * kGuardChunk, hi = lo + kGuardChunk < n ? lo + kGuardChunk : n;
+        ema_range(ema, p, lo, hi, a, threadIdx.x);
+    }
 }

@@ -25,13 +25,14 @@ def test_scene(net, lr_scene: torch.Tensor, hr_scene: torch.Tensor, patch: int =
 
 
 def test(net, scenes: Iterable[Tuple[torch.Tensor, torch.Tensor]], patch: int = 32, stride: int = 16,
-         ssim_range: float = 2.0, ensemble=None) -> Tuple[float, float]:
+         ssim_range: float = 2.0, ensemble=None, sharded: bool = True) -> Tuple[float, float]:
     """Mean PSNR / SSIM over the scenes of one test set (reference test.py:72-110).  Under torch.distributed every rank
-    takes a contiguous share of the scenes (lft_amd.dp.shard_range) and the sums are combined."""
+    takes a contiguous share of the scenes (lft_amd.dp.shard_range) and the sums are combined; sharded=False: the calling rank
+    does every scene itself and no collective is issued (validation on rank 0 between two training epochs)."""
     import torch.distributed as dist
     scenes = list(scenes)
     rank, _, world = dp.env_world()
-    if not (dist.is_available() and dist.is_initialized()):
+    if not sharded or not (dist.is_available() and dist.is_initialized()):
         rank, world = 0, 1
     b, e = dp.shard_range(len(scenes), rank, world)
     acc = np.zeros(3, dtype=np.float64)
@@ -47,7 +48,7 @@ def test(net, scenes: Iterable[Tuple[torch.Tensor, torch.Tensor]], patch: int = 
     return float(acc[0] / acc[2]), float(acc[1] / acc[2])
 
 
-def test_sets(net, args, log=print, patch: int = None, stride: int = None, ssim_range: float = 2.0, ensemble=None):
+def test_sets(net, args, log=print, patch: int = None, stride: int = None, ssim_range: float = 2.0, ensemble=None, sharded: bool = True):
     """The reference's test.py main loop (:60-69) over the test tree of utils_datasets.MultiTestSetDataLoader:
     ``<path_for_test>/SR_{A}x{A}_{s}x/<dataset>/<scene>.h5`` read by lft_amd.datasets (h5lite), every scene through `test_scene`.
     args: path_for_test, angRes, scale_factor (+ patch_size_for_test / stride_for_test as option.py names them).
@@ -59,7 +60,7 @@ def test_sets(net, args, log=print, patch: int = None, stride: int = None, ssim_
     out = {}
     for name, loader in zip(names, loaders):
         scenes = ((lr.squeeze(), hr.squeeze()) for lr, hr in loader)                       # test.py:76-77
-        p, s = test(net, scenes, patch, stride, ssim_range, ensemble)
+        p, s = test(net, scenes, patch, stride, ssim_range, ensemble, sharded)
         out[name] = (p, s)
         log("Test on %s, psnr/ssim is %.2f/%.3f" % (name, p, s))                           # test.py:66
     return out

@@ -10,10 +10,15 @@ Two ways in:
     fused Adam update are five enqueues per step.  ``TrainStep(..., max_grad_norm=..., guard=True)`` swaps the update for
     the guarded one (lft_adam_step_guarded): gradient-norm clipping, a step with a non-finite gradient skipped, frozen
     (``requires_grad = False``) tensors left alone -- all decided on the device, no host round trip inside the step.
+    ``TrainStep(..., ema_decay=...)`` keeps an exponential moving average of the weights in a fourth flat buffer (lft_ema_update,
+    which obeys the guard); ``state_dict()`` / ``load_state_dict()`` carry moments, counters and the average across a restart.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import logging
+from collections import OrderedDict
 from typing import List, Optional
 
 import torch
@@ -195,6 +200,64 @@ def guard_read(guard: torch.Tensor) -> _lib.GuardReport:
     return rep
 
 
+# ---------------------------------------------------------------------------------------------- EMA of the weights
+def ema_decay_at(decay: float, warmup: bool, t: int) -> float:
+    """d_t of lft_ema_update as the kernel forms it: the decay crosses the C ABI as a float, the rest is double."""
+    d = float(torch.tensor(decay, dtype=torch.float32))
+    return min(d, (1.0 + t) / (10.0 + t)) if warmup else d
+
+
+def ema_update(ema, p, decay, warmup=True, step=0, guard=None):
+    """lft_ema_update on flat fp32 tensors: ema += (1 - d_t) * (p - ema).  With a guard block t is its steps_applied and a skipped
+    step or a frozen segment leaves ema alone; without one t = step.  Only enqueues."""
+    _lib.check(_lib.lib().lft_ema_update(ema.data_ptr(), p.data_ptr(), p.numel(), decay, int(bool(warmup)), int(step),
+                                         None if guard is None else guard.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream),
+               "lft_ema_update")
+
+
+# ---------------------------------------------------------------------------------------------- saved optimizer state
+STATE_VERSION = 1
+log = logging.getLogger(__name__)
+
+
+class StateError(ValueError):
+    """A saved training state that does not fit the TrainStep it is loaded into; the message names the field."""
+
+
+def check_state(sd: dict, own: dict) -> List[str]:
+    """Compare a saved state (TrainStep.state_dict()) with the description of the receiving step (the same keys, tensors left out:
+    `ema` is True / False there).  Raises StateError, naming the field, for what cannot be continued; returns one line for every
+    field the caller was free to change."""
+    if not isinstance(sd, dict) or "version" not in sd:
+        raise StateError("version: not a TrainStep state (no format version)")
+    if int(sd["version"]) > STATE_VERSION:
+        raise StateError(f"version: the state has format {sd['version']}, this build reads up to {STATE_VERSION}")
+    missing = [k for k in ("m", "v", "ema", "t", "guard", "floats", "scale", "channels", "A", "trainable") if k not in sd]
+    if missing:
+        raise StateError(f"{missing[0]}: missing from the state")
+    for k in ("floats", "scale", "channels"):
+        if int(sd[k]) != int(own[k]):
+            raise StateError(f"{k}: the state was saved with {sd[k]}, this step has {own[k]}")
+    if [bool(x) for x in sd["trainable"]] != [bool(x) for x in own["trainable"]]:
+        raise StateError("trainable: the state was saved with another set of frozen tensors")
+    if (sd["ema"] is not None) != bool(own["ema"]):
+        raise StateError("ema: " + ("the state holds averaged weights, this step keeps none" if sd["ema"] is not None
+                                    else "this step keeps averaged weights, the state holds none"))
+    if bool(sd["guard"]) != bool(own["guard"]):
+        raise StateError("guard: " + ("a guarded state (Adam's step count is steps_applied) cannot continue an unguarded step"
+                                      if sd["guard"] else "an unguarded state (Adam's step count is t) cannot continue a guarded step"))
+    if sd["guard"]:
+        for k in ("steps_applied", "steps_skipped", "steps_clipped"):
+            if k not in sd:
+                raise StateError(f"{k}: missing from a guarded state")
+    for k in ("m", "v", "ema"):
+        if sd[k] is not None and (tuple(sd[k].shape) != (int(own["floats"]),) or sd[k].dtype != torch.float32):
+            raise StateError(f"{k}: expected {own['floats']} float32 values, got {tuple(sd[k].shape)} {sd[k].dtype}")
+    return [f"{k}: saved with {sd.get(k)!r}, continuing with {own[k]!r}"
+            for k in ("A", "math", "lr", "betas", "eps", "weight_decay", "max_grad_norm", "ema_decay", "ema_warmup")
+            if k in sd and sd[k] != own[k]]
+
+
 class LFTFunction(torch.autograd.Function):
     """autograd node of the whole network: forward saves the tape, backward returns the 78 parameter gradients (None for a
     parameter that does not need one) and, when the input needs one, the gradient of lr (lft_train_backward_input)."""
@@ -241,8 +304,13 @@ class TrainStep:
     """
 
     def __init__(self, net, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, math: Optional[str] = None,
-                 graph: bool = True, weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, guard: bool = False):
+                 graph: bool = True, weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, guard: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         self.net, self.lr, self.betas, self.eps = net, float(lr), betas, float(eps)
+        if ema_decay is not None and not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
         if max_grad_norm is not None and max_grad_norm != max_grad_norm:
             raise ValueError("max_grad_norm is NaN")
         clip = max_grad_norm is not None and 0.0 < max_grad_norm < float("inf")
@@ -277,20 +345,22 @@ class TrainStep:
                 off += k
         self.params = ps
         self._guard = None
-        if self.guard:                     # one segment per parameter tensor, state-dict order; trainable as of now
+        self._segments, off = [], 0        # one segment per parameter tensor, state-dict order; trainable as of now
+        for p in ps:
+            self._segments.append((off, p.numel(), bool(p.requires_grad)))
+            off += p.numel()
+        self._counter0 = {"steps_skipped": 0, "steps_clipped": 0}      # what a loaded state adds to the block's own counters
+        if self.guard:
             table = param_table(net.channels, self.s)
             assert [tuple(p.shape) for p in ps] == [tuple(sh) for _, sh, _ in table]
             self.segment_names = [name for name, _, _ in table]
-            segs, off = [], 0
-            for p in ps:
-                segs.append((off, p.numel(), p.requires_grad))
-                off += p.numel()
             with torch.cuda.device(dev):
-                self._guard = guard_new(segs, n, dev)
+                self._guard = guard_new(self._segments, n, dev)
         # Replicas must start from the same weights (the reference has no DP; torch's DDP broadcasts rank 0's
         # parameters at construction): a network built from scratch draws its weights from this process's own RNG.
         from .dp import broadcast_
         broadcast_(self.flat_params, src=0, group=self.group)
+        self.ema = None if self.ema_decay is None else self.flat_params.clone()
         self.t = 0
         self._tape = None
         self.last_out = None               # [B,1,A*h*s,A*w*s]: what the network produced in the last step (before the update), for per-batch metrics
@@ -406,6 +476,8 @@ class TrainStep:
             else:
                 adam_step_guarded(self.flat_params, self.flat_grads, self.m, self.v, self._guard, self.lr, self.betas[0], self.betas[1],
                                   self.eps, gscale, self.weight_decay, self.max_grad_norm)
+            if self.ema is not None:
+                ema_update(self.ema, self.flat_params, self.ema_decay, self.ema_warmup, self.t, self._guard)
         self.net._packed = None            # the inference path must re-pack the new weights
         return loss.clone()
 
@@ -421,8 +493,83 @@ class TrainStep:
             r = guard_read(self._guard)
         return {"grad_norm": float(r.grad_norm), "clip_coef": float(r.clip_coef), "skipped": bool(r.skipped_last),
                 "nonfinite": int(r.nonfinite_last), "bad_parameter": self.segment_names[r.bad_segment] if r.bad_segment >= 0 else None,
-                "steps_applied": int(r.steps_applied), "steps_skipped": int(r.steps_skipped), "steps_clipped": int(r.steps_clipped),
+                "steps_applied": int(r.steps_applied), "steps_skipped": int(r.steps_skipped) + self._counter0["steps_skipped"],
+                "steps_clipped": int(r.steps_clipped) + self._counter0["steps_clipped"],
                 "param_norms": {name: float(r.seg_norm[i]) for i, name in enumerate(self.segment_names)}}
+
+    # ------------------------------------------------------------------ averaged weights
+    def _need_ema(self):
+        if self.ema is None:
+            raise _lib.LftError("no averaged weights: construct TrainStep(..., ema_decay=...)")
+
+    def ema_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """The averaged weights under the network's parameter names, CPU tensors: the 'state_dict' of a reference-format checkpoint."""
+        self._need_ema()
+        host = self.ema.cpu()
+        return OrderedDict((name, host[first:first + count].view(p.shape).clone())
+                           for name, p, (first, count, _) in zip(self.net._names, self.params, self._segments))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the network runs with the averaged weights: the CONTENTS of flat_params and ema are exchanged in place
+        (the parameters are views and captured graphs hold their addresses) and exchanged back on exit.  Do not step() inside."""
+        self._need_ema()
+
+        def exchange():
+            with torch.no_grad():
+                tmp = self.flat_params.clone()
+                self.flat_params.copy_(self.ema)
+                self.ema.copy_(tmp)
+            self.net._packed = None
+
+        exchange()
+        try:
+            yield self.net
+        finally:
+            exchange()
+
+    # ------------------------------------------------------------------ saving and resuming
+    def _describe(self) -> dict:
+        """Everything of state_dict() but the tensors and the counters."""
+        return {"version": STATE_VERSION, "lr": self.lr, "betas": tuple(float(b) for b in self.betas), "eps": self.eps,
+                "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm, "guard": self.guard, "math": self.math,
+                "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup, "A": int(self.A), "scale": int(self.s),
+                "channels": int(self.net.channels), "floats": int(self.flat_params.numel()),
+                "trainable": [bool(t) for _, _, t in self._segments]}
+
+    def state_dict(self) -> dict:
+        """What a restart needs beside the weights (those stay in the reference-format checkpoint): Adam's moments, the averaged
+        weights, the step counters and the hyper-parameters, as CPU tensors and Python scalars.  With the guard: ONE synchronising
+        read of the guard block."""
+        sd = self._describe()
+        sd.update(m=self.m.cpu(), v=self.v.cpu(), ema=None if self.ema is None else self.ema.cpu(), t=int(self.t))
+        if self.guard:
+            rep = self.guard_report()
+            sd.update({k: rep[k] for k in ("steps_applied", "steps_skipped", "steps_clipped")})
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Continue from a state_dict(): m, v and ema are copied IN PLACE (captured graphs stay valid), t is set, the guard block is
+        written again with the state's steps_applied and the other two counters go on from the state's.  StateError, naming the
+        field, for a state of another network shape, another set of frozen tensors, a newer format, averaged weights on one side
+        only, or a guarded state into an unguarded step (or the reverse); a different math, lr or max_grad_norm is logged."""
+        own = self._describe()
+        own["ema"] = self.ema is not None
+        for line in check_state(sd, own):
+            log.warning("training state: %s", line)
+        dev = self.flat_params.device
+        with torch.no_grad():
+            self.m.copy_(sd["m"])
+            self.v.copy_(sd["v"])
+            if self.ema is not None:
+                self.ema.copy_(sd["ema"])
+        self.t = int(sd["t"])
+        if self.guard:
+            with torch.cuda.device(dev):
+                segs = (_lib.GuardSegment * len(self._segments))(*[_lib.GuardSegment(int(f), int(c), int(t)) for f, c, t in self._segments])
+                _lib.check(_lib.lib().lft_guard_init(self._guard.data_ptr(), segs, len(segs), self.flat_params.numel(),
+                                                     int(sd["steps_applied"]), torch.cuda.current_stream(dev).cuda_stream), "lft_guard_init")
+            self._counter0 = {k: int(sd[k]) for k in ("steps_skipped", "steps_clipped")}
 
 
 def names(channels: int = 64, scale: int = 2):

@@ -11,6 +11,7 @@ float32 tensors.  ``TensorPatchSource`` wraps arrays already in memory; ``lft_am
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from collections import OrderedDict
 from typing import List, Optional, Sequence, Tuple
@@ -29,10 +30,7 @@ def checkpoint_name(model_name: str, angRes: int, scale: int, epoch: int) -> str
 
 def save_checkpoint(net, path: str, epoch: int) -> None:
     """``{'epoch': int, 'state_dict': OrderedDict}`` with CPU tensors (reference train.py:101-105)."""
-    sd = net.module.state_dict() if hasattr(net, "module") else net.state_dict()
-    state = {"epoch": int(epoch), "state_dict": OrderedDict((k, v.detach().cpu().clone()) for k, v in sd.items())}
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save(state, path)
+    save_weights(net.module.state_dict() if hasattr(net, "module") else net.state_dict(), path, epoch)
 
 
 def load_checkpoint(net, path: str) -> int:
@@ -53,6 +51,114 @@ def load_checkpoint(net, path: str) -> int:
     if hasattr(net, "_packed"):
         net._packed = None
     return int(ckpt.get("epoch", 0)) if isinstance(ckpt, dict) else 0
+
+
+def save_weights(state_dict, path: str, epoch: int) -> None:
+    """A reference-format checkpoint from a ready state dict (the averaged weights of TrainStep.ema_state_dict())."""
+    state = {"epoch": int(epoch), "state_dict": OrderedDict((k, v.detach().cpu().clone()) for k, v in state_dict.items())}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(state, path)
+
+
+def ema_checkpoint_name(model_name: str, angRes: int, scale: int, epoch: int) -> str:
+    return "%s_%dx%d_%dx_epoch_%02d_ema_model.pth" % (model_name, angRes, angRes, scale, epoch)
+
+
+def best_checkpoint_name(model_name: str, angRes: int, scale: int) -> str:
+    return "%s_%dx%d_%dx_best_model.pth" % (model_name, angRes, angRes, scale)
+
+
+# ---------------------------------------------------------------------------------------------- the training state file
+STATE_FILE_VERSION = 1
+_FOLLOWS = "<broadcast>"                    # stands for a tensor of the state on the ranks that do not read the file
+
+
+def training_state_name(model_name: str, angRes: int, scale: int) -> str:
+    """The ONE state file of a run, overwritten every epoch (the per-epoch model files are the history)."""
+    return "%s_%dx%d_%dx_training_state.pth" % (model_name, angRes, angRes, scale)
+
+
+def save_training_state(path: str, ts, epoch: int, extra: Optional[dict] = None) -> None:
+    """Everything a restart needs beside the model checkpoint of `epoch`: TrainStep.state_dict(), the epoch and `extra` (fit puts
+    the loss history, last_metrics / last_guard, seed, global batch, world size and the best validation score there).  Written to a
+    temporary name in the same directory and moved into place: a process killed mid-save leaves the previous file intact."""
+    state = dict(extra or {})
+    for k in ("file_version", "epoch", "train_step"):
+        if k in state:
+            raise ValueError(f"extra must not hold the reserved key {k!r}")
+    state.update(file_version=STATE_FILE_VERSION, epoch=int(epoch), train_step=ts.state_dict())
+    path = os.path.abspath(path)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    try:
+        torch.save(state, tmp)
+        os.replace(tmp, path)
+    except BaseException:
+        with contextlib.suppress(OSError):
+            os.remove(tmp)
+        raise
+
+
+def check_state_file(state) -> None:
+    """StateError, naming the field, for what is not a training state file of this or an older format."""
+    from .train import StateError
+    if not isinstance(state, dict):
+        raise StateError("file_version: not a training state file")
+    for k in ("file_version", "epoch", "train_step"):
+        if k not in state:
+            raise StateError(f"{k}: missing from the training state file")
+    if int(state["file_version"]) > STATE_FILE_VERSION:
+        raise StateError(f"file_version: the file has format {state['file_version']}, this build reads up to {STATE_FILE_VERSION}")
+    if not isinstance(state["train_step"], dict):
+        raise StateError("train_step: not a TrainStep state")
+    if int(state["epoch"]) < 0:
+        raise StateError(f"epoch: {state['epoch']}")
+
+
+def load_training_state(path: str, ts, model_name: Optional[str] = None, group=None) -> dict:
+    """Read a file of save_training_state into the TrainStep `ts` and return its other fields ('epoch' and the extras).
+    model_name: also load the reference-format model checkpoint of the state's epoch from the same directory (into ts.net, in place).
+    Data parallel: ONLY RANK 0 READS -- no shared file system is assumed; the small fields travel as one object broadcast, then the
+    weights, m, v and ema through dp.broadcast_.  An error on rank 0 is raised on every rank."""
+    import torch.distributed as dist
+    from .train import StateError
+    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    rank = dist.get_rank(group) if multi else 0
+    state, err = None, None
+    if rank == 0:
+        try:
+            state = torch.load(path, map_location="cpu")
+            check_state_file(state)
+            if model_name is not None:
+                load_checkpoint(ts.net, os.path.join(os.path.dirname(os.path.abspath(path)),
+                                                     checkpoint_name(model_name, ts.A, ts.s, int(state["epoch"]))))
+        except Exception as e:                  # noqa: BLE001 -- handed to every rank below
+            err = e
+    if multi:
+        box = [None]
+        if rank == 0:
+            if err is not None:
+                box = [{"error": "%s: %s" % (type(err).__name__, err)}]
+            else:
+                lean = dict(state)
+                lean["train_step"] = {k: (_FOLLOWS if torch.is_tensor(v) else v) for k, v in state["train_step"].items()}
+                box = [lean]
+        dist.broadcast_object_list(box, src=0, group=group)
+        if rank != 0:
+            if "error" in box[0]:
+                raise StateError("rank 0 could not read the training state: " + box[0]["error"])
+            state = box[0]
+            own = {"m": ts.m, "v": ts.v, "ema": ts.ema if ts.ema is not None else torch.empty(0)}   # placeholders of the right kind
+            state["train_step"] = {k: (own[k] if isinstance(v, str) and v == _FOLLOWS else v) for k, v in state["train_step"].items()}
+    if err is not None:
+        raise err
+    ts.load_state_dict(state["train_step"])     # the same refusals on every rank, before any collective
+    if multi:
+        for buf in (ts.flat_params, ts.m, ts.v, ts.ema):
+            if buf is not None:
+                dp.broadcast_(buf, src=0, group=group)
+        ts.net._packed = None
+    return {k: v for k, v in state.items() if k != "train_step"}
 
 
 # ---------------------------------------------------------------------------------------------- schedule / sampling
@@ -158,7 +264,8 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         start_epoch: int = 0, ckpt_dir: Optional[str] = None, model_name: str = "LFT", seed: int = 0,
         use_augmentation: bool = True, log=print, max_batches_per_epoch: Optional[int] = None, decay_rate: float = 0.0,
         batch_metrics: bool = False, ssim_range: float = 2.0, gpu_augment: bool = False, max_grad_norm: Optional[float] = None,
-        guard: bool = False):
+        guard: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = True, save_state: bool = False,
+        resume: Optional[str] = None, validate=None, val_weights: str = "live"):
     """Train ``net`` (lft_amd.module.get_model on this rank's GPU) like reference train.py:86-110.  ``batch_size`` is
     the GLOBAL batch (reference --batch_size).  Returns the list of per-epoch mean losses (global).
     batch_metrics: also compute the reference's per-batch ``cal_metrics(args, label, out)`` (train.py:121-124: per-view PSNR / SSIM of
@@ -170,19 +277,51 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
     max_grad_norm / guard: the guarded update of TrainStep (gradient-norm clipping; a step with a non-finite gradient is skipped
     instead of destroying the weights).  The guard block is read ONCE per epoch and the epoch line gains
     'grad norm %.3g, clipped %d, skipped %d (first bad: <parameter>)' -- norm and parameter of the epoch's last step, counts of the
-    epoch; an epoch in which every step was skipped is reported with a warning.  ``fit.last_guard`` holds the per-epoch reports."""
+    epoch; an epoch in which every step was skipped is reported with a warning.  ``fit.last_guard`` holds the per-epoch reports.
+    ema_decay / ema_warmup: TrainStep keeps an exponential moving average of the weights; with ckpt_dir every epoch also writes
+    '..._epoch_%02d_ema_model.pth' in the reference's format.
+    save_state: after every epoch (rank 0) the one training state file of ckpt_dir is rewritten (save_training_state).
+    resume: path of such a file.  The model checkpoint of its epoch (same directory) and the state are loaded, training goes on at
+    the state's epoch (``start_epoch`` is ignored) and the returned history covers all epochs.  The per-epoch RNG derives from (seed,
+    epoch, rank) and the learning rate from the epoch, so for the same seed, world size and global batch the continued run equals
+    the uninterrupted one bit for bit; if one of them differs training continues and the log says so.
+    validate: callable(net) -> float (higher is better), called on rank 0 after each epoch -- inside TrainStep.ema_weights() with
+    val_weights='ema'.  The score joins the epoch line; an improvement writes '..._best_model.pth' (the validated weights, reference
+    format) and is remembered, with its epoch, in the state file (``fit.best``)."""
     import torch.distributed as dist
     from .train import TrainStep
     rank, _, world = dp.env_world()
     if not (dist.is_available() and dist.is_initialized()):
         rank, world = 0, 1
     dev = next(net.parameters()).device
+    if val_weights not in ("live", "ema"):
+        raise ValueError(f"val_weights must be 'live' or 'ema', got {val_weights!r}")
+    if val_weights == "ema" and validate is not None and ema_decay is None:
+        raise ValueError("val_weights='ema' needs an ema_decay")
+    if save_state and not ckpt_dir:
+        raise ValueError("save_state needs a ckpt_dir")
     ts = TrainStep(net, lr=lr, weight_decay=decay_rate,            # reference train.py:82 weight_decay=args.decay_rate
-                   max_grad_norm=max_grad_norm, guard=guard)
+                   max_grad_norm=max_grad_norm, guard=guard, ema_decay=ema_decay, ema_warmup=ema_warmup)
     history = []
     fit.last_metrics = []
     fit.last_guard = []
+    fit.best = {"score": None, "epoch": None}
     seen = {"steps_clipped": 0, "steps_skipped": 0}
+    if resume:
+        state = load_training_state(resume, ts, model_name=model_name)
+        start_epoch = int(state["epoch"])
+        history = [float(x) for x in state.get("history", [])]
+        fit.last_metrics = [tuple(x) for x in state.get("last_metrics", [])]
+        fit.last_guard = list(state.get("last_guard", []))
+        fit.best = dict(state.get("best") or fit.best)
+        if ts.guard and fit.last_guard:
+            seen = {k: fit.last_guard[-1][k] for k in seen}
+        now = {"seed": seed, "global_batch": batch_size, "world": world}
+        changed = ["%s %s (saved with %s)" % (k, v, state[k]) for k, v in now.items() if k in state and state[k] != v]
+        if rank == 0:
+            log("resuming after epoch %d from %s" % (start_epoch, resume))
+            if changed:
+                log("WARNING: continuing with " + ", ".join(changed) + ": this run will not reproduce the uninterrupted one")
     for epoch in range(start_epoch, epochs):
         ts.lr = step_lr(lr, epoch, n_steps, gamma)
         rng = np.random.Generator(np.random.PCG64([seed, epoch, rank, 17]))
@@ -229,9 +368,24 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
                 warn = ("WARNING: every step of epoch %d was skipped for non-finite gradients (last seen in %s): the weights did not move"
                         % (epoch + 1, rep["bad_parameter"]))
         if rank == 0:
+            if validate is not None:
+                with (ts.ema_weights() if val_weights == "ema" else contextlib.nullcontext()), torch.no_grad():
+                    score = float(validate(net))
+                    msg += ", val(%s) %.4f" % (val_weights, score)
+                    if fit.best["score"] is None or score > fit.best["score"]:
+                        fit.best = {"score": score, "epoch": epoch + 1}
+                        if ckpt_dir:                                   # the weights that were validated
+                            save_checkpoint(net, os.path.join(ckpt_dir, best_checkpoint_name(model_name, net.angRes, net.factor)), epoch + 1)
             log(msg)
             if warn:
                 log(warn)
             if ckpt_dir:
                 save_checkpoint(net, os.path.join(ckpt_dir, checkpoint_name(model_name, net.angRes, net.factor, epoch + 1)), epoch + 1)
+                if ts.ema is not None:
+                    save_weights(ts.ema_state_dict(), os.path.join(ckpt_dir, ema_checkpoint_name(model_name, net.angRes, net.factor, epoch + 1)),
+                                 epoch + 1)
+                if save_state:
+                    save_training_state(os.path.join(ckpt_dir, training_state_name(model_name, net.angRes, net.factor)), ts, epoch + 1,
+                                        {"history": list(history), "last_metrics": list(fit.last_metrics), "last_guard": list(fit.last_guard),
+                                         "seed": seed, "global_batch": batch_size, "world": world, "best": dict(fit.best)})
     return history

@@ -6,7 +6,10 @@
 One process per GPU, each with its own --batch patches (weak scaling); a step = forward-with-tape, L1 loss + its
 gradient, backward, ONE all-reduce of the flat gradient buffer (RCCL), fused Adam.  Same timing protocol as bench.py
 (barrier + synchronize on both sides, max over ranks).  Prints one JSON line on rank 0.  --phases adds a per-phase
-breakdown from HIP events on the step's stream (forward / loss / backward / all-reduce / adam)."""
+breakdown from HIP events on the step's stream (forward / loss / backward / all-reduce / adam).
+--ema_decay D keeps the EMA of the weights (lft_ema_update after the Adam kernel); with --alternate R a second TrainStep WITHOUT the
+EMA is built beside it and R rounds of --steps steps alternate between the two in this one process: "ms_per_step_rounds" then holds
+both series, the only fair way to see a difference of this size."""
 import argparse, json, os, sys, time
 from types import SimpleNamespace
 
@@ -30,7 +33,11 @@ def main():
     ap.add_argument("--math", default="bf16x3", choices=["fp32", "bf16x3", "bf16x6"])
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--guard", action="store_true", help="the guarded Adam step (lft_adam_step_guarded, no clipping) in place of lft_adam_step")
+    ap.add_argument("--ema_decay", type=float, default=None, help="keep an exponential moving average of the weights (lft_ema_update every step)")
+    ap.add_argument("--alternate", type=int, default=0, metavar="R", help="with --ema_decay: R rounds alternating with an identical step that keeps no EMA")
     args = ap.parse_args()
+    if args.alternate and args.ema_decay is None:
+        ap.error("--alternate compares with and without the EMA: it needs --ema_decay")
     from lft_amd import dp, train as T
     from lft_amd.params import deterministic_state, synthetic_lr
     from model import LFT
@@ -42,12 +49,15 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=dev)
     A, S, H = args.ang, args.scale, args.lr
-    net = LFT.get_model(SimpleNamespace(channels=64, angRes=A, scale_factor=S))
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in deterministic_state(64, S, seed=1).items()})
-    net = net.to(dev).train()
+
+    def new_net():
+        net = LFT.get_model(SimpleNamespace(channels=64, angRes=A, scale_factor=S))
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in deterministic_state(64, S, seed=1).items()})
+        return net.to(dev).train()
+
     lr = torch.from_numpy(synthetic_lr(args.batch, A, H, H, seed=rank)).to(dev)
     hr = torch.from_numpy(np.random.Generator(np.random.PCG64([2, rank])).random((args.batch, 1, A * H * S, A * H * S), dtype=np.float32)).to(dev)
-    ts = T.TrainStep(net, lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard)
+    ts = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard, ema_decay=args.ema_decay)
 
     def sync():
         if dist is not None:
@@ -63,6 +73,20 @@ def main():
         losses.append(ts.step(lr, hr))
     sync()
     dt = dp.barrier_max_seconds(time.perf_counter() - t0, dev)
+    rounds = None
+    if args.alternate:
+        base = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard)
+        for _ in range(args.warmup):
+            base.step(lr, hr)
+        rounds = {"ema": [], "no_ema": []}
+        for _ in range(args.alternate):
+            for name, step in (("no_ema", base), ("ema", ts)):
+                sync()
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    step.step(lr, hr)
+                sync()
+                rounds[name].append(1e3 * dp.barrier_max_seconds(time.perf_counter() - t1, dev) / args.steps)
     lv = [float(x) for x in losses]
     assert all(np.isfinite(lv)), lv
     if rank == 0:
@@ -75,7 +99,9 @@ def main():
                           "global_batch": args.batch * world, "parallelism": f"dp{world} (one flat-gradient all-reduce per step)"},
                "loss_first_last": [lv[0], lv[-1]],
                "tflops_algorithmic": 3 * flops_fwd * args.batch * world * args.steps / dt / 1e12,
-               "tape_gib": T.tape_bytes(args.batch, A, H, H, S) / 2**30, "guard": bool(args.guard)}
+               "tape_gib": T.tape_bytes(args.batch, A, H, H, S) / 2**30, "guard": bool(args.guard), "ema_decay": args.ema_decay}
+        if rounds:
+            out["ms_per_step_rounds"] = rounds
         if args.guard:
             rep = ts.guard_report()
             out["guard_report"] = {k: rep[k] for k in ("grad_norm", "steps_applied", "steps_skipped", "steps_clipped")}

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--angRes", type=int, default=5)
     ap.add_argument("--scale_factor", type=int, default=4)
@@ -41,7 +41,37 @@ def main():
     ap.add_argument("--gpu_augment", action="store_true", help="augment with one lft_dihedral_batch launch per tensor (same batches, bit for bit)")
     ap.add_argument("--max_grad_norm", type=float, default=None, help="clip the global gradient norm (as torch's clip_grad_norm_); implies --guard")
     ap.add_argument("--guard", action="store_true", help="guarded Adam step: a step with a NaN / inf gradient is skipped and reported, frozen tensors stay put")
-    args = ap.parse_args()
+    ap.add_argument("--ema_decay", type=float, default=None, help="keep an exponential moving average of the weights (e.g. 0.999); every epoch also writes ..._ema_model.pth")
+    ap.add_argument("--no_ema_warmup", action="store_true", help="use --ema_decay from the first step instead of min(decay, (1 + t) / (10 + t))")
+    ap.add_argument("--save_state", action="store_true", help="rewrite the training state file (moments, counters, EMA, history) after every epoch")
+    ap.add_argument("--resume", default=None, metavar="auto|PATH", help="continue from a training state file; auto: the one in the checkpoint directory if there is one, else start fresh")
+    ap.add_argument("--path_for_test", default=None, help="the reference's test tree: validate on it after every epoch (mean PSNR over the sets; the EMA weights with --ema_decay) and keep ..._best_model.pth")
+    args = ap.parse_args(argv)
+    if args.resume and args.use_pre_pth:
+        ap.error("--resume restores the weights of its own epoch: it cannot be combined with --use_pre_pth")
+    return args
+
+
+def checkpoint_dir(args) -> str:
+    return os.path.join(args.path_log, "SR_%dx%d_%dx" % (args.angRes, args.angRes, args.scale_factor), args.model_name, "checkpoints")
+
+
+def resolve_resume(args, log=print):
+    """The state file to continue from, or None for a fresh start."""
+    from lft_amd import trainer
+    if not args.resume:
+        return None
+    if args.resume != "auto":
+        return args.resume
+    path = os.path.join(checkpoint_dir(args), trainer.training_state_name(args.model_name, args.angRes, args.scale_factor))
+    if os.path.exists(path):
+        return path
+    log("--resume auto: no %s, starting fresh" % path)
+    return None
+
+
+def main():
+    args = parse_args()
     import importlib
     from lft_amd import dp, trainer
     rank, local, world = dp.env_world()
@@ -65,11 +95,28 @@ def main():
         src = trainer.TensorPatchSource(torch.from_numpy(z["Lr_SAI_y"]), torch.from_numpy(z["Hr_SAI_y"]))
     else:
         src = trainer.SyntheticPatchSource(args.synthetic or 64, args.angRes, args.scale_factor, 32, seed=0)
-    ckpt_dir = os.path.join(args.path_log, "SR_%dx%d_%dx" % (args.angRes, args.angRes, args.scale_factor), args.model_name, "checkpoints")
+    ckpt_dir = checkpoint_dir(args)
+    # only rank 0 looks for the file: the others learn from it whether there is something to resume
+    resume = resolve_resume(args) if rank == 0 else None
+    if world > 1:
+        box = [resume]
+        dist.broadcast_object_list(box, src=0)
+        resume = box[0]
+    validate = None
+    if args.path_for_test:
+        from lft_amd import evaluate
+
+        def validate(n):
+            was_training = n.training
+            res = evaluate.test_sets(n, args, log=lambda *_: None, sharded=False)   # rank 0 alone: no collective
+            n.train(was_training)
+            return float(np.mean([p for p, _ in res.values()]))
     trainer.fit(net, src, args.epoch, args.batch_size, lr=args.lr, n_steps=args.n_steps, gamma=args.gamma, start_epoch=start,
                 ckpt_dir=ckpt_dir, model_name=args.model_name, max_batches_per_epoch=args.max_batches or None,
                 decay_rate=args.decay_rate, batch_metrics=args.batch_metrics, gpu_augment=args.gpu_augment,
-                max_grad_norm=args.max_grad_norm, guard=args.guard)
+                max_grad_norm=args.max_grad_norm, guard=args.guard, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
+                save_state=args.save_state, resume=resume, validate=validate,
+                val_weights="ema" if args.ema_decay is not None else "live")
 
 
 if __name__ == "__main__":
