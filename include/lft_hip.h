@@ -252,6 +252,39 @@ int lft_train_step_profiled(const float* const* params, int nparams, const float
 /* get_loss (reference LFT.py:269-277, torch.nn.L1Loss): *loss = mean |sr - hr|; if dsr != NULL also
  * dsr = gscale * sign(sr - hr) (gscale = 1/n for d loss / d sr).  scratch1024: 1024 floats of device scratch. */
 int lft_l1_loss(const float* sr, const float* hr, long long n, float* dsr, float gscale, float* loss, float* scratch1024, void* stream);
+/* ---- light-field training loss: a pixel penalty plus the same penalty on the epipolar-plane-image (EPI) gradients ----
+ * sr and hr are fp32 [B,1,A*H,A*W]; H x W is the HR view size; view (a1,a2) occupies rows a1*H... and columns a2*W....
+ * d = sr - hr, seen as d[b,a1,y,a2,x]; n = B*A*A*H*W.  The penalty rho is chosen by an enum:
+ *   LFT_LOSS_L1          rho(x) = |x|                  rho'(x) = sign(x), with rho'(0) = 0
+ *   LFT_LOSS_MSE         rho(x) = x^2                  rho'(x) = 2x
+ *   LFT_LOSS_CHARBONNIER rho(x) = sqrt(x^2 + eps^2)    rho'(x) = x / sqrt(x^2 + eps^2)
+ * Pixel term: P = (1/n) sum rho(d).
+ * EPI term, from four forward differences of d:
+ *   Dx : x+1 minus x, inside a view: x = 0..W-2, never across a view border      n_x = B*A*A*H*(W-1)
+ *   Dy : y+1 minus y, inside a view                                              n_y = B*A*A*(H-1)*W
+ *   Dv : view a2+1 minus view a2 at the same (a1,y,x)                            n_v = B*A*(A-1)*H*W
+ *   Du : view a1+1 minus view a1 at the same (a2,y,x)                            n_u = B*A*(A-1)*H*W
+ * (Dv, Dx) is the gradient of the horizontal EPI (a1 and y fixed), (Du, Dy) that of the vertical EPI.  E is the mean, over the T
+ * differences that exist (count above 0), of (1/n_t) sum rho(D_t d); E = 0 if T = 0.  The gradient operator is linear, so this is
+ * exactly rho applied to (EPI gradient of SR - EPI gradient of HR).
+ *   total = w_pix*P + w_epi*E
+ *   d total / d sr = w_pix*rho'(d)/n + (w_epi/T) sum_t (1/n_t)*(rho'(D_t d at the pair ending here) - rho'(D_t d at the pair starting here)):
+ * at most nine contributions per pixel.  Every n_t scales with B, so a mean over equal local shards averages to the global-batch
+ * objective, as for L1.
+ * lft_lf_loss: loss3[0..2] = {total, P, E}; dsr (may be NULL: values only) = gscale * d total / d sr, fully overwritten -- gscale = 1
+ * gives the gradient itself, the 1/n factors are inside, unlike lft_l1_loss.  scratch: lft_lf_loss_scratch_bytes bytes of device
+ * memory, 8-byte aligned.  Two launches (one stencil pass, one fold of fp64 per-block partial sums in a fixed order: no atomics,
+ * bit-reproducible); no allocation, no synchronisation, graph-capturable; 16-byte accesses where the row pitch A*W and the pointers
+ * allow, scalar ones otherwise; any H, W >= 1, A*A <= 128.
+ * Refused before anything is launched -- LFT_ERR_ARG: null sr, hr, loss3 or scratch, misaligned pointers; an unknown penalty;
+ * Charbonnier with eps <= 0 or NaN; negative or NaN weights, or both weights zero; NaN gscale; dsr overlapping sr or hr (the stencil
+ * reads neighbours: in place would race).  LFT_ERR_SHAPE: non-positive sizes; A*A > 128. */
+#define LFT_LOSS_L1 0
+#define LFT_LOSS_MSE 1
+#define LFT_LOSS_CHARBONNIER 2
+int lft_lf_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes);
+int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, int penalty, float eps, float w_pix, float w_epi,
+                float* dsr, float gscale, float* loss3, void* scratch, void* stream);
 /* torch.optim.Adam step (train.py:77-83: betas (0.9, 0.999), eps 1e-8, weight_decay = --decay_rate, default 0) on one
  * flat fp32 buffer; step counts from 1; the gradient is multiplied by gscale first (1/world_size after a sum all-reduce),
  * then weight_decay * p is added (torch's L2 form); bias corrections are computed in double, as torch does. */

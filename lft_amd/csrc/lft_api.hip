@@ -39,6 +39,7 @@ namespace {
 #if LFT_TU != 1
 #include "lft_attn_maps.cuh" // attention weights from the tape's Q | K (lft_train_attn_maps)
 #include "lft_optim.cuh"     // guarded Adam step: gradient statistics, skip / clip decision, update (lft_adam_step_guarded)
+#include "lft_loss.cuh"      // pixel + EPI-gradient loss with L1 / MSE / Charbonnier penalty (lft_lf_loss)
 #endif
 #if LFT_TU != 2
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
@@ -1295,6 +1296,70 @@ int lft_l1_loss(const float* sr, const float* hr, long long n, float* dsr, float
     LFT_LAUNCH_OK("k_l1_partial");
     k_l1_final<<<1, 64, 0, st>>>(scratch1024, nb, 1.0f / (float)n, loss);
     LFT_LAUNCH_OK("k_l1_final");
+    return 0;
+}
+// ---- light-field loss (lft_loss.cuh) ----
+namespace {
+struct LossShape { long long n; int nblocks[2]; };     // stencil blocks of the scalar and of the 16-byte path
+int loss_shape(int B, int A, int H, int W, LossShape* s) {
+    if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "sizes must be positive, got B %d A %d H %d W %d", B, A, H, W);
+    if ((long long)A * A > 128) return fail(LFT_ERR_SHAPE, "A * A = %lld views, at most 128 are supported", (long long)A * A);
+    s->n = (long long)B * A * A * H * W;
+    for (int v = 0; v < 2; ++v)
+        s->nblocks[v] = (int)std::min<long long>(kLossMaxBlocks, (s->n / (v ? 4 : 1) + kLossThreads - 1) / kLossThreads);
+    return 0;
+}
+}  // namespace
+int lft_lf_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
+    LossShape s;
+    if (int rc = loss_shape(B, A, H, W, &s)) return rc;
+    *out_bytes = (size_t)s.nblocks[0] * kLossSums * sizeof(double);
+    return 0;
+}
+int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, int penalty, float eps, float w_pix, float w_epi,
+                float* dsr, float gscale, float* loss3, void* scratch, void* stream) {
+    if (!sr || !hr || !loss3 || !scratch) return fail(LFT_ERR_ARG, "null pointer");
+    if ((((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)dsr | (uintptr_t)loss3) & 3) || ((uintptr_t)scratch & 7))
+        return fail(LFT_ERR_ARG, "sr, hr, dsr and loss3 must be 4-byte aligned, scratch 8-byte aligned");
+    if (penalty != LFT_LOSS_L1 && penalty != LFT_LOSS_MSE && penalty != LFT_LOSS_CHARBONNIER) return fail(LFT_ERR_ARG, "unknown penalty %d", penalty);
+    if (penalty == LFT_LOSS_CHARBONNIER && !(eps > 0.0f)) return fail(LFT_ERR_ARG, "the Charbonnier eps must be positive, got %g", (double)eps);
+    if (!(w_pix >= 0.0f) || !(w_epi >= 0.0f)) return fail(LFT_ERR_ARG, "weights must not be negative or NaN, got %g and %g", (double)w_pix, (double)w_epi);
+    if (w_pix == 0.0f && w_epi == 0.0f) return fail(LFT_ERR_ARG, "both weights are zero");
+    if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "gscale is NaN");
+    LossShape s;
+    if (int rc = loss_shape(B, A, H, W, &s)) return rc;
+    if (dsr && (((uintptr_t)dsr < (uintptr_t)(sr + s.n) && (uintptr_t)sr < (uintptr_t)(dsr + s.n)) ||
+                ((uintptr_t)dsr < (uintptr_t)(hr + s.n) && (uintptr_t)hr < (uintptr_t)(dsr + s.n))))
+        return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the stencil reads neighbours, in place would race");
+    const double n = (double)s.n;
+    const double nt[4] = {n / W * (W - 1), n / H * (H - 1), n / A * (A - 1), n / A * (A - 1)};      // n_x, n_y, n_v, n_u: exact in double
+    int T = 0;
+    for (double c : nt) T += c > 0.0;
+    LossFoldArgs f = {};
+    f.inv_n = 1.0 / n; f.inv_T = T ? 1.0 / T : 0.0; f.w_pix = (double)w_pix; f.w_epi = (double)w_epi;
+    float ct[4];
+    for (int t = 0; t < 4; ++t) {
+        f.inv_nt[t] = nt[t] > 0.0 ? 1.0 / nt[t] : 0.0;
+        ct[t] = (float)((double)w_epi * f.inv_T * f.inv_nt[t]);
+    }
+    const LossArgs a = {B, A, H, W, eps * eps, (float)((double)w_pix * f.inv_n), ct[0], ct[1], ct[2], ct[3], gscale};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(scratch);
+    const bool vec = ((long long)A * W) % 4 == 0 && !(((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)dsr) & 15);
+    const int nb = s.nblocks[vec];
+    const bool grad = dsr != nullptr;
+    if (int rc = dispatch<LFT_LOSS_L1, LFT_LOSS_MSE, LFT_LOSS_CHARBONNIER>(penalty, [&](auto PEN) {
+            return dispatch<true, false>(vec, [&](auto VEC4) {
+                return dispatch<true, false>(grad, [&](auto GRAD) {
+                    k_lf_loss<PEN, VEC4 ? 4 : 1, GRAD><<<nb, kLossThreads, 0, st>>>(sr, hr, dsr, a, part);
+                    return 0;
+                });
+            });
+        })) return rc;
+    LFT_LAUNCH_OK("k_lf_loss");
+    k_lf_loss_fold<<<1, kLossThreads, 0, st>>>(part, nb, f, loss3);
+    LFT_LAUNCH_OK("k_lf_loss_fold");
     return 0;
 }
 int lft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,

@@ -312,7 +312,17 @@ class PipelinedForward:
 
 
 class get_loss(nn.Module):
-    """Mean absolute error between SR and HR mosaics (reference model/LFT.py:269-277)."""
+    """Mean absolute error between SR and HR mosaics (reference model/LFT.py:269-277).  If ``args`` carries an ``lft_loss`` attribute
+    (a spec of lft_amd.loss.LFLoss: a dict or a penalty name), ``get_loss(args)`` is that LFLoss instead, for ``args.angRes`` views."""
+
+    def __new__(cls, args=None):
+        if args is not None and hasattr(args, "lft_loss"):
+            from .loss import LFLoss
+            loss = LFLoss.from_spec(args.lft_loss)
+            if loss.angRes is None and hasattr(args, "angRes"):
+                loss.angRes = int(args.angRes)
+            return loss
+        return super().__new__(cls)
 
     def __init__(self, args=None):
         super().__init__()

@@ -12,6 +12,8 @@ Two ways in:
     (``requires_grad = False``) tensors left alone -- all decided on the device, no host round trip inside the step.
     ``TrainStep(..., ema_decay=...)`` keeps an exponential moving average of the weights in a fourth flat buffer (lft_ema_update,
     which obeys the guard); ``state_dict()`` / ``load_state_dict()`` carry moments, counters and the average across a restart.
+    ``TrainStep(..., loss=LFLoss(...))`` minimises another objective (lft_amd.loss: MSE / Charbonnier, EPI-gradient term) with
+    lft_lf_loss in the place of lft_l1_loss, inside the same captured step.
 """
 from __future__ import annotations
 
@@ -305,7 +307,7 @@ class TrainStep:
 
     def __init__(self, net, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, math: Optional[str] = None,
                  graph: bool = True, weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, guard: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, loss=None):
         self.net, self.lr, self.betas, self.eps = net, float(lr), betas, float(eps)
         if ema_decay is not None and not 0.0 <= ema_decay < 1.0:
             raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
@@ -365,6 +367,28 @@ class TrainStep:
         self._tape = None
         self.last_out = None               # [B,1,A*h*s,A*w*s]: what the network produced in the last step (before the update), for per-batch metrics
         self._scratch = torch.empty(1024 + 1, dtype=torch.float32, device=dev)
+        # loss: None or 'l1' -- the reference's L1 through lft_l1_loss, the bits of every earlier version; an lft_amd.loss.LFLoss (or
+        # its spec) other than pure L1 -- lft_lf_loss at the same place, (total, P, E) of the last step in last_loss_terms
+        self.loss, self.last_loss_terms, self._loss_scratch = None, None, {}
+        if loss is not None and loss != "l1":
+            from .loss import LFLoss
+            loss = LFLoss.from_spec(loss)
+            if loss.angRes is None:
+                loss.angRes = int(self.A)
+            if loss.angRes != self.A:
+                raise ValueError(f"the loss was built for angRes {loss.angRes}, the network has {self.A}")
+            if not loss.is_plain_l1():
+                self.loss = loss
+                self.last_loss_terms = torch.zeros(3, dtype=torch.float32, device=dev)
+
+    def _loss_scratch_for(self, hr):
+        """Scratch of lft_lf_loss for this batch shape: allocated once, outside any capture."""
+        key = tuple(hr.shape)
+        if key not in self._loss_scratch:
+            from .loss import scratch_bytes
+            B, _, R, C = hr.shape
+            self._loss_scratch[key] = torch.empty(scratch_bytes(B, self.A, R // self.A, C // self.A), dtype=torch.uint8, device=hr.device)
+        return self._loss_scratch[key]
 
     def _fwd_loss_bwd(self, lr_in, hr, tape, dout, loss, on_bucket=None):
         L = _lib.lib()
@@ -372,8 +396,13 @@ class TrainStep:
         stream = torch.cuda.current_stream(dev).cuda_stream
         out, _ = train_forward(self.params, lr_in, self.A, self.s, tape=tape, math=self.math)
         n = out.numel()
-        _lib.check(L.lft_l1_loss(out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, loss.data_ptr(),
-                                 self._scratch.data_ptr(), stream), "lft_l1_loss")
+        if self.loss is None:
+            _lib.check(L.lft_l1_loss(out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, loss.data_ptr(),
+                                     self._scratch.data_ptr(), stream), "lft_l1_loss")
+        else:
+            from .loss import lf_loss
+            lf_loss(out, hr, self.A, self.loss.penalty, self.loss.eps, self.loss.pixel_weight, self.loss.epi_weight, dsr=dout,
+                    loss3=self.last_loss_terms, scratch=self._loss_scratch[tuple(hr.shape)])
         if on_bucket is None:
             train_backward(self.params, lr_in, tape, dout, self.A, self.s, grads=self.flat_grads, math=self.math)
         else:
@@ -449,7 +478,9 @@ class TrainStep:
             handles.append(dp.sum_gradients_start_(self.flat_grads[first:first + count], self.group))
 
         with torch.cuda.device(dev):
-            loss = self._scratch[1024:1025]
+            loss = self._scratch[1024:1025] if self.loss is None else self.last_loss_terms[:1]
+            if self.loss is not None:
+                self._loss_scratch_for(hr)
             if self.use_graph:
                 g = self._graph_for(lr_in.contiguous().float(), hr.contiguous().float(), bucketed=exchange)
                 g["lr"].copy_(lr_in)

@@ -265,7 +265,7 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         use_augmentation: bool = True, log=print, max_batches_per_epoch: Optional[int] = None, decay_rate: float = 0.0,
         batch_metrics: bool = False, ssim_range: float = 2.0, gpu_augment: bool = False, max_grad_norm: Optional[float] = None,
         guard: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = True, save_state: bool = False,
-        resume: Optional[str] = None, validate=None, val_weights: str = "live"):
+        resume: Optional[str] = None, validate=None, val_weights: str = "live", loss=None):
     """Train ``net`` (lft_amd.module.get_model on this rank's GPU) like reference train.py:86-110.  ``batch_size`` is
     the GLOBAL batch (reference --batch_size).  Returns the list of per-epoch mean losses (global).
     batch_metrics: also compute the reference's per-batch ``cal_metrics(args, label, out)`` (train.py:121-124: per-view PSNR / SSIM of
@@ -287,7 +287,11 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
     the uninterrupted one bit for bit; if one of them differs training continues and the log says so.
     validate: callable(net) -> float (higher is better), called on rank 0 after each epoch -- inside TrainStep.ema_weights() with
     val_weights='ema'.  The score joins the epoch line; an improvement writes '..._best_model.pth' (the validated weights, reference
-    format) and is remembered, with its epoch, in the state file (``fit.best``)."""
+    format) and is remembered, with its epoch, in the state file (``fit.best``).
+    loss: an lft_amd.loss.LFLoss, its spec (a dict) or a penalty name -- the objective of TrainStep(loss=...); None: the reference's L1.
+    The components are summed on the device and the epoch line gains 'pix %.5f, epi %.5f' (the means of the pixel and the EPI term;
+    not for a spec that is the plain L1, which runs the reference's kernel).  The spec goes into the state file; a resume with another
+    one continues and says so."""
     import torch.distributed as dist
     from .train import TrainStep
     rank, _, world = dp.env_world()
@@ -301,7 +305,11 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
     if save_state and not ckpt_dir:
         raise ValueError("save_state needs a ckpt_dir")
     ts = TrainStep(net, lr=lr, weight_decay=decay_rate,            # reference train.py:82 weight_decay=args.decay_rate
-                   max_grad_norm=max_grad_norm, guard=guard, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                   max_grad_norm=max_grad_norm, guard=guard, ema_decay=ema_decay, ema_warmup=ema_warmup, loss=loss)
+    loss_spec = None
+    if loss is not None:
+        from .loss import LFLoss
+        loss_spec = (ts.loss or LFLoss.from_spec(loss)).spec()
     history = []
     fit.last_metrics = []
     fit.last_guard = []
@@ -316,7 +324,7 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         fit.best = dict(state.get("best") or fit.best)
         if ts.guard and fit.last_guard:
             seen = {k: fit.last_guard[-1][k] for k in seen}
-        now = {"seed": seed, "global_batch": batch_size, "world": world}
+        now = {"seed": seed, "global_batch": batch_size, "world": world, "loss": loss_spec}
         changed = ["%s %s (saved with %s)" % (k, v, state[k]) for k, v in now.items() if k in state and state[k] != v]
         if rank == 0:
             log("resuming after epoch %d from %s" % (start_epoch, resume))
@@ -329,6 +337,7 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         if max_batches_per_epoch:
             batches = batches[:max_batches_per_epoch]
         total = torch.zeros(3 if batch_metrics else 1, device=dev)
+        terms = torch.zeros(3, device=dev)                         # (total, P, E) of TrainStep(loss=...)
         last = None
         for ix in batches:
             a, b = source.get(ix)
@@ -336,6 +345,8 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
             if use_augmentation:
                 a, b = (augment_gpu if gpu_augment else augment)(a, b, rng)
             loss = ts.step(a, b)
+            if ts.last_loss_terms is not None:
+                terms += ts.last_loss_terms
             if batch_metrics:
                 from . import metrics
                 p, s = metrics.view_metrics(b, ts.last_out, net.angRes, ssim_range)
@@ -348,12 +359,19 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
             host = mean.cpu() if dist.get_backend() == "gloo" else mean
             dist.all_reduce(host)
             mean = host.to(dev) / world
+            if ts.last_loss_terms is not None:
+                host = terms.cpu() if dist.get_backend() == "gloo" else terms
+                dist.all_reduce(host)
+                terms = host.to(dev) / world
         history.append(float(mean[0]))
         if batch_metrics:
             fit.last_metrics.append((float(mean[1]), float(mean[2])))
             msg = "The %dth Train, loss is: %.5f, psnr is %.5f, ssim is %.5f" % (epoch + 1, history[-1], *fit.last_metrics[-1])   # train.py:90-91
         else:
             msg = "The %dth Train, loss is: %.5f, lr %.3g" % (epoch + 1, history[-1], ts.lr)
+        if ts.last_loss_terms is not None:
+            pix, epi = (terms[1:] / max(1, len(batches))).tolist()
+            msg += ", pix %.5f, epi %.5f" % (pix, epi)
         if last is not None and not batch_metrics:
             with torch.no_grad():
                 msg += ", psnr(last batch) %.3f" % psnr_gpu(net(last[0]), last[1])
@@ -387,5 +405,6 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
                 if save_state:
                     save_training_state(os.path.join(ckpt_dir, training_state_name(model_name, net.angRes, net.factor)), ts, epoch + 1,
                                         {"history": list(history), "last_metrics": list(fit.last_metrics), "last_guard": list(fit.last_guard),
-                                         "seed": seed, "global_batch": batch_size, "world": world, "best": dict(fit.best)})
+                                         "seed": seed, "global_batch": batch_size, "world": world, "best": dict(fit.best),
+                                         "loss": loss_spec})
     return history

@@ -9,7 +9,10 @@ gradient, backward, ONE all-reduce of the flat gradient buffer (RCCL), fused Ada
 breakdown from HIP events on the step's stream (forward / loss / backward / all-reduce / adam).
 --ema_decay D keeps the EMA of the weights (lft_ema_update after the Adam kernel); with --alternate R a second TrainStep WITHOUT the
 EMA is built beside it and R rounds of --steps steps alternate between the two in this one process: "ms_per_step_rounds" then holds
-both series, the only fair way to see a difference of this size."""
+both series, the only fair way to see a difference of this size.
+--loss {l1,mse,charbonnier} / --epi_weight W: the step minimises an lft_amd.loss.LFLoss (lft_lf_loss in the place of lft_l1_loss), and
+"loss_ms" holds the event-timed milliseconds of the loss launches alone -- lft_lf_loss and, alternating with it in this one process on
+the same tensors, lft_l1_loss (medians over 50 calls each)."""
 import argparse, json, os, sys, time
 from types import SimpleNamespace
 
@@ -18,6 +21,37 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def time_loss_launches(ts, hr, calls=50):
+    """Median event-timed milliseconds of one lft_lf_loss call (the step's objective) and of one lft_l1_loss call on the same tensors,
+    the two alternating."""
+    from lft_amd import _lib
+    from lft_amd.loss import lf_loss
+    sr, dout = ts.last_out, torch.empty_like(hr)
+    n = sr.numel()
+    stream = torch.cuda.current_stream(hr.device).cuda_stream
+    scratch = ts._loss_scratch_for(hr)
+
+    def run_lf():
+        lf_loss(sr, hr, ts.A, ts.loss.penalty, ts.loss.eps, ts.loss.pixel_weight, ts.loss.epi_weight, dsr=dout, loss3=ts.last_loss_terms,
+                scratch=scratch)
+
+    def run_l1():
+        _lib.check(_lib.lib().lft_l1_loss(sr.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, ts._scratch[1024:].data_ptr(),
+                                          ts._scratch.data_ptr(), stream), "lft_l1_loss")
+
+    ms = {"lft_lf_loss": [], "lft_l1_loss": []}
+    for i in range(calls + 5):
+        for name, run in (("lft_l1_loss", run_l1), ("lft_lf_loss", run_lf)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            e1.synchronize()
+            if i >= 5:
+                ms[name].append(e0.elapsed_time(e1))
+    return {k: float(np.median(v)) for k, v in ms.items()}
 
 
 def main():
@@ -35,6 +69,8 @@ def main():
     ap.add_argument("--guard", action="store_true", help="the guarded Adam step (lft_adam_step_guarded, no clipping) in place of lft_adam_step")
     ap.add_argument("--ema_decay", type=float, default=None, help="keep an exponential moving average of the weights (lft_ema_update every step)")
     ap.add_argument("--alternate", type=int, default=0, metavar="R", help="with --ema_decay: R rounds alternating with an identical step that keeps no EMA")
+    ap.add_argument("--loss", default=None, choices=["l1", "mse", "charbonnier"], help="penalty of an LFLoss objective; default: the reference's L1 step")
+    ap.add_argument("--epi_weight", type=float, default=0.0, help="weight of the EPI-gradient term of --loss")
     args = ap.parse_args()
     if args.alternate and args.ema_decay is None:
         ap.error("--alternate compares with and without the EMA: it needs --ema_decay")
@@ -57,7 +93,8 @@ def main():
 
     lr = torch.from_numpy(synthetic_lr(args.batch, A, H, H, seed=rank)).to(dev)
     hr = torch.from_numpy(np.random.Generator(np.random.PCG64([2, rank])).random((args.batch, 1, A * H * S, A * H * S), dtype=np.float32)).to(dev)
-    ts = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard, ema_decay=args.ema_decay)
+    spec = None if args.loss is None else {"penalty": args.loss, "epi_weight": args.epi_weight}
+    ts = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard, ema_decay=args.ema_decay, loss=spec)
 
     def sync():
         if dist is not None:
@@ -87,6 +124,9 @@ def main():
                     step.step(lr, hr)
                 sync()
                 rounds[name].append(1e3 * dp.barrier_max_seconds(time.perf_counter() - t1, dev) / args.steps)
+    loss_ms = None
+    if ts.loss is not None:
+        loss_ms = time_loss_launches(ts, hr)
     lv = [float(x) for x in losses]
     assert all(np.isfinite(lv)), lv
     if rank == 0:
@@ -102,6 +142,9 @@ def main():
                "tape_gib": T.tape_bytes(args.batch, A, H, H, S) / 2**30, "guard": bool(args.guard), "ema_decay": args.ema_decay}
         if rounds:
             out["ms_per_step_rounds"] = rounds
+        if loss_ms:
+            out["loss"] = ts.loss.spec()
+            out["loss_ms"] = loss_ms
         if args.guard:
             rep = ts.guard_report()
             out["guard_report"] = {k: rep[k] for k in ("grad_norm", "steps_applied", "steps_skipped", "steps_clipped")}

@@ -46,10 +46,21 @@ def parse_args(argv=None):
     ap.add_argument("--save_state", action="store_true", help="rewrite the training state file (moments, counters, EMA, history) after every epoch")
     ap.add_argument("--resume", default=None, metavar="auto|PATH", help="continue from a training state file; auto: the one in the checkpoint directory if there is one, else start fresh")
     ap.add_argument("--path_for_test", default=None, help="the reference's test tree: validate on it after every epoch (mean PSNR over the sets; the EMA weights with --ema_decay) and keep ..._best_model.pth")
+    ap.add_argument("--loss", default="l1", choices=["l1", "mse", "charbonnier"], help="the penalty of the objective (lft_amd.loss.LFLoss); l1 alone is the reference's loss")
+    ap.add_argument("--charbonnier_eps", type=float, default=1e-3)
+    ap.add_argument("--pixel_weight", type=float, default=1.0, help="weight of the pixel term")
+    ap.add_argument("--epi_weight", type=float, default=0.0, help="weight of the EPI-gradient term (the penalty on the gradients of the epipolar-plane images)")
     args = ap.parse_args(argv)
     if args.resume and args.use_pre_pth:
         ap.error("--resume restores the weights of its own epoch: it cannot be combined with --use_pre_pth")
     return args
+
+
+def loss_spec(args):
+    """The spec for fit(loss=...), or None for the reference's L1 (which keeps the lft_l1_loss step)."""
+    if args.loss == "l1" and args.pixel_weight == 1.0 and args.epi_weight == 0.0:
+        return None
+    return {"penalty": args.loss, "eps": args.charbonnier_eps, "pixel_weight": args.pixel_weight, "epi_weight": args.epi_weight}
 
 
 def checkpoint_dir(args) -> str:
@@ -116,7 +127,7 @@ def main():
                 decay_rate=args.decay_rate, batch_metrics=args.batch_metrics, gpu_augment=args.gpu_augment,
                 max_grad_norm=args.max_grad_norm, guard=args.guard, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
                 save_state=args.save_state, resume=resume, validate=validate,
-                val_weights="ema" if args.ema_decay is not None else "live")
+                val_weights="ema" if args.ema_decay is not None else "live", loss=loss_spec(args))
 
 
 if __name__ == "__main__":
