@@ -165,11 +165,15 @@ int make_dims(int B, int A, int h, int w, int s, int prec, Dims* d) {
 
 // Fragment counts per stream
 constexpr int kFragsConv = 72, kFragsAng = 64, kFragsSpa1 = 240, kFragsSpa1NoQ = 208, kFragsSpa2 = 176;
+// 16-bit part B (k_spa_b) runs the 1x1x1 conv folded into the FFN's second Linear: kSpaBFrags fragments (lft_kernels_b.cuh)
+inline int frags_spa2(int prec) { return prec == LFT_PREC_F32 ? kFragsSpa2 : kSpaBFrags; }
 inline int frags_up(const Dims& d) { return d.nchunk * (4 + 2 * d.gt); }
 
 struct PackedLayout {
     size_t conv0_w, ln_ang[kLayers], ln_spa[kLayers], ang_pe, petok[kLayers], spa_pe_img;
     size_t w01, s_w01;          // 16-bit only: conv_init.0 composed with conv_init0, fp32 [64][kW01K], and its 12 fragments
+    size_t spa_geom;            // 16-bit, lane-major view sizes only: k_spa_b's geometry table (k_spa_b_geom)
+    size_t wlw2[kLayers];       // 16-bit only: the 1x1x1 conv composed with feed_forward.4, fp32 [64][256] (k_compose_wlw2)
     size_t s_conv[3], s_ang[kLayers], s_spa1[kLayers], s_spa2[kLayers], s_up, total;
 };
 
@@ -192,9 +196,13 @@ PackedLayout packed_layout(const Dims& d, int prec) {
     for (int l = 0; l < kLayers; ++l) {
         L.s_ang[l] = take(kFragsAng * fragb);
         L.s_spa1[l] = take(kFragsSpa1 * fragb);
-        L.s_spa2[l] = take(kFragsSpa2 * fragb);
+        L.s_spa2[l] = take(frags_spa2(prec) * fragb);
     }
     L.s_up = take((size_t)frags_up(d) * fragb);
+    for (int l = 0; l < kLayers; ++l) L.wlw2[l] = take(lp ? 64 * 256 * 4 : 0);
+    // 16-bit with the lane-major hand-off (tok_lane_major): k_spa_b's per-lane geometry, one entry per query tile of a view
+    const bool geom = lp && d.hw % (32 * kNwSpa1) == 0 && d.w % 32 == 0;
+    L.spa_geom = take(geom ? (size_t)((d.h + kAttTY - 1) / kAttTY) * ((d.w + kAttTX - 1) / kAttTX) * kSpaBGeomTileBytes : 0);
     L.total = o;
     return L;
 }
@@ -354,6 +362,12 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
     k_pe_tables<T><<<blocks_for(std::max<long long>((long long)((d.V + 31) / 32) * 2048, (long long)d.hw * 64), 256), 256, 0, st>>>(
         at<float>(packed, L.ang_pe), at<T>(packed, L.spa_pe_img), d.V, d.h, d.w);
     LFT_LAUNCH_OK("k_pe_tables");
+    if constexpr (sizeof(T) == 2) {
+        if (tok_lane_major<T>(d)) {     // the per-lane geometry of k_spa_b depends on h, w only: built once per view size
+            k_spa_b_geom<<<(unsigned)(((d.h + kAttTY - 1) / kAttTY) * ((d.w + kAttTX - 1) / kAttTX)), 256, 0, st>>>(at<unsigned>(packed, L.spa_geom), d.h, d.w);
+            LFT_LAUNCH_OK("k_spa_b_geom");
+        }
+    }
     for (int l = 0; l < kLayers; ++l) {
         const float* const* q = P + 4 + 18 * l;
         float* lnS = at<float>(packed, L.ln_spa[l]);
@@ -389,12 +403,26 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
             // Row-major K / V: labels are the channels themselves -- natural packing.  Lane-major Q / K / V (tok_lane_major): k_spa1
             // wrote each head's 16 channels in acc order, so label 8 h + j is channel acc(h, j) -- acc-order packing.
             ops.push_back(lin_op(q[4], 0, 128, 128, 0, 8, (sizeof(T) == 2 && tok_lane_major<T>(d)) ? 1 : 0, 1.0f));
-            for (int c = 0; c < 4; ++c) {
-                ops.push_back(lin_op(q[7], 64 * c, 64, 128, 0, 8, 1, 1.0f));
-                ops.push_back(lin_op(q[8], 0, 128, 256, 64 * c, 4, 1, 1.0f));
+            if constexpr (sizeof(T) == 2) {
+                // No non-linearity stands between feed_forward.4 (W2) and the 1x1x1 conv (Wl, reference LFT.py:171-174, 187-189):
+                // y = Wl (t + W2 hid) = Wl t + (Wl W2) hid.  Wl W2 [64][256] is composed in fp32 and rounded once by k_pack.
+                // Stream: Wo[4x8] Wl[2x8] {W1c[2x8] WlW2c[2x4]} x4
+                float* wlw2 = at<float>(packed, L.wlw2[l]);
+                k_compose_wlw2<<<blocks_for(64 * 256, 256), 256, 0, st>>>(q[9], q[8], wlw2);
+                LFT_LAUNCH_OK("k_compose_wlw2");
+                ops.push_back(lin_op(q[9], 0, 64, 128, 0, 8, 1, 1.0f));
+                for (int c = 0; c < 4; ++c) {
+                    ops.push_back(lin_op(q[7], 64 * c, 64, 128, 0, 8, 1, 1.0f));
+                    ops.push_back(lin_op(wlw2, 0, 64, 256, 64 * c, 4, 1, 1.0f));
+                }
+            } else {
+                for (int c = 0; c < 4; ++c) {
+                    ops.push_back(lin_op(q[7], 64 * c, 64, 128, 0, 8, 1, 1.0f));
+                    ops.push_back(lin_op(q[8], 0, 128, 256, 64 * c, 4, 1, 1.0f));
+                }
+                ops.push_back(lin_op(q[9], 0, 64, 128, 0, 8, 1, 1.0f));
             }
-            ops.push_back(lin_op(q[9], 0, 64, 128, 0, 8, 1, 1.0f));
-            if ((rc = run_pack<T>(ops, at<T>(packed, L.s_spa2[l]), kFragsSpa2, st))) return rc;
+            if ((rc = run_pack<T>(ops, at<T>(packed, L.s_spa2[l]), frags_spa2(prec), st))) return rc;
         }
         // embedded spatial position tokens of this layer (reference LFT.py:180), [h*w][128] in the activation type
         if ((rc = launch_spa1<T, true>((unsigned)((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1)), at<T>(packed, L.spa_pe_img), at<T>(packed, L.s_spa1[l]), nullptr, nullptr,
@@ -541,7 +569,7 @@ int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, 
                  if (int r = allow_lds(k_spa_b<T, SK, LM, YL>, kSpaBLds, "k_spa_b")) return r;
                  k_spa_b<T, SK, LM, YL><<<ntile, 256, kSpaBLds, st>>>(tok, q, k, v, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.h, d.w,
                                                                       at<unsigned>(ws, W.status), at<T>(packed, L.s_spa1[l]) + (size_t)kFragsSpa1NoQ * 512,
-                                                                      at<T>(packed, L.petok[l]));
+                                                                      at<T>(packed, L.petok[l]), at<unsigned>(packed, L.spa_geom));
                  return 0;
              }))) return rc;
         LFT_LAUNCH_OK("k_spa_b");

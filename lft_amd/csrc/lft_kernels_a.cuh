@@ -300,6 +300,16 @@ __global__ void k_compose_w01(const float* __restrict__ w0, const float* __restr
     }
     w01[idx] = v;
 }
+// The 16-bit part B folds the 1x1x1 conv into the FFN's second Linear (k_spa_b): wl [64][128], w2 [128][256] -> wlw2 [64][256]
+// fp32, summed in channel order (pack time; k_pack rounds it once to the operand type)
+__global__ void k_compose_wlw2(const float* __restrict__ wl, const float* __restrict__ w2, float* __restrict__ wlw2) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 64 * 256) return;
+    const int o = idx >> 8, k = idx & 255;
+    float v = 0.0f;
+    for (int c = 0; c < 128; ++c) v += wl[o * 128 + c] * w2[c * 256 + k];
+    wlw2[idx] = v;
+}
 // View (a1, a2) of image b inside the LR mosaic [B,1,A*h,A*w]; row stride A*w (see k_conv0).
 LFT_DEV const float* lr_view(const float* __restrict__ lr, int im, int A, int h, int w) {
     const int V = A * A, b = im / V, v = im - b * V, a1 = v / A, a2 = v - a1 * A;

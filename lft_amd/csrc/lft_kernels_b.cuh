@@ -201,12 +201,16 @@ __global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa2(const T* __restrict__
 // exactly the B operand of out_proj in "acc order", so the attention output never goes to memory (k_spa_attn_mfma wrote
 // 26 MB per launch at B = 4 and k_spa2 read them back through an LDS transposition).  A workgroup = a 4 x 32 tile of
 // queries of one view image, wave c owning the 8 x 4 block of columns 8c .. 8c+7, as in k_spa_attn_mfma; the same 32
-// tokens then go through  t = tok + O Wo^T ; t += W2 relu(W1 LN'(t)) ; y = Wl t (+ global skip)  as in k_spa2.
-// Stream: Wo[4x8, ACC order] {W1c[2x8] W2c[4x4]} x4  Wl[2x8]  (176 fragments) through an 8-fragment-chunk ring, so that
-// ring + K/V halo tiles stay below 80 KiB and two workgroups share a CU.  TOK / skip / Y are row-major [token][channel];
+// tokens then go through  t = tok + O Wo^T ; y = Wl (t + W2 relu(W1 LN'(t))) (+ global skip).  Nothing non-linear stands between
+// W2 and Wl, so the tail computes  y = Wl t + (Wl W2) relu(W1 LN'(t))  with Wl W2 composed in fp32 at pack time (k_compose_wlw2)
+// and rounded once: per hidden chunk a [2x4] product into the 32 registers of y instead of a [4x4] one into t, and no separate
+// Wl pass over a re-converted t at the end (-32 MFMAs, -32 fragments of weight DMA per workgroup, -4 ring chunks of 22).
+// Stream: Wo[4x8, ACC order] Wl[2x8] {W1c[2x8] WlW2c[2x4]} x4  (kSpaBFrags = 144 fragments) through an 8-fragment-chunk ring, so
+// that ring + K/V halo tiles stay below 80 KiB and two workgroups share a CU.  TOK / skip / Y are row-major [token][channel];
 // a wave's 8 x 4 block is two 4 x 4 blocks side by side (BlkRows: token 16 b + 4 py + px).
 // ------------------------------------------------------------------------------------------
 constexpr int kSpaBChunk = 8;                                 // fragments per ring chunk in phase B
+constexpr int kSpaBFrags = 32 + 16 + 4 * (16 + 8);            // Wo, Wl, four chunks of {W1c, WlW2c}
 constexpr int kAdTile = kAttHR * kAttHC * 64;                 // one tensor's halo tile in LDS: 8 x 36 tokens x 64 B
 constexpr int kAdPerWave = 2 * kAdTile / 1024 / 4;            // LDS-DMA pieces per wave and head pair (9)
 static_assert(2 * kAdTile == 4 * kAdPerWave * 1024, "the K and V tiles must split into whole pieces over 4 waves");
@@ -251,7 +255,11 @@ template <int N> LFT_DEV void wait_vm_only() {
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
-template <int N> LFT_DEV void wait_vm_q(raw16& a, raw16& b) {          // s_waitcnt vmcnt(N); names the asm-loaded registers so no use moves above it
+template <int N> LFT_DEV void wait_vm_3(raw16& a, raw16& b, raw16& c) {
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int N> LFT_DEV void wait_vm_q(raw16& a, raw16& b) {         // s_waitcnt vmcnt(N); names the asm-loaded registers so no use moves above it
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
@@ -272,14 +280,98 @@ template <typename T> LFT_DEV void q_head_pair(const raw16 (&wr)[8], const Frag<
     q1 = acc_to_frag(q, 1, T());
 }
 
+// ------------------------------------------------------------------------------------------
+// Per-lane geometry of a k_spa_b workgroup.  It depends on the query tile (ty, tx), the wave, the lane and on h, w only -- not on
+// the image, the layer or the step -- so the lane-major shape class (w % 32 == 0, hw % 128 == 0) reads it from a table built once
+// per view size at pack time (k_spa_b_geom, next to k_pe_tables); every other shape computes it in the kernel's prologue with the
+// same three functions.
+// ------------------------------------------------------------------------------------------
+// Byte offsets of this lane's LDS-DMA units from the image's first token, head pair 0 (see the kernel for the unit layout).
+template <bool TOKLM> LFT_DEV void spa_b_dma_offsets(int wave, int lane, int y0, int x0, int h, int w, int (&dofs)[kAdPerWave]) {
+    // unit u = (16 (9 (wave & 1) + i) + lane / 4, lane & 3): the slot advances by 16 per piece -- one division for the
+    // first slot, then row / column by carry (the kernel is bound by vector-instruction issue, prologue included)
+    const int s0 = (wave & 1) * kAdPerWave * 16 + (lane >> 2), piece = lane & 3;
+    int row = s0 / kAttHC, col = s0 % kAttHC;
+#pragma unroll
+    for (int i = 0; i < kAdPerWave; ++i) {
+        const int gy = min(max(y0 - 2 + row, 0), h - 1), gx = min(max(x0 - 2 + col, 0), w - 1);
+        const int tk = gy * w + gx;
+        // Bank swizzle: the four 16-byte quarters of a token's 64 bytes are stored XOR-permuted by (halo row parity, bit 2 of the
+        // halo column).  A score tile's K read (16 tokens = 2 rows x 8 columns, one quarter) and a V^T transposing read (8 tokens of
+        // one row, two quarters) then touch all 64 banks once per 32-lane half; unswizzled (64-byte token stride) both are 4-way.
+        const int pq = piece ^ att_swz(row, col);
+        const int pconst = TOKLM ? ((pq >> 1) * 512 + (pq & 1) * 256) * 2 : pq * 16;               // lane-major: piece = (head, half)
+        dofs[i] = (TOKLM ? ((tk & ~31) << 8) + ((tk & 31) << 4) : tk * 256) + pconst;
+        col += 16;
+        if (col >= kAttHC) { col -= kAttHC; row += 1; }
+    }
+}
+// Window masks of the lane's query row qy (ymask: bit r = halo row r inside the window, empty when the window is) and, per 4 x 4
+// block b, of the lane's query column (xs[b]: bit e = neighbourhood column 4 (g4 & 1) + e): the 0 / -inf bias of a score element is
+// the product of the two (window, image border, the `min(h, x+3)` quirk of LFT.py:155).
+LFT_DEV void spa_b_window_masks(int lane, int qy, int y0, int x0, int bxl, int h, int w, unsigned& ymask, unsigned (&xs)[2]) {
+    const int g4 = lane >> 4;
+    const int wy0 = max(0, qy - 2), wy1 = min(h, qy + 3), cy0 = y0 - 2;
+    const int ya = min(max(wy0 - cy0, 0), 8), yb = min(max(wy1 - cy0, 0), 8);
+    ymask = ((1u << yb) - 1u) & ~((1u << ya) - 1u);                     // halo rows inside the window (empty when yb <= ya)
+    const int gx4 = 4 * (g4 & 1);
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        // the lane's query in block b: same row, column (lane & 3) of the block (the lane's OWN token r is one of the two)
+        const int bqx = x0 + bxl + 4 * b + (lane & 3), cx0 = x0 + bxl + 4 * b - 2;
+        const int wx0 = max(0, bqx - 2), wx1 = min(min(h, bqx + 3), w);                   // reference LFT.py:155 (sic)
+        const int xa = min(max(wx0 - cx0, 0), 8), xb = min(max(wx1 - cx0, 0), 8);
+        xs[b] = (((1u << xb) - 1u) & ~((1u << xa) - 1u)) >> gx4;                            // bit e: neighbourhood column gx4 + e
+    }
+}
+// K rows as the A operand of v_mfma_f32_16x16x16: lane 16 g + qi reads labels 4 g .. 4 g + 3 (8 bytes) of key qi of the tile;
+// V^T by transposing reads: lane 16 g + 4 q + p supplies the address of key 4 g + q, channels 4 p .. 4 p + 3.  One base each;
+// block, tile and head are compile-time offsets folded into the instructions.
+// With the quarter swizzle (att_swz) the label quarter 2 hl + gq of a token sits in stored quarter (2 hl + gq) ^ s(row, col);
+// s's column bit is (b ^ lane bit), so there are two bases, selected at compile time by hl ^ b.
+LFT_DEV void spa_b_read_bases(int lane, int bxl, int (&kb)[2], int (&vb)[2]) {
+    const int g4 = lane >> 4, qi = lane & 15;
+    const int ktok = ((qi >> 3) * kAttHC + bxl + (qi & 7)) * 64, ks0 = (qi >> 3) & 1, ks1 = (qi >> 2) & 1;
+    const int vtok = ((g4 >> 1) * kAttHC + bxl + 4 * (g4 & 1) + (qi >> 2)) * 64, vs0 = (g4 >> 1) & 1, vs1 = g4 & 1, vp = qi & 3;
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+        kb[x] = ktok + 32 * (x ^ ks1) + 16 * ((g4 >> 1) ^ ks0) + 8 * (g4 & 1);
+        vb[x] = kAdTile + vtok + 32 * (x ^ vs1) + 16 * ((vp >> 1) ^ vs0) + 8 * (vp & 1);
+    }
+}
+// The table of the lane-major shape class: per query tile (ty * tiles_x + tx) and wave three 1 KiB pieces of one 16-byte unit per
+// lane -- piece 0: dofs[0..3], piece 1: dofs[4..7], piece 2: dofs[8], kb[0] | kb[1] << 16, vb[0] | vb[1] << 16 (LDS offsets below
+// 2^16), ymask | xs[0] << 8 | xs[1] << 16 -- so that a wave's load of a piece is one contiguous KiB.
+constexpr int kSpaBGeomPieces = 3, kSpaBGeomTileBytes = 4 * kSpaBGeomPieces * 1024;
+__global__ __launch_bounds__(256) void k_spa_b_geom(unsigned* __restrict__ tab, int h, int w) {
+    const int tiles_x = (w + kAttTX - 1) / kAttTX;
+    const int tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
+    const int lane = threadIdx.x & 63, r = lane & 31, wave = threadIdx.x >> 6;
+    const int y0 = ty * kAttTY, x0 = tx * kAttTX, bxl = 8 * wave;
+    const int qy = y0 + ((r >> 2) & 3);
+    int dofs[kAdPerWave], kb[2], vb[2];
+    unsigned ymask, xs[2];
+    spa_b_dma_offsets<true>(wave, lane, y0, x0, h, w, dofs);
+    spa_b_window_masks(lane, qy, y0, x0, bxl, h, w, ymask, xs);
+    spa_b_read_bases(lane, bxl, kb, vb);
+    unsigned* dst = tab + ((size_t)(tile * 4 + wave) * kSpaBGeomPieces * 64 + lane) * 4;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dst[(i >> 2) * 256 + (i & 3)] = (unsigned)dofs[i];
+    dst[512] = (unsigned)dofs[8];
+    dst[513] = (unsigned)kb[0] | ((unsigned)kb[1] << 16);
+    dst[514] = (unsigned)vb[0] | ((unsigned)vb[1] << 16);
+    dst[515] = ymask | (xs[0] << 8) | (xs[1] << 16);
+}
+
 template <typename T, bool SKIP, bool TOKLM = false, bool YLM = false>   // TOKLM: k_spa1 wrote the tokens as lane-major 32-token tiles (w % 32 == 0: a tile = 32 columns of one image row); YLM: write the output so (consumer: k_up)
 __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, const T* __restrict__ Q, const T* __restrict__ K,
                                                   const T* __restrict__ Vv, const T* __restrict__ ws, const float* __restrict__ ln,
                                                   const T* __restrict__ skip, T* __restrict__ Y, int h, int w, unsigned* __restrict__ status,
-                                                  const T* __restrict__ wq, const T* __restrict__ petok) {   // wq / petok: TOKLM only (Q is computed here)
+                                                  const T* __restrict__ wq, const T* __restrict__ petok,     // wq / petok: TOKLM only (Q is computed here)
+                                                  const unsigned* __restrict__ geom) {                      // geom: TOKLM only (k_spa_b_geom's table)
     static_assert(sizeof(T) == 2, "k_spa_b is the 16-bit (bf16 / f16) part B; fp32 uses k_win_attn_lds + k_spa2");
     typedef typename H16<T>::v8 V8;
-    using Ring = WRingPipe<T, kSpaBChunk, 4, kSpaBSlots, 176>;        // weight fragments double-buffered in registers across the chunk barrier
+    using Ring = WRingPipe<T, kSpaBChunk, 4, kSpaBSlots, kSpaBFrags>;        // weight fragments double-buffered in registers across the chunk barrier
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const bufA = smem;                                          // each buffer: K tile, then V tile, of one head pair
     char* const bufB = smem + 2 * kAdTile;
@@ -310,25 +402,7 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
     // u covers 16 tokens; lane l moves 16-byte unit 64 u + l = (token slot, quarter).  Tokens outside the image are
     // fetched from the clamped position: finite values that the -inf bias (K) / zero probability (V) keep out of the result.
     int dofs[kAdPerWave];                                             // byte offsets of this lane's units from the image's first token, head pair 0
-    {
-        // unit u = (16 (9 (wave & 1) + i) + lane / 4, lane & 3): the slot advances by 16 per piece -- one division for the
-        // first slot, then row / column by carry (the kernel is bound by vector-instruction issue, prologue included)
-        const int s0 = (wave & 1) * kAdPerWave * 16 + (lane >> 2), piece = lane & 3;
-        int row = s0 / kAttHC, col = s0 % kAttHC;
-#pragma unroll
-        for (int i = 0; i < kAdPerWave; ++i) {
-            const int gy = min(max(y0 - 2 + row, 0), h - 1), gx = min(max(x0 - 2 + col, 0), w - 1);
-            const int tk = gy * w + gx;
-            // Bank swizzle: the four 16-byte quarters of a token's 64 bytes are stored XOR-permuted by (halo row parity, bit 2 of the
-            // halo column).  A score tile's K read (16 tokens = 2 rows x 8 columns, one quarter) and a V^T transposing read (8 tokens of
-            // one row, two quarters) then touch all 64 banks once per 32-lane half; unswizzled (64-byte token stride) both are 4-way.
-            const int pq = piece ^ att_swz(row, col);
-            const int pconst = TOKLM ? ((pq >> 1) * 512 + (pq & 1) * 256) * 2 : pq * 16;               // lane-major: piece = (head, half)
-            dofs[i] = (TOKLM ? ((tk & ~31) << 8) + ((tk & 31) << 4) : tk * 256) + pconst;
-            col += 16;
-            if (col >= kAttHC) { col -= kAttHC; row += 1; }
-        }
-    }
+    if constexpr (!TOKLM) spa_b_dma_offsets<false>(wave, lane, y0, x0, h, w, dofs);     // TOKLM: from the table, in the prologue below
     constexpr int kDmaPair = TOKLM ? 2048 : 64;                       // bytes from one head pair to the next
     // Issued from inline asm (glds16_asm): the compiler must not know about the pieces in flight, or it drains them in
     // front of the next LDS read.
@@ -346,52 +420,37 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
     // issued last in the prologue: between an asm load and its wait the compiler must have no reason to touch the
     // destination registers (it does not know they are pending).
     // Lane-major form (TOKLM): there are no query loads -- Q is COMPUTED in the prologue (below) -- and the iterations' waits
-    // are the same counts without them:  [tok pe Wq01 D0 D1] wait(34) LN | wait(26) Q0 Wq2 | wait(26) Q1 Wq3 | wait(8) Q2 |
+    // are the same counts without them:  [geom ln tok pe Wq01] wait(34): the table | [D0 D1] wait(34) LN | wait(26) Q0 Wq2 | wait(26) Q1 Wq3 | wait(8) Q2 |
     // wait(0) Q3 | it0 .. D2 | it1: wait(9) .. D3 | it2: wait(9) .. R0-3 | it3: wait(8) ..
     // Score tiles: per block b (columns bxl + 4 b ..) the 8 x 8 key neighbourhood = halo rows 0..7, halo columns bxl + 4 b .. + 7,
     // cut into four 16-key tiles (tile t = halo rows 2 t, 2 t + 1, key kk -> row kk / 8, column kk % 8).  S^T[key, query] of tile
     // (b, t): lane 16 g + qi holds query qi of block b against keys 4 g .. 4 g + 3 (register e), i.e. halo row 2 t + (g >> 1),
     // neighbourhood columns 4 (g & 1) + e.  The 0 / -inf bias (window, image border, the `min(h, x+3)` quirk of LFT.py:155) is the
     // product of a row mask and a column mask of the lane's query: one bit-field extract + AND per element.
-    const int g4 = lane >> 4, qi = lane & 15;
+    const int g4 = lane >> 4;
     f32x4 bias[2][4];
     int kb[2], vb[2];
+    raw16 geo2;                                                       // TOKLM: the table's third piece (dofs[8], read bases, window masks)
     auto setup_tiles = [&]() __attribute__((always_inline)) {
-    {
-        const int wy0 = max(0, qy - 2), wy1 = min(h, qy + 3), cy0 = y0 - 2;
-        const int ya = min(max(wy0 - cy0, 0), 8), yb = min(max(wy1 - cy0, 0), 8);
-        const unsigned ymask = ((1u << yb) - 1u) & ~((1u << ya) - 1u);     // halo rows inside the window (empty when yb <= ya)
-        const int gy = g4 >> 1, gx4 = 4 * (g4 & 1);
+        unsigned ymask, xs[2];
+        if constexpr (TOKLM) {                                        // the masks and the read bases (spa_b_read_bases) come from the table
+            ymask = geo2[3] & 0xffu; xs[0] = (geo2[3] >> 8) & 0xffu; xs[1] = geo2[3] >> 16;
+            kb[0] = (int)(geo2[1] & 0xffffu); kb[1] = (int)(geo2[1] >> 16);
+            vb[0] = (int)(geo2[2] & 0xffffu); vb[1] = (int)(geo2[2] >> 16);
+        } else {
+            spa_b_window_masks(lane, qy, y0, x0, bxl, h, w, ymask, xs);
+            spa_b_read_bases(lane, bxl, kb, vb);
+        }
+        const int gy = g4 >> 1;
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            // the lane's query in block b: same row, column (lane & 3) of the block (the lane's OWN token r is one of the two)
-            const int bqx = x0 + bxl + 4 * b + (lane & 3), cx0 = x0 + bxl + 4 * b - 2;
-            const int wx0 = max(0, bqx - 2), wx1 = min(min(h, bqx + 3), w);                   // reference LFT.py:155 (sic)
-            const int xa = min(max(wx0 - cx0, 0), 8), xb = min(max(wx1 - cx0, 0), 8);
-            const unsigned xs = (((1u << xb) - 1u) & ~((1u << xa) - 1u)) >> gx4;                // bit e: neighbourhood column gx4 + e
+        for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const unsigned inval = ~(xs & (unsigned)__builtin_amdgcn_sbfe((int)ymask, 2 * t + gy, 1));
+                const unsigned inval = ~(xs[b] & (unsigned)__builtin_amdgcn_sbfe((int)ymask, 2 * t + gy, 1));
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     bias[b][t][e] = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_sbfe((int)inval, e, 1) & 0xff800000u);   // 0 inside the window, -inf outside
             }
-        }
-    }
-    // K rows as the A operand of v_mfma_f32_16x16x16: lane 16 g + qi reads labels 4 g .. 4 g + 3 (8 bytes) of key qi of the tile;
-    // V^T by transposing reads: lane 16 g + 4 q + p supplies the address of key 4 g + q, channels 4 p .. 4 p + 3.  One base each;
-    // block, tile and head are compile-time offsets folded into the instructions.
-    // With the quarter swizzle (att_swz) the label quarter 2 hl + gq of a token sits in stored quarter (2 hl + gq) ^ s(row, col);
-    // s's column bit is (b ^ lane bit), so there are two bases, selected at compile time by hl ^ b.
-    {
-        const int ktok = ((qi >> 3) * kAttHC + bxl + (qi & 7)) * 64, ks0 = (qi >> 3) & 1, ks1 = (qi >> 2) & 1;
-        const int vtok = ((g4 >> 1) * kAttHC + bxl + 4 * (g4 & 1) + (qi >> 2)) * 64, vs0 = (g4 >> 1) & 1, vs1 = g4 & 1, vp = qi & 3;
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            kb[x] = ktok + 32 * (x ^ ks1) + 16 * ((g4 >> 1) ^ ks0) + 8 * (g4 & 1);
-            vb[x] = kAdTile + vtok + 32 * (x ^ vs1) + 16 * ((vp >> 1) ^ vs0) + 8 * (vp & 1);
-        }
-    }
     };
     unsigned bad = 0;                                                 // non-finite activation seen (layernorm_acc; published at the end)
     Frag<T> qfr[8];                                                   // TOKLM: this block's queries, all 8 heads, acc order
@@ -409,12 +468,21 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
         const char* psrc = reinterpret_cast<const char*>(petok + ((long long)ty_ * w + x0) * 128 + lane_piece);
         const char* wsrc = reinterpret_cast<const char*>(wq) + lane * 16;
         const int pi = min((int)threadIdx.x * 4, 252);                   // as params_load: threads beyond 64 re-read the last piece
+        // the geometry table first: the DMA offsets must be here before the K / V tiles can be requested
+        raw16 geo0, geo1;
+        const char* gsrc = reinterpret_cast<const char*>(geom) + (size_t)(bid % (tiles_x * tiles_y)) * kSpaBGeomTileBytes
+                           + wave * (kSpaBGeomPieces * 1024) + lane * 16;
+        ld16_async_ofs<0>(gsrc, geo0); ld16_async_ofs<1024>(gsrc, geo1); ld16_async_ofs<2048>(gsrc, geo2);
         ld16_async(ln + pi, lnv1);                                       // norm.{weight,bias}
         ld16_async(ln + 256 + pi, lnv);
         ld16_async_x8(tsrc, tokr);
         ld16_async_x8(psrc, per);
         ld16_async_x8(wsrc, wqa);                                         // head pair 0: fragments (nt = 0, ks = 0..7)
         ld16_async_x8(wsrc + 8 * 1024, wqb);                              // head pair 1
+        wait_vm_3<2 + 32>(geo0, geo1, geo2);                             // the table is the oldest: everything else stays in flight
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { dofs[i] = (int)geo0[i]; dofs[4 + i] = (int)geo1[i]; }
+        dofs[8] = (int)geo2[0];
         stage(0, bufA);
         stage(1, bufB);
         // (setup_tiles() stays behind the Q projection.  Round 4 tried it here, under the first memory round trip: with 52 asm loads
@@ -423,7 +491,7 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
         // (No LFT_STAMP between here and the last Wq wait: a stamp is compiler-visible code with live registers of its own -- in the
         // diagnostic build it made hipcc spill and MOVE asm-loaded registers that were still in flight, and the kernel faulted on a
         // garbage address.  Run tools/asm_load_hazards.py on a diagnostic listing before launching it.)
-        // in flight: 2 + 16 + 16 + 18 = 52.  Tokens, position tokens and LayerNorm parameters first:
+        // in flight: 2 + 16 + 16 + 18 = 52 (the three table pieces have landed).  Tokens, position tokens and LayerNorm parameters first:
         wait_vm_8<16 + 2 * kAdPerWave>(tokr);
         wait_vm_8<16 + 2 * kAdPerWave>(per);
         asm volatile("" : "+v"(lnv), "+v"(lnv1));
@@ -590,7 +658,7 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
         }
     }
     char* scr = bufB + kSpaBScratchOfs + wave * TileIO<4, T>::BYTES;
-    f32x16 t[4], n[4];
+    f32x16 t[4];
     if constexpr (TOKLM) {
         // Row rr of this wave's 8 x 4 block = lanes 8 wave .. 8 wave + 7 of the lane-major tile of image row y0 + rr: the 16-byte
         // piece [k-step][32 hh + column] holds exactly registers 8k .. 8k+7 of this lane's accumulator tile (load_tile_lm).
@@ -611,29 +679,27 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
     ring.start();
     linear_ring_at<0, 4, 8>(ring, of, t);                             // t = tok + O Wo^T
     LFT_STAMP(27);
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) n[nt] = t[nt];
-    layernorm_acc<4, true>(n, lds_ln, lds_ln + 128, hh, bad);                  // t carries whatever overflowed in tok / Q / K / V / the attention
     Frag<T> f[8];
-    acc_frags<4, T>(n, f);
-    auto ffn_chunk = [&](auto cc) __attribute__((always_inline)) {                                   // hidden units 64 c .. 64 c + 63: stream positions 32 + 32 c ..
+    acc_frags<4, T>(t, f);
+    f32x16 y[2];
+    zero_acc<2>(y);
+    linear_ring_at<32, 2, 8>(ring, f, y);                             // y = Wl t: t is rounded as it was in front of the 1x1x1 conv
+    layernorm_acc<4, true>(t, lds_ln, lds_ln + 128, hh, bad);                  // in place (t is dead behind it); t carries whatever overflowed in tok / Q / K / V / the attention
+    acc_frags<4, T>(t, f);
+    auto ffn_chunk = [&](auto cc) __attribute__((always_inline)) {                                   // hidden units 64 c .. 64 c + 63: stream positions 48 + 24 c ..
         constexpr int C = decltype(cc)::value;
         f32x16 hid[2];
         zero_acc<2>(hid);
-        linear_ring_at<32 + 32 * C, 2, 8>(ring, f, hid);
+        linear_ring_at<48 + 24 * C, 2, 8>(ring, f, hid);
         Frag<T> hf[4];
         acc_frags_relu<2>(hid, hf);
-        linear_ring_at<32 + 32 * C + 16, 4, 4>(ring, hf, t);
+        linear_ring_at<48 + 24 * C + 16, 2, 4>(ring, hf, y);         // y += (Wl W2)c relu(hid)
     };
     ffn_chunk(std::integral_constant<int, 0>());
     ffn_chunk(std::integral_constant<int, 1>());
     ffn_chunk(std::integral_constant<int, 2>());
     ffn_chunk(std::integral_constant<int, 3>());
     LFT_STAMP(28);
-    acc_frags<4, T>(t, f);
-    f32x16 y[2];
-    zero_acc<2>(y);
-    linear_ring_at<160, 2, 8>(ring, f, y);
     LFT_STAMP(29);
     BlkRows ry = rows; ry.img_row_bytes = w * 128; ry.tok_bytes = 128;
     if (SKIP) {
