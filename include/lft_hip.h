@@ -285,6 +285,34 @@ int lft_l1_loss(const float* sr, const float* hr, long long n, float* dsr, float
 int lft_lf_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes);
 int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, int penalty, float eps, float w_pix, float w_epi,
                 float* dsr, float gscale, float* loss3, void* scratch, void* stream);
+/* ---- structural training term: one minus the Gaussian-window SSIM, value and gradient ----
+ * sr and hr are fp32 [B,1,A*H,A*W]; H x W is the HR view size; view (a1,a2) occupies rows a1*H... and columns a2*W....
+ * Per view the SSIM map is exactly that of lft_view_metrics (k_view_metrics): normalised separable 11x11 Gaussian g, sigma 1.5;
+ * mu = g * v, sigma^2 = (121/120) (g * v^2 - mu^2), sigma_xy likewise; C1 = (0.01 R)^2, C2 = (0.03 R)^2 with R = ssim_range;
+ *   S_q = (2 mu_x mu_y + C1)(2 sigma_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(sigma_x^2 + sigma_y^2 + C2))      x = hr, y = sr
+ * at the interior pixels 5 <= y < H-5, 5 <= x < W-5 only; a window never crosses a view border.  S_view is the mean of the map over
+ * the interior, and
+ *   S = the PLAIN mean of S_view over all B*A*A views,    Q = 1 - S.
+ * This is NOT cal_metrics' "mean over the views above 0" (what fit and evaluate log per set): that rule drops views by their value
+ * and is not differentiable.  Every count scales with B, so a mean over equal local shards averages to the global-batch objective,
+ * as for L1 and lft_lf_loss.
+ * Gradient: d S / d y(p) = (1 / (views * interior pixels)) sum_q g(q - p) [a(q) + b(q) y(p) + c(q) x(p)], with
+ *   b = 2 (121/120) dS_q/d sigma_y^2,  c = (121/120) dS_q/d sigma_xy,  a = dS_q/d mu_y - b mu_y - c mu_x,
+ * all zero at centres q outside the interior: three more separable filter passes.  ALL arithmetic between the fp32 loads and the fp32
+ * stores is fp64, as in lft_view_metrics: E[v^2] - mu^2 cancels, and an all-fp32 evaluation is wrong by 1e-5 ... 6.5e-5 of the
+ * largest gradient element on smooth inputs, where the fp64 one leaves the store rounding.
+ * lft_ssim_loss: *ssim_out = S.  accumulate == 0: *total = w_ssim*Q, and dsr (may be NULL: values only) is fully overwritten with
+ * gscale * w_ssim * dQ/dsr.  accumulate == 1: both are ADDED, in stream order, to what total and dsr already hold (one rounding of
+ * the fp64 sum) -- this is how the term follows lft_lf_loss in a training step.  scratch: lft_ssim_loss_scratch_bytes bytes of
+ * device memory, 8-byte aligned.  Two launches (one 16x16-tile stencil pass with a halo of 10, one fold of fp64 per-tile partial
+ * sums in a fixed order: no atomics, bit-reproducible); no allocation, no synchronisation, graph-capturable; any row pitch and any
+ * 4-byte aligned pointers: the tile loads and stores are scalar, one 64-byte row segment per 16 lanes.
+ * Refused before anything is launched -- LFT_ERR_ARG: null sr, hr, total, ssim_out or scratch, misaligned pointers; ssim_range or
+ * w_ssim not finite or <= 0; NaN gscale; accumulate other than 0 or 1; dsr overlapping sr or hr.  LFT_ERR_SHAPE: non-positive
+ * sizes; H < 11 or W < 11 (the rule of lft_view_metrics); more than 2^31 - 1 tiles. */
+int lft_ssim_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes);
+int lft_ssim_loss(const float* sr, const float* hr, int B, int A, int H, int W, float ssim_range, float w_ssim,
+                  float* dsr, float gscale, int accumulate, float* total, float* ssim_out, void* scratch, void* stream);
 /* torch.optim.Adam step (train.py:77-83: betas (0.9, 0.999), eps 1e-8, weight_decay = --decay_rate, default 0) on one
  * flat fp32 buffer; step counts from 1; the gradient is multiplied by gscale first (1/world_size after a sum all-reduce),
  * then weight_decay * p is added (torch's L2 form); bias corrections are computed in double, as torch does. */

@@ -40,6 +40,7 @@ namespace {
 #include "lft_attn_maps.cuh" // attention weights from the tape's Q | K (lft_train_attn_maps)
 #include "lft_optim.cuh"     // guarded Adam step: gradient statistics, skip / clip decision, update (lft_adam_step_guarded)
 #include "lft_loss.cuh"      // pixel + EPI-gradient loss with L1 / MSE / Charbonnier penalty (lft_lf_loss)
+#include "lft_ssim_loss.cuh" // structural term 1 - SSIM and its gradient, fp64 inside (lft_ssim_loss)
 #endif
 #if LFT_TU != 2
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
@@ -1388,6 +1389,58 @@ int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, in
     LFT_LAUNCH_OK("k_lf_loss");
     k_lf_loss_fold<<<1, kLossThreads, 0, st>>>(part, nb, f, loss3);
     LFT_LAUNCH_OK("k_lf_loss_fold");
+    return 0;
+}
+// ---- structural loss term (lft_ssim_loss.cuh) ----
+namespace {
+struct SsimShape { long long n, nblocks, views; int tiles_x, ntiles; };
+int ssim_shape(int B, int A, int H, int W, SsimShape* s) {
+    if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "sizes must be positive, got B %d A %d H %d W %d", B, A, H, W);
+    if (H < 11 || W < 11) return fail(LFT_ERR_SHAPE, "views of %dx%d are smaller than the 11x11 SSIM window", H, W);
+    s->tiles_x = (W + kSsimTile - 1) / kSsimTile;
+    const long long ntiles = (long long)s->tiles_x * ((H + kSsimTile - 1) / kSsimTile);
+    s->views = (long long)B * A * A;
+    s->n = s->views * H * W;
+    s->nblocks = s->views * ntiles;
+    if (s->nblocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%lld tiles, more than one launch holds", s->nblocks);
+    s->ntiles = (int)ntiles;
+    return 0;
+}
+}  // namespace
+int lft_ssim_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
+    SsimShape s;
+    if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
+    *out_bytes = (size_t)s.nblocks * sizeof(double);
+    return 0;
+}
+int lft_ssim_loss(const float* sr, const float* hr, int B, int A, int H, int W, float ssim_range, float w_ssim,
+                  float* dsr, float gscale, int accumulate, float* total, float* ssim_out, void* scratch, void* stream) {
+    if (!sr || !hr || !total || !ssim_out || !scratch) return fail(LFT_ERR_ARG, "null pointer");
+    if ((((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)dsr | (uintptr_t)total | (uintptr_t)ssim_out) & 3) || ((uintptr_t)scratch & 7))
+        return fail(LFT_ERR_ARG, "sr, hr, dsr, total and ssim_out must be 4-byte aligned, scratch 8-byte aligned");
+    if (!(ssim_range > 0.0f) || !std::isfinite(ssim_range)) return fail(LFT_ERR_ARG, "ssim_range must be positive and finite, got %g", (double)ssim_range);
+    if (!(w_ssim > 0.0f) || !std::isfinite(w_ssim)) return fail(LFT_ERR_ARG, "w_ssim must be positive and finite, got %g", (double)w_ssim);
+    if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "gscale is NaN");
+    if (accumulate != 0 && accumulate != 1) return fail(LFT_ERR_ARG, "accumulate must be 0 or 1, got %d", accumulate);
+    SsimShape s;
+    if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
+    if (dsr && (((uintptr_t)dsr < (uintptr_t)(sr + s.n) && (uintptr_t)sr < (uintptr_t)(dsr + s.n)) ||
+                ((uintptr_t)dsr < (uintptr_t)(hr + s.n) && (uintptr_t)hr < (uintptr_t)(dsr + s.n))))
+        return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the windows read neighbours, in place would race");
+    const double R = (double)ssim_range, count = (double)s.views * (H - 2 * kSsimR) * (W - 2 * kSsimR);
+    SsimArgs a = {};
+    a.A = A; a.H = H; a.W = W; a.tiles_x = s.tiles_x; a.ntiles = s.ntiles; a.accumulate = accumulate;
+    a.C1 = (0.01 * R) * (0.01 * R); a.C2 = (0.03 * R) * (0.03 * R);                  // as lft_view_metrics forms them
+    a.k = -(double)gscale * (double)w_ssim / count;                                   // Q = 1 - S
+    const SsimFoldArgs f = {1.0 / count, (double)w_ssim, accumulate};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(scratch);
+    if (dsr) k_ssim_loss<true><<<(unsigned)s.nblocks, kSsimThreads, 0, st>>>(sr, hr, dsr, a, part);
+    else k_ssim_loss<false><<<(unsigned)s.nblocks, kSsimThreads, 0, st>>>(sr, hr, dsr, a, part);
+    LFT_LAUNCH_OK("k_ssim_loss");
+    k_ssim_loss_fold<<<1, kSsimThreads, 0, st>>>(part, s.nblocks, f, total, ssim_out);
+    LFT_LAUNCH_OK("k_ssim_loss_fold");
     return 0;
 }
 int lft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,

@@ -2,6 +2,9 @@
 penalty on the gradients of the epipolar-plane images (EPIs), the structure term that keeps parallax lines straight.  The definition
 is in include/lft_hip.h (lft_lf_loss); on a HIP device value and gradient come from that one fused kernel, on the CPU from torch ops.
 
+``LFLoss(..., ssim_weight=a)`` adds a structural term a * (1 - S), S the plain mean over all views of the Gaussian-window SSIM that
+``lft_view_metrics`` reports (lft_ssim_loss in include/lft_hip.h: fp64 inside, value and gradient from one more fused kernel).
+
 ``TrainStep(loss=LFLoss(...))`` / ``fit(loss=...)`` put the kernel inside the captured step; ``LFLoss()(SR, HR)`` under autograd serves
 the reference's own loop; ``epi_error`` is the EPI term with the L1 penalty as an evaluation figure of angular consistency.
 """
@@ -18,6 +21,7 @@ from . import _lib
 
 PENALTIES = {"l1": _lib.LOSS_L1, "mse": _lib.LOSS_MSE, "charbonnier": _lib.LOSS_CHARBONNIER}
 _SPEC_KEYS = ("penalty", "eps", "pixel_weight", "epi_weight", "angRes")
+_SSIM_KEYS = ("ssim_weight", "ssim_range")
 
 
 def scratch_bytes(B: int, A: int, H: int, W: int) -> int:
@@ -74,29 +78,112 @@ def lf_loss_torch(sr: torch.Tensor, hr: torch.Tensor, angRes: int, penalty="l1",
     return pixel_weight * P + epi_weight * E, P, E
 
 
+def ssim_scratch_bytes(B: int, A: int, H: int, W: int) -> int:
+    n = ctypes.c_size_t(0)
+    _lib.check(_lib.lib().lft_ssim_loss_scratch_bytes(B, A, H, W, ctypes.byref(n)), "lft_ssim_loss_scratch_bytes")
+    return n.value
+
+
+def ssim_loss(sr: torch.Tensor, hr: torch.Tensor, angRes: int, ssim_range: float = 2.0, ssim_weight: float = 1.0,
+              dsr: Optional[torch.Tensor] = None, gscale: float = 1.0, accumulate: bool = False, total: Optional[torch.Tensor] = None,
+              ssim_out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """lft_ssim_loss on contiguous float32 HIP tensors [B,1,A*H,A*W]: returns (total, ssim_out), one-element device tensors holding
+    ssim_weight * (1 - S) and S, and, if `dsr` is given, writes gscale * ssim_weight * d(1 - S) / d sr there.  accumulate: total and
+    dsr are added to instead (both must then be given).  total / ssim_out / scratch: buffers to use.  Only enqueues."""
+    if not sr.is_cuda:
+        raise _lib.LftError("lft_ssim_loss runs on a HIP device only")
+    for t in (sr, hr) + (() if dsr is None else (dsr,)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != sr.shape or t.device != sr.device or t.dim() != 4 or t.shape[1] != 1:
+            raise _lib.LftError("sr, hr and dsr must be contiguous float32 tensors [B,1,A*H,A*W] on one device")
+    B, _, R, C = sr.shape
+    A = int(angRes)
+    if A < 1 or R % A or C % A:
+        raise _lib.LftError(f"a {R} x {C} mosaic does not divide into {A} x {A} views")
+    H, W = R // A, C // A
+    if accumulate and total is None:
+        raise _lib.LftError("accumulate adds to `total`: pass the tensor that holds the other terms")
+    for t in (total, ssim_out):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != sr.device):
+            raise _lib.LftError("total and ssim_out are one-element float32 tensors on the device of sr")
+    with torch.cuda.device(sr.device):
+        if total is None:
+            total = torch.empty(1, dtype=torch.float32, device=sr.device)
+        if ssim_out is None:
+            ssim_out = torch.empty(1, dtype=torch.float32, device=sr.device)
+        if scratch is None:
+            scratch = torch.empty(ssim_scratch_bytes(B, A, H, W), dtype=torch.uint8, device=sr.device)
+        _lib.check(_lib.lib().lft_ssim_loss(sr.data_ptr(), hr.data_ptr(), B, A, H, W, ssim_range, ssim_weight,
+                                            None if dsr is None else dsr.data_ptr(), gscale, int(bool(accumulate)), total.data_ptr(),
+                                            ssim_out.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(sr.device).cuda_stream),
+                   "lft_ssim_loss")
+    return total, ssim_out
+
+
+def ssim_loss_torch(sr: torch.Tensor, hr: torch.Tensor, angRes: int, ssim_range: float = 2.0) -> torch.Tensor:
+    """S of include/lft_hip.h (lft_ssim_loss) with torch ops, in the tensors' own dtype (the CPU path of LFLoss), differentiable: the
+    plain mean over all views of the interior mean of the Gaussian-window SSIM map.  Valid-mode separable conv2d per view."""
+    B, _, R, C = sr.shape
+    A = int(angRes)
+    H, W = R // A, C // A
+    if H < 11 or W < 11:
+        raise ValueError(f"views of {H}x{W} are smaller than the 11x11 SSIM window")
+    k = torch.arange(-5, 6, dtype=torch.float64)
+    g = torch.exp(-0.5 * k * k / (1.5 * 1.5))
+    g = (g / g.sum()).to(dtype=sr.dtype, device=sr.device)
+
+    def views(t):
+        return t.reshape(B, A, H, A, W).permute(0, 1, 3, 2, 4).reshape(B * A * A, 1, H, W)
+
+    def filt(t):
+        return torch.nn.functional.conv2d(torch.nn.functional.conv2d(t, g.view(1, 1, 1, 11)), g.view(1, 1, 11, 1))
+
+    x, y = views(hr), views(sr)
+    mx, my = filt(x), filt(y)
+    cov = 121.0 / 120.0
+    vx, vy, vxy = cov * (filt(x * x) - mx * mx), cov * (filt(y * y) - my * my), cov * (filt(x * y) - mx * my)
+    C1, C2 = (0.01 * ssim_range) ** 2, (0.03 * ssim_range) ** 2
+    smap = ((2 * mx * my + C1) * (2 * vxy + C2)) / ((mx * mx + my * my + C1) * (vx + vy + C2))
+    return smap.mean(dim=(1, 2, 3)).mean()
+
+
 class _LFLossFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, sr, hr, A, pen, eps, w_pix, w_epi):
+    def forward(ctx, sr, hr, A, pen, eps, w_pix, w_epi, w_ssim, ssim_range):
         sr_c, hr_c = sr.detach().contiguous().float(), hr.detach().contiguous().float()
         dsr = torch.empty_like(sr_c)
-        loss3 = lf_loss(sr_c, hr_c, A, pen, eps, w_pix, w_epi, dsr=dsr)
+        lf = w_pix > 0.0 or w_epi > 0.0
+        terms = torch.zeros(4 if w_ssim > 0.0 else 3, dtype=torch.float32, device=sr_c.device)
+        if lf:
+            lf_loss(sr_c, hr_c, A, pen, eps, w_pix, w_epi, dsr=dsr, loss3=terms[:3])
+        if w_ssim > 0.0:
+            ssim_loss(sr_c, hr_c, A, ssim_range, w_ssim, dsr=dsr, accumulate=lf, total=terms[0:1], ssim_out=terms[3:4])
         ctx.save_for_backward(dsr)
-        ctx.mark_non_differentiable(loss3)
-        return loss3[0].clone(), loss3
+        ctx.mark_non_differentiable(terms)
+        return terms[0].clone(), terms
 
     @staticmethod
     def backward(ctx, gtotal, _gterms):
         (dsr,) = ctx.saved_tensors
-        return gtotal * dsr, None, None, None, None, None, None
+        return gtotal * dsr, None, None, None, None, None, None, None, None
 
 
 class LFLoss(nn.Module):
     """total = pixel_weight * mean rho(SR - HR) + epi_weight * (rho on the EPI gradients of SR - HR), rho = 'l1', 'mse' or
     'charbonnier' (sqrt(x^2 + eps^2)).  angRes: views per side of the mosaics; needed for the EPI term (``get_loss(args)`` and
-    TrainStep fill it in).  ``forward`` returns the total -- with a gradient for SR only -- and leaves (total, P, E) in ``.terms``."""
+    TrainStep fill it in).  ``forward`` returns the total -- with a gradient for SR only -- and leaves (total, P, E) in ``.terms``.
 
-    def __init__(self, penalty: str = "l1", eps: float = 1e-3, pixel_weight: float = 1.0, epi_weight: float = 0.0, angRes: Optional[int] = None):
+    ssim_weight > 0 adds ssim_weight * (1 - S): S is the plain mean over all views of the SSIM that lft_view_metrics computes with
+    data range ``ssim_range`` (2.0 is what fit and evaluate report with, so the term is one minus the logged figure).  ``.terms``
+    is then (total, P, E, S), the spec carries the two keys, and pixel_weight == epi_weight == 0 is the pure structural objective."""
+
+    def __init__(self, penalty: str = "l1", eps: float = 1e-3, pixel_weight: float = 1.0, epi_weight: float = 0.0, angRes: Optional[int] = None,
+                 ssim_weight: float = 0.0, ssim_range: float = 2.0):
         super().__init__()
+        ssim_weight, ssim_range = float(ssim_weight), float(ssim_range)
+        if not (ssim_weight >= 0.0 and math.isfinite(ssim_weight)):
+            raise ValueError(f"ssim_weight must be finite and not negative, got {ssim_weight}")
+        if not (ssim_range > 0.0 and math.isfinite(ssim_range)):
+            raise ValueError(f"ssim_range must be positive and finite, got {ssim_range}")
         if penalty not in PENALTIES:
             raise ValueError(f"penalty must be one of {sorted(PENALTIES)}, got {penalty!r}")
         eps, pixel_weight, epi_weight = float(eps), float(pixel_weight), float(epi_weight)
@@ -105,17 +192,21 @@ class LFLoss(nn.Module):
         for name, w in (("pixel_weight", pixel_weight), ("epi_weight", epi_weight)):
             if not (w >= 0.0 and math.isfinite(w)):
                 raise ValueError(f"{name} must be finite and not negative, got {w}")
-        if pixel_weight == 0.0 and epi_weight == 0.0:
+        if pixel_weight == 0.0 and epi_weight == 0.0 and ssim_weight == 0.0:
             raise ValueError("pixel_weight and epi_weight are both zero")
         if angRes is not None and int(angRes) < 1:
             raise ValueError(f"angRes must be positive, got {angRes}")
         self.penalty, self.eps, self.pixel_weight, self.epi_weight = penalty, eps, pixel_weight, epi_weight
+        self.ssim_weight, self.ssim_range = ssim_weight, ssim_range
         self.angRes = None if angRes is None else int(angRes)
         self.terms = None
 
     def spec(self) -> dict:
-        return {"penalty": self.penalty, "eps": self.eps, "pixel_weight": self.pixel_weight, "epi_weight": self.epi_weight,
-                "angRes": self.angRes}
+        d = {"penalty": self.penalty, "eps": self.eps, "pixel_weight": self.pixel_weight, "epi_weight": self.epi_weight,
+             "angRes": self.angRes}
+        if self.ssim_weight > 0.0:                                # without the term: the five keys of every earlier state file
+            d.update(ssim_weight=self.ssim_weight, ssim_range=self.ssim_range)
+        return d
 
     @classmethod
     def from_spec(cls, d) -> "LFLoss":
@@ -124,32 +215,47 @@ class LFLoss(nn.Module):
         if isinstance(d, str):
             d = {"penalty": d}
         if not isinstance(d, dict):
-            raise ValueError(f"a loss spec is a dict with keys out of {_SPEC_KEYS}, got {type(d).__name__}")
-        unknown = sorted(set(d) - set(_SPEC_KEYS))
+            raise ValueError(f"a loss spec is a dict with keys out of {_SPEC_KEYS + _SSIM_KEYS}, got {type(d).__name__}")
+        unknown = sorted(set(d) - set(_SPEC_KEYS + _SSIM_KEYS))
         if unknown:
-            raise ValueError(f"unknown key(s) {unknown} in the loss spec; known: {_SPEC_KEYS}")
+            raise ValueError(f"unknown key(s) {unknown} in the loss spec; known: {_SPEC_KEYS + _SSIM_KEYS}")
         return cls(**d)
 
     def is_plain_l1(self) -> bool:
         """The reference's objective, which TrainStep serves with lft_l1_loss."""
-        return self.penalty == "l1" and self.pixel_weight == 1.0 and self.epi_weight == 0.0
+        return self.penalty == "l1" and self.pixel_weight == 1.0 and self.epi_weight == 0.0 and self.ssim_weight == 0.0
+
+    def has_lf_terms(self) -> bool:
+        """False for the pure structural objective, which skips lft_lf_loss."""
+        return self.pixel_weight > 0.0 or self.epi_weight > 0.0
 
     def _args(self):
         A = self.angRes
         if A is None:                                             # the pixel term alone does not look at the views
             if self.epi_weight > 0.0:
                 raise ValueError("the EPI term needs angRes: LFLoss(..., angRes=A)")
+            if self.ssim_weight > 0.0:
+                raise ValueError("the SSIM term needs angRes: LFLoss(..., angRes=A)")
             A = 1
         return A, self.penalty, self.eps, self.pixel_weight, self.epi_weight
 
     def forward(self, SR, HR):
         if SR.is_cuda:
             A, pen, eps, wp, we = self._args()
-            total, terms = _LFLossFunction.apply(SR, HR, A, pen, eps, wp, we)
+            total, terms = _LFLossFunction.apply(SR, HR, A, pen, eps, wp, we, self.ssim_weight, self.ssim_range)
             self.terms = terms
             return total
-        total, P, E = lf_loss_torch(SR, HR, *self._args())
-        self.terms = torch.stack([total.detach(), P.detach(), E.detach()])
+        args = self._args()
+        if self.has_lf_terms():
+            total, P, E = lf_loss_torch(SR, HR, *args)
+        else:
+            total = P = E = SR.new_zeros(())
+        if self.ssim_weight == 0.0:
+            self.terms = torch.stack([total.detach(), P.detach(), E.detach()])
+            return total
+        S = ssim_loss_torch(SR, HR, args[0], self.ssim_range)
+        total = total + self.ssim_weight * (1.0 - S)
+        self.terms = torch.stack([total.detach(), P.detach(), E.detach(), S.detach()])
         return total
 
 

@@ -368,8 +368,9 @@ class TrainStep:
         self.last_out = None               # [B,1,A*h*s,A*w*s]: what the network produced in the last step (before the update), for per-batch metrics
         self._scratch = torch.empty(1024 + 1, dtype=torch.float32, device=dev)
         # loss: None or 'l1' -- the reference's L1 through lft_l1_loss, the bits of every earlier version; an lft_amd.loss.LFLoss (or
-        # its spec) other than pure L1 -- lft_lf_loss at the same place, (total, P, E) of the last step in last_loss_terms
-        self.loss, self.last_loss_terms, self._loss_scratch = None, None, {}
+        # its spec) other than pure L1 -- lft_lf_loss at the same place, (total, P, E) of the last step in last_loss_terms; with
+        # ssim_weight > 0 lft_ssim_loss follows it, adds to the same dout and total, and leaves S in a fourth entry
+        self.loss, self.last_loss_terms, self._loss_scratch, self._ssim_scratch = None, None, {}, {}
         if loss is not None and loss != "l1":
             from .loss import LFLoss
             loss = LFLoss.from_spec(loss)
@@ -379,15 +380,20 @@ class TrainStep:
                 raise ValueError(f"the loss was built for angRes {loss.angRes}, the network has {self.A}")
             if not loss.is_plain_l1():
                 self.loss = loss
-                self.last_loss_terms = torch.zeros(3, dtype=torch.float32, device=dev)
+                self.last_loss_terms = torch.zeros(4 if loss.ssim_weight > 0.0 else 3, dtype=torch.float32, device=dev)
 
     def _loss_scratch_for(self, hr):
-        """Scratch of lft_lf_loss for this batch shape: allocated once, outside any capture."""
+        """Scratch of lft_lf_loss (and of lft_ssim_loss) for this batch shape: allocated once, outside any capture."""
         key = tuple(hr.shape)
+        B, _, R, C = hr.shape
+        if self.loss.ssim_weight > 0.0 and (R // self.A < 11 or C // self.A < 11):      # before anything is allocated, enqueued or captured
+            raise ValueError(f"the SSIM term needs HR views of at least 11x11 (its window), got views of {R // self.A}x{C // self.A}")
         if key not in self._loss_scratch:
             from .loss import scratch_bytes
-            B, _, R, C = hr.shape
             self._loss_scratch[key] = torch.empty(scratch_bytes(B, self.A, R // self.A, C // self.A), dtype=torch.uint8, device=hr.device)
+        if self.loss.ssim_weight > 0.0 and key not in self._ssim_scratch:
+            from .loss import ssim_scratch_bytes
+            self._ssim_scratch[key] = torch.empty(ssim_scratch_bytes(B, self.A, R // self.A, C // self.A), dtype=torch.uint8, device=hr.device)
         return self._loss_scratch[key]
 
     def _fwd_loss_bwd(self, lr_in, hr, tape, dout, loss, on_bucket=None):
@@ -400,9 +406,14 @@ class TrainStep:
             _lib.check(L.lft_l1_loss(out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, loss.data_ptr(),
                                      self._scratch.data_ptr(), stream), "lft_l1_loss")
         else:
-            from .loss import lf_loss
-            lf_loss(out, hr, self.A, self.loss.penalty, self.loss.eps, self.loss.pixel_weight, self.loss.epi_weight, dsr=dout,
-                    loss3=self.last_loss_terms, scratch=self._loss_scratch[tuple(hr.shape)])
+            from .loss import lf_loss, ssim_loss
+            lf = self.loss.has_lf_terms()
+            if lf:
+                lf_loss(out, hr, self.A, self.loss.penalty, self.loss.eps, self.loss.pixel_weight, self.loss.epi_weight, dsr=dout,
+                        loss3=self.last_loss_terms, scratch=self._loss_scratch[tuple(hr.shape)])
+            if self.loss.ssim_weight > 0.0:                    # P and E stay 0 in the pure structural objective
+                ssim_loss(out, hr, self.A, self.loss.ssim_range, self.loss.ssim_weight, dsr=dout, accumulate=lf,
+                          total=self.last_loss_terms[0:1], ssim_out=self.last_loss_terms[3:4], scratch=self._ssim_scratch[tuple(hr.shape)])
         if on_bucket is None:
             train_backward(self.params, lr_in, tape, dout, self.A, self.s, grads=self.flat_grads, math=self.math)
         else:

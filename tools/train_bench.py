@@ -12,7 +12,9 @@ EMA is built beside it and R rounds of --steps steps alternate between the two i
 both series, the only fair way to see a difference of this size.
 --loss {l1,mse,charbonnier} / --epi_weight W: the step minimises an lft_amd.loss.LFLoss (lft_lf_loss in the place of lft_l1_loss), and
 "loss_ms" holds the event-timed milliseconds of the loss launches alone -- lft_lf_loss and, alternating with it in this one process on
-the same tensors, lft_l1_loss (medians over 50 calls each)."""
+the same tensors, lft_l1_loss (medians over 50 calls each).
+--ssim_weight W / --ssim_range R: the objective gains W * (1 - SSIM) (lft_ssim_loss right after lft_lf_loss, accumulating into the same
+gradient); "loss_ms" then also times that call."""
 import argparse, json, os, sys, time
 from types import SimpleNamespace
 
@@ -27,7 +29,7 @@ def time_loss_launches(ts, hr, calls=50):
     """Median event-timed milliseconds of one lft_lf_loss call (the step's objective) and of one lft_l1_loss call on the same tensors,
     the two alternating."""
     from lft_amd import _lib
-    from lft_amd.loss import lf_loss
+    from lft_amd.loss import lf_loss, ssim_loss
     sr, dout = ts.last_out, torch.empty_like(hr)
     n = sr.numel()
     stream = torch.cuda.current_stream(hr.device).cuda_stream
@@ -41,9 +43,16 @@ def time_loss_launches(ts, hr, calls=50):
         _lib.check(_lib.lib().lft_l1_loss(sr.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, ts._scratch[1024:].data_ptr(),
                                           ts._scratch.data_ptr(), stream), "lft_l1_loss")
 
-    ms = {"lft_lf_loss": [], "lft_l1_loss": []}
+    def run_ssim():
+        ssim_loss(sr, hr, ts.A, ts.loss.ssim_range, ts.loss.ssim_weight, dsr=dout, accumulate=ts.loss.has_lf_terms(),
+                  total=ts.last_loss_terms[0:1], ssim_out=ts.last_loss_terms[3:4], scratch=ts._ssim_scratch[tuple(hr.shape)])
+
+    runs = [("lft_l1_loss", run_l1)] + ([("lft_lf_loss", run_lf)] if ts.loss.has_lf_terms() else [])
+    if ts.loss.ssim_weight > 0.0:
+        runs.append(("lft_ssim_loss", run_ssim))
+    ms = {name: [] for name, _ in runs}
     for i in range(calls + 5):
-        for name, run in (("lft_l1_loss", run_l1), ("lft_lf_loss", run_lf)):
+        for name, run in runs:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             run()
@@ -71,6 +80,8 @@ def main():
     ap.add_argument("--alternate", type=int, default=0, metavar="R", help="with --ema_decay: R rounds alternating with an identical step that keeps no EMA")
     ap.add_argument("--loss", default=None, choices=["l1", "mse", "charbonnier"], help="penalty of an LFLoss objective; default: the reference's L1 step")
     ap.add_argument("--epi_weight", type=float, default=0.0, help="weight of the EPI-gradient term of --loss")
+    ap.add_argument("--ssim_weight", type=float, default=0.0, help="weight of the structural term 1 - SSIM (lft_ssim_loss)")
+    ap.add_argument("--ssim_range", type=float, default=2.0, help="data range of that SSIM; 2 is what fit and evaluate report with")
     args = ap.parse_args()
     if args.alternate and args.ema_decay is None:
         ap.error("--alternate compares with and without the EMA: it needs --ema_decay")
@@ -93,7 +104,9 @@ def main():
 
     lr = torch.from_numpy(synthetic_lr(args.batch, A, H, H, seed=rank)).to(dev)
     hr = torch.from_numpy(np.random.Generator(np.random.PCG64([2, rank])).random((args.batch, 1, A * H * S, A * H * S), dtype=np.float32)).to(dev)
-    spec = None if args.loss is None else {"penalty": args.loss, "epi_weight": args.epi_weight}
+    spec = None if args.loss is None and args.ssim_weight == 0.0 else {"penalty": args.loss or "l1", "epi_weight": args.epi_weight}
+    if args.ssim_weight > 0.0:
+        spec.update(ssim_weight=args.ssim_weight, ssim_range=args.ssim_range)
     ts = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard, ema_decay=args.ema_decay, loss=spec)
 
     def sync():

@@ -50,6 +50,8 @@ def parse_args(argv=None):
     ap.add_argument("--charbonnier_eps", type=float, default=1e-3)
     ap.add_argument("--pixel_weight", type=float, default=1.0, help="weight of the pixel term")
     ap.add_argument("--epi_weight", type=float, default=0.0, help="weight of the EPI-gradient term (the penalty on the gradients of the epipolar-plane images)")
+    ap.add_argument("--ssim_weight", type=float, default=0.0, help="weight of the structural term 1 - SSIM (the mean over all views of the SSIM the epoch line reports)")
+    ap.add_argument("--ssim_range", type=float, default=2.0, help="data range of that SSIM; 2 is what the epoch line and the tests report with")
     args = ap.parse_args(argv)
     if args.resume and args.use_pre_pth:
         ap.error("--resume restores the weights of its own epoch: it cannot be combined with --use_pre_pth")
@@ -58,9 +60,12 @@ def parse_args(argv=None):
 
 def loss_spec(args):
     """The spec for fit(loss=...), or None for the reference's L1 (which keeps the lft_l1_loss step)."""
-    if args.loss == "l1" and args.pixel_weight == 1.0 and args.epi_weight == 0.0:
+    if args.loss == "l1" and args.pixel_weight == 1.0 and args.epi_weight == 0.0 and args.ssim_weight == 0.0:
         return None
-    return {"penalty": args.loss, "eps": args.charbonnier_eps, "pixel_weight": args.pixel_weight, "epi_weight": args.epi_weight}
+    spec = {"penalty": args.loss, "eps": args.charbonnier_eps, "pixel_weight": args.pixel_weight, "epi_weight": args.epi_weight}
+    if args.ssim_weight > 0.0:
+        spec.update(ssim_weight=args.ssim_weight, ssim_range=args.ssim_range)
+    return spec
 
 
 def checkpoint_dir(args) -> str:
