@@ -415,6 +415,28 @@ int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, i
                      const float* sr_y, const double* weights_h, const int* indices_h, int taps_h, const double* weights_w,
                      const int* indices_w, int taps_w, const double* minv, void* out, int out_class, void* stream);
 
+/* ---- synthetic refocus: a focal stack from the views of a light field (added to ABI 5 without a new version number) ----
+ *   R_d[y, x, c] = sum_{u,v} a[u,v] * S(L[u,v,:,:,c], y + d*(u-uc), x + d*(v-uc)),   uc = (A-1)/2,
+ * d the slope in pixels per view step: a Lambertian plane L[u,v,y,x] = f(y - d0*(u-uc), x - d0*(v-uc)) comes back as f at d = +d0.
+ * S is separable, rows (y) first, `taps` taps per axis: 1 nearest, 2 linear, 4 Keys cubic (a = -0.5).
+ * lf: element (b, u, v, y, x, c) of the B light fields of A x A views, H x W pixels, C <= 4 channels at
+ *     b*strides[0] + u*strides[1] + v*strides[2] + y*strides[3] + x*strides[4] + c*strides[5] (strides: HOST array of 6, >= 0):
+ *     views [A, A, H, W, C] and the network's mosaic [B, 1, A*H, A*W] are both read in place.  LFT_LF_UINT8 enters as x / 255,
+ *     LFT_LF_FLOAT32 as stored.
+ * table: DEVICE array of D * A*A records, slope-major, views in (u, v) order (lft_amd/refocus.py:shift_table computes them in
+ *     fp64 and rounds once).  Tap k of the row filter reads row clamp(y + oy + k, 0, H-1) with weight wy[k], tap k of the column
+ *     filter column clamp(x + ox + k, 0, W-1) with weight wx[k]; weights beyond `taps` are ignored; a is the view's aperture
+ *     weight; a view with skip != 0 is not read at all.
+ * out: [B, D, H, W, C]; LFT_LF_FLOAT32 stores the fp32 sum, unclipped, LFT_LF_UINT8 clips to [0, 1], * 255, rounds half to even.
+ * Sums are fp32, over the views in (u, v) order and the taps in table order, one fused multiply-add per step after a sum's first
+ * product: a pixel's bits do not depend on the image around its taps or on the launch shape.  A view must span less than 2^31
+ * elements (LFT_ERR_SHAPE otherwise).  The call only enqueues on `stream` (graph-capturable), allocates nothing,
+ * and refuses with LFT_ERR_ARG / LFT_ERR_SHAPE before anything is launched: A < 1, C outside 1..4, taps not 1, 2 or 4, D < 1,
+ * classes other than the above, negative sizes or strides, a null pointer with a non-empty shape (B, H or W == 0: no work, 0). */
+typedef struct { int oy, ox; float wy[4], wx[4]; float a; int skip; } lft_refocus_record;   /* 48 bytes */
+int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
+                int taps, void* out, int out_class, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

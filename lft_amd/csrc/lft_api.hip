@@ -45,6 +45,7 @@ namespace {
 #if LFT_TU != 2
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
 #include "lft_colour.cuh"    // colour path: RGB light field -> Y mosaic; SR Y + up-scaled chroma -> RGB views
+#include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
 #endif
 }  // namespace
 
@@ -1126,6 +1127,41 @@ int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, i
     else if (lf_class == LFT_LF_FLOAT32) k_colour_merge<float><<<grid, 256, 0, st>>>(a);
     else k_colour_merge<double><<<grid, 256, 0, st>>>(a);
     LFT_LAUNCH_OK("k_colour_merge");
+    return 0;
+}
+
+// ---- synthetic refocus (lft_refocus.cuh) ----
+int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
+                int taps, void* out, int out_class, void* stream) {
+    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_refocus: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", lf_class);
+    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_refocus: output class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", out_class);
+    if (A < 1 || A > 4096) return fail(LFT_ERR_ARG, "lft_refocus: angRes %d outside 1 .. 4096", A);      // A*A records indexed in int
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_refocus: %d channels (1 .. 4)", C);
+    if (taps != 1 && taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "lft_refocus: %d taps (1, 2 or 4)", taps);
+    if (D < 1) return fail(LFT_ERR_ARG, "lft_refocus: %d slopes", D);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_refocus: negative size in B = %d, views of %d x %d", B, H, W);
+    if (B == 0 || H == 0 || W == 0) return 0;                       // an empty stack: nothing to read or write
+    if (!lf || !strides || !table || !out) return fail(LFT_ERR_ARG, "lft_refocus: null pointer");
+    for (int i = 0; i < 6; ++i)
+        if (strides[i] < 0) return fail(LFT_ERR_ARG, "lft_refocus: stride %d is negative (%lld)", i, strides[i]);
+    if ((double)(H - 1) * (double)strides[3] + (double)(W - 1) * (double)strides[4] + (double)(C - 1) * (double)strides[5] > 2147483647.0)
+        return fail(LFT_ERR_SHAPE, "lft_refocus: a view of %d x %d x %d with these strides spans more than 2^31 elements", H, W, C);
+    const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, tiles = tiles_x * (((long long)H + kRfTile - 1) / kRfTile);
+    if (tiles * D * B > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "lft_refocus: %d stacks of %d slopes over views of %d x %d need more than 2^31 blocks", B, D, H, W);
+    RefocusArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 3; ++i) a.st[i] = strides[i];
+    a.sy = (int)strides[3]; a.sx = (int)strides[4]; a.sc = (int)strides[5];
+    a.A = A; a.H = H; a.W = W; a.D = D; a.tiles_x = (int)tiles_x; a.tiles = (int)tiles;
+    a.table = static_cast<const int*>(table); a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(tiles * D * B));
+    if (lf_class == LFT_LF_UINT8) refocus_kernel<uint8_t>(C, taps)<<<grid, 256, 0, st>>>(a);
+    else refocus_kernel<float>(C, taps)<<<grid, 256, 0, st>>>(a);
+    LFT_LAUNCH_OK("k_refocus");
     return 0;
 }
 

@@ -35,6 +35,20 @@ def write_views(out_dir: str, views: torch.Tensor, prefix: str, mosaic_name=None
     return paths
 
 
+def load_model(args, dev):
+    """The network of --angRes / --scale_factor / --precision with the weights of --path_pre_pth, on `dev`."""
+    from model import LFT
+    net = LFT.get_model(SimpleNamespace(channels=64, angRes=args.angRes, scale_factor=args.scale_factor),
+                        precision=args.precision).to(dev).eval()
+    trainer.load_checkpoint(net, args.path_pre_pth)
+    return net
+
+
+def load_field(path: str, A: int, dev) -> torch.Tensor:
+    """The centre A x A views of the light-field .mat at `path` on `dev`, in the stored class and memory order."""
+    return prepare.to_device(prepare.load_lf(path), A, dev)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--angRes", type=int, default=5)
@@ -50,12 +64,9 @@ def main(argv=None):
     ap.add_argument("--stride_for_test", type=int, default=16)
     args = ap.parse_args(argv)
 
-    from model import LFT
     dev = torch.device("cuda", 0)
-    net = LFT.get_model(SimpleNamespace(channels=64, angRes=args.angRes, scale_factor=args.scale_factor),
-                        precision=args.precision).to(dev).eval()
-    trainer.load_checkpoint(net, args.path_pre_pth)
-    lf = prepare.to_device(prepare.load_lf(args.lf), args.angRes, dev)
+    net = load_model(args, dev)
+    lf = load_field(args.lf, args.angRes, dev)
     os.makedirs(args.out_dir, exist_ok=True)
     sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble)
     paths = write_views(args.out_dir, sr, "view", "mosaic.png" if args.mosaic else None)
