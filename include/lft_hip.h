@@ -437,6 +437,55 @@ typedef struct { int oy, ox; float wy[4], wx[4]; float a; int skip; } lft_refocu
 int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
                 int taps, void* out, int out_class, void* stream);
 
+/* ---- disparity from a light field: plane sweep, windowed aggregation, winner-take-all (added to ABI 5 without a new version
+ * number) ----
+ * Inputs are the same as for lft_refocus:
+ * - B light fields of A x A views, H x W pixels, C <= 4 channels, read in place through six element strides.
+ * - uint8 enters as x/255, float32 as stored.
+ * - Slopes d_0 < d_1 < ... < d_{D-1} are strictly increasing; they need not be uniform.
+ * - aperture, interp (1, 2 or 4 taps) and the table are those of refocus.shift_table.
+ * - The sample s_k[u,v,y,x,c] = S(L[u,v,:,:,c], y + d_k(u-uc), x + d_k(v-uc)) is exactly refocus's: rows first, clamped taps,
+ *   weights not renormalised.
+ *
+ * The outputs are defined as follows.
+ *
+ * 1. Moments. m_k[y,x,c] = sum_{u,v} a*s, which is the refocus stack. q_k[y,x,c] = sum_{u,v} a*s^2.
+ * 2. Raw cost. V_k[y,x] = sum_c max(q_k - m_k^2, 0). This is the aperture-weighted variance of the views at slope d_k, summed
+ *    over channels.
+ * 3. Aggregated cost. E_k[y,x] = (2r+1)^-2 * sum_{dy,dx in [-r,r]} V_k[clamp(y+dy,0,H-1), clamp(x+dx,0,W-1)].
+ *    - The radius r is in 0..8. r = 0 gives E = V.
+ * 4. Index. k* = argmin_k E_k, the lowest k on an exact tie.
+ * 5. Sub-sample refinement. All of it is fp32, each step a single rounded operation, with the compiler's contraction off as in
+ *    k_refocus.
+ *    - For 0 < k* < D-1: den = (E_{k*-1} - E_{k*}) + (E_{k*+1} - E_{k*}). Both terms are >= 0, so there is no cancellation.
+ *    - delta = 0.5*(E_{k*-1} - E_{k*+1})/den if den > 0, clamped to [-0.5, 0.5]. Otherwise, and at either end of the sweep,
+ *      delta = 0.
+ *    - disparity = d_{k*} + delta*(d_{k*+1} - d_{k*}) for delta >= 0, and d_{k*} + delta*(d_{k*} - d_{k*-1}) for delta < 0.
+ *    - The slopes are rounded once to fp32 on the host.
+ * 6. Confidence. Ebar = (sum_k E_k)/D, summed in k order. conf = 1 - E_{k*}/Ebar if Ebar > 0, else 0.
+ *    - A flat region, A = 1 and D = 1 all give 0.
+ * 7. All-in-focus. aif[y,x,c] = m_{k*(y,x)}[y,x,c], fp32 or uint8 by refocus's rule.
+ *    - m is accumulated in refocus's order: views in (u,v) order, taps in table order, explicit FMAs.
+ *    - So aif equals lft_refocus's fp32 stack gathered at k*, bit for bit.
+ *
+ * A pixel's results must not depend on the tile, on the image around the support of its taps and window, or on the launch
+ * shape. That requires a fixed aggregation order, dy then dx.
+ *
+ * lf, lf_class, strides, table, taps: as for lft_refocus.  slopes: DEVICE array of D floats, the slopes of the table rounded to fp32
+ *     (their order is the caller's to check: the array is on the device).  radius: r.
+ * scratch: DEVICE, 4-byte aligned, lft_disparity_scratch_bytes(B, D, H, W, C, flags) bytes, flags LFT_DISPARITY_AIF when aif is
+ *     asked for: V [B, D, H, W] and behind it m [B, D, H, W, C], both fp32.  Its contents after the call are unspecified.
+ * disparity, confidence: fp32 [B, H, W]; index: int32 [B, H, W]; cost: NULL, or fp32 [B, D, H, W] for E; aif: NULL, or
+ *     [B, H, W, C] of aif_class (LFT_LF_FLOAT32 the fp32 sum, LFT_LF_UINT8 clipped to [0, 1], * 255, rounded half to even).
+ * lft_disparity only enqueues on `stream` (two kernels; graph-capturable), allocates nothing, and refuses with LFT_ERR_ARG /
+ * LFT_ERR_SHAPE and a message starting "lft_disparity:" before anything is launched: lft_refocus's rules, a radius outside 0..8,
+ * a null scratch or a null required output with a non-empty shape (B, H or W == 0: no work, 0). */
+#define LFT_DISPARITY_AIF 1
+int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes);
+int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
+                  const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
+                  float* cost, void* aif, int aif_class, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

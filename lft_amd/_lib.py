@@ -13,7 +13,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_vo
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LFT_LIB_PATH") or os.path.join(HERE, "liblft_hip.so")   # LFT_LIB_PATH: experiment builds (tools/ab_build.py)
-SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_optim.cuh", "lft_loss.cuh", "lft_ssim_loss.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh", "lft_colour.cuh", "lft_refocus.cuh"]
+SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_optim.cuh", "lft_loss.cuh", "lft_ssim_loss.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh", "lft_colour.cuh", "lft_refocus.cuh", "lft_disparity.cuh"]
 ABI_VERSION = 5                      # LFT_ABI_VERSION of include/lft_hip.h: lib() refuses a library that reports another one
 STATUS_NONFINITE = 1001              # LFT_STATUS_NONFINITE
 
@@ -185,6 +185,9 @@ _SIGS = {
                                  c_void_p]),
     "lft_refocus": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_void_p, c_int, c_int, c_void_p, c_int,
                             c_void_p]),
+    "lft_disparity_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "lft_disparity": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_void_p, c_void_p, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     # test-only entry point (include/lft_hip_test.h)
     "lft_mfma_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lft_prod_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -199,6 +202,8 @@ EMA_EXPORTS = ("lft_ema_update",)                                               
 LOSS_EXPORTS = ("lft_lf_loss_scratch_bytes", "lft_lf_loss")                                         # likewise
 SSIM_LOSS_EXPORTS = ("lft_ssim_loss_scratch_bytes", "lft_ssim_loss")                                 # likewise
 REFOCUS_EXPORTS = ("lft_refocus",)                                                                   # likewise
+DISPARITY_EXPORTS = ("lft_disparity_scratch_bytes", "lft_disparity")                                 # likewise
+DISPARITY_AIF = 1                                               # LFT_DISPARITY_AIF of include/lft_hip.h
 LOSS_L1, LOSS_MSE, LOSS_CHARBONNIER = 0, 1, 2                   # LFT_LOSS_* of include/lft_hip.h
 BLOCK_UPSAMPLE, BLOCK_SPA, BLOCK_ANG, BLOCK_INIT = 0, 1, 2, 3    # LFT_BLOCK_* of include/lft_hip.h
 LF_UINT8, LF_FLOAT32, LF_FLOAT64 = 0, 1, 2                      # LFT_LF_* of include/lft_hip.h
@@ -220,7 +225,7 @@ def lib() -> ctypes.CDLL:
         if got != ABI_VERSION:              # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
             raise LftError(f"{LIB_PATH} reports ABI version {got}, this binding needs {ABI_VERSION}: rebuild it (__graft_entry__.build())")
         for name, (res, args) in _SIGS.items():
-            if name in TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS and not hasattr(L, name):
+            if name in TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS + DISPARITY_EXPORTS and not hasattr(L, name):
                 continue        # an older LFT_LIB_PATH build of the same ABI version (A/B runs): everything else is there, and asking it for a missing entry point raises
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args

@@ -46,6 +46,7 @@ namespace {
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
 #include "lft_colour.cuh"    // colour path: RGB light field -> Y mosaic; SR Y + up-scaled chroma -> RGB views
 #include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
+#include "lft_disparity.cuh" // disparity: plane-sweep cost volume, windowed aggregation, winner-take-all (lft_disparity)
 #endif
 }  // namespace
 
@@ -1162,6 +1163,76 @@ int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C,
     if (lf_class == LFT_LF_UINT8) refocus_kernel<uint8_t>(C, taps)<<<grid, 256, 0, st>>>(a);
     else refocus_kernel<float>(C, taps)<<<grid, 256, 0, st>>>(a);
     LFT_LAUNCH_OK("k_refocus");
+    return 0;
+}
+
+// ---- disparity from a plane sweep (lft_disparity.cuh) ----
+// the floats of V [B, D, H, W] (and of m [B, D, H, W, C] behind it): 0 when they do not fit 2^40 bytes
+static size_t disparity_floats(int B, int D, int H, int W, int C, int flags, size_t* vol_floats) {
+    const double vol = (double)B * D * H * W, all = vol * (flags & LFT_DISPARITY_AIF ? 1 + C : 1);
+    if (all * 4.0 > 1099511627776.0) return 0;
+    *vol_floats = (size_t)B * D * H * W;
+    return *vol_floats * (size_t)(flags & LFT_DISPARITY_AIF ? 1 + C : 1);
+}
+int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_disparity: out_bytes is null");
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_disparity: %d channels (1 .. 4)", C);
+    if (D < 1) return fail(LFT_ERR_ARG, "lft_disparity: %d slopes", D);
+    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "lft_disparity: unknown flags 0x%x", flags);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_disparity: negative size in B = %d, views of %d x %d", B, H, W);
+    size_t vol = 0;
+    const size_t n = disparity_floats(B, D, H, W, C, flags, &vol);
+    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
+    *out_bytes = n * sizeof(float);
+    return 0;
+}
+int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
+                  const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
+                  float* cost, void* aif, int aif_class, void* stream) {
+    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_disparity: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", lf_class);
+    if (aif_class != LFT_LF_UINT8 && aif_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_disparity: all-in-focus class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", aif_class);
+    if (A < 1 || A > 4096) return fail(LFT_ERR_ARG, "lft_disparity: angRes %d outside 1 .. 4096", A);
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_disparity: %d channels (1 .. 4)", C);
+    if (taps != 1 && taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "lft_disparity: %d taps (1, 2 or 4)", taps);
+    if (D < 1) return fail(LFT_ERR_ARG, "lft_disparity: %d slopes", D);
+    if (radius < 0 || radius > kDpMaxR) return fail(LFT_ERR_ARG, "lft_disparity: radius %d outside 0 .. %d", radius, kDpMaxR);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_disparity: negative size in B = %d, views of %d x %d", B, H, W);
+    if (B == 0 || H == 0 || W == 0) return 0;                       // empty maps: nothing to read or write
+    if (!lf || !strides || !table || !slopes || !scratch || !disparity || !confidence || !index)
+        return fail(LFT_ERR_ARG, "lft_disparity: null pointer");
+    for (int i = 0; i < 6; ++i)
+        if (strides[i] < 0) return fail(LFT_ERR_ARG, "lft_disparity: stride %d is negative (%lld)", i, strides[i]);
+    if ((double)(H - 1) * (double)strides[3] + (double)(W - 1) * (double)strides[4] + (double)(C - 1) * (double)strides[5] > 2147483647.0)
+        return fail(LFT_ERR_SHAPE, "lft_disparity: a view of %d x %d x %d with these strides spans more than 2^31 elements", H, W, C);
+    const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, tiles = tiles_x * (((long long)H + kRfTile - 1) / kRfTile);
+    const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
+    if (tiles * D * B > 0x7fffffffLL || ptiles * B > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "lft_disparity: %d sweeps of %d slopes over views of %d x %d need more than 2^31 blocks", B, D, H, W);
+    size_t vol = 0;
+    if (!disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol))
+        return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_disparity: scratch must be 4-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SweepArgs s{};
+    s.lf = lf;
+    for (int i = 0; i < 3; ++i) s.st[i] = strides[i];
+    s.sy = (int)strides[3]; s.sx = (int)strides[4]; s.sc = (int)strides[5];
+    s.A = A; s.H = H; s.W = W; s.D = D; s.tiles_x = (int)tiles_x; s.tiles = (int)tiles;
+    s.table = static_cast<const int*>(table);
+    s.vol = static_cast<float*>(scratch); s.stack = aif ? s.vol + vol : nullptr;
+    const dim3 grid((unsigned)(tiles * D * B));
+    if (lf_class == LFT_LF_UINT8) sweep_kernel<uint8_t>(C, taps)<<<grid, 256, 0, st>>>(s);
+    else sweep_kernel<float>(C, taps)<<<grid, 256, 0, st>>>(s);
+    LFT_LAUNCH_OK("k_sweep_cost");
+    PickArgs p{};
+    p.vol = s.vol; p.stack = s.stack; p.slopes = slopes;
+    p.H = H; p.W = W; p.D = D; p.C = C; p.r = radius; p.tiles_x = (int)ptiles_x; p.tiles = (int)ptiles;
+    p.disparity = disparity; p.confidence = confidence; p.index = index; p.cost = cost; p.aif = aif;
+    p.aif_f32 = aif_class == LFT_LF_FLOAT32;
+    k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
+    LFT_LAUNCH_OK("k_disparity_pick");
     return 0;
 }
 

@@ -1,0 +1,94 @@
+"""Disparity map, confidence and all-in-focus image of one light field (GPU box): angular consistency as a number.
+
+  python tools/disparity.py --lf scene.mat --angRes 5 --out_dir out/ --slopes=-2:2:33 --radius 2 [--aperture full|disk|gaussian]
+                            [--interp nearest|linear|cubic]
+                            [--path_pre_pth LFT_5x5_4x.pth.tar --scale_factor 4 [--precision ..] [--self_ensemble ..]] [--bicubic]
+
+The scene is a light-field .mat with the variable LF [U, V, H, W, C]; its centre angRes x angRes views are used.  Without
+--path_pre_pth and --bicubic the raw views are swept.  With --path_pre_pth the light field first goes through
+lft_amd.colour.super_resolve_lf; --bicubic does the same with colour.bicubic_lf and the prefix bicubic_ (--scale_factor says how
+far).  Slopes are in pixels of the views being swept per view step, LO:HI:N or a comma list, strictly increasing.  Writes
+<out_dir>/disparity.png (the slope range mapped to 0 .. 255, grey as RGB), confidence.png (0 .. 1 mapped to 0 .. 255, grey as RGB),
+all_in_focus.png and disparity.npy (fp32 [H, W], slope units) from one lft_amd.disparity.disparity call.  With both
+--path_pre_pth and --bicubic it prints one JSON line with lft_amd.disparity.disparity_error of the super-resolved views against
+the bicubic ones: the mean absolute disparity difference over the pixels where the bicubic sweep is confident, and their share."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from lft_amd import colour, disparity, png  # noqa: E402
+from refocus import parse_slopes  # noqa: E402  (tools/refocus.py)
+import super_resolve  # noqa: E402  (the loader of the scene and of the network)
+
+
+def grey(x: torch.Tensor, lo: float, hi: float) -> np.ndarray:
+    """fp32 [H, W] -> uint8 [H, W, 3]: lo .. hi mapped to 0 .. 255, rounded half to even, clipped."""
+    g = ((x - lo) * (255.0 / (hi - lo)) if hi > lo else torch.zeros_like(x)).clamp(0, 255).round().to(torch.uint8)
+    return g[..., None].expand(-1, -1, 3).contiguous().cpu().numpy()
+
+
+def write_maps(out_dir, views, slopes, args, prefix=""):
+    """views: [A, A, H, W, 3] on the GPU (uint8, or float32 in [0, 1]).  Returns the paths written."""
+    r = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus=True,
+                            aif_dtype=torch.uint8)
+    paths = [os.path.join(out_dir, prefix + name) for name in ("disparity.png", "confidence.png", "all_in_focus.png", "disparity.npy")]
+    png.write_png(paths[0], grey(r.disparity, min(slopes), max(slopes)))
+    png.write_png(paths[1], grey(r.confidence, 0.0, 1.0))
+    png.write_png(paths[2], r.all_in_focus.cpu().numpy())
+    np.save(paths[3], r.disparity.cpu().numpy())
+    return paths
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--lf", required=True, help="light-field .mat (variable LF)")
+    ap.add_argument("--angRes", type=int, default=5)
+    ap.add_argument("--out_dir", required=True)
+    ap.add_argument("--slopes", default="-2:2:33", help="LO:HI:N or a comma list, pixels per view step, strictly increasing")
+    ap.add_argument("--radius", type=int, default=2, help="the cost is averaged over (2 radius + 1)^2 pixels, 0 .. 8")
+    ap.add_argument("--aperture", default="full", choices=("full", "disk", "gaussian"))
+    ap.add_argument("--interp", default="linear", choices=tuple(disparity.TAPS))
+    ap.add_argument("--min_confidence", type=float, default=0.5, help="pixels counted by the printed disparity_error")
+    ap.add_argument("--path_pre_pth", default=None, help="checkpoint in the reference's format: sweep the super-resolved views")
+    ap.add_argument("--scale_factor", type=int, default=4)
+    ap.add_argument("--bicubic", action="store_true", help="sweep the bicubic baseline (prefix bicubic_)")
+    ap.add_argument("--self_ensemble", default=None)
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "fp16"))
+    ap.add_argument("--patch_size_for_test", type=int, default=32)
+    ap.add_argument("--stride_for_test", type=int, default=16)
+    args = ap.parse_args(argv)
+
+    dev = torch.device("cuda", 0)
+    slopes = parse_slopes(args.slopes)
+    lf = super_resolve.load_field(args.lf, args.angRes, dev)
+    os.makedirs(args.out_dir, exist_ok=True)
+    paths = []
+    sr = base = None
+    if args.path_pre_pth:
+        net = super_resolve.load_model(args, dev)
+        sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble)
+        paths += write_maps(args.out_dir, sr, slopes, args)
+    if args.bicubic:
+        base = colour.bicubic_lf(lf, args.angRes, args.scale_factor)
+        paths += write_maps(args.out_dir, base, slopes, args, "bicubic_")
+    if sr is None and base is None:
+        raw = lf if lf.dtype in (torch.uint8, torch.float32) else lf.float()
+        paths += write_maps(args.out_dir, raw, slopes, args)
+    if sr is not None and base is not None:
+        err, share = disparity.disparity_error(sr, base, slopes, min_confidence=args.min_confidence, aperture=args.aperture,
+                                               interp=args.interp, radius=args.radius)
+        print(json.dumps({"disparity_error": err, "confident_share": share, "min_confidence": args.min_confidence,
+                          "against": "bicubic", "slopes": [min(slopes), max(slopes), len(slopes)], "radius": args.radius}))
+    print(f"{args.out_dir}: {len(paths)} files, {len(slopes)} slopes from {min(slopes):g} to {max(slopes):g}")
+    return paths
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,103 @@
+"""Cost of a disparity map (GPU box).  Prints one JSON line.
+
+Workload: 5 x 5 views of 512 x 512 x 3 uint8 (the 4x output of a 128 x 128 scene), 33 slopes from -2 to 2, linear, full aperture,
+radius 2.
+  * ``maps_ms``: one `disparity.disparity` call (k_sweep_cost + k_disparity_pick): disparity, confidence and index.
+  * ``maps_aif_ms``: the same with the all-in-focus image (the sweep also writes its fp32 stack, the pick gathers from it).
+  * ``torch_ms``: a composition of stock torch ops of the same definition up to the index -- per slope and view one F.grid_sample
+    (bilinear, border padding, align_corners) of the fp32 view, accumulated into the two moments with the aperture weight;
+    max(q - m^2, 0) summed over the channels; F.avg_pool2d on the replicate-padded volume; argmin.  Its sampling grids and the
+    fp32 views are made outside the timed region.
+The three are timed in the same process, alternating, in `--rounds` rounds (HIP events around `--reps` / `--torch_reps` calls after
+a warm-up); ``kernels_faster_in_every_round`` is the condition the design rests on.  ``index_agreement`` is the share of pixels
+where the two pick the same slope (their costs differ by fp32 rounding and the composition's fp32 grid coordinates).
+
+  python tools/disparity_bench.py [--rounds 3] [--reps 200] [--torch_reps 10] [--warmup 3] [--out profiles/disparity_bench.txt]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from lft_amd import disparity  # noqa: E402
+from refocus_bench import timed, torch_grids  # noqa: E402  (tools/refocus_bench.py: the same views, the same grids)
+
+A, H, W, C, D, RADIUS = 5, 512, 512, 3, 33, 2
+
+
+def torch_index(planes, grids, weights):
+    """planes: [A*A, C, H, W] fp32 -> (index [H, W], E [D, H, W]): D * A^2 resampling ops, each with full-size temporaries."""
+    vol = []
+    for g in grids:
+        m, q = torch.zeros_like(planes[0:1]), torch.zeros_like(planes[0:1])
+        for n in range(A * A):
+            s = F.grid_sample(planes[n:n + 1], g[n], mode="bilinear", padding_mode="border", align_corners=True)
+            m.add_(s, alpha=weights[n])
+            q.addcmul_(s, s, value=weights[n])
+        vol.append((q - m * m).clamp_(min=0).sum(1))
+    E = F.avg_pool2d(F.pad(torch.cat(vol)[None], (RADIUS,) * 4, mode="replicate"), 2 * RADIUS + 1, stride=1)[0]
+    return E.argmin(0), E
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--torch_reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the line to this file")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    slopes = [float(x) for x in np.linspace(-2.0, 2.0, D)]
+    lf = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (A, A, H, W, C)).astype(np.uint8)).to(dev)
+    planes = (lf.float() / 255).permute(0, 1, 4, 2, 3).reshape(A * A, C, H, W).contiguous()
+    grids = torch_grids(slopes, dev)
+    weights = [1.0 / (A * A)] * (A * A)
+
+    def maps():
+        return disparity.disparity(lf, slopes, interp="linear", radius=RADIUS)
+
+    def maps_aif():
+        return disparity.disparity(lf, slopes, interp="linear", radius=RADIUS, all_in_focus=True)
+
+    def composed():
+        return torch_index(planes, grids, weights)
+
+    for _ in range(args.warmup):
+        maps(), maps_aif(), composed()
+    ours = disparity.disparity(lf, slopes, interp="linear", radius=RADIUS, cost_volume=True)
+    index, E = composed()
+    agree = float((ours.index.long() == index).double().mean())
+    diff = float((ours.cost - E).abs().max())
+    torch.cuda.synchronize()
+    rounds = []
+    for _ in range(args.rounds):
+        rounds.append({"maps_ms": round(timed(maps, args.reps), 4), "maps_aif_ms": round(timed(maps_aif, args.reps), 4),
+                       "torch_ms": round(timed(composed, args.torch_reps), 4)})
+    read = D * A * A * H * W * C                                          # every slope reads the views once, as bytes
+    vol = D * H * W * 4                                                   # V: written by the sweep, read by the pick (halo apart)
+    nbytes = read + 2 * vol + 3 * H * W * 4
+    nbytes_aif = nbytes + D * H * W * C * 4 + H * W * C * 4 + H * W * C   # the stack written, one of D slices gathered, bytes out
+    best, best_aif = min(r["maps_ms"] for r in rounds), min(r["maps_aif_ms"] for r in rounds)
+    line = json.dumps({"bench": "disparity", "device": torch.cuda.get_device_name(0), "A": A, "view": [H, W, C], "in": "uint8", "D": D,
+                       "interp": "linear", "radius": RADIUS, "aperture": "full", "reps": args.reps, "torch_reps": args.torch_reps,
+                       "rounds": rounds, "maps_ms_best": best, "maps_aif_ms_best": best_aif, "contract_bytes": nbytes,
+                       "contract_bytes_aif": nbytes_aif, "maps_GBps": round(nbytes / (best * 1e-3) / 1e9, 1),
+                       "maps_aif_GBps": round(nbytes_aif / (best_aif * 1e-3) / 1e9, 1), "torch_ops_per_map": 3 * D * A * A + 4 * D + 4,
+                       "index_agreement": agree, "max_abs_diff_cost": diff,
+                       "kernels_faster_in_every_round": all(max(r["maps_ms"], r["maps_aif_ms"]) < r["torch_ms"] for r in rounds)})
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
