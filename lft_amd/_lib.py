@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
@@ -14,12 +15,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LFT_LIB_PATH") or os.path.join(HERE, "liblft_hip.so")   # LFT_LIB_PATH: experiment builds (tools/ab_build.py)
 SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_optim.cuh", "lft_loss.cuh", "lft_ssim_loss.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh", "lft_colour.cuh", "lft_refocus.cuh", "lft_disparity.cuh"]
-ABI_VERSION = 5                      # LFT_ABI_VERSION of include/lft_hip.h: lib() refuses a library that reports another one
-STATUS_NONFINITE = 1001              # LFT_STATUS_NONFINITE
 
-PREC_F32, PREC_BF16, PREC_F16 = 0, 1, 2
-MATH_F32, MATH_BF16X3, MATH_BF16X6 = 0, 1, 2
-NUM_PARAMS = 78
+
+def _header_text(header: str) -> str:
+    """include/<header> without its comments."""
+    with open(os.path.join(HERE, "..", "include", header)) as f:
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+
+
+# The integer constants of include/lft_hip.h under their names without the LFT_ prefix: ABI_VERSION (lib() refuses a library that
+# reports another one), STATUS_NONFINITE, NUM_PARAMS, PREC_*, MATH_*, ERR_*, LOSS_*, BLOCK_*, LF_*, MAPS_*, GRAD_BUCKETS,
+# DISPARITY_AIF, GUARD_MAX_SEGMENTS.
+globals().update({k: int(v) for k, v in re.findall(r"^#define LFT_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", _header_text("lft_hip.h"), flags=re.M)})
 
 _lib = None
 
@@ -106,9 +113,6 @@ def compile_and_link(hipcc, lib_path, extra=()):
     if r.returncode != 0:
         raise LftError("link failed:\n" + r.stdout + r.stderr)
 
-GUARD_MAX_SEGMENTS = 128              # LFT_GUARD_MAX_SEGMENTS
-
-
 class GuardSegment(ctypes.Structure):          # lft_segment
     _fields_ = [("first", c_longlong), ("count", c_longlong), ("trainable", c_int)]
 
@@ -119,96 +123,41 @@ class GuardReport(ctypes.Structure):           # lft_guard_report
                 ("steps_clipped", c_longlong), ("seg_norm", c_float * GUARD_MAX_SEGMENTS)]
 
 
-_SIGS = {
-    "lft_version": (c_int, []),
-    "lft_last_error": (c_char_p, []),
-    "lft_packed_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_pack_weights": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_status_reset": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_status_read": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(ctypes.c_uint)]),
-    "lft_forward_profiled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                     c_int, POINTER(c_float), POINTER(c_char_p), POINTER(c_int)]),
-    "lft_kernel_time": (c_int, [c_char_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float)]),
-    "lft_bicubic_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_init_features_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_ang_block_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_spa_block_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_upsample_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_scene_counts": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
-    "lft_scene_divide": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_scene_integrate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_dihedral_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "lft_dihedral_expand": (c_int, [c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_int, c_void_p]),
-    "lft_dihedral_merge": (c_int, [c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_int, c_void_p]),
-    "lft_scene_integrate_ens": (c_int, [c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_train_tape_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_train_grad_floats": (c_int, [c_int, POINTER(c_size_t)]),
-    "lft_train_tape_offset": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_train_forward": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_train_backward": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_train_backward_input": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_lr_grad_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_train_backward_buckets": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                           c_void_p, c_void_p, c_void_p]),
-    "lft_train_block_backward": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_train_grad_bucket": (c_int, [c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
-    "lft_train_step_profiled": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_void_p, c_int, POINTER(c_float), POINTER(c_char_p), POINTER(c_int)]),
-    "lft_attn_maps_floats": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_train_attn_maps": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_l1_loss": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "lft_lf_loss_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_lf_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_float,
-                            c_void_p, c_void_p, c_void_p]),
-    "lft_ssim_loss_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_ssim_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_float, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p]),
-    "lft_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_void_p]),
-    "lft_guard_bytes": (c_int, [c_int, POINTER(c_size_t)]),
-    "lft_guard_init": (c_int, [c_void_p, POINTER(GuardSegment), c_int, c_longlong, c_longlong, c_void_p]),
-    "lft_adam_step_guarded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float,
-                                      c_float, c_float, c_float, c_void_p, c_void_p]),
-    "lft_guard_read": (c_int, [c_void_p, c_void_p, POINTER(GuardReport)]),
-    "lft_ema_update": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_int, c_longlong, c_void_p, c_void_p]),
-    "lft_view_metrics_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_view_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "lft_lf_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_int,
-                               POINTER(c_int), c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                               c_void_p, c_void_p, c_void_p]),
-    "lft_lf_luma": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_void_p, c_void_p]),
-    "lft_colour_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_int, c_int, c_void_p,
-                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), c_void_p, c_int,
-                                 c_void_p]),
-    "lft_refocus": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_void_p, c_int, c_int, c_void_p, c_int,
-                            c_void_p]),
-    "lft_disparity_scratch_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "lft_disparity": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong), c_void_p, c_void_p, c_int, c_int, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    # test-only entry point (include/lft_hip_test.h)
-    "lft_mfma_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "lft_prod_selftest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "lft_init_features_legacy_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_conv0_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "lft_tail_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-}
+def _ctype(ctype: str, where: str):
+    """ctypes type of a C type as the headers write it: scalars exactly, const char* and size_t* typed, every other pointer and
+    the callback typedef lft_bucket_fn as c_void_p.  A scalar this does not know is an error, not a guess."""
+    base = " ".join(re.sub(r"\bconst\b|\*", " ", ctype).split())
+    if "*" in ctype:
+        return {"const char*": c_char_p, "size_t*": POINTER(c_size_t)}.get(ctype.strip(), c_void_p)
+    if base == "lft_bucket_fn":
+        return c_void_p
+    if base not in _SCALARS:
+        raise LftError(f"{where}: no ctypes type for the C type '{ctype.strip()}'")
+    return _SCALARS[base]
+
+
+def _prototypes(header: str) -> dict:
+    """{name: (restype, [argtypes])} of every `int lft_...(...);` and `const char* lft_...(...);` of a header (one parameter =
+    type + name, or `void` for none)."""
+    sigs = {}
+    for res, name, params in re.findall(r"^(int|const char\*)\s+(lft_\w+)\s*\(([^)]*)\)\s*;", _header_text(header), flags=re.M):
+        args = [] if params.strip() == "void" else [re.sub(r"\w+\s*$", "", p) for p in params.split(",")]
+        sigs[name] = (_ctype(res, name), [_ctype(a, name) for a in args])
+    return sigs
+
+
+_SCALARS = {"int": c_int, "unsigned": ctypes.c_uint, "float": c_float, "double": ctypes.c_double, "long long": c_longlong, "size_t": c_size_t}
+TEST_EXPORTS = tuple(_prototypes("lft_hip_test.h"))             # declared in include/lft_hip_test.h, not in the product header
+_SIGS = {**_prototypes("lft_hip.h"), **_prototypes("lft_hip_test.h")}
 EXPORTS = tuple(_SIGS)
-TEST_EXPORTS = ("lft_mfma_selftest", "lft_prod_selftest", "lft_init_features_legacy_fwd", "lft_conv0_fwd", "lft_tail_fwd")   # declared in include/lft_hip_test.h, not in the product header
 GUARD_EXPORTS = ("lft_guard_bytes", "lft_guard_init", "lft_adam_step_guarded", "lft_guard_read")   # added to ABI 5 without a new version number
 EMA_EXPORTS = ("lft_ema_update",)                                                                  # likewise
 LOSS_EXPORTS = ("lft_lf_loss_scratch_bytes", "lft_lf_loss")                                         # likewise
 SSIM_LOSS_EXPORTS = ("lft_ssim_loss_scratch_bytes", "lft_ssim_loss")                                 # likewise
 REFOCUS_EXPORTS = ("lft_refocus",)                                                                   # likewise
 DISPARITY_EXPORTS = ("lft_disparity_scratch_bytes", "lft_disparity")                                 # likewise
-DISPARITY_AIF = 1                                               # LFT_DISPARITY_AIF of include/lft_hip.h
-LOSS_L1, LOSS_MSE, LOSS_CHARBONNIER = 0, 1, 2                   # LFT_LOSS_* of include/lft_hip.h
-BLOCK_UPSAMPLE, BLOCK_SPA, BLOCK_ANG, BLOCK_INIT = 0, 1, 2, 3    # LFT_BLOCK_* of include/lft_hip.h
-LF_UINT8, LF_FLOAT32, LF_FLOAT64 = 0, 1, 2                      # LFT_LF_* of include/lft_hip.h
-MAPS_MEAN, MAPS_HEADS = 0, 1                                    # LFT_MAPS_* of include/lft_hip.h
-GRAD_BUCKETS = 3
+# what an older LFT_LIB_PATH build of the same ABI version (A/B runs) may lack: lib() binds everything else unconditionally
+OPTIONAL_EXPORTS = frozenset(TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS + DISPARITY_EXPORTS)
 BUCKET_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_size_t, c_size_t)     # lft_bucket_fn of include/lft_hip.h: 0 = go on, else stop
 
 
@@ -225,8 +174,8 @@ def lib() -> ctypes.CDLL:
         if got != ABI_VERSION:              # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
             raise LftError(f"{LIB_PATH} reports ABI version {got}, this binding needs {ABI_VERSION}: rebuild it (__graft_entry__.build())")
         for name, (res, args) in _SIGS.items():
-            if name in TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS + DISPARITY_EXPORTS and not hasattr(L, name):
-                continue        # an older LFT_LIB_PATH build of the same ABI version (A/B runs): everything else is there, and asking it for a missing entry point raises
+            if name in OPTIONAL_EXPORTS and not hasattr(L, name):
+                continue        # everything else is there, and asking the library for a missing entry point raises
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

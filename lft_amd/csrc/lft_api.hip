@@ -1,12 +1,10 @@
 // lft_api.hip -- C ABI of liblft_hip.so (see include/lft_hip.h): buffer layouts, weight packing plan,
 // kernel launches.  Host-side code only enqueues work on the caller's stream.
 //
-// The library is built from this file as TWO translation units with different compiler flags (lft_amd/_lib.py):
-//   LFT_TU == 1   inference, scene tiling, metrics, debug entry points   -- with -fno-slp-vectorize: hipcc's SLP pass packs
-//                 neighbouring scalar f32 operations into v_pk_*_f32, which issue slower beside MFMAs than the two scalar
-//                 instructions (+1.4 % on the bench without it; the kernels pack explicitly, f32x2, where that was measured to pay)
-//   LFT_TU == 2   the fp32 training step -- default flags: the SLP pass also decides which of its multiply-adds are
-//                 contracted, and the step's last-bit behaviour is pinned by the gradient fixtures
+// The library is built from this file as TWO translation units, only so that they compile in parallel; both get the same
+// compiler flags (COMMON_FLAGS + UNIT_FLAGS of lft_amd/_lib.py, where each flag's reason is written down):
+//   LFT_TU == 1   inference, scene tiling, metrics, data preparation, colour, refocus, disparity, debug entry points
+//   LFT_TU == 2   the fp32 training step, its losses and optimizer
 //   LFT_TU == 0   everything in one unit (tools, resource reports).
 // Every kernel and helper is local to its unit (anonymous namespace); the units share only the error buffer.
 #include "../../include/lft_hip.h"
@@ -146,6 +144,13 @@ template <typename F> int by_prec(int prec, F&& f) {
     if (prec == LFT_PREC_BF16) return f(bf16_t{});
     return f(f16_t{});
 }
+// f(T{}) with T the stored type of a light field of class `lf_class` (validated by the caller beforehand).  F64 = false: the caller
+// accepts LFT_LF_UINT8 and LFT_LF_FLOAT32 only, and no double variant of its kernel is built.
+template <bool F64 = true, typename F> int by_lf_class(int lf_class, F&& f) {
+    if (lf_class == LFT_LF_UINT8) return f(uint8_t{});
+    if constexpr (!F64) return f(float{});
+    else return lf_class == LFT_LF_FLOAT32 ? f(float{}) : f(double{});
+}
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Dims {
@@ -227,6 +232,17 @@ WorkLayout work_layout(const Dims& d, int prec) {
     W.total = o;
     return W;
 }
+// What an inference entry point works with: the shape, both buffer layouts, the stream and the precision.  Made once per call by
+// make_fwd, after the entry point's own null-pointer (and layer) checks; the stage functions below take it as `c`.
+struct Fwd { Dims d; PackedLayout L; WorkLayout W; hipStream_t st; int prec; };
+int make_fwd(int B, int A, int h, int w, int s, int prec, void* stream, Fwd* c) {
+    if (int rc = make_dims(B, A, h, w, s, prec, &c->d)) return rc;
+    c->L = packed_layout(c->d, prec);            // does not depend on B
+    c->W = work_layout(c->d, prec);
+    c->st = static_cast<hipStream_t>(stream);
+    c->prec = prec;
+    return 0;
+}
 
 // Dynamic LDS sizes (bytes) and the opt-in above the 64 KiB default (a workgroup may use all 160 KiB of a CU).
 template <typename T> size_t lds_conv64(int w) { return WRing<T, kConv64Chunk, kNwConv>::LDS_BYTES + ConvIn<T, kNwConv>::bytes(w) + kNwConv * TileIO<2, T>::BYTES + kConvZeroRow; }
@@ -273,8 +289,10 @@ void conv_ops(std::vector<PackOp>& v, const float* w, int nout) {   // [nout][64
         for (int ks = 0; ks < 4; ++ks) v.push_back(lin_op(w, 0, nout, 576, 16 * ks, 1, 0, 1.0f, 9, tap));
 }
 
-template <typename T>
-int run_pack(std::vector<PackOp>& ops, T* dst, int expect_frags, hipStream_t st) {
+// The packing plan, LFT_PACK_MAXOPS operations per launch: launch(a, nf, total) enqueues the kernel `name` for the nf fragments of
+// batch a, which follow the `total` fragments of the batches before it.
+template <typename Launch>
+int pack_batches(std::vector<PackOp>& ops, int expect_frags, const char* name, Launch&& launch) {
     int total = 0;
     size_t i = 0;
     while (i < ops.size()) {
@@ -286,12 +304,19 @@ int run_pack(std::vector<PackOp>& ops, T* dst, int expect_frags, hipStream_t st)
             nf += ops[i].ntiles * ops[i].ksteps;
             ++a.nops; ++i;
         }
-        k_pack<T><<<nf, 64, 0, st>>>(a, dst + (size_t)total * 512);
-        LFT_LAUNCH_OK("k_pack");
+        if (int rc = launch(a, nf, total)) return rc;
+        LFT_LAUNCH_OK(name);
         total += nf;
     }
     if (total != expect_frags) return fail(LFT_ERR_ARG, "internal: stream has %d fragments, expected %d", total, expect_frags);
     return 0;
+}
+template <typename T>
+int run_pack(std::vector<PackOp>& ops, T* dst, int expect_frags, hipStream_t st) {
+    return pack_batches(ops, expect_frags, "k_pack", [&](const PackArgs& a, int nf, int total) {
+        k_pack<T><<<nf, 64, 0, st>>>(a, dst + (size_t)total * 512);
+        return 0;
+    });
 }
 
 // Lane-major hand-off of the spatial tokens from k_spa1 to part B: every workgroup tile of k_spa1 must be full, and the bf16
@@ -326,7 +351,8 @@ template <typename T> bool tok_lane_major(const Dims& d) {
 //   3x75 / 3x347, test_too_wide_view_is_refused one column more (LFT_ERR_SHAPE from allow_lds, nothing launched).
 template <typename T, bool PE_ONLY>
 int launch_spa1(unsigned nwg, const T* in, const T* ws, const float* ln, const T* petok, T* tok, T* q, T* k, T* v, T* pe_out,
-                int nimg, const Dims& d, hipStream_t st, unsigned* status) {
+                int nimg, const Fwd& c, unsigned* status) {
+    const Dims& d = c.d;
     const size_t l16 = lds_spa1<T, 16>(d.w), l8 = lds_spa1<T, 8>(d.w);
     const size_t share = kMaxLds / kSpaOcc;                               // LDS per workgroup if kSpaOcc of them share a CU
     const bool use8 = (l16 > share && l8 <= share) || l16 > kMaxLds;
@@ -337,44 +363,45 @@ int launch_spa1(unsigned nwg, const T* in, const T* ws, const float* ln, const T
             constexpr bool WQ = !(LM && sizeof(T) == 2);
             const size_t lds = CH == 8 ? l8 : l16;
             if (int rc = allow_lds(k_spa1<T, PE_ONLY, CH, LM, WQ>, lds, "k_spa1")) return rc;
-            k_spa1<T, PE_ONLY, CH, LM, WQ><<<nwg, 64 * kNwSpa1, lds, st>>>(in, ws, ln, petok, tok, q, k, v, pe_out, nimg, d.h, d.w, status);
+            k_spa1<T, PE_ONLY, CH, LM, WQ><<<nwg, 64 * kNwSpa1, lds, c.st>>>(in, ws, ln, petok, tok, q, k, v, pe_out, nimg, d.h, d.w, status);
             return 0;
         });
     });
 }
 
 template <typename T>
-int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipStream_t st) {
-    const PackedLayout L = packed_layout(d, prec);
+int pack_impl(const Fwd& c, const float* const* P, void* packed) {
+    const Dims& d = c.d;
+    const hipStream_t st = c.st;
     const float kAngScale = 0.35355339059327373f * LFT_LOG2E;   // 1/sqrt(8) (head_dim 8), exp2 softmax
     const float kSpaScale = 0.25f * LFT_LOG2E;                   // 1/sqrt(16)
     int rc;
-    k_copy_f32<<<3, 256, 0, st>>>(P[0], at<float>(packed, L.conv0_w), 576);
+    k_copy_f32<<<3, 256, 0, st>>>(P[0], at<float>(packed, c.L.conv0_w), 576);
     LFT_LAUNCH_OK("k_copy_f32");
     for (int i = 0; i < 3; ++i) {
         std::vector<PackOp> ops;
         conv_ops(ops, P[1 + i], 64);
-        if ((rc = run_pack<T>(ops, at<T>(packed, L.s_conv[i]), kFragsConv, st))) return rc;
+        if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_conv[i]), kFragsConv, st))) return rc;
     }
     if constexpr (sizeof(T) == 2) {     // conv_init.0 o conv_init0, composed in fp32, then rounded to ConvLrOp (half, also in bf16 mode: lft_kernels_a.cuh)
-        k_compose_w01<<<blocks_for(64 * kW01K, 256), 256, 0, st>>>(P[0], P[1], at<float>(packed, L.w01));
+        k_compose_w01<<<blocks_for(64 * kW01K, 256), 256, 0, st>>>(P[0], P[1], at<float>(packed, c.L.w01));
         LFT_LAUNCH_OK("k_compose_w01");
-        std::vector<PackOp> ops{lin_op(at<float>(packed, L.w01), 0, 64, kW01K, 0, kW01K / 16, 0, 1.0f)};
-        if ((rc = run_pack<ConvLrOp>(ops, at<ConvLrOp>(packed, L.s_w01), kW01Frags, st))) return rc;
+        std::vector<PackOp> ops{lin_op(at<float>(packed, c.L.w01), 0, 64, kW01K, 0, kW01K / 16, 0, 1.0f)};
+        if ((rc = run_pack<ConvLrOp>(ops, at<ConvLrOp>(packed, c.L.s_w01), kW01Frags, st))) return rc;
     }
     k_pe_tables<T><<<blocks_for(std::max<long long>((long long)((d.V + 31) / 32) * 2048, (long long)d.hw * 64), 256), 256, 0, st>>>(
-        at<float>(packed, L.ang_pe), at<T>(packed, L.spa_pe_img), d.V, d.h, d.w);
+        at<float>(packed, c.L.ang_pe), at<T>(packed, c.L.spa_pe_img), d.V, d.h, d.w);
     LFT_LAUNCH_OK("k_pe_tables");
     if constexpr (sizeof(T) == 2) {
         if (tok_lane_major<T>(d)) {     // the per-lane geometry of k_spa_b depends on h, w only: built once per view size
-            k_spa_b_geom<<<(unsigned)(((d.h + kAttTY - 1) / kAttTY) * ((d.w + kAttTX - 1) / kAttTX)), 256, 0, st>>>(at<unsigned>(packed, L.spa_geom), d.h, d.w);
+            k_spa_b_geom<<<(unsigned)(((d.h + kAttTY - 1) / kAttTY) * ((d.w + kAttTX - 1) / kAttTX)), 256, 0, st>>>(at<unsigned>(packed, c.L.spa_geom), d.h, d.w);
             LFT_LAUNCH_OK("k_spa_b_geom");
         }
     }
     for (int l = 0; l < kLayers; ++l) {
         const float* const* q = P + 4 + 18 * l;
-        float* lnS = at<float>(packed, L.ln_spa[l]);
-        float* lnA = at<float>(packed, L.ln_ang[l]);
+        float* lnS = at<float>(packed, c.L.ln_spa[l]);
+        float* lnA = at<float>(packed, c.L.ln_ang[l]);
         const int srcS[4] = {1, 2, 5, 6}, srcA[4] = {10, 11, 14, 15};
         for (int j = 0; j < 4; ++j) {
             k_copy_f32<<<1, 256, 0, st>>>(q[srcS[j]], lnS + 128 * j, 128);
@@ -389,7 +416,7 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
             ops.push_back(lin_op(q[13], 0, 64, 64, 0, 4, 1, 1.0f));
             ops.push_back(lin_op(q[16], 0, 128, 64, 0, 4, 1, 1.0f));
             ops.push_back(lin_op(q[17], 0, 64, 128, 0, 8, 1, 1.0f));
-            if ((rc = run_pack<T>(ops, at<T>(packed, L.s_ang[l]), kFragsAng, st))) return rc;
+            if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_ang[l]), kFragsAng, st))) return rc;
         }
         {   // spatial part 1: token embedding conv + in_proj
             std::vector<PackOp> ops;
@@ -397,7 +424,7 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
             ops.push_back(lin_op(q[3], 256, 128, 128, 0, 8, 1, 1.0f));          // Wv (consumed first)
             ops.push_back(lin_op(q[3], 128, 128, 128, 0, 8, 1, 1.0f));          // Wk
             ops.push_back(lin_op(q[3], 0, 128, 128, 0, 8, 1, kSpaScale));      // Wq: last -- k_spa1's ring ends before it when part B computes Q itself (kFragsSpa1NoQ)
-            if ((rc = run_pack<T>(ops, at<T>(packed, L.s_spa1[l]), kFragsSpa1, st))) return rc;
+            if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_spa1[l]), kFragsSpa1, st))) return rc;
         }
         {   // spatial part 2: out_proj, FFN in 4 chunks, 1x1x1 conv.  out_proj's operand: bf16 -- the attention accumulators
             // inside k_spa_b (acc order); fp32 -- the attention output read back from memory by k_spa2 (natural k)
@@ -410,7 +437,7 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
                 // No non-linearity stands between feed_forward.4 (W2) and the 1x1x1 conv (Wl, reference LFT.py:171-174, 187-189):
                 // y = Wl (t + W2 hid) = Wl t + (Wl W2) hid.  Wl W2 [64][256] is composed in fp32 and rounded once by k_pack.
                 // Stream: Wo[4x8] Wl[2x8] {W1c[2x8] WlW2c[2x4]} x4
-                float* wlw2 = at<float>(packed, L.wlw2[l]);
+                float* wlw2 = at<float>(packed, c.L.wlw2[l]);
                 k_compose_wlw2<<<blocks_for(64 * 256, 256), 256, 0, st>>>(q[9], q[8], wlw2);
                 LFT_LAUNCH_OK("k_compose_wlw2");
                 ops.push_back(lin_op(q[9], 0, 64, 128, 0, 8, 1, 1.0f));
@@ -425,11 +452,11 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
                 }
                 ops.push_back(lin_op(q[9], 0, 64, 128, 0, 8, 1, 1.0f));
             }
-            if ((rc = run_pack<T>(ops, at<T>(packed, L.s_spa2[l]), frags_spa2(prec), st))) return rc;
+            if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_spa2[l]), frags_spa2(c.prec), st))) return rc;
         }
         // embedded spatial position tokens of this layer (reference LFT.py:180), [h*w][128] in the activation type
-        if ((rc = launch_spa1<T, true>((unsigned)((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1)), at<T>(packed, L.spa_pe_img), at<T>(packed, L.s_spa1[l]), nullptr, nullptr,
-                                       nullptr, nullptr, nullptr, nullptr, at<T>(packed, L.petok[l]), 1, d, st, nullptr))) return rc;
+        if ((rc = launch_spa1<T, true>((unsigned)((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1)), at<T>(packed, c.L.spa_pe_img), at<T>(packed, c.L.s_spa1[l]), nullptr, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, at<T>(packed, c.L.petok[l]), 1, c, nullptr))) return rc;
         LFT_LAUNCH_OK("k_spa1<pe>");
     }
     {   // up-sampler: per 32-row chunk of the 1x1 conv, followed by the matching columns of the overlap-add matrix
@@ -440,7 +467,7 @@ int pack_impl(const float* const* P, void* packed, const Dims& d, int prec, hipS
             m.kind = 1; m.s = d.s; m.ntiles = d.gt;
             ops.push_back(m);
         }
-        if ((rc = run_pack<T>(ops, at<T>(packed, L.s_up), frags_up(d), st))) return rc;
+        if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_up), frags_up(d), st))) return rc;
     }
     return 0;
 }
@@ -455,19 +482,21 @@ void launch_assemble(const float* lr, const float* g, float* out, int B, int A, 
 // ---------------------------------------------------------------------------- stages
 // The front end as it was before the composition, and as fp32 still runs it: conv_init0 to memory, three 64 -> 64 convs.
 template <typename T>
-int init_features_x0(const void* packed, const PackedLayout& L, const float* lr, T* x0, T* ta, T* tb, T* feat, const Dims& d, hipStream_t st) {
+int init_features_x0(const Fwd& c, const void* packed, const float* lr, T* x0, T* ta, T* tb, T* feat) {
+    const Dims& d = c.d;
+    const hipStream_t st = c.st;
     const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
     const size_t lds = lds_conv64<T>(d.w);
     int rc;
     if ((rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64"))) return rc;
     if ((rc = allow_lds(k_conv64<T, 1>, lds, "k_conv64"))) return rc;
-    k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, st>>>(lr, at<float>(packed, L.conv0_w), x0, d.B, d.A, d.h, d.w);
+    k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, st>>>(lr, at<float>(packed, c.L.conv0_w), x0, d.B, d.A, d.h, d.w);
     LFT_LAUNCH_OK("k_conv0");
-    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(x0, ta, nullptr, at<T>(packed, L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
+    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(x0, ta, nullptr, at<T>(packed, c.L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
     LFT_LAUNCH_OK("k_conv64");
-    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(ta, tb, nullptr, at<T>(packed, L.s_conv[1]), nimg, d.h, d.w, ConvLr{});
+    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(ta, tb, nullptr, at<T>(packed, c.L.s_conv[1]), nimg, d.h, d.w, ConvLr{});
     LFT_LAUNCH_OK("k_conv64");
-    k_conv64<T, 1><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, x0, at<T>(packed, L.s_conv[2]), nimg, d.h, d.w, ConvLr{});
+    k_conv64<T, 1><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, x0, at<T>(packed, c.L.s_conv[2]), nimg, d.h, d.w, ConvLr{});
     LFT_LAUNCH_OK("k_conv64");
     return 0;
 }
@@ -475,25 +504,28 @@ int init_features_x0(const void* packed, const PackedLayout& L, const float* lr,
 // residual of conv_init.4 (k_conv64<T, 2>); x0 and ta are never written.  Both launches carry the name "k_conv64": the
 // benchmark's per-kernel tables are indexed by the names lft_forward_profiled returns.
 template <typename T>
-int init_features(const void* packed, const PackedLayout& L, const float* lr, T* x0, T* ta, T* tb, T* feat, const Dims& d, hipStream_t st) {
-    if constexpr (sizeof(T) == 4) return init_features_x0<T>(packed, L, lr, x0, ta, tb, feat, d, st);
+int init_features(const Fwd& c, const void* packed, const float* lr, T* x0, T* ta, T* tb, T* feat) {
+    if constexpr (sizeof(T) == 4) return init_features_x0<T>(c, packed, lr, x0, ta, tb, feat);
     else {
+        const Dims& d = c.d;
+        const hipStream_t st = c.st;
         const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
         const size_t lds = lds_conv64_lr<T>(d.w);
         int rc;
-        if (L.s_w01 + kW01Frags * 1024 != L.s_conv[1]) return fail(LFT_ERR_ARG, "internal: W01 fragments are not in front of conv_init.2's stream");
+        if (c.L.s_w01 + kW01Frags * 1024 != c.L.s_conv[1]) return fail(LFT_ERR_ARG, "internal: W01 fragments are not in front of conv_init.2's stream");
         if ((rc = allow_lds(k_conv64_lr<T>, lds, "k_conv64"))) return rc;
         if ((rc = allow_lds(k_conv64<T, 2>, lds, "k_conv64"))) return rc;
-        k_conv64_lr<T><<<nwg, 64 * kNwConv, lds, st>>>(lr, tb, at<T>(packed, L.s_w01), d.A, nimg, d.h, d.w);
+        k_conv64_lr<T><<<nwg, 64 * kNwConv, lds, st>>>(lr, tb, at<T>(packed, c.L.s_w01), d.A, nimg, d.h, d.w);
         LFT_LAUNCH_OK("k_conv64");
-        k_conv64<T, 2><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, nullptr, at<T>(packed, L.s_conv[2]), nimg, d.h, d.w,
-                                                      ConvLr{lr, at<float>(packed, L.conv0_w), d.A});
+        k_conv64<T, 2><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, nullptr, at<T>(packed, c.L.s_conv[2]), nimg, d.h, d.w,
+                                                      ConvLr{lr, at<float>(packed, c.L.conv0_w), d.A});
         LFT_LAUNCH_OK("k_conv64");
         return 0;
     }
 }
 template <typename T, int CT, int LL>      // LL: score registers of the last key tile that can hold a view, which covers rows acc_row(i, 0) and acc_row(i, 1) = +4 of register i
-int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* out, const Dims& d, hipStream_t st, unsigned* status) {
+int ang_multi(const Fwd& c, const void* packed, int l, const T* in, T* out, unsigned* status) {
+    const Dims& d = c.d;
     constexpr bool WLDS = sizeof(T) == 2;                                   // fp32 weights (128 KiB) stay in L2
     constexpr int NG = (sizeof(T) == 2 && CT <= 3) ? 2 : 1;                 // positions per workgroup (they share the LDS weights)
     constexpr size_t FB = 1024 * FragInfo<T>::PIECES;
@@ -502,8 +534,8 @@ int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* 
     int rc;
     const unsigned grid = std::min<unsigned>(blocks_for(npix, NG), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds));
     if ((rc = allow_lds(k_ang_multi<T, CT, WLDS, NG, LL>, lds, "k_ang_multi"))) return rc;
-    k_ang_multi<T, CT, WLDS, NG, LL><<<grid, 64 * CT * NG, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]), at<float>(packed, L.ln_ang[l]),
-                                                                     at<float>(packed, L.ang_pe), d.V, d.hw, npix, status);
+    k_ang_multi<T, CT, WLDS, NG, LL><<<grid, 64 * CT * NG, lds, c.st>>>(in, out, at<T>(packed, c.L.s_ang[l]), at<float>(packed, c.L.ln_ang[l]),
+                                                                     at<float>(packed, c.L.ang_pe), d.V, d.hw, npix, status);
     LFT_LAUNCH_OK("k_ang");
     return 0;
 }
@@ -517,9 +549,10 @@ int ang_multi(const void* packed, const PackedLayout& L, int l, const T* in, T* 
 //   V 100    (A 10)      k_ang_multi<T, 4, LL 9>   case  A10_s4_B1_3x5;                                               many_positions[10-*]
 //   V 121    (A 11)      k_ang_multi<T, 4, LL 13>  case  A11_s2_B1_4x3;                                               many_positions[11-*]
 template <typename T>
-int ang_block(const void* packed, const PackedLayout& L, int l, const T* in, T* out, const Dims& d, hipStream_t st, unsigned* status = nullptr) {
+int ang_block(const Fwd& c, const void* packed, int l, const T* in, T* out, unsigned* status = nullptr) {
+    const Dims& d = c.d;
     // V = A*A (make_dims): above 32 views only 36, 49 | 64 | 81 | 100 | 121 occur, with 4, 17 | 32 | 17 | 4 | 25 rows in the last key tile
-    auto multi = [&](auto CT, auto LL) { return ang_multi<T, CT, LL>(packed, L, l, in, out, d, st, status); };
+    auto multi = [&](auto CT, auto LL) { return ang_multi<T, CT, LL>(c, packed, l, in, out, status); };
     if (d.V > 100) return multi(int_c<4>{}, int_c<13>{});
     if (d.V > 96) return multi(int_c<4>{}, int_c<9>{});
     if (d.V > 64) return multi(int_c<3>{}, int_c<9>{});
@@ -531,18 +564,19 @@ int ang_block(const void* packed, const PackedLayout& L, int l, const T* in, T* 
     const unsigned grid = std::min<unsigned>(blocks_for(npix, 4), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds));
     // V <= 25 (5 x 5 and smaller): score rows 25..31 are never a view
     if ((rc = allow_lds(k_ang<T, 13>, lds, "k_ang"))) return rc;
-    k_ang<T, 13><<<grid, 256, lds, st>>>(in, out, at<T>(packed, L.s_ang[l]), at<float>(packed, L.ln_ang[l]),
-                                         at<float>(packed, L.ang_pe), d.V, d.hw, npix, status);
+    k_ang<T, 13><<<grid, 256, lds, c.st>>>(in, out, at<T>(packed, c.L.s_ang[l]), at<float>(packed, c.L.ln_ang[l]),
+                                         at<float>(packed, c.L.ang_pe), d.V, d.hw, npix, status);
     LFT_LAUNCH_OK("k_ang");
     return 0;
 }
 // SpaTrans = part A (k_spa1: token embedding, LayerNorm, Q / K / V) + part B (attention and the per-token tail).
 template <typename T>
-int spa_part_a(const void* packed, const PackedLayout& L, int l, const T* in, void* ws, const WorkLayout& W, const Dims& d, hipStream_t st) {
+int spa_part_a(const Fwd& c, const void* packed, int l, const T* in, void* ws) {
+    const Dims& d = c.d;
     const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1));
     int rc;
-    if ((rc = launch_spa1<T, false>((unsigned)nwg, in, at<T>(packed, L.s_spa1[l]), at<float>(packed, L.ln_spa[l]), at<T>(packed, L.petok[l]),
-                                    at<T>(ws, W.tok), at<T>(ws, W.q), at<T>(ws, W.k), at<T>(ws, W.v), nullptr, nimg, d, st, at<unsigned>(ws, W.status)))) return rc;
+    if ((rc = launch_spa1<T, false>((unsigned)nwg, in, at<T>(packed, c.L.s_spa1[l]), at<float>(packed, c.L.ln_spa[l]), at<T>(packed, c.L.petok[l]),
+                                    at<T>(ws, c.W.tok), at<T>(ws, c.W.q), at<T>(ws, c.W.k), at<T>(ws, c.W.v), nullptr, nimg, c, at<unsigned>(ws, c.W.status)))) return rc;
     LFT_LAUNCH_OK("k_spa1");
     return 0;
 }
@@ -558,11 +592,12 @@ template <typename F> int with_tail_variant(bool skip, bool tok_lm, bool out_lm,
     });
 }
 template <typename T>
-int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, T* out, void* ws, const WorkLayout& W,
-               const Dims& d, hipStream_t st, bool out_lm = false) {      // out_lm: lane-major output tiles, only for the up-sampler
+int spa_part_b(const Fwd& c, const void* packed, int l, const T* skip, T* out, void* ws, bool out_lm = false) {      // out_lm: lane-major output tiles, only for the up-sampler
+    const Dims& d = c.d;
+    const hipStream_t st = c.st;
     const int nimg = d.B * d.V;
-    T *tok = at<T>(ws, W.tok), *q = at<T>(ws, W.q), *k = at<T>(ws, W.k), *v = at<T>(ws, W.v), *o = at<T>(ws, W.o);
-    const float* ln = at<float>(packed, L.ln_spa[l]);
+    T *tok = at<T>(ws, c.W.tok), *q = at<T>(ws, c.W.q), *k = at<T>(ws, c.W.k), *v = at<T>(ws, c.W.v), *o = at<T>(ws, c.W.o);
+    const float* ln = at<float>(packed, c.L.ln_spa[l]);
     const bool lm = tok_lane_major<T>(d);      // must match launch_spa1's choice
     int rc;
     if constexpr (sizeof(T) == 2) {
@@ -570,9 +605,9 @@ int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, 
         const unsigned ntile = (unsigned)(nimg * ((d.h + kAttTY - 1) / kAttTY) * ((d.w + kAttTX - 1) / kAttTX));
         if ((rc = with_tail_variant(skip, lm, out_lm, [&](auto SK, auto LM, auto YL) {
                  if (int r = allow_lds(k_spa_b<T, SK, LM, YL>, kSpaBLds, "k_spa_b")) return r;
-                 k_spa_b<T, SK, LM, YL><<<ntile, 256, kSpaBLds, st>>>(tok, q, k, v, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.h, d.w,
-                                                                      at<unsigned>(ws, W.status), at<T>(packed, L.s_spa1[l]) + (size_t)kFragsSpa1NoQ * 512,
-                                                                      at<T>(packed, L.petok[l]), at<unsigned>(packed, L.spa_geom));
+                 k_spa_b<T, SK, LM, YL><<<ntile, 256, kSpaBLds, st>>>(tok, q, k, v, at<T>(packed, c.L.s_spa2[l]), ln, skip, out, d.h, d.w,
+                                                                      at<unsigned>(ws, c.W.status), at<T>(packed, c.L.s_spa1[l]) + (size_t)kFragsSpa1NoQ * 512,
+                                                                      at<T>(packed, c.L.petok[l]), at<unsigned>(packed, c.L.spa_geom));
                  return 0;
              }))) return rc;
         LFT_LAUNCH_OK("k_spa_b");
@@ -588,7 +623,7 @@ int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, 
         const unsigned nb = blocks_for(d.ntok, 32 * kNwSpa2);
         if ((rc = with_tail_variant(skip, lm, out_lm, [&](auto SK, auto LM, auto YL) {
                  if (int r = allow_lds(k_spa2<T, SK, LM, YL>, lds_spa2<T>(), "k_spa2")) return r;
-                 k_spa2<T, SK, LM, YL><<<nb, 64 * kNwSpa2, lds_spa2<T>(), st>>>(tok, o, at<T>(packed, L.s_spa2[l]), ln, skip, out, d.ntok, at<unsigned>(ws, W.status));
+                 k_spa2<T, SK, LM, YL><<<nb, 64 * kNwSpa2, lds_spa2<T>(), st>>>(tok, o, at<T>(packed, c.L.s_spa2[l]), ln, skip, out, d.ntok, at<unsigned>(ws, c.W.status));
                  return 0;
              }))) return rc;
         LFT_LAUNCH_OK("k_spa2");
@@ -596,68 +631,66 @@ int spa_part_b(const void* packed, const PackedLayout& L, int l, const T* skip, 
     }
 }
 template <typename T>
-int spa_block(const void* packed, const PackedLayout& L, int l, const T* in, const T* skip, T* out, void* ws, const WorkLayout& W,
-              const Dims& d, hipStream_t st, bool out_lm = false) {
-    int rc;
-    if ((rc = spa_part_a<T>(packed, L, l, in, ws, W, d, st))) return rc;
-    return spa_part_b<T>(packed, L, l, skip, out, ws, W, d, st, out_lm);
+int spa_block(const Fwd& c, const void* packed, int l, const T* in, const T* skip, T* out, void* ws, bool out_lm = false) {
+    if (int rc = spa_part_a<T>(c, packed, l, in, ws)) return rc;
+    return spa_part_b<T>(c, packed, l, skip, out, ws, out_lm);
 }
 template <typename T>
-int upsample(const void* packed, const PackedLayout& L, const T* body, const float* lr, float* out, void* ws, const WorkLayout& W,
-             const Dims& d, hipStream_t st, bool in_lm = false) {
-    float* g = at<float>(ws, W.g);
+int upsample(const Fwd& c, const void* packed, const T* body, const float* lr, float* out, void* ws, bool in_lm = false) {
+    const Dims& d = c.d;
+    const hipStream_t st = c.st;
+    float* g = at<float>(ws, c.W.g);
     const unsigned nb = blocks_for(d.ntok, 32 * kNwUp);
     int rc = dispatch<1, 2>(d.gt, [&](auto GT) {
         return dispatch<true, false>(in_lm, [&](auto LM) {
             if (int r = allow_lds(k_up<T, GT, LM>, lds_up<T>(), "k_up")) return r;
-            k_up<T, GT, LM><<<nb, 64 * kNwUp, lds_up<T>(), st>>>(body, at<T>(packed, L.s_up), g, d.ntok, d.nchunk, d.gp);
+            k_up<T, GT, LM><<<nb, 64 * kNwUp, lds_up<T>(), st>>>(body, at<T>(packed, c.L.s_up), g, d.ntok, d.nchunk, d.gp);
             return 0;
         });
     });
     if (rc) return rc;
     LFT_LAUNCH_OK("k_up");
-    launch_assemble(lr, g, out, d.B, d.A, d.h, d.w, d.s, st, 0, at<unsigned>(ws, W.status));
+    launch_assemble(lr, g, out, d.B, d.A, d.h, d.w, d.s, st, 0, at<unsigned>(ws, c.W.status));
     LFT_LAUNCH_OK("k_assemble");
     return 0;
 }
 
 template <typename T>
-int forward_impl(const void* packed, const float* lr, float* out, void* ws, const Dims& d, int prec, hipStream_t st) {
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    T *x0 = at<T>(ws, W.x0), *feat = at<T>(ws, W.feat), *xa = at<T>(ws, W.xa), *xb = at<T>(ws, W.xb);
+int forward_impl(const Fwd& c, const void* packed, const float* lr, float* out, void* ws) {
+    const Dims& d = c.d;
+    T *x0 = at<T>(ws, c.W.x0), *feat = at<T>(ws, c.W.feat), *xa = at<T>(ws, c.W.xa), *xb = at<T>(ws, c.W.xb);
     int rc;
-    if ((rc = init_features<T>(packed, L, lr, x0, xa, xb, feat, d, st))) return rc;
+    if ((rc = init_features<T>(c, packed, lr, x0, xa, xb, feat))) return rc;
     const T* cur = feat;
     for (int l = 0; l < kLayers; ++l) {                  // angular first, then spatial (reference LFT.py:249-250)
-        if ((rc = ang_block<T>(packed, L, l, cur, xa, d, st, at<unsigned>(ws, W.status)))) return rc;
+        if ((rc = ang_block<T>(c, packed, l, cur, xa, at<unsigned>(ws, c.W.status)))) return rc;
         const bool last = l == kLayers - 1;                  // its output only feeds the up-sampler: same 32-token tiling, lane-major tiles
-        if ((rc = spa_block<T>(packed, L, l, xa, last ? feat : nullptr, xb, ws, W, d, st, last && tok_lane_major<T>(d)))) return rc;
+        if ((rc = spa_block<T>(c, packed, l, xa, last ? feat : nullptr, xb, ws, last && tok_lane_major<T>(d)))) return rc;
         cur = xb;
     }
-    return upsample<T>(packed, L, xb, lr, out, ws, W, d, st, tok_lane_major<T>(d));
+    return upsample<T>(c, packed, xb, lr, out, ws, tok_lane_major<T>(d));
 }
 
 // Mean duration of ONE kernel of the forward, launched `reps` times back to back between two HIP events on `stream` (no
 // event between launches, unlike lft_forward_profiled).  Inputs are whatever a previous lft_forward left in the
 // workspace.  Synchronises the stream.  kernel: "k_conv64", "k_ang", "k_spa1", "k_spa_b" (bf16) / "k_spa2" ... see below.
 template <typename T>
-int kernel_time_impl(const char* name, const void* packed, void* ws, const Dims& d, int prec, int reps, hipStream_t st, float* ms_out) {
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    T *x0 = at<T>(ws, W.x0), *feat = at<T>(ws, W.feat), *xa = at<T>(ws, W.xa), *xb = at<T>(ws, W.xb);
+int kernel_time_impl(const Fwd& c, const char* name, const void* packed, void* ws, int reps, float* ms_out) {
+    const Dims& d = c.d;
+    const hipStream_t st = c.st;
+    T *x0 = at<T>(ws, c.W.x0), *feat = at<T>(ws, c.W.feat), *xa = at<T>(ws, c.W.xa), *xb = at<T>(ws, c.W.xb);
     const std::string k(name);
     auto once = [&]() -> int {
-        if (k == "k_ang") return ang_block<T>(packed, L, 1, xb, xa, d, st, at<unsigned>(ws, W.status));
-        if (k == "k_spa1") return spa_part_a<T>(packed, L, 1, xa, ws, W, d, st);
-        if (k == "k_spa_b" || k == "k_spa_attn+k_spa2") return spa_part_b<T>(packed, L, 1, nullptr, xb, ws, W, d, st);
+        if (k == "k_ang") return ang_block<T>(c, packed, 1, xb, xa, at<unsigned>(ws, c.W.status));
+        if (k == "k_spa1") return spa_part_a<T>(c, packed, 1, xa, ws);
+        if (k == "k_spa_b" || k == "k_spa_attn+k_spa2") return spa_part_b<T>(c, packed, 1, nullptr, xb, ws);
         if (k == "k_conv64") {
             const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
             const size_t lds = lds_conv64<T>(d.w);
             int rc;
             if ((rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64"))) return rc;
             // input: xb, which every forward writes (the 16-bit front end no longer writes x0); output: x0, which nothing reads
-            k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(xb, x0, nullptr, at<T>(packed, L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
+            k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(xb, x0, nullptr, at<T>(packed, c.L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
             LFT_LAUNCH_OK("k_conv64");
             return 0;
         }
@@ -681,6 +714,94 @@ int kernel_time_impl(const char* name, const void* packed, void* ws, const Dims&
 }
 #include "lft_train_host.cuh"
 
+// The tape fields lft_train_tape_offset knows: top level, and per layer behind "ang<l>." / "spa<l>."
+template <typename S> struct TapeField { const char* name; size_t S::*member; };
+constexpr TapeField<TrainLayout> kTapeTop[] = {{"x0", &TrainLayout::x0}, {"feat", &TrainLayout::feat}, {"c1", &TrainLayout::c1}, {"c2", &TrainLayout::c2},
+                                               {"c3", &TrainLayout::c3}, {"body", &TrainLayout::body}, {"act", &TrainLayout::act}, {"skip", &TrainLayout::skip}};
+constexpr TapeField<AngTape> kTapeAng[] = {{"n", &AngTape::n}, {"qk", &AngTape::qk}, {"v", &AngTape::v}, {"o", &AngTape::o},
+                                           {"t1", &AngTape::t1}, {"m", &AngTape::m}, {"hdn", &AngTape::hdn}, {"y", &AngTape::y}};
+constexpr TapeField<SpaTape> kTapeSpa[] = {{"tok", &SpaTape::tok}, {"n", &SpaTape::n}, {"qk", &SpaTape::qk}, {"v", &SpaTape::v}, {"o", &SpaTape::o},
+                                           {"t1", &SpaTape::t1}, {"m", &SpaTape::m}, {"hdn", &SpaTape::hdn}, {"t2", &SpaTape::t2}, {"y", &SpaTape::y},
+                                           {"petok", &SpaTape::petok}};
+template <typename S, size_t N> bool tape_field(const TapeField<S> (&table)[N], const S& tape, const std::string& name, size_t* out) {
+    for (const auto& f : table)
+        if (name == f.name) { *out = tape.*f.member; return true; }
+    return false;
+}
+
+#if LFT_TU != 2
+// ---- the light field [U,V,H,W,C] with five strides (data preparation, colour path); nothing is launched when a check fails ----
+// The array itself: pointers, stored class, sizes, strides.  `shape` is the code of a bad size: lft_lf_prepare has always answered
+// LFT_ERR_ARG there, the colour path LFT_ERR_SHAPE.
+int lf_array_ok(const char* who, int shape, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides) {
+    if (!lf || !strides) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
+        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", who, lf_class);
+    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
+        return fail(shape, "%s: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", who, U, V, H, W, C);
+    for (int i = 0; i < 5; ++i)
+        if (strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, strides[i]);
+    return 0;
+}
+// Its centre A x A views.  `index`: what the message calls the centre-view index ("the scripts' centre-view index" for
+// lft_lf_prepare, which follows the MATLAB scripts).  A separate step because lft_lf_prepare checks its scale factor in between.
+int centre_views_ok(const char* who, int shape, const char* index, int U, int V, int A) {
+    if (A < 1 || A > U || A > V) return fail(shape, "%s: angRes %d outside the %d x %d views", who, A, U, V);
+    if ((U - A) % 2 || (V - A) % 2)
+        return fail(shape, "%s: U-A = %d and V-A = %d must be even (%s 0.5*(U-A+2) is not an integer)", who, U - A, V - A, index);
+    return 0;
+}
+// what lft_lf_luma and lft_colour_merge ask of the light field: both of the above, and a grid with one y block per view
+int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A) {
+    if (int rc = lf_array_ok(who, LFT_ERR_SHAPE, lf, lf_class, U, V, H, W, C, strides)) return rc;
+    if (int rc = centre_views_ok(who, LFT_ERR_SHAPE, "the centre-view index", U, V, A)) return rc;
+    if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
+    return 0;
+}
+// ---- B light fields [B,A,A,H,W,C] read in place through six strides, one 32 x 32 output tile per workgroup (refocus, disparity) ----
+struct WindowedLf {         // the arguments lft_refocus and lft_disparity share, and what windowed_lf_ok derives from them
+    const void* lf; int lf_class, B, A, H, W, C; const long long* strides; const void* table; int D, taps;
+    long long tiles_x, tiles;           // kRfTile tiles of a view; tiles == 0: an empty shape, no work and no error
+};
+int too_many_blocks(const char* who, const WindowedLf& l, const char* work) {
+    return fail(LFT_ERR_SHAPE, "%s: %d %s of %d slopes over views of %d x %d need more than 2^31 blocks", who, l.B, work, l.D, l.H, l.W);
+}
+// Every check the two entry points share, in the order they have always made them; nothing is launched when one fails.  The caller's
+// own arguments sit in between: `out_class` (called `out_name` in the message), `radius` (lft_disparity only; 0 for lft_refocus),
+// `own_null` (one of the caller's other pointers is null).  `work`: what too_many_blocks calls the B batches.
+int windowed_lf_ok(const char* who, WindowedLf& l, int out_class, const char* out_name, int radius, bool own_null, const char* work) {
+    if (l.lf_class != LFT_LF_UINT8 && l.lf_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", who, l.lf_class);
+    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "%s: %s class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", who, out_name, out_class);
+    if (l.A < 1 || l.A > 4096) return fail(LFT_ERR_ARG, "%s: angRes %d outside 1 .. 4096", who, l.A);      // A*A records indexed in int
+    if (l.C < 1 || l.C > 4) return fail(LFT_ERR_ARG, "%s: %d channels (1 .. 4)", who, l.C);
+    if (l.taps != 1 && l.taps != 2 && l.taps != 4) return fail(LFT_ERR_ARG, "%s: %d taps (1, 2 or 4)", who, l.taps);
+    if (l.D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, l.D);
+    if (radius < 0 || radius > kDpMaxR) return fail(LFT_ERR_ARG, "%s: radius %d outside 0 .. %d", who, radius, kDpMaxR);
+    if (l.B < 0 || l.H < 0 || l.W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, views of %d x %d", who, l.B, l.H, l.W);
+    l.tiles_x = l.tiles = 0;
+    if (l.B == 0 || l.H == 0 || l.W == 0) return 0;                 // nothing to read or write
+    if (!l.lf || !l.strides || !l.table || own_null) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    for (int i = 0; i < 6; ++i)
+        if (l.strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, l.strides[i]);
+    if ((double)(l.H - 1) * (double)l.strides[3] + (double)(l.W - 1) * (double)l.strides[4] + (double)(l.C - 1) * (double)l.strides[5] > 2147483647.0)
+        return fail(LFT_ERR_SHAPE, "%s: a view of %d x %d x %d with these strides spans more than 2^31 elements", who, l.H, l.W, l.C);
+    l.tiles_x = ((long long)l.W + kRfTile - 1) / kRfTile;
+    l.tiles = l.tiles_x * (((long long)l.H + kRfTile - 1) / kRfTile);
+    if (l.tiles * l.D * l.B > 0x7fffffffLL) return too_many_blocks(who, l, work);
+    return 0;
+}
+// the members RefocusArgs and SweepArgs have in common
+template <typename Args> void fill_windowed(Args& a, const WindowedLf& l) {
+    a.lf = l.lf;
+    for (int i = 0; i < 3; ++i) a.st[i] = l.strides[i];
+    a.sy = (int)l.strides[3]; a.sx = (int)l.strides[4]; a.sc = (int)l.strides[5];
+    a.A = l.A; a.H = l.H; a.W = l.W; a.D = l.D; a.tiles_x = (int)l.tiles_x; a.tiles = (int)l.tiles;
+    a.table = static_cast<const int*>(l.table);
+}
+#endif
+
 }  // namespace
 
 // ================================================================================ C ABI
@@ -691,54 +812,51 @@ int lft_version(void) { return LFT_ABI_VERSION; }
 const char* lft_last_error(void) { return g_err; }
 
 int lft_packed_bytes(int A, int h, int w, int s, int prec, size_t* out_bytes) {
-    Dims d; int rc;
+    Fwd c;
     if (!out_bytes) return fail(LFT_ERR_ARG, "out_bytes is null");
-    if ((rc = make_dims(1, A, h, w, s, prec, &d))) return rc;
-    *out_bytes = packed_layout(d, prec).total;
+    if (int rc = make_fwd(1, A, h, w, s, prec, nullptr, &c)) return rc;
+    *out_bytes = c.L.total;
     return 0;
 }
 int lft_workspace_bytes(int B, int A, int h, int w, int s, int prec, size_t* out_bytes) {
-    Dims d; int rc;
+    Fwd c;
     if (!out_bytes) return fail(LFT_ERR_ARG, "out_bytes is null");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    *out_bytes = work_layout(d, prec).total;
+    if (int rc = make_fwd(B, A, h, w, s, prec, nullptr, &c)) return rc;
+    *out_bytes = c.W.total;
     return 0;
 }
 
 int lft_pack_weights(const float* const* params, int nparams, void* packed, int A, int h, int w, int s, int prec, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!params || !packed) return fail(LFT_ERR_ARG, "null pointer");
     if (nparams != LFT_NUM_PARAMS) return fail(LFT_ERR_ARG, "expected %d parameter tensors, got %d", LFT_NUM_PARAMS, nparams);
     for (int i = 0; i < nparams; ++i)
         if (!params[i]) return fail(LFT_ERR_ARG, "parameter %d is null", i);
-    if ((rc = make_dims(1, A, h, w, s, prec, &d))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return by_prec(prec, [&](auto t) { using T = decltype(t); return pack_impl<T>(params, packed, d, prec, st); });
+    if (int rc = make_fwd(1, A, h, w, s, prec, stream, &c)) return rc;
+    return by_prec(prec, [&](auto t) { return pack_impl<decltype(t)>(c, params, packed); });
 }
 
 int lft_forward(const void* packed, const float* lr, float* out, void* workspace, int B, int A, int h, int w, int s, int prec, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!packed || !lr || !out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return by_prec(prec, [&](auto t) { using T = decltype(t); return forward_impl<T>(packed, lr, out, workspace, d, prec, st); });
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
+    return by_prec(prec, [&](auto t) { return forward_impl<decltype(t)>(c, packed, lr, out, workspace); });
 }
 
 int lft_status_reset(void* workspace, int B, int A, int h, int w, int s, int prec, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    LFT_HIP_OK(hipMemsetAsync(at<char>(workspace, work_layout(d, prec).status), 0, 256, static_cast<hipStream_t>(stream)));
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
+    LFT_HIP_OK(hipMemsetAsync(at<char>(workspace, c.W.status), 0, 256, c.st));
     return 0;
 }
 int lft_status_read(const void* workspace, int B, int A, int h, int w, int s, int prec, void* stream, unsigned* host_flags) {
-    Dims d; int rc;
+    Fwd c;
     if (!workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     unsigned flags = 0;
-    LFT_HIP_OK(hipMemcpyAsync(&flags, at<char>(workspace, work_layout(d, prec).status), sizeof(flags), hipMemcpyDeviceToHost, st));
-    LFT_HIP_OK(hipStreamSynchronize(st));
+    LFT_HIP_OK(hipMemcpyAsync(&flags, at<char>(workspace, c.W.status), sizeof(flags), hipMemcpyDeviceToHost, c.st));
+    LFT_HIP_OK(hipStreamSynchronize(c.st));
     if (host_flags) *host_flags = flags;
     if (flags == 0) return 0;
     return fail(LFT_STATUS_NONFINITE, "non-finite activations or outputs since the last lft_status_reset (flags 0x%x)%s", flags,
@@ -755,11 +873,10 @@ int lft_forward_profiled(const void* packed, const float* lr, float* out, void* 
 
 int lft_kernel_time(const char* kernel, const void* packed, void* workspace, int B, int A, int h, int w, int s, int prec, int reps,
                     void* stream, float* ms_out) {
-    Dims d; int rc;
+    Fwd c;
     if (!kernel || !packed || !workspace || !ms_out || reps < 1) return fail(LFT_ERR_ARG, "bad argument");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return by_prec(prec, [&](auto t) { using T = decltype(t); return kernel_time_impl<T>(kernel, packed, workspace, d, prec, reps, st, ms_out); });
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
+    return by_prec(prec, [&](auto t) { return kernel_time_impl<decltype(t)>(c, kernel, packed, workspace, reps, ms_out); });
 }
 
 int lft_bicubic_fwd(const float* lr, float* out, int B, int A, int h, int w, int s, void* stream) {
@@ -772,53 +889,45 @@ int lft_bicubic_fwd(const float* lr, float* out, int B, int A, int h, int w, int
     return 0;
 }
 
-int lft_init_features_fwd(const void* packed, const float* lr, void* act_out, void* workspace, int B, int A, int h, int w, int s,
-                          int prec, void* stream) {
-    Dims d; int rc;
+// lft_init_features_fwd, and (legacy, test-only: include/lft_hip_test.h) the front end as it ran before the composition
+static int init_features_entry(bool legacy, const void* packed, const float* lr, void* act_out, void* workspace, int B, int A, int h, int w, int s,
+                               int prec, void* stream) {
+    Fwd c;
     if (!packed || !lr || !act_out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
-        return init_features<T>(packed, L, lr, at<T>(workspace, W.x0), at<T>(workspace, W.xa), at<T>(workspace, W.xb), static_cast<T*>(act_out), d, st);
+        T *x0 = at<T>(workspace, c.W.x0), *xa = at<T>(workspace, c.W.xa), *xb = at<T>(workspace, c.W.xb), *feat = static_cast<T*>(act_out);
+        return legacy ? init_features_x0<T>(c, packed, lr, x0, xa, xb, feat) : init_features<T>(c, packed, lr, x0, xa, xb, feat);
     });
 }
-
+int lft_init_features_fwd(const void* packed, const float* lr, void* act_out, void* workspace, int B, int A, int h, int w, int s,
+                          int prec, void* stream) {
+    return init_features_entry(false, packed, lr, act_out, workspace, B, A, h, w, s, prec, stream);
+}
 int lft_init_features_legacy_fwd(const void* packed, const float* lr, void* act_out, void* workspace, int B, int A, int h, int w, int s,
                                  int prec, void* stream) {
-    Dims d; int rc;
-    if (!packed || !lr || !act_out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return by_prec(prec, [&](auto t) {
-        using T = decltype(t);
-        return init_features_x0<T>(packed, L, lr, at<T>(workspace, W.x0), at<T>(workspace, W.xa), at<T>(workspace, W.xb), static_cast<T*>(act_out), d, st);
-    });
+    return init_features_entry(true, packed, lr, act_out, workspace, B, A, h, w, s, prec, stream);
 }
 
 int lft_conv0_fwd(const void* packed, const float* lr, void* x0_out, int recomputed, int B, int A, int h, int w, int s, int prec, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!packed || !lr || !x0_out) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     if (recomputed && prec == LFT_PREC_F32) return fail(LFT_ERR_ARG, "conv_init0 is recomputed in the 16-bit precisions only");
-    const PackedLayout L = packed_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
+        const Dims& d = c.d;
         const int nimg = d.B * d.V;
-        const float* w0 = at<float>(packed, L.conv0_w);
+        const float* w0 = at<float>(packed, c.L.conv0_w);
         if constexpr (sizeof(T) == 2) {
             if (recomputed) {
-                k_conv0_recomputed<T><<<nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv)), 64 * kNwConv, 0, st>>>(static_cast<T*>(x0_out), nimg, d.h, d.w, ConvLr{lr, w0, d.A});
+                k_conv0_recomputed<T><<<nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv)), 64 * kNwConv, 0, c.st>>>(static_cast<T*>(x0_out), nimg, d.h, d.w, ConvLr{lr, w0, d.A});
                 LFT_LAUNCH_OK("k_conv0_recomputed");
                 return 0;
             }
         }
-        k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, st>>>(lr, w0, static_cast<T*>(x0_out), d.B, d.A, d.h, d.w);
+        k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, c.st>>>(lr, w0, static_cast<T*>(x0_out), d.B, d.A, d.h, d.w);
         LFT_LAUNCH_OK("k_conv0");
         return 0;
     });
@@ -826,44 +935,36 @@ int lft_conv0_fwd(const void* packed, const float* lr, void* x0_out, int recompu
 
 int lft_ang_block_fwd(const void* packed, int layer, const void* act_in, void* act_out, int B, int A, int h, int w, int s, int prec,
                       void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!packed || !act_in || !act_out) return fail(LFT_ERR_ARG, "null pointer");
     if (layer < 0 || layer >= kLayers) return fail(LFT_ERR_ARG, "layer %d out of range", layer);
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
-        return ang_block<T>(packed, L, layer, static_cast<const T*>(act_in), static_cast<T*>(act_out), d, st);
+        return ang_block<T>(c, packed, layer, static_cast<const T*>(act_in), static_cast<T*>(act_out));
     });
 }
 
 int lft_spa_block_fwd(const void* packed, int layer, const void* act_in, const void* skip, void* act_out, void* workspace, int B, int A,
                       int h, int w, int s, int prec, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!packed || !act_in || !act_out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
     if (layer < 0 || layer >= kLayers) return fail(LFT_ERR_ARG, "layer %d out of range", layer);
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
-        return spa_block<T>(packed, L, layer, static_cast<const T*>(act_in), static_cast<const T*>(skip), static_cast<T*>(act_out), workspace, W, d, st);
+        return spa_block<T>(c, packed, layer, static_cast<const T*>(act_in), static_cast<const T*>(skip), static_cast<T*>(act_out), workspace);
     });
 }
 
 int lft_upsample_fwd(const void* packed, const void* act_in, const float* lr, float* out, void* workspace, int B, int A, int h, int w,
                      int s, int prec, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!packed || !act_in || !lr || !out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
-        return upsample<T>(packed, L, static_cast<const T*>(act_in), lr, out, workspace, W, d, st);
+        return upsample<T>(c, packed, static_cast<const T*>(act_in), lr, out, workspace);
     });
 }
 
@@ -871,20 +972,17 @@ int lft_upsample_fwd(const void* packed, const void* act_in, const float* lr, fl
 // then the up-sampler -- with the hand-off between the two chosen by the caller.
 int lft_tail_fwd(const void* packed, const void* act_in, const void* skip, const float* lr, float* out, void* workspace,
                  int B, int A, int h, int w, int s, int prec, int handoff, void* stream) {
-    Dims d; int rc;
+    Fwd c;
     if (!packed || !act_in || !skip || !lr || !out || !workspace) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = make_dims(B, A, h, w, s, prec, &d))) return rc;
-    const PackedLayout L = packed_layout(d, prec);
-    const WorkLayout W = work_layout(d, prec);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = make_fwd(B, A, h, w, s, prec, stream, &c)) return rc;
     return by_prec(prec, [&](auto t) {
         using T = decltype(t);
         const bool lm = handoff != 0;
-        if (lm && !tok_lane_major<T>(d))
-            return fail(LFT_ERR_SHAPE, "lft_tail_fwd: views of %dx%d have no lane-major hand-off in this precision", d.h, d.w);
-        T* xb = at<T>(workspace, W.xb);
-        if (int r = spa_block<T>(packed, L, kLayers - 1, static_cast<const T*>(act_in), static_cast<const T*>(skip), xb, workspace, W, d, st, lm)) return r;
-        return upsample<T>(packed, L, xb, lr, out, workspace, W, d, st, lm);
+        if (lm && !tok_lane_major<T>(c.d))
+            return fail(LFT_ERR_SHAPE, "lft_tail_fwd: views of %dx%d have no lane-major hand-off in this precision", c.d.h, c.d.w);
+        T* xb = at<T>(workspace, c.W.xb);
+        if (int r = spa_block<T>(c, packed, kLayers - 1, static_cast<const T*>(act_in), static_cast<const T*>(skip), xb, workspace, lm)) return r;
+        return upsample<T>(c, packed, xb, lr, out, workspace, lm);
     });
 }
 
@@ -987,11 +1085,8 @@ int lft_scene_integrate_ens(const float* sr_variants, float* sr_scene, unsigned 
 
 int lft_mfma_selftest(const float* Am, const float* Bm, const float* W2, float* C, float* D, int prec, void* stream) {
     if (!Am || !Bm || !W2 || !C || !D) return fail(LFT_ERR_ARG, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (prec == LFT_PREC_F32) k_selftest<float><<<1, 64, 0, st>>>(Am, Bm, W2, C, D);
-    else if (prec == LFT_PREC_BF16) k_selftest<bf16_t><<<1, 64, 0, st>>>(Am, Bm, W2, C, D);
-    else if (prec == LFT_PREC_F16) k_selftest<f16_t><<<1, 64, 0, st>>>(Am, Bm, W2, C, D);
-    else return fail(LFT_ERR_ARG, "bad prec %d", prec);
+    if (prec != LFT_PREC_F32 && prec != LFT_PREC_BF16 && prec != LFT_PREC_F16) return fail(LFT_ERR_ARG, "bad prec %d", prec);
+    by_prec(prec, [&](auto t) { k_selftest<decltype(t)><<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(Am, Bm, W2, C, D); return 0; });
     LFT_LAUNCH_OK("k_selftest");
     return 0;
 }
@@ -1019,19 +1114,10 @@ int lft_view_metrics(const float* label, const float* out, int B, int A, int h, 
 int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
                    const int* crops, int n_crops, int crop_h, int crop_w, const double* weights_h, const int* indices_h, int taps_h,
                    const double* weights_w, const int* indices_w, int taps_w, float* hr, float* lr, void* stream) {
-    if (!lf || !strides || !crops || !weights_h || !indices_h || !weights_w || !indices_w || !hr || !lr)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: null pointer");
-    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", lf_class);
-    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", U, V, H, W, C);
-    for (int i = 0; i < 5; ++i)
-        if (strides[i] < 0) return fail(LFT_ERR_ARG, "lft_lf_prepare: stride %d is negative (%lld)", i, strides[i]);
+    if (!crops || !weights_h || !indices_h || !weights_w || !indices_w || !hr || !lr) return fail(LFT_ERR_ARG, "lft_lf_prepare: null pointer");
+    if (int rc = lf_array_ok("lft_lf_prepare", LFT_ERR_ARG, lf, lf_class, U, V, H, W, C, strides)) return rc;
     if (s != 2 && s != 4) return fail(LFT_ERR_ARG, "lft_lf_prepare: scale factor must be 2 or 4, got %d", s);
-    if (A < 1 || A > U || A > V) return fail(LFT_ERR_ARG, "lft_lf_prepare: angRes %d outside the %d x %d views", A, U, V);
-    if ((U - A) % 2 || (V - A) % 2)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: U-A = %d and V-A = %d must be even (the scripts' centre-view index 0.5*(U-A+2) is not an integer)",
-                    U - A, V - A);
+    if (int rc = centre_views_ok("lft_lf_prepare", LFT_ERR_ARG, "the scripts' centre-view index", U, V, A)) return rc;
     if (n_crops < 0 || crop_h < 1 || crop_w < 1 || crop_h > H || crop_w > W)
         return fail(LFT_ERR_ARG, "lft_lf_prepare: %d crops of %d x %d in views of %d x %d", n_crops, crop_h, crop_w, H, W);
     for (int i = 0; i < n_crops; ++i) {
@@ -1056,33 +1142,13 @@ int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int
         for (int i = 0; i < nb; ++i) { c.y0[i] = crops[2 * (n0 + i)]; c.x0[i] = crops[2 * (n0 + i) + 1]; }
         a.n0 = n0;
         const dim3 grid(tiles, (unsigned)(A * A), (unsigned)nb);
-        if (lf_class == LFT_LF_UINT8) k_lf_prepare<uint8_t><<<grid, 256, 0, st>>>(a, c);
-        else if (lf_class == LFT_LF_FLOAT32) k_lf_prepare<float><<<grid, 256, 0, st>>>(a, c);
-        else k_lf_prepare<double><<<grid, 256, 0, st>>>(a, c);
+        by_lf_class(lf_class, [&](auto t) { k_lf_prepare<decltype(t)><<<grid, 256, 0, st>>>(a, c); return 0; });
         LFT_LAUNCH_OK("k_lf_prepare");
     }
     return 0;
 }
 
 // ---- colour path (lft_colour.cuh) ----
-namespace {
-// what lft_lf_luma and lft_colour_merge ask of the light field; nothing is launched when this fails
-int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A) {
-    if (!lf || !strides) return fail(LFT_ERR_ARG, "%s: null pointer", who);
-    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
-        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", who, lf_class);
-    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
-        return fail(LFT_ERR_SHAPE, "%s: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", who, U, V, H, W, C);
-    for (int i = 0; i < 5; ++i)
-        if (strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, strides[i]);
-    if (A < 1 || A > U || A > V) return fail(LFT_ERR_SHAPE, "%s: angRes %d outside the %d x %d views", who, A, U, V);
-    if ((U - A) % 2 || (V - A) % 2)
-        return fail(LFT_ERR_SHAPE, "%s: U-A = %d and V-A = %d must be even (the centre-view index 0.5*(U-A+2) is not an integer)", who, U - A, V - A);
-    if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
-    return 0;
-}
-}  // namespace
-
 int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, float* y_out,
                 void* stream) {
     if (!y_out) return fail(LFT_ERR_ARG, "lft_lf_luma: null pointer");
@@ -1093,11 +1159,8 @@ int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C,
     a.lf = lf;
     for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
     a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.H = H; a.W = W; a.y = y_out;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks, (unsigned)(A * A));
-    if (lf_class == LFT_LF_UINT8) k_lf_luma<uint8_t><<<grid, 256, 0, st>>>(a);
-    else if (lf_class == LFT_LF_FLOAT32) k_lf_luma<float><<<grid, 256, 0, st>>>(a);
-    else k_lf_luma<double><<<grid, 256, 0, st>>>(a);
+    by_lf_class(lf_class, [&](auto t) { k_lf_luma<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
     LFT_LAUNCH_OK("k_lf_luma");
     return 0;
 }
@@ -1122,11 +1185,8 @@ int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, i
     a.sr_y = sr_y; a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w;
     for (int i = 0; i < 9; ++i) a.minv[i] = minv[i];
     a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)tiles, (unsigned)(A * A));
-    if (lf_class == LFT_LF_UINT8) k_colour_merge<uint8_t><<<grid, 256, 0, st>>>(a);
-    else if (lf_class == LFT_LF_FLOAT32) k_colour_merge<float><<<grid, 256, 0, st>>>(a);
-    else k_colour_merge<double><<<grid, 256, 0, st>>>(a);
+    by_lf_class(lf_class, [&](auto t) { k_colour_merge<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
     LFT_LAUNCH_OK("k_colour_merge");
     return 0;
 }
@@ -1134,34 +1194,14 @@ int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, i
 // ---- synthetic refocus (lft_refocus.cuh) ----
 int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
                 int taps, void* out, int out_class, void* stream) {
-    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "lft_refocus: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", lf_class);
-    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "lft_refocus: output class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", out_class);
-    if (A < 1 || A > 4096) return fail(LFT_ERR_ARG, "lft_refocus: angRes %d outside 1 .. 4096", A);      // A*A records indexed in int
-    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_refocus: %d channels (1 .. 4)", C);
-    if (taps != 1 && taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "lft_refocus: %d taps (1, 2 or 4)", taps);
-    if (D < 1) return fail(LFT_ERR_ARG, "lft_refocus: %d slopes", D);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_refocus: negative size in B = %d, views of %d x %d", B, H, W);
-    if (B == 0 || H == 0 || W == 0) return 0;                       // an empty stack: nothing to read or write
-    if (!lf || !strides || !table || !out) return fail(LFT_ERR_ARG, "lft_refocus: null pointer");
-    for (int i = 0; i < 6; ++i)
-        if (strides[i] < 0) return fail(LFT_ERR_ARG, "lft_refocus: stride %d is negative (%lld)", i, strides[i]);
-    if ((double)(H - 1) * (double)strides[3] + (double)(W - 1) * (double)strides[4] + (double)(C - 1) * (double)strides[5] > 2147483647.0)
-        return fail(LFT_ERR_SHAPE, "lft_refocus: a view of %d x %d x %d with these strides spans more than 2^31 elements", H, W, C);
-    const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, tiles = tiles_x * (((long long)H + kRfTile - 1) / kRfTile);
-    if (tiles * D * B > 0x7fffffffLL)
-        return fail(LFT_ERR_SHAPE, "lft_refocus: %d stacks of %d slopes over views of %d x %d need more than 2^31 blocks", B, D, H, W);
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
+    if (int rc = windowed_lf_ok("lft_refocus", l, out_class, "output", 0, !out, "stacks")) return rc;
+    if (!l.tiles) return 0;                                         // an empty stack
     RefocusArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 3; ++i) a.st[i] = strides[i];
-    a.sy = (int)strides[3]; a.sx = (int)strides[4]; a.sc = (int)strides[5];
-    a.A = A; a.H = H; a.W = W; a.D = D; a.tiles_x = (int)tiles_x; a.tiles = (int)tiles;
-    a.table = static_cast<const int*>(table); a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)(tiles * D * B));
-    if (lf_class == LFT_LF_UINT8) refocus_kernel<uint8_t>(C, taps)<<<grid, 256, 0, st>>>(a);
-    else refocus_kernel<float>(C, taps)<<<grid, 256, 0, st>>>(a);
+    fill_windowed(a, l);
+    a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
+    const dim3 grid((unsigned)(l.tiles * D * B));
+    by_lf_class<false>(lf_class, [&](auto t) { refocus_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
     LFT_LAUNCH_OK("k_refocus");
     return 0;
 }
@@ -1189,42 +1229,22 @@ int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, si
 int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
                   const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
                   float* cost, void* aif, int aif_class, void* stream) {
-    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "lft_disparity: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", lf_class);
-    if (aif_class != LFT_LF_UINT8 && aif_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "lft_disparity: all-in-focus class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", aif_class);
-    if (A < 1 || A > 4096) return fail(LFT_ERR_ARG, "lft_disparity: angRes %d outside 1 .. 4096", A);
-    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_disparity: %d channels (1 .. 4)", C);
-    if (taps != 1 && taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "lft_disparity: %d taps (1, 2 or 4)", taps);
-    if (D < 1) return fail(LFT_ERR_ARG, "lft_disparity: %d slopes", D);
-    if (radius < 0 || radius > kDpMaxR) return fail(LFT_ERR_ARG, "lft_disparity: radius %d outside 0 .. %d", radius, kDpMaxR);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_disparity: negative size in B = %d, views of %d x %d", B, H, W);
-    if (B == 0 || H == 0 || W == 0) return 0;                       // empty maps: nothing to read or write
-    if (!lf || !strides || !table || !slopes || !scratch || !disparity || !confidence || !index)
-        return fail(LFT_ERR_ARG, "lft_disparity: null pointer");
-    for (int i = 0; i < 6; ++i)
-        if (strides[i] < 0) return fail(LFT_ERR_ARG, "lft_disparity: stride %d is negative (%lld)", i, strides[i]);
-    if ((double)(H - 1) * (double)strides[3] + (double)(W - 1) * (double)strides[4] + (double)(C - 1) * (double)strides[5] > 2147483647.0)
-        return fail(LFT_ERR_SHAPE, "lft_disparity: a view of %d x %d x %d with these strides spans more than 2^31 elements", H, W, C);
-    const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, tiles = tiles_x * (((long long)H + kRfTile - 1) / kRfTile);
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
+    if (int rc = windowed_lf_ok("lft_disparity", l, aif_class, "all-in-focus", radius, !slopes || !scratch || !disparity || !confidence || !index, "sweeps"))
+        return rc;
+    if (!l.tiles) return 0;                                         // empty maps
     const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
-    if (tiles * D * B > 0x7fffffffLL || ptiles * B > 0x7fffffffLL)
-        return fail(LFT_ERR_SHAPE, "lft_disparity: %d sweeps of %d slopes over views of %d x %d need more than 2^31 blocks", B, D, H, W);
+    if (ptiles * B > 0x7fffffffLL) return too_many_blocks("lft_disparity", l, "sweeps");
     size_t vol = 0;
     if (!disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol))
         return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
     if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_disparity: scratch must be 4-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     SweepArgs s{};
-    s.lf = lf;
-    for (int i = 0; i < 3; ++i) s.st[i] = strides[i];
-    s.sy = (int)strides[3]; s.sx = (int)strides[4]; s.sc = (int)strides[5];
-    s.A = A; s.H = H; s.W = W; s.D = D; s.tiles_x = (int)tiles_x; s.tiles = (int)tiles;
-    s.table = static_cast<const int*>(table);
+    fill_windowed(s, l);
     s.vol = static_cast<float*>(scratch); s.stack = aif ? s.vol + vol : nullptr;
-    const dim3 grid((unsigned)(tiles * D * B));
-    if (lf_class == LFT_LF_UINT8) sweep_kernel<uint8_t>(C, taps)<<<grid, 256, 0, st>>>(s);
-    else sweep_kernel<float>(C, taps)<<<grid, 256, 0, st>>>(s);
+    const dim3 grid((unsigned)(l.tiles * D * B));
+    by_lf_class<false>(lf_class, [&](auto t) { sweep_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
     LFT_LAUNCH_OK("k_sweep_cost");
     PickArgs p{};
     p.vol = s.vol; p.stack = s.stack; p.slopes = slopes;
@@ -1261,28 +1281,11 @@ int lft_train_tape_offset(const char* name, int B, int A, int h, int w, int s, s
     const TrainLayout T = train_layout(d);
     if (T.rc) return T.rc;
     const std::string n(name);
-    auto layer = [&](char c) { return c - '0'; };
-    if (n == "x0") *out_float_offset = T.x0; else if (n == "feat") *out_float_offset = T.feat;
-    else if (n == "c1") *out_float_offset = T.c1; else if (n == "c2") *out_float_offset = T.c2; else if (n == "c3") *out_float_offset = T.c3;
-    else if (n == "body") *out_float_offset = T.body; else if (n == "act") *out_float_offset = T.act;
-    else if (n == "skip") *out_float_offset = T.skip;
-    else if (n.size() > 5 && n.compare(0, 3, "ang") == 0 && n[3] >= '0' && n[3] < '0' + kLayers && n[4] == '.') {
-        const AngTape& a = T.ang[layer(n[3])];
-        const std::string f = n.substr(5);
-        if (f == "n") *out_float_offset = a.n; else if (f == "qk") *out_float_offset = a.qk; else if (f == "v") *out_float_offset = a.v;
-        else if (f == "o") *out_float_offset = a.o; else if (f == "t1") *out_float_offset = a.t1; else if (f == "m") *out_float_offset = a.m;
-        else if (f == "hdn") *out_float_offset = a.hdn; else if (f == "y") *out_float_offset = a.y;
-        else return fail(LFT_ERR_ARG, "unknown tape field %s", name);
-    } else if (n.size() > 5 && n.compare(0, 3, "spa") == 0 && n[3] >= '0' && n[3] < '0' + kLayers && n[4] == '.') {
-        const SpaTape& a = T.spa[layer(n[3])];
-        const std::string f = n.substr(5);
-        if (f == "tok") *out_float_offset = a.tok; else if (f == "n") *out_float_offset = a.n; else if (f == "qk") *out_float_offset = a.qk;
-        else if (f == "v") *out_float_offset = a.v; else if (f == "o") *out_float_offset = a.o;
-        else if (f == "t1") *out_float_offset = a.t1; else if (f == "m") *out_float_offset = a.m; else if (f == "hdn") *out_float_offset = a.hdn;
-        else if (f == "t2") *out_float_offset = a.t2; else if (f == "y") *out_float_offset = a.y; else if (f == "petok") *out_float_offset = a.petok;
-        else return fail(LFT_ERR_ARG, "unknown tape field %s", name);
-    } else return fail(LFT_ERR_ARG, "unknown tape field %s", name);
-    return 0;
+    const bool layered = n.size() > 5 && n[3] >= '0' && n[3] < '0' + kLayers && n[4] == '.';      // "ang<l>.<field>", "spa<l>.<field>"
+    const bool found = layered && n.compare(0, 3, "ang") == 0 ? tape_field(kTapeAng, T.ang[n[3] - '0'], n.substr(5), out_float_offset)
+                     : layered && n.compare(0, 3, "spa") == 0 ? tape_field(kTapeSpa, T.spa[n[3] - '0'], n.substr(5), out_float_offset)
+                                                              : tape_field(kTapeTop, T, n, out_float_offset);
+    return found ? 0 : fail(LFT_ERR_ARG, "unknown tape field %s", name);
 }
 // The checks every training entry point shares, after its own null pointers: the parameter array, the shape, the math mode.
 static int train_args(const float* const* params, int nparams, int B, int A, int h, int w, int s, int math, Dims* d) {
@@ -1436,6 +1439,9 @@ int lft_l1_loss(const float* sr, const float* hr, long long n, float* dsr, float
 }
 // ---- light-field loss (lft_loss.cuh) ----
 namespace {
+// do the n floats at a and the n floats at b share memory / does a gradient image (may be null) share memory with either input
+inline bool meets(const float* a, const float* b, long long n) { return (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n); }
+inline bool overlaps(const float* dsr, const float* sr, const float* hr, long long n) { return dsr && (meets(dsr, sr, n) || meets(dsr, hr, n)); }
 struct LossShape { long long n; int nblocks[2]; };     // stencil blocks of the scalar and of the 16-byte path
 int loss_shape(int B, int A, int H, int W, LossShape* s) {
     if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "sizes must be positive, got B %d A %d H %d W %d", B, A, H, W);
@@ -1465,9 +1471,7 @@ int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, in
     if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "gscale is NaN");
     LossShape s;
     if (int rc = loss_shape(B, A, H, W, &s)) return rc;
-    if (dsr && (((uintptr_t)dsr < (uintptr_t)(sr + s.n) && (uintptr_t)sr < (uintptr_t)(dsr + s.n)) ||
-                ((uintptr_t)dsr < (uintptr_t)(hr + s.n) && (uintptr_t)hr < (uintptr_t)(dsr + s.n))))
-        return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the stencil reads neighbours, in place would race");
+    if (overlaps(dsr, sr, hr, s.n)) return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the stencil reads neighbours, in place would race");
     const double n = (double)s.n;
     const double nt[4] = {n / W * (W - 1), n / H * (H - 1), n / A * (A - 1), n / A * (A - 1)};      // n_x, n_y, n_v, n_u: exact in double
     int T = 0;
@@ -1532,9 +1536,7 @@ int lft_ssim_loss(const float* sr, const float* hr, int B, int A, int H, int W, 
     if (accumulate != 0 && accumulate != 1) return fail(LFT_ERR_ARG, "accumulate must be 0 or 1, got %d", accumulate);
     SsimShape s;
     if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
-    if (dsr && (((uintptr_t)dsr < (uintptr_t)(sr + s.n) && (uintptr_t)sr < (uintptr_t)(dsr + s.n)) ||
-                ((uintptr_t)dsr < (uintptr_t)(hr + s.n) && (uintptr_t)hr < (uintptr_t)(dsr + s.n))))
-        return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the windows read neighbours, in place would race");
+    if (overlaps(dsr, sr, hr, s.n)) return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the windows read neighbours, in place would race");
     const double R = (double)ssim_range, count = (double)s.views * (H - 2 * kSsimR) * (W - 2 * kSsimR);
     SsimArgs a = {};
     a.A = A; a.H = H; a.W = W; a.tiles_x = s.tiles_x; a.ntiles = s.ntiles; a.accumulate = accumulate;
@@ -1568,7 +1570,14 @@ constexpr size_t kGuardHostMax = 256;
 std::mutex g_guard_mu;
 std::map<const void*, GuardHost> g_guards;
 unsigned long long g_guard_seq = 0;
-
+// what lft_guard_init remembered of the block at `guard` (to *h, which may be null), or the refusal of a block it never saw
+int find_guard(const void* guard, GuardHost* h) {
+    std::lock_guard<std::mutex> lock(g_guard_mu);
+    auto it = g_guards.find(guard);
+    if (it == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
+    if (h) *h = it->second;
+    return 0;
+}
 }  // namespace
 
 int lft_guard_bytes(int nseg, size_t* out_bytes) {
@@ -1619,12 +1628,7 @@ int lft_adam_step_guarded(float* p, const float* g, float* m, float* v, long lon
     if (weight_decay < 0.0f) return fail(LFT_ERR_ARG, "weight decay must not be negative");
     if (std::isnan(max_norm)) return fail(LFT_ERR_ARG, "max_norm is NaN (<= 0 or +inf switches clipping off)");
     GuardHost h;
-    {
-        std::lock_guard<std::mutex> lock(g_guard_mu);
-        auto it = g_guards.find(guard);
-        if (it == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
-        h = it->second;
-    }
+    if (int rc = find_guard(guard, &h)) return rc;
     if (n != h.n) return fail(LFT_ERR_SHAPE, "n = %lld, but the guard block was initialised for %lld", n, h.n);
     hipStream_t st = static_cast<hipStream_t>(stream);
     GuardBlock* gb = static_cast<GuardBlock*>(guard);
@@ -1639,10 +1643,7 @@ int lft_adam_step_guarded(float* p, const float* g, float* m, float* v, long lon
 }
 int lft_guard_read(const void* guard, void* stream, lft_guard_report* host) {
     if (!guard || !host) return fail(LFT_ERR_ARG, "null pointer");
-    {
-        std::lock_guard<std::mutex> lock(g_guard_mu);
-        if (g_guards.find(guard) == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
-    }
+    if (int rc = find_guard(guard, nullptr)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     LFT_HIP_OK(hipMemcpyAsync(host, guard, sizeof(lft_guard_report), hipMemcpyDeviceToHost, st));   // the report is the block's first member
     LFT_HIP_OK(hipStreamSynchronize(st));
@@ -1652,7 +1653,7 @@ int lft_ema_update(float* ema, const float* p, long long n, float decay, int war
     if (!ema || !p) return fail(LFT_ERR_ARG, "null pointer");
     if (((uintptr_t)ema | (uintptr_t)p) & 3) return fail(LFT_ERR_ARG, "ema and p must be 4-byte aligned");
     if (n < 1) return fail(LFT_ERR_ARG, "n must be positive, got %lld", n);
-    if ((uintptr_t)ema < (uintptr_t)(p + n) && (uintptr_t)p < (uintptr_t)(ema + n)) return fail(LFT_ERR_ARG, "ema and p overlap");
+    if (meets(ema, p, n)) return fail(LFT_ERR_ARG, "ema and p overlap");
     if (!(decay >= 0.0f && decay < 1.0f)) return fail(LFT_ERR_ARG, "decay %g outside [0, 1)", (double)decay);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!guard) {
@@ -1663,12 +1664,7 @@ int lft_ema_update(float* ema, const float* p, long long n, float decay, int war
         return 0;
     }
     GuardHost h;
-    {
-        std::lock_guard<std::mutex> lock(g_guard_mu);
-        auto it = g_guards.find(guard);
-        if (it == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
-        h = it->second;
-    }
+    if (int rc = find_guard(guard, &h)) return rc;
     if (n != h.n) return fail(LFT_ERR_ARG, "n = %lld, but the guard block was initialised for %lld", n, h.n);
     k_ema_guarded<<<h.nblocks, kGuardThreads, 0, st>>>(ema, p, static_cast<const GuardBlock*>(guard), decay, warmup != 0);
     LFT_LAUNCH_OK("k_ema_guarded");

@@ -169,23 +169,9 @@ TrainLayout train_layout(const Dims& d) {
 }
 
 int run_pack_split(std::vector<PackOp>& ops, float* dst, int expect_frags, hipStream_t st, int mm) {      // mm = 1, 2
-    int total = 0;
-    size_t i = 0;
-    while (i < ops.size()) {
-        PackArgs a{};
-        int nf = 0;
-        while (i < ops.size() && a.nops < LFT_PACK_MAXOPS) {
-            a.op[a.nops] = ops[i];
-            a.op[a.nops].frag0 = nf;
-            nf += ops[i].ntiles * ops[i].ksteps;
-            ++a.nops; ++i;
-        }
-        if (int rc = dispatch<1, 2>(mm, [&](auto MM) { k_pack_split<MM><<<nf, 64, 0, st>>>(a, dst + (size_t)total * frag_floats(MM)); return 0; })) return rc;
-        LFT_LAUNCH_OK("k_pack_split");
-        total += nf;
-    }
-    if (total != expect_frags) return fail(LFT_ERR_ARG, "internal: stream has %d fragments, expected %d", total, expect_frags);
-    return 0;
+    return pack_batches(ops, expect_frags, "k_pack_split", [&](const PackArgs& a, int nf, int total) {
+        return dispatch<1, 2>(mm, [&](auto MM) { k_pack_split<MM><<<nf, 64, 0, st>>>(a, dst + (size_t)total * frag_floats(MM)); return 0; });
+    });
 }
 
 // ---- launch helpers ----
