@@ -27,7 +27,7 @@
  *    View sizes: any h, w >= 1 up to the width limit -- w <= 75 in LFT_PREC_F32, w <= 347 in LFT_PREC_BF16 / LFT_PREC_F16 (the
  *    convolutions keep two image rows of a view in the 160 KiB of LDS); a wider view is refused with LFT_ERR_SHAPE before anything
  *    is launched.  Tested against the oracle, one view size per class of the kernels' tiling (the table above launch_spa1 in
- *    lft_amd/csrc/lft_api.hip): views below 128 pixels, 32- and 64-wide views with h*w % 128 == 0, ragged sizes (13x11, 17x19,
+ *    lft_amd/csrc/lft_network.hip): views below 128 pixels, 32- and 64-wide views with h*w % 128 == 0, ragged sizes (13x11, 17x19,
  *    35x37, 31x32), sizes that are lane-major in fp32 only (16x24, 24x16), 62x64, both sides of the k_spa1 chunk switch (53x55 |
  *    54x56 in 16 bit, 57x59 | 58x60 in fp32), and the widest views (3x75, 3x347; init_features only).
  *    Training (lft_train_*): the GEMM and weight-gradient kernels are chosen by the token count N = B*A*A*h*w and the view width;

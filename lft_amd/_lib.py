@@ -14,7 +14,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_vo
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LFT_LIB_PATH") or os.path.join(HERE, "liblft_hip.so")   # LFT_LIB_PATH: experiment builds (tools/ab_build.py)
-SOURCES = ["lft_api.hip", "lft_common.cuh", "lft_kernels_a.cuh", "lft_kernels_b.cuh", "lft_train.cuh", "lft_train_host.cuh", "lft_attn_maps.cuh", "lft_optim.cuh", "lft_loss.cuh", "lft_ssim_loss.cuh", "lft_metrics.cuh", "lft_prepare.cuh", "lft_ensemble.cuh", "lft_colour.cuh", "lft_refocus.cuh", "lft_disparity.cuh"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".cuh")))     # every source of the library, under CSRC
 
 
 def _header_text(header: str) -> str:
@@ -41,8 +41,8 @@ def _stamp_path(lib_path: str) -> str:
 
 
 def _flags_stamp() -> str:
-    """What the library was built with: the compile / link commands themselves (the per-unit flags live in this file, not
-    in a source the mtime check sees)."""
+    """What the library was built with: the compile / link commands themselves (the flags live in this file, not in a source
+    the mtime check sees)."""
     return "\n".join(" ".join(c) for c in build_commands("hipcc", "liblft_hip.so"))
 
 
@@ -50,7 +50,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(HERE, "..", "include", "lft_hip.h")]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(HERE, "..", "include", h) for h in ("lft_hip.h", "lft_hip_test.h")]
     if any(os.path.getmtime(d) > t for d in deps):
         return True
     # a change of compiler flags must rebuild too; a shipped library without a stamp (the GPU box gets the .so, not the
@@ -73,45 +73,78 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
-# Flags of both translation units (lft_api.hip compiles as LFT_TU=1, the inference side, and LFT_TU=2, the training step: two
-# units only so that they build in parallel).
+# The library's translation units, in build order (csrc/<unit>.hip; the longest compile first, they run in parallel):
+#   lft_network      the network: the inference path with its per-stage test entry points, the fp32 training step and the
+#                    attention maps from its tape; lft_version / lft_last_error.  One unit, not two: see the file's header
+#   lft_lightfield   scene tiling, dihedral transforms, view metrics, data preparation, colour, refocus, disparity
+#   lft_objective    losses, Adam, the guarded step, the EMA
+# A unit emits the kernels of the headers it includes, so each includes only what it launches from.
+UNITS = ("lft_network", "lft_lightfield", "lft_objective")
+INFERENCE_UNIT = "lft_network"          # where the forward's kernels are (tools/isa_mix.py, the listing the hazard tests mutate)
+# The kernels emitted by more than one unit (fragments of their mangled names), with who launches each: none.  The kernels that
+# inference and training both launch -- k_conv0<float>, k_pack<float>, k_assemble_t<2> and <4> -- are emitted once, since the two
+# share lft_network; the other units share no launch with it or with each other (tests/test_host.py asserts exactly this set).
+SHARED_KERNELS = ()
+# Flags of every unit.
 # -amdgpu-schedule-relaxed-occupancy: the kernels' occupancy is set by their LDS footprint and launch bounds, so the
 #   scheduler may spend registers on a better instruction order (+1.2 %, k_spa1 43 -> 41 us event-timed); no arithmetic changes.
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring scalar f32 operations into v_pk_*_f32, which issue slower beside
-#   MFMAs than the two scalar instructions (+1.4 % on the inference bench).  Until round 3 the training unit kept the default
+#   MFMAs than the two scalar instructions (+1.4 % on the inference bench).  Until round 3 the training code kept the default
 #   because the pass also decides which fp32 multiply-adds get contracted, enough to flip a ReLU unit in the screened-seed
 #   gradient test; the kink-aligned gradient tests (tests/test_gpu_train.py) pass with and without the flag, so the flags
-#   are no longer pinned by a test and both units use the same set.
-COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-schedule-relaxed-occupancy=true", "-fPIC"]
-UNIT_FLAGS = {1: ["-fno-slp-vectorize"], 2: ["-fno-slp-vectorize"]}
+#   are no longer pinned by a test and every unit uses the same set.
+COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-schedule-relaxed-occupancy=true", "-fPIC", "-fno-slp-vectorize"]
 
 
 def _objects(lib_path):
     d = os.path.join(os.path.dirname(lib_path), "_build")
-    return d, {tu: os.path.join(d, os.path.basename(lib_path) + f".tu{tu}.o") for tu in UNIT_FLAGS}
+    return d, {u: os.path.join(d, os.path.basename(lib_path) + f".{u}.o") for u in UNITS}
 
 
-def build_commands(hipcc, lib_path, extra=()):
-    _, objs = _objects(lib_path)
-    src = os.path.join(CSRC, "lft_api.hip")
-    cmds = [[hipcc, *COMMON_FLAGS, *UNIT_FLAGS[tu], *extra, f"-DLFT_TU={tu}", "-c", src, "-o", objs[tu]] for tu in sorted(objs)]
-    cmds.append([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", *[objs[tu] for tu in sorted(objs)], "-o", lib_path])
-    return cmds
+def unit_commands(hipcc, form, out, extra=()):
+    """One compile line per unit, {unit: command}, all with COMMON_FLAGS.  form "object": the build, out(unit) the object file;
+    "listing": the device assembly of the product (hipcc -S) to out(unit); "device": device-only with the caller's `extra`
+    arguments (which say what to emit) to out(unit)."""
+    mode = {"object": ["-c"], "listing": ["--cuda-device-only", "-S"], "device": ["--cuda-device-only"]}[form]
+    return {u: [hipcc, *COMMON_FLAGS, *extra, *mode, os.path.join(CSRC, u + ".hip"), "-o", out(u)] for u in UNITS}
 
 
-def compile_and_link(hipcc, lib_path, extra=()):
-    """Both units in parallel, then the link; raises LftError with the compiler output on failure."""
-    d, _ = _objects(lib_path)
-    os.makedirs(d, exist_ok=True)
-    cmds = build_commands(hipcc, lib_path, extra)
-    procs = [subprocess.Popen(c, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for c in cmds[:-1]]
+def run_parallel(cmds):
+    """Run the commands at the same time (one per unit: four processes); raises LftError with the compiler output of the first
+    that failed."""
+    procs = [subprocess.Popen(c, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for c in cmds]
     outs = [p.communicate()[0] for p in procs]
     for p, o, c in zip(procs, outs, cmds):
         if p.returncode != 0:
             raise LftError("hipcc failed: " + " ".join(c) + "\n" + o)
+
+
+def listings(isa_dir, hipcc="/opt/rocm/bin/hipcc", reuse=False, extra=()):
+    """{unit: path} of the device assembly listings of the product build, isa_dir/<unit>.s; reuse: keep the ones already there."""
+    os.makedirs(isa_dir, exist_ok=True)
+    paths = {u: os.path.join(isa_dir, u + ".s") for u in UNITS}
+    cmds = unit_commands(hipcc, "listing", paths.get, extra)
+    run_parallel([cmds[u] for u in UNITS if not (reuse and os.path.exists(paths[u]))])
+    return paths
+
+
+def build_commands(hipcc, lib_path, extra=()):
+    _, objs = _objects(lib_path)
+    cmds = list(unit_commands(hipcc, "object", objs.get, extra).values())
+    cmds.append([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", *objs.values(), "-o", lib_path])
+    return cmds
+
+
+def compile_and_link(hipcc, lib_path, extra=()):
+    """The units in parallel, then the link; raises LftError with the compiler output on failure."""
+    d, _ = _objects(lib_path)
+    os.makedirs(d, exist_ok=True)
+    cmds = build_commands(hipcc, lib_path, extra)
+    run_parallel(cmds[:-1])
     r = subprocess.run(cmds[-1], capture_output=True, text=True)
     if r.returncode != 0:
         raise LftError("link failed:\n" + r.stdout + r.stderr)
+
 
 class GuardSegment(ctypes.Structure):          # lft_segment
     _fields_ = [("first", c_longlong), ("count", c_longlong), ("trainable", c_int)]

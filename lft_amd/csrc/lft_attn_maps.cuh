@@ -5,6 +5,9 @@
 // (angular) times the Q | K read, so the results of a workgroup go through LDS or a flat element loop: every store instruction
 // of a wave covers one contiguous run of the output (measured times and what bounds them: DESIGN.md section 10).
 #pragma once
+#include "lft_win_attn.cuh"
+
+namespace {
 
 // ------------------------------------------------------------------------------------------
 // Angular maps.  One workgroup per pixel (b, y, x); sequence = the V views, 8 heads of 8 channels, scale 1/sqrt(8).
@@ -163,3 +166,5 @@ __global__ __launch_bounds__(256) void k_win_maps(const float* __restrict__ QK, 
         }
     }
 }
+
+}  // namespace

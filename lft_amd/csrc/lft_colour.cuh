@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+namespace {
+
 constexpr int kColTile = 32;         // HR extent of a tile
 constexpr int kColSpan = 24;         // staged LR region: at most kColSpan rows x kColSpan columns (32 / 2 + 6 taps + slack)
 constexpr int kColMaxTaps = 6;       // ceil(4) + 2, before all-zero tap columns are dropped (4 are left for s = 2 and 4)
@@ -188,3 +190,5 @@ __global__ __launch_bounds__(256) void k_colour_merge(ColourArgs a) {
         }
     }
 }
+
+}  // namespace

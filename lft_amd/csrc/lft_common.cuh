@@ -21,6 +21,18 @@
 #include <stdint.h>
 #include <utility>
 
+// In-kernel phase stamps (LFT_STAMP) and other timing experiments live in lft_experiment.cuh, which only a diagnostic
+// build includes (-DLFT_EXPERIMENT, tools/stamp_report.py); in the product build LFT_STAMP() is empty and nothing else of
+// that header exists.
+#ifdef LFT_EXPERIMENT
+#include "lft_experiment.cuh"
+#else
+#define LFT_STAMP(slot) ((void)0)
+#define LFT_STAMP_IT(slot, it_ofs) ((void)0)
+#endif
+
+namespace {
+
 typedef __bf16 bf16_t;
 // Register pairs for the vector-instruction-bound phases: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32, one instruction per pair.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -42,16 +54,6 @@ typedef unsigned int raw16 __attribute__((ext_vector_type(4), may_alias));
 
 #define LFT_DEV static __device__ __forceinline__
 #define LFT_MEM __device__ __forceinline__
-
-// In-kernel phase stamps (LFT_STAMP) and other timing experiments live in lft_experiment.cuh, which only a diagnostic
-// build includes (-DLFT_EXPERIMENT, tools/stamp_report.py); in the product build LFT_STAMP() is empty and nothing else of
-// that header exists.
-#ifdef LFT_EXPERIMENT
-#include "lft_experiment.cuh"
-#else
-#define LFT_STAMP(slot) ((void)0)
-#define LFT_STAMP_IT(slot, it_ofs) ((void)0)
-#endif
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one private 4 MiB L2): consecutive block
 // ids -- i.e. neighbouring tiles, which share halo rows -- land on eight different L2s and each fetches the shared rows
@@ -1015,3 +1017,5 @@ LFT_DEV void linear_acc(const T* __restrict__ w, int f0, int lane, const Frag<T>
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) mma(load_wfrag(w, f0 + nt * KS + ks, lane), x[ks], y[nt]);
 }
+
+}  // namespace

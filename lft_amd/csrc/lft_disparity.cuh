@@ -54,6 +54,8 @@
 
 #include "lft_refocus.cuh"
 
+namespace {
+
 constexpr int kDpMaxR = 8;                                           // largest aggregation radius
 constexpr int kDpTile = 16;                                          // tile of k_disparity_pick: one pixel per lane
 constexpr int kDpCols = kDpTile + 2 * kDpMaxR;                       // rows and columns of a V tile with the largest halo (32)
@@ -276,3 +278,5 @@ inline void (*sweep_kernel(int C, int taps))(SweepArgs) {
                                                {k_sweep_cost<T, 4, 1>, k_sweep_cost<T, 4, 2>, k_sweep_cost<T, 4, 4>}};
     return k[C - 1][taps == 4 ? 2 : taps - 1];
 }
+
+}  // namespace

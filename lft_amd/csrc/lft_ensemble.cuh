@@ -16,6 +16,11 @@
 // The merge adds the variants in ascending code order and multiplies once by 1.0f / E -- nothing a compiler could contract
 // into an FMA -- so the same operations in torch give the same bits.
 // ------------------------------------------------------------------------------------------
+#pragma once
+#include "lft_common.cuh"
+
+namespace {
+
 constexpr int DH_TILE = 32;
 
 LFT_DEV int dihedral_nth_code(unsigned mask, int k) {      // code of the k-th set bit of mask (ascending); k < popcount(mask)
@@ -156,3 +161,5 @@ __global__ __launch_bounds__(256) void k_scene_integrate_ens(const float* __rest
         if (ty + 8 * r < na && tx < nb)
             out[(size_t)(u_ * h0 + Y0 + ty + 8 * r) * ((size_t)A * w0) + (size_t)v_ * w0 + X0 + tx] = acc[r] * inv;
 }
+
+}  // namespace

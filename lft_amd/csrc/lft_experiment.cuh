@@ -2,7 +2,8 @@
 // this file: lft_common.cuh pulls it in under #ifdef LFT_EXPERIMENT, and lft_amd/_lib.py never defines that macro.
 //
 // Per-phase s_memtime stamps of wave 0 of every workgroup go to a side buffer that no kernel reads; the report tool copies
-// the buffer to the host through lft_debug_read_stamps (defined at the end of lft_api.hip under the same macro).
+// the buffer to the host through lft_debug_read_stamps (defined in lft_network.hip under the same macro; every unit has its
+// own buffer, and the kernels that stamp are all in that one).
 #pragma once
 
 #ifdef LFT_ISA_MARKS
@@ -12,6 +13,7 @@
 #define LFT_STAMP(slot) do { __builtin_amdgcn_sched_barrier(0); asm volatile("; LFT_MARK %0" :: "n"(slot)); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define LFT_STAMP_IT(slot, it_ofs) LFT_STAMP(slot)       // a loop body's marks: the same phase in every iteration
 #else
+namespace {
 __device__ unsigned long long g_lft_stamps[4096 * 32];    // 32 slots per workgroup: k_spa1 uses 0..15, k_spa_b / k_spa2 16..31
 static __device__ __forceinline__ void lft_stamp(int slot) {
     unsigned long long t;
@@ -20,6 +22,7 @@ static __device__ __forceinline__ void lft_stamp(int slot) {
     __builtin_amdgcn_sched_barrier(0);
     if (threadIdx.x == 0 && blockIdx.x < 4096) g_lft_stamps[blockIdx.x * 32 + slot] = t;
 }
+}  // namespace
 #define LFT_STAMP(slot) lft_stamp(slot)
 #define LFT_STAMP_IT(slot, it_ofs) lft_stamp((slot) + (it_ofs))
 #endif

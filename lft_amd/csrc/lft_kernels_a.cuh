@@ -2,6 +2,8 @@
 #pragma once
 #include "lft_common.cuh"
 
+namespace {
+
 // ------------------------------------------------------------------------------------------
 // Weight packing.  A stream is a sequence of fragments in exactly the order a kernel consumes
 // them.  One PackOp describes ntiles x ksteps fragments (nt-major) cut from a row-major fp32 matrix:
@@ -91,10 +93,6 @@ __global__ void k_pe_tables(float* __restrict__ ang_pe, T* __restrict__ spa_img,
         const int p = idx >> 6, c = idx & 63;
         spa_img[idx] = (T)((pe_value(p / w, c) + pe_value(p % w, c)) / 2.0f);
     }
-}
-__global__ void k_copy_f32(const float* __restrict__ src, float* __restrict__ dst, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -288,28 +286,6 @@ constexpr int kW01K = 96, kW01Frags = 12;
 // of the W01 product, taken as fragments (acc_frags), then holds channels 16 ks + 8 h + j in element j of fragment ks
 // -- the natural order of a token row in memory, so conv_init.2 consumes the tile with the stream it always had.
 __host__ __device__ __forceinline__ int conv01_row_channel(int rho) { return (rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1); }
-// w0 [64][9], w1 [64][64][9] -> w01 [64][kW01K] fp32 (pack time; k_pack rounds it to ConvLrOp)
-__global__ void k_compose_w01(const float* __restrict__ w0, const float* __restrict__ w1, float* __restrict__ w01) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= 64 * kW01K) return;
-    const int rho = idx / kW01K, k = idx - rho * kW01K;
-    float v = 0.0f;
-    if (k < 81) {
-        const int o = conv01_row_channel(rho), t1 = k / 9, t0 = k - 9 * t1;
-        for (int c = 0; c < 64; ++c) v += w1[o * 576 + c * 9 + t1] * w0[c * 9 + t0];
-    }
-    w01[idx] = v;
-}
-// The 16-bit part B folds the 1x1x1 conv into the FFN's second Linear (k_spa_b): wl [64][128], w2 [128][256] -> wlw2 [64][256]
-// fp32, summed in channel order (pack time; k_pack rounds it once to the operand type)
-__global__ void k_compose_wlw2(const float* __restrict__ wl, const float* __restrict__ w2, float* __restrict__ wlw2) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= 64 * 256) return;
-    const int o = idx >> 8, k = idx & 255;
-    float v = 0.0f;
-    for (int c = 0; c < 128; ++c) v += wl[o * 128 + c] * w2[c * 256 + k];
-    wlw2[idx] = v;
-}
 // View (a1, a2) of image b inside the LR mosaic [B,1,A*h,A*w]; row stride A*w (see k_conv0).
 LFT_DEV const float* lr_view(const float* __restrict__ lr, int im, int A, int h, int w) {
     const int V = A * A, b = im / V, v = im - b * V, a1 = v / A, a2 = v - a1 * A;
@@ -854,3 +830,5 @@ __global__ __launch_bounds__(64 * CT * NG) void k_ang_multi(const T* __restrict_
     }
     publish_status(status, bad);
 }
+
+}  // namespace

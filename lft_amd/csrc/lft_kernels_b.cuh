@@ -4,6 +4,8 @@
 #include "lft_common.cuh"
 #include "lft_kernels_a.cuh"
 
+namespace {
+
 // ------------------------------------------------------------------------------------------
 // SpaTrans part 1 (reference LFT.py:164-169, 179-186): per 32-token tile of one view image
 //   tok = conv3x3(x; MLP.weight as [128,64,3,3])            (unfold + Linear 576->128)
@@ -343,25 +345,6 @@ LFT_DEV void spa_b_read_bases(int lane, int bxl, int (&kb)[2], int (&vb)[2]) {
 // lane -- piece 0: dofs[0..3], piece 1: dofs[4..7], piece 2: dofs[8], kb[0] | kb[1] << 16, vb[0] | vb[1] << 16 (LDS offsets below
 // 2^16), ymask | xs[0] << 8 | xs[1] << 16 -- so that a wave's load of a piece is one contiguous KiB.
 constexpr int kSpaBGeomPieces = 3, kSpaBGeomTileBytes = 4 * kSpaBGeomPieces * 1024;
-__global__ __launch_bounds__(256) void k_spa_b_geom(unsigned* __restrict__ tab, int h, int w) {
-    const int tiles_x = (w + kAttTX - 1) / kAttTX;
-    const int tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
-    const int lane = threadIdx.x & 63, r = lane & 31, wave = threadIdx.x >> 6;
-    const int y0 = ty * kAttTY, x0 = tx * kAttTX, bxl = 8 * wave;
-    const int qy = y0 + ((r >> 2) & 3);
-    int dofs[kAdPerWave], kb[2], vb[2];
-    unsigned ymask, xs[2];
-    spa_b_dma_offsets<true>(wave, lane, y0, x0, h, w, dofs);
-    spa_b_window_masks(lane, qy, y0, x0, bxl, h, w, ymask, xs);
-    spa_b_read_bases(lane, bxl, kb, vb);
-    unsigned* dst = tab + ((size_t)(tile * 4 + wave) * kSpaBGeomPieces * 64 + lane) * 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dst[(i >> 2) * 256 + (i & 3)] = (unsigned)dofs[i];
-    dst[512] = (unsigned)dofs[8];
-    dst[513] = (unsigned)kb[0] | ((unsigned)kb[1] << 16);
-    dst[514] = (unsigned)vb[0] | ((unsigned)vb[1] << 16);
-    dst[515] = ymask | (xs[0] << 8) | (xs[1] << 16);
-}
 
 template <typename T, bool SKIP, bool TOKLM = false, bool YLM = false>   // TOKLM: k_spa1 wrote the tokens as lane-major 32-token tiles (w % 32 == 0: a tile = 32 columns of one image row); YLM: write the output so (consumer: k_up)
 __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, const T* __restrict__ Q, const T* __restrict__ K,
@@ -393,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void k_spa_b(const T* __restrict__ TOK, con
     const long long qtok = img0 + min(qy, h - 1) * w + min(qx, w - 1);
     // row-major Q: [token][128], head hd = channels 16 hd .. (natural order); lane-major: piece [k-step hd][32 hh + column] of
     // the tile of image row qy (acc order -- K / V come in the same order, so the dot products agree, and the channel order
-    // of V^T's rows, i.e. of the attention output, is undone by packing Wo in natural k order: lft_api.hip)
+    // of V^T's rows, i.e. of the attention output, is undone by packing Wo in natural k order: lft_network.hip, pack_impl)
     const T* qptr = TOKLM ? Q + (img0 + (long long)min(qy, h - 1) * w + x0) * 128 + (32 * hh + bxl + qpx) * 8
                                : Q + qtok * 128 + 8 * hh;
     constexpr int kQHead = TOKLM ? 512 : 16, kQPair = 2 * kQHead;     // element stride from one head / head pair to the next
@@ -809,16 +792,6 @@ LFT_DEV float bicubic_at(const float* __restrict__ view, int stride, int h, int 
     }
     return acc;
 }
-// The per-view bicubic skip on its own (lft_bicubic_fwd: unit tests of reference LFT.py:255-266).
-__global__ __launch_bounds__(256) void k_bicubic(const float* __restrict__ lr, float* __restrict__ out, int B, int A, int h, int w, int s) {
-    // grid: x = 256-pixel column groups, y = HR mosaic row, z = batch
-    const int HR_H = A * h * s, HR_W = A * w * s;
-    const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
-    if (X >= HR_W) return;
-    const int a1 = Y / (h * s), a2 = X / (w * s);
-    const float* view = lr + (size_t)b * (A * h) * (A * w) + (size_t)(a1 * h) * (A * w) + a2 * w;
-    out[((size_t)b * HR_H + Y) * HR_W + X] = bicubic_at(view, A * w, h, w, Y - a1 * h * s, X - a2 * w * s, s);
-}
 
 // The gather is tiled: a workgroup owns an 8 x 8 block of LR mosaic pixels =
 // an 8S x 8S block of output pixels, and stages the (8+2)^2 footprints it can touch in LDS with coalesced 16-byte
@@ -927,42 +900,6 @@ __global__ __launch_bounds__(256) void k_assemble_t(const float* __restrict__ lr
 }
 
 // ------------------------------------------------------------------------------------------
-// Scene tiling around the hot path (reference utils/utils.py:91-157, driven by test.py:83-101): a whole scene is
-// cut into overlapping A*patch x A*patch mosaics on the GPU, super-resolved as ONE batch, and re-assembled from
-// the central stride*s region of every SR patch -- instead of the reference's batch-1 Python double loop.
-// Both kernels are pure gathers (one thread per output element), HBM-bound.
-// ------------------------------------------------------------------------------------------
-LFT_DEV int reflect_idx(int i, int n) {             // symmetric extension, edge repeated (ImageExtend, utils.py:126-138)
-    i = i < 0 ? -i - 1 : i;
-    return i >= n ? 2 * n - 1 - i : i;
-}
-__global__ __launch_bounds__(256) void k_scene_divide(const float* __restrict__ scene, float* __restrict__ patches,
-                                                      int A, int h0, int w0, int patch, int stride, int nv) {
-    // grid: x over the A*patch columns, y = row of the patch mosaic, z = patch index ku*nv + kv
-    const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, n = blockIdx.z;
-    const int P = A * patch;
-    if (X >= P) return;
-    const int bdr = (patch - stride) / 2, ku = n / nv, kv = n - ku * nv;
-    const int u = Y / patch, y = Y - u * patch, v = X / patch, x = X - v * patch;
-    const int ey = ku * stride + y, ex = kv * stride + x;
-    float val = 0.0f;                                   // beyond the extended view: zero fill (utils.py:109-113)
-    if (ey < h0 + 2 * bdr && ex < w0 + 2 * bdr)
-        val = scene[(size_t)(u * h0 + reflect_idx(ey - bdr, h0)) * (A * w0) + v * w0 + reflect_idx(ex - bdr, w0)];
-    patches[((size_t)n * P + Y) * P + X] = val;
-}
-__global__ __launch_bounds__(256) void k_scene_integrate(const float* __restrict__ sub, float* __restrict__ out,
-                                                         int A, int pz, int stride, int h0, int w0, int nv) {
-    // grid: x over the A*w0 columns of the SR scene mosaic, y = its rows; pz, stride, h0, w0 are in SR pixels
-    const int Xm = blockIdx.x * 256 + threadIdx.x, Ym = blockIdx.y;
-    if (Xm >= A * w0) return;
-    const int bdr = (pz - stride) / 2;
-    const int u = Ym / h0, Y = Ym - u * h0, v = Xm / w0, X = Xm - v * w0;
-    const int ku = Y / stride, i = Y - ku * stride, kv = X / stride, j = X - kv * stride;
-    const int P = A * pz;
-    out[(size_t)Ym * (A * w0) + Xm] = sub[((size_t)(ku * nv + kv) * P + u * pz + bdr + i) * P + v * pz + bdr + j];
-}
-
-// ------------------------------------------------------------------------------------------
 // MFMA layout self-test: C[32x32] = A[32x16] * B[16x32] through the same fragment helpers the
 // kernels use (natural k order), and the acc-order re-use path D = W2 * C.  Checked from Python
 // with asymmetric integer data (guide rule: never validate a layout with symmetric operands).
@@ -1011,3 +948,5 @@ __global__ __launch_bounds__(64) void k_selftest(const float* __restrict__ Am, c
 #pragma unroll
     for (int i = 0; i < 16; ++i) Dout[acc_row(i, hh) * 32 + r] = d[i];
 }
+
+}  // namespace

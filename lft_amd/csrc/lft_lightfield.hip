@@ -1,0 +1,338 @@
+// lft_lightfield.hip -- what handles light fields around the network, in the C ABI of liblft_hip.so (include/lft_hip.h): scene
+// tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus and disparity.
+#include "lft_host.cuh"
+#include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
+#include "lft_metrics.cuh"
+#include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
+#include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
+#include "lft_colour.cuh"    // colour path: RGB light field -> Y mosaic; SR Y + up-scaled chroma -> RGB views
+#include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
+#include "lft_disparity.cuh" // disparity: plane-sweep cost volume, windowed aggregation, winner-take-all (lft_disparity)
+
+namespace {
+
+// ---- the light field [U,V,H,W,C] with five strides (data preparation, colour path); nothing is launched when a check fails ----
+// The array itself: pointers, stored class, sizes, strides.  `shape` is the code of a bad size: lft_lf_prepare has always answered
+// LFT_ERR_ARG there, the colour path LFT_ERR_SHAPE.
+int lf_array_ok(const char* who, int shape, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides) {
+    if (!lf || !strides) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
+        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", who, lf_class);
+    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
+        return fail(shape, "%s: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", who, U, V, H, W, C);
+    for (int i = 0; i < 5; ++i)
+        if (strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, strides[i]);
+    return 0;
+}
+// Its centre A x A views.  `index`: what the message calls the centre-view index ("the scripts' centre-view index" for
+// lft_lf_prepare, which follows the MATLAB scripts).  A separate step because lft_lf_prepare checks its scale factor in between.
+int centre_views_ok(const char* who, int shape, const char* index, int U, int V, int A) {
+    if (A < 1 || A > U || A > V) return fail(shape, "%s: angRes %d outside the %d x %d views", who, A, U, V);
+    if ((U - A) % 2 || (V - A) % 2)
+        return fail(shape, "%s: U-A = %d and V-A = %d must be even (%s 0.5*(U-A+2) is not an integer)", who, U - A, V - A, index);
+    return 0;
+}
+// what lft_lf_luma and lft_colour_merge ask of the light field: both of the above, and a grid with one y block per view
+int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A) {
+    if (int rc = lf_array_ok(who, LFT_ERR_SHAPE, lf, lf_class, U, V, H, W, C, strides)) return rc;
+    if (int rc = centre_views_ok(who, LFT_ERR_SHAPE, "the centre-view index", U, V, A)) return rc;
+    if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
+    return 0;
+}
+// ---- B light fields [B,A,A,H,W,C] read in place through six strides, one 32 x 32 output tile per workgroup (refocus, disparity) ----
+struct WindowedLf {         // the arguments lft_refocus and lft_disparity share, and what windowed_lf_ok derives from them
+    const void* lf; int lf_class, B, A, H, W, C; const long long* strides; const void* table; int D, taps;
+    long long tiles_x, tiles;           // kRfTile tiles of a view; tiles == 0: an empty shape, no work and no error
+};
+int too_many_blocks(const char* who, const WindowedLf& l, const char* work) {
+    return fail(LFT_ERR_SHAPE, "%s: %d %s of %d slopes over views of %d x %d need more than 2^31 blocks", who, l.B, work, l.D, l.H, l.W);
+}
+// Every check the two entry points share, in the order they have always made them; nothing is launched when one fails.  The caller's
+// own arguments sit in between: `out_class` (called `out_name` in the message), `radius` (lft_disparity only; 0 for lft_refocus),
+// `own_null` (one of the caller's other pointers is null).  `work`: what too_many_blocks calls the B batches.
+int windowed_lf_ok(const char* who, WindowedLf& l, int out_class, const char* out_name, int radius, bool own_null, const char* work) {
+    if (l.lf_class != LFT_LF_UINT8 && l.lf_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", who, l.lf_class);
+    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "%s: %s class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", who, out_name, out_class);
+    if (l.A < 1 || l.A > 4096) return fail(LFT_ERR_ARG, "%s: angRes %d outside 1 .. 4096", who, l.A);      // A*A records indexed in int
+    if (l.C < 1 || l.C > 4) return fail(LFT_ERR_ARG, "%s: %d channels (1 .. 4)", who, l.C);
+    if (l.taps != 1 && l.taps != 2 && l.taps != 4) return fail(LFT_ERR_ARG, "%s: %d taps (1, 2 or 4)", who, l.taps);
+    if (l.D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, l.D);
+    if (radius < 0 || radius > kDpMaxR) return fail(LFT_ERR_ARG, "%s: radius %d outside 0 .. %d", who, radius, kDpMaxR);
+    if (l.B < 0 || l.H < 0 || l.W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, views of %d x %d", who, l.B, l.H, l.W);
+    l.tiles_x = l.tiles = 0;
+    if (l.B == 0 || l.H == 0 || l.W == 0) return 0;                 // nothing to read or write
+    if (!l.lf || !l.strides || !l.table || own_null) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    for (int i = 0; i < 6; ++i)
+        if (l.strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, l.strides[i]);
+    if ((double)(l.H - 1) * (double)l.strides[3] + (double)(l.W - 1) * (double)l.strides[4] + (double)(l.C - 1) * (double)l.strides[5] > 2147483647.0)
+        return fail(LFT_ERR_SHAPE, "%s: a view of %d x %d x %d with these strides spans more than 2^31 elements", who, l.H, l.W, l.C);
+    l.tiles_x = ((long long)l.W + kRfTile - 1) / kRfTile;
+    l.tiles = l.tiles_x * (((long long)l.H + kRfTile - 1) / kRfTile);
+    if (l.tiles * l.D * l.B > 0x7fffffffLL) return too_many_blocks(who, l, work);
+    return 0;
+}
+// the members RefocusArgs and SweepArgs have in common
+template <typename Args> void fill_windowed(Args& a, const WindowedLf& l) {
+    a.lf = l.lf;
+    for (int i = 0; i < 3; ++i) a.st[i] = l.strides[i];
+    a.sy = (int)l.strides[3]; a.sx = (int)l.strides[4]; a.sc = (int)l.strides[5];
+    a.A = l.A; a.H = l.H; a.W = l.W; a.D = l.D; a.tiles_x = (int)l.tiles_x; a.tiles = (int)l.tiles;
+    a.table = static_cast<const int*>(l.table);
+}
+
+}  // namespace
+
+// ================================================================================ C ABI
+extern "C" {
+
+static int scene_counts(int h0, int w0, int patch, int stride, int* nu, int* nv) {
+    if (h0 < 1 || w0 < 1 || patch < 1 || stride < 1 || stride > patch) return fail(LFT_ERR_SHAPE, "bad scene tiling (h0=%d w0=%d patch=%d stride=%d)", h0, w0, patch, stride);
+    const int bdr = (patch - stride) / 2, h = h0 + 2 * bdr, w = w0 + 2 * bdr;
+    if (h < patch || w < patch) return fail(LFT_ERR_SHAPE, "view %dx%d is smaller than one patch after extension", h0, w0);
+    *nu = (h - patch) / stride + ((h - patch) % stride ? 2 : 1);
+    *nv = (w - patch) / stride + ((w - patch) % stride ? 2 : 1);
+    return 0;
+}
+int lft_scene_counts(int h0, int w0, int patch, int stride, int* num_u, int* num_v) {
+    if (!num_u || !num_v) return fail(LFT_ERR_ARG, "null pointer");
+    return scene_counts(h0, w0, patch, stride, num_u, num_v);
+}
+int lft_scene_divide(const float* scene, float* patches, int A, int h0, int w0, int patch, int stride, void* stream) {
+    int nu, nv, rc;
+    if (!scene || !patches || A < 1) return fail(LFT_ERR_ARG, "bad argument");
+    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
+    const dim3 grid((unsigned)((A * patch + 255) / 256), (unsigned)(A * patch), (unsigned)(nu * nv));
+    k_scene_divide<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(scene, patches, A, h0, w0, patch, stride, nv);
+    LFT_LAUNCH_OK("k_scene_divide");
+    return 0;
+}
+int lft_scene_integrate(const float* sr_patches, float* sr_scene, int A, int h0, int w0, int patch, int stride, int s, void* stream) {
+    int nu, nv, rc;
+    if (!sr_patches || !sr_scene || A < 1 || s < 1) return fail(LFT_ERR_ARG, "bad argument");
+    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
+    const dim3 grid((unsigned)((A * w0 * s + 255) / 256), (unsigned)(A * h0 * s));
+    k_scene_integrate<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_patches, sr_scene, A, patch * s, stride * s, h0 * s, w0 * s, nv);
+    LFT_LAUNCH_OK("k_scene_integrate");
+    return 0;
+}
+
+// ---- dihedral transforms (lft_ensemble.cuh) ----
+static int dihedral_args(const void* in, const void* out, unsigned mask, int B, int H, int W, int* E, unsigned* blocks) {
+    if (!in || !out) return fail(LFT_ERR_ARG, "null pointer");
+    if (in == out) return fail(LFT_ERR_ARG, "the transforms do not work in place (in == out)");
+    if (mask == 0 || mask > 0xFFu) return fail(LFT_ERR_ARG, "mask 0x%x: one bit per dihedral code 0..7, at least one set", mask);
+    if (B < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "bad image batch (B=%d H=%d W=%d)", B, H, W);
+    *E = __builtin_popcount(mask);
+    const unsigned long long n = (unsigned long long)B * (unsigned long long)((H + DH_TILE - 1) / DH_TILE) * (unsigned long long)((W + DH_TILE - 1) / DH_TILE);
+    if (n * 8ull > 0x7fffffffull) return fail(LFT_ERR_SHAPE, "batch of %d images of %dx%d needs more than 2^31 blocks", B, H, W);
+    *blocks = (unsigned)n;
+    return 0;
+}
+int lft_dihedral_batch(const float* in, float* out, const int* codes, int B, int H, int W, void* stream) {
+    int E, rc; unsigned blocks;
+    if (!codes) return fail(LFT_ERR_ARG, "null pointer");
+    if ((rc = dihedral_args(in, out, 1u, B, H, W, &E, &blocks))) return rc;
+    k_dihedral<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, codes, 1u, 1, H, W);
+    LFT_LAUNCH_OK("k_dihedral");
+    return 0;
+}
+int lft_dihedral_expand(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream) {
+    int E, rc; unsigned blocks;
+    if ((rc = dihedral_args(in, out, mask, B, H, W, &E, &blocks))) return rc;
+    k_dihedral<<<blocks * (unsigned)E, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, nullptr, mask, E, H, W);
+    LFT_LAUNCH_OK("k_dihedral");
+    return 0;
+}
+int lft_dihedral_merge(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream) {
+    int E, rc; unsigned blocks;
+    if ((rc = dihedral_args(in, out, mask, B, H, W, &E, &blocks))) return rc;
+    k_dihedral_merge<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, mask, E, H, W);
+    LFT_LAUNCH_OK("k_dihedral_merge");
+    return 0;
+}
+int lft_scene_integrate_ens(const float* sr_variants, float* sr_scene, unsigned mask, int A, int h0, int w0, int patch, int stride, int s,
+                            void* stream) {
+    int nu, nv, rc;
+    if (!sr_variants || !sr_scene) return fail(LFT_ERR_ARG, "null pointer");
+    if (sr_variants == sr_scene) return fail(LFT_ERR_ARG, "the merge does not work in place (in == out)");
+    if (mask == 0 || mask > 0xFFu) return fail(LFT_ERR_ARG, "mask 0x%x: one bit per dihedral code 0..7, at least one set", mask);
+    if (A < 1 || s < 1) return fail(LFT_ERR_SHAPE, "bad scene (A=%d s=%d)", A, s);
+    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
+    // the variants are A*patch*s square mosaics by construction, so a transposing code needs no further shape check
+    const int S = stride * s, ts = (S + DH_TILE - 1) / DH_TILE;
+    const unsigned long long n = (unsigned long long)nu * nv * A * A * ts * ts;
+    if (n > 0x7fffffffull) return fail(LFT_ERR_SHAPE, "scene needs more than 2^31 blocks");
+    k_scene_integrate_ens<<<(unsigned)n, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_variants, sr_scene, mask, __builtin_popcount(mask),
+                                                                                    A, patch * s, S, h0 * s, w0 * s, nv);
+    LFT_LAUNCH_OK("k_scene_integrate_ens");
+    return 0;
+}
+
+// ================================================================================ metrics
+int lft_view_metrics_scratch_bytes(int B, int A, int h, int w, size_t* out_bytes) {
+    if (!out_bytes || B < 1 || A < 1 || h < 1 || w < 1) return fail(LFT_ERR_ARG, "bad argument");
+    const size_t ntiles = (size_t)((h + kMetTile - 1) / kMetTile) * ((w + kMetTile - 1) / kMetTile);
+    *out_bytes = (size_t)B * A * A * ntiles * 3 * sizeof(double);
+    return 0;
+}
+int lft_view_metrics(const float* label, const float* out, int B, int A, int h, int w, float ssim_range, float* psnr, float* ssim,
+                     void* scratch, void* stream) {
+    if (!label || !out || !psnr || !ssim || !scratch || B < 1 || A < 1) return fail(LFT_ERR_ARG, "bad argument");
+    if (h < 11 || w < 11) return fail(LFT_ERR_SHAPE, "views of %dx%d are smaller than the 11x11 SSIM window", h, w);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int ntiles = ((h + kMetTile - 1) / kMetTile) * ((w + kMetTile - 1) / kMetTile), nviews = B * A * A;
+    const double C1 = (0.01 * ssim_range) * (0.01 * ssim_range), C2 = (0.03 * ssim_range) * (0.03 * ssim_range);
+    k_view_metrics<<<dim3((unsigned)ntiles, (unsigned)nviews), 256, 0, st>>>(label, out, static_cast<double*>(scratch), A, h, w, C1, C2);
+    LFT_LAUNCH_OK("k_view_metrics");
+    k_view_metrics_final<<<blocks_for(nviews, 64), 64, 0, st>>>(static_cast<const double*>(scratch), nviews, ntiles, h, w, psnr, ssim);
+    LFT_LAUNCH_OK("k_view_metrics_final");
+    return 0;
+}
+int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
+                   const int* crops, int n_crops, int crop_h, int crop_w, const double* weights_h, const int* indices_h, int taps_h,
+                   const double* weights_w, const int* indices_w, int taps_w, float* hr, float* lr, void* stream) {
+    if (!crops || !weights_h || !indices_h || !weights_w || !indices_w || !hr || !lr) return fail(LFT_ERR_ARG, "lft_lf_prepare: null pointer");
+    if (int rc = lf_array_ok("lft_lf_prepare", LFT_ERR_ARG, lf, lf_class, U, V, H, W, C, strides)) return rc;
+    if (s != 2 && s != 4) return fail(LFT_ERR_ARG, "lft_lf_prepare: scale factor must be 2 or 4, got %d", s);
+    if (int rc = centre_views_ok("lft_lf_prepare", LFT_ERR_ARG, "the scripts' centre-view index", U, V, A)) return rc;
+    if (n_crops < 0 || crop_h < 1 || crop_w < 1 || crop_h > H || crop_w > W)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d crops of %d x %d in views of %d x %d", n_crops, crop_h, crop_w, H, W);
+    for (int i = 0; i < n_crops; ++i) {
+        const int y0 = crops[2 * i], x0 = crops[2 * i + 1];
+        if (y0 < 0 || x0 < 0 || y0 > H - crop_h || x0 > W - crop_w)
+            return fail(LFT_ERR_ARG, "lft_lf_prepare: crop %d at (%d, %d) of %d x %d is outside the %d x %d view", i, y0, x0, crop_h, crop_w, H, W);
+    }
+    if (taps_h < 1 || taps_w < 1 || taps_h > kPrepMaxTaps || taps_w > kPrepMaxTaps)
+        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kPrepMaxTaps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PrepArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s;
+    a.ch = crop_h; a.cw = crop_w; a.oh = (crop_h + s - 1) / s; a.ow = (crop_w + s - 1) / s; a.ph = taps_h; a.pw = taps_w;
+    a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w; a.hr = hr; a.lr = lr;
+    const int TO = kPrepTileHr / s;
+    const unsigned tiles = (unsigned)(((a.oh + TO - 1) / TO) * ((a.ow + TO - 1) / TO));
+    for (int n0 = 0; n0 < n_crops; n0 += kPrepCrops) {
+        const int nb = std::min(kPrepCrops, n_crops - n0);
+        PrepCrops c{};
+        for (int i = 0; i < nb; ++i) { c.y0[i] = crops[2 * (n0 + i)]; c.x0[i] = crops[2 * (n0 + i) + 1]; }
+        a.n0 = n0;
+        const dim3 grid(tiles, (unsigned)(A * A), (unsigned)nb);
+        by_lf_class(lf_class, [&](auto t) { k_lf_prepare<decltype(t)><<<grid, 256, 0, st>>>(a, c); return 0; });
+        LFT_LAUNCH_OK("k_lf_prepare");
+    }
+    return 0;
+}
+
+// ---- colour path (lft_colour.cuh) ----
+int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, float* y_out,
+                void* stream) {
+    if (!y_out) return fail(LFT_ERR_ARG, "lft_lf_luma: null pointer");
+    if (int rc = colour_lf_ok("lft_lf_luma", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
+    const long long blocks = ((long long)H * W + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "lft_lf_luma: views of %d x %d need more than 2^31 blocks", H, W);
+    LumaArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.H = H; a.W = W; a.y = y_out;
+    const dim3 grid((unsigned)blocks, (unsigned)(A * A));
+    by_lf_class(lf_class, [&](auto t) { k_lf_luma<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
+    LFT_LAUNCH_OK("k_lf_luma");
+    return 0;
+}
+
+int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
+                     const float* sr_y, const double* weights_h, const int* indices_h, int taps_h, const double* weights_w,
+                     const int* indices_w, int taps_w, const double* minv, void* out, int out_class, void* stream) {
+    if (!weights_h || !indices_h || !weights_w || !indices_w || !minv || !out) return fail(LFT_ERR_ARG, "lft_colour_merge: null pointer");
+    if (int rc = colour_lf_ok("lft_colour_merge", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
+    if (s != 2 && s != 4) return fail(LFT_ERR_SHAPE, "lft_colour_merge: scale factor must be 2 or 4, got %d", s);
+    if (taps_h < 1 || taps_w < 1 || taps_h > kColMaxTaps || taps_w > kColMaxTaps)
+        return fail(LFT_ERR_ARG, "lft_colour_merge: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kColMaxTaps);
+    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_colour_merge: output class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", out_class);
+    const long long tiles = (((long long)s * H + kColTile - 1) / kColTile) * (((long long)s * W + kColTile - 1) / kColTile);
+    if ((long long)s * H > 0x7fffffffLL || (long long)s * W > 0x7fffffffLL || tiles > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "lft_colour_merge: views of %d x %d at %dx need more than 2^31 blocks", H, W, s);
+    ColourArgs a{};
+    a.lf = lf;
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s; a.H = H; a.W = W; a.ph = taps_h; a.pw = taps_w;
+    a.sr_y = sr_y; a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w;
+    for (int i = 0; i < 9; ++i) a.minv[i] = minv[i];
+    a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
+    const dim3 grid((unsigned)tiles, (unsigned)(A * A));
+    by_lf_class(lf_class, [&](auto t) { k_colour_merge<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
+    LFT_LAUNCH_OK("k_colour_merge");
+    return 0;
+}
+
+// ---- synthetic refocus (lft_refocus.cuh) ----
+int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
+                int taps, void* out, int out_class, void* stream) {
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
+    if (int rc = windowed_lf_ok("lft_refocus", l, out_class, "output", 0, !out, "stacks")) return rc;
+    if (!l.tiles) return 0;                                         // an empty stack
+    RefocusArgs a{};
+    fill_windowed(a, l);
+    a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
+    const dim3 grid((unsigned)(l.tiles * D * B));
+    by_lf_class<false>(lf_class, [&](auto t) { refocus_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
+    LFT_LAUNCH_OK("k_refocus");
+    return 0;
+}
+
+// ---- disparity from a plane sweep (lft_disparity.cuh) ----
+// the floats of V [B, D, H, W] (and of m [B, D, H, W, C] behind it): 0 when they do not fit 2^40 bytes
+static size_t disparity_floats(int B, int D, int H, int W, int C, int flags, size_t* vol_floats) {
+    const double vol = (double)B * D * H * W, all = vol * (flags & LFT_DISPARITY_AIF ? 1 + C : 1);
+    if (all * 4.0 > 1099511627776.0) return 0;
+    *vol_floats = (size_t)B * D * H * W;
+    return *vol_floats * (size_t)(flags & LFT_DISPARITY_AIF ? 1 + C : 1);
+}
+int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_disparity: out_bytes is null");
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_disparity: %d channels (1 .. 4)", C);
+    if (D < 1) return fail(LFT_ERR_ARG, "lft_disparity: %d slopes", D);
+    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "lft_disparity: unknown flags 0x%x", flags);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_disparity: negative size in B = %d, views of %d x %d", B, H, W);
+    size_t vol = 0;
+    const size_t n = disparity_floats(B, D, H, W, C, flags, &vol);
+    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
+    *out_bytes = n * sizeof(float);
+    return 0;
+}
+int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
+                  const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
+                  float* cost, void* aif, int aif_class, void* stream) {
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
+    if (int rc = windowed_lf_ok("lft_disparity", l, aif_class, "all-in-focus", radius, !slopes || !scratch || !disparity || !confidence || !index, "sweeps"))
+        return rc;
+    if (!l.tiles) return 0;                                         // empty maps
+    const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
+    if (ptiles * B > 0x7fffffffLL) return too_many_blocks("lft_disparity", l, "sweeps");
+    size_t vol = 0;
+    if (!disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol))
+        return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_disparity: scratch must be 4-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SweepArgs s{};
+    fill_windowed(s, l);
+    s.vol = static_cast<float*>(scratch); s.stack = aif ? s.vol + vol : nullptr;
+    const dim3 grid((unsigned)(l.tiles * D * B));
+    by_lf_class<false>(lf_class, [&](auto t) { sweep_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
+    LFT_LAUNCH_OK("k_sweep_cost");
+    PickArgs p{};
+    p.vol = s.vol; p.stack = s.stack; p.slopes = slopes;
+    p.H = H; p.W = W; p.D = D; p.C = C; p.r = radius; p.tiles_x = (int)ptiles_x; p.tiles = (int)ptiles;
+    p.disparity = disparity; p.confidence = confidence; p.index = index; p.cost = cost; p.aif = aif;
+    p.aif_f32 = aif_class == LFT_LF_FLOAT32;
+    k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
+    LFT_LAUNCH_OK("k_disparity_pick");
+    return 0;
+}
+
+}  // extern "C"

@@ -10,6 +10,10 @@
 //   k_lf_loss_fold            : one workgroup adds the per-block partials in a fixed order and writes {total, P, E}.
 // No atomics: the same bits every run.  Every element offset is formed in 64 bits.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
 
 constexpr int kLossThreads = 256;
 constexpr int kLossMaxBlocks = 2048;            // beyond it the stencil pass strides over the mosaic; bounds the fold
@@ -188,3 +192,31 @@ __global__ __launch_bounds__(kLossThreads) void k_lf_loss_fold(const double* __r
         loss3[2] = (float)E;
     }
 }
+
+// L1 loss (reference LFT.py:269-277) and its gradient: loss = mean |sr - hr|; dsr = sign(sr - hr) * gscale.
+__global__ __launch_bounds__(256) void k_l1_partial(const float* __restrict__ sr, const float* __restrict__ hr, float* __restrict__ dsr,
+                                                    float gscale, long long n, float* __restrict__ part) {
+    __shared__ float red[256];
+    float s = 0.0f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float d = sr[i] - hr[i];
+        s += fabsf(d);
+        if (dsr) dsr[i] = d > 0.0f ? gscale : (d < 0.0f ? -gscale : 0.0f);
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+__global__ void k_l1_final(const float* __restrict__ part, int nb, float inv_n, float* __restrict__ loss) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        float s = 0.0f;
+        for (int i = 0; i < nb; ++i) s += part[i];
+        *loss = s * inv_n;
+    }
+}
+
+}  // namespace

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+namespace {
+
 constexpr int kMetTile = 16, kMetR = 5, kMetIn = kMetTile + 2 * kMetR;       // 16x16 outputs need a 26x26 input tile
 
 // part[(view*ntiles + tile)*3 + {0,1,2}] = sum of the SSIM map over the tile's interior pixels, sum of squared error
@@ -85,3 +87,5 @@ __global__ void k_view_metrics_final(const double* __restrict__ part, int nviews
     psnr[view] = (float)(10.0 * log10(range * range / (se / ((double)h * w))));
     ssim[view] = (float)(s / ((double)(h - 2 * kMetR) * (w - 2 * kMetR)));
 }
+
+}  // namespace

@@ -1,175 +1,28 @@
-// lft_api.hip -- C ABI of liblft_hip.so (see include/lft_hip.h): buffer layouts, weight packing plan,
-// kernel launches.  Host-side code only enqueues work on the caller's stream.
+// lft_network.hip -- the network in the C ABI of liblft_hip.so (include/lft_hip.h): the inference path (buffer layouts, weight
+// packing plan, stage functions, per-stage test entry points) and the fp32 training step (tape queries, forward, the backward
+// variants, gradient buckets, attention maps from the tape; the step itself is lft_train_host.cuh).  Host-side code only enqueues
+// work on the caller's stream.  The library's other units: lft_lightfield.hip, lft_objective.hip (lft_amd/_lib.py: UNITS).
 //
-// The library is built from this file as TWO translation units, only so that they compile in parallel; both get the same
-// compiler flags (COMMON_FLAGS + UNIT_FLAGS of lft_amd/_lib.py, where each flag's reason is written down):
-//   LFT_TU == 1   inference, scene tiling, metrics, data preparation, colour, refocus, disparity, debug entry points
-//   LFT_TU == 2   the fp32 training step, its losses and optimizer
-//   LFT_TU == 0   everything in one unit (tools, resource reports).
-// Every kernel and helper is local to its unit (anonymous namespace); the units share only the error buffer.
-#include "../../include/lft_hip.h"
-#include "../../include/lft_hip_test.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <cstdarg>
-#include <cstdio>
-#include <cmath>
-#include <map>
-#include <mutex>
-#include <set>
-#include <string>
-#include <algorithm>
-#include <type_traits>
-#include <utility>
-#include <vector>
-
-#ifndef LFT_TU
-#define LFT_TU 0
-#endif
-
-namespace {
-#include "lft_kernels_a.cuh"
-#include "lft_kernels_b.cuh"
-#include "lft_metrics.cuh"
-#include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
-#include "lft_train.cuh"     // training kernels; the fp32 inference path shares their LDS-tiled window attention
-#if LFT_TU != 1
+// Inference and training are ONE unit because hipcc's code for the fp32 inference kernels (k_conv64, k_ang, k_spa1, k_spa2,
+// k_up with T = float) depends on whether the training kernels, which instantiate the same fp32 helpers of lft_common.cuh, are
+// compiled in the same module: built apart, twelve of them come out with other instructions (tools/kernel_diff.py).
+#include "lft_pack_host.cuh"
+#include "lft_kernels_infer.cuh"
+#include "lft_win_attn.cuh"   // fp32: the LDS-tiled window attention of the training step
+#include "lft_train_host.cuh"
 #include "lft_attn_maps.cuh" // attention weights from the tape's Q | K (lft_train_attn_maps)
-#include "lft_optim.cuh"     // guarded Adam step: gradient statistics, skip / clip decision, update (lft_adam_step_guarded)
-#include "lft_loss.cuh"      // pixel + EPI-gradient loss with L1 / MSE / Charbonnier penalty (lft_lf_loss)
-#include "lft_ssim_loss.cuh" // structural term 1 - SSIM and its gradient, fp64 inside (lft_ssim_loss)
-#endif
-#if LFT_TU != 2
-#include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
-#include "lft_colour.cuh"    // colour path: RGB light field -> Y mosaic; SR Y + up-scaled chroma -> RGB views
-#include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
-#include "lft_disparity.cuh" // disparity: plane-sweep cost volume, windowed aggregation, winner-take-all (lft_disparity)
-#endif
-}  // namespace
 
-#if LFT_TU == 2
-extern thread_local char lft_g_err[512];
-#else
-__attribute__((visibility("hidden"))) thread_local char lft_g_err[512] = "";
-#endif
-#define g_err lft_g_err
+// the library's error buffer and profiler (declared in lft_host.cuh)
+char* lft_err_buf() {
+    static thread_local char err[kErrLen] = "";
+    return err;
+}
+LftProfiler& lft_prof() {
+    static thread_local LftProfiler prof;
+    return prof;
+}
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define LFT_HIP_OK(expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail((int)e_, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-// Optional per-kernel timing (lft_forward_profiled): an event is recorded on the launch stream after each kernel.
-struct Profiler {
-    bool on = false;
-    hipStream_t st = nullptr;
-    std::vector<hipEvent_t> ev;
-    std::vector<const char*> names;
-};
-thread_local Profiler g_prof;
-// Launch name with the call's shape appended ("k_lin:128>256", profiled runs only); interned, so the pointer stays valid.
-inline const char* prof_name(const char* plain, const char* fmt, ...) {
-    if (!g_prof.on) return plain;
-    static thread_local std::set<std::string> names;
-    char buf[96];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return names.insert(buf).first->c_str();
-}
-inline void prof_mark(const char* name) {
-    if (!g_prof.on) return;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, g_prof.st);
-    g_prof.ev.push_back(e);
-    g_prof.names.push_back(name);
-}
-
-#define LFT_LAUNCH_OK(name)                                                                  \
-    do {                                                                                     \
-        hipError_t e_ = hipGetLastError();                                                   \
-        if (e_ != hipSuccess) return fail((int)e_, "launch %s: %s", name, hipGetErrorString(e_)); \
-        prof_mark(name);                                                                     \
-    } while (0)
-// run() with an event recorded on st after every kernel it launches, then synchronised: the first max_records launches' names
-// and times go to names_out / ms_out, their number to *n_out.  run()'s error comes first, then the synchronisation's.
-template <typename Run> int run_profiled(hipStream_t st, int max_records, float* ms_out, const char** names_out, int* n_out, Run&& run) {
-    g_prof.on = true; g_prof.st = st; g_prof.ev.clear(); g_prof.names.clear();
-    prof_mark("start");
-    const int rc = run();
-    g_prof.on = false;
-    hipError_t e = hipStreamSynchronize(st);
-    int n = 0;
-    for (size_t i = 1; i < g_prof.ev.size() && n < max_records; ++i, ++n) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, g_prof.ev[i - 1], g_prof.ev[i]);
-        ms_out[n] = ms;
-        names_out[n] = g_prof.names[i];
-    }
-    for (hipEvent_t ev : g_prof.ev) (void)hipEventDestroy(ev);
-    g_prof.ev.clear(); g_prof.names.clear();
-    *n_out = n;
-    if (rc) return rc;
-    if (e != hipSuccess) return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
-    return 0;
-}
-
-constexpr int kLayers = 4;   // reference LFT.py:15
-
-// Compile-time dispatch: f(std::integral_constant<decltype(V), V>{}) for the V of Vs that equals the runtime value v, so that a
-// generic lambda can name the kernel variant, e.g. dispatch<true, false>(lm, [&](auto LM) { k<T, LM><<<...>>>(...); return 0; }).
-// Vs lists every value a caller passes; any other is an internal error.
-template <auto... Vs, typename V, typename F> int dispatch(V v, F&& f) {
-    int rc = 0;
-    if (((v == Vs && ((rc = f(std::integral_constant<decltype(Vs), Vs>{})), true)) || ...)) return rc;
-    return fail(LFT_ERR_ARG, "internal: no kernel variant for %d", (int)v);
-}
-template <int V> using int_c = std::integral_constant<int, V>;
-// f(T{}) with T the element type of precision `prec` (validated by make_dims beforehand).
-template <typename F> int by_prec(int prec, F&& f) {
-    if (prec == LFT_PREC_F32) return f(float{});
-    if (prec == LFT_PREC_BF16) return f(bf16_t{});
-    return f(f16_t{});
-}
-// f(T{}) with T the stored type of a light field of class `lf_class` (validated by the caller beforehand).  F64 = false: the caller
-// accepts LFT_LF_UINT8 and LFT_LF_FLOAT32 only, and no double variant of its kernel is built.
-template <bool F64 = true, typename F> int by_lf_class(int lf_class, F&& f) {
-    if (lf_class == LFT_LF_UINT8) return f(uint8_t{});
-    if constexpr (!F64) return f(float{});
-    else return lf_class == LFT_LF_FLOAT32 ? f(float{}) : f(double{});
-}
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Dims {
-    int B, A, V, h, w, hw, s, gp, gt, nchunk;
-    long long ntok;
-};
-
-int make_dims(int B, int A, int h, int w, int s, int prec, Dims* d) {
-    if (prec != LFT_PREC_F32 && prec != LFT_PREC_BF16 && prec != LFT_PREC_F16)
-        return fail(LFT_ERR_ARG, "prec must be LFT_PREC_F32, LFT_PREC_BF16 or LFT_PREC_F16, got %d", prec);
-    if (B < 1 || A < 1 || h < 1 || w < 1) return fail(LFT_ERR_SHAPE, "B, A, h, w must be positive (B=%d A=%d h=%d w=%d)", B, A, h, w);
-    if (s != 2 && s != 4) return fail(LFT_ERR_SHAPE, "scale factor must be 2 or 4, got %d", s);
-    if (A * A > 128) return fail(LFT_ERR_UNSUPPORTED, "angRes %d (A*A=%d views > 128) is not implemented in this build", A, A * A);
-    if ((long long)B * A * A * h * w > (1LL << 27)) return fail(LFT_ERR_SHAPE, "too many tokens");
-    d->B = B; d->A = A; d->V = A * A; d->h = h; d->w = w; d->hw = h * w; d->s = s;
-    d->gp = (s + 2) * (s + 2); d->gt = (d->gp + 31) / 32; d->nchunk = 2 * s * s;
-    d->ntok = (long long)B * d->V * d->hw;
-    return 0;
-}
 
 // Fragment counts per stream
 constexpr int kFragsConv = 72, kFragsAng = 64, kFragsSpa1 = 240, kFragsSpa1NoQ = 208, kFragsSpa2 = 176;
@@ -255,68 +108,10 @@ template <typename T, int CH = kSpaChunk> size_t lds_spa1(int w) {      // the t
 template <typename T> size_t lds_spa2() { return WRing<T, kSpaChunk, kNwSpa2>::LDS_BYTES + kLdsParams + kNwSpa2 * TileIO<4, T>::BYTES; }
 template <typename T> size_t lds_up() { return WRing<T, kUpChunk, kNwUp>::LDS_BYTES + kNwUp * TileIO<2, T>::BYTES; }
 template <typename T> size_t lds_ang() { return (size_t)kFragsAng * 1024 * FragInfo<T>::PIECES + kLdsParams + 4 * TileIO<2, T>::BYTES; }
-constexpr size_t kMaxLds = 160 * 1024;
-template <typename K> int allow_lds(K kernel, size_t bytes, const char* name) {
-    if (bytes > kMaxLds) return fail(LFT_ERR_SHAPE, "%s needs %zu B of LDS (> 160 KiB): view width too large for this build", name, bytes);
-    if (bytes <= 64 * 1024) return 0;
-    // The attribute is sticky per kernel: set it once per (kernel, size) so that steady-state forwards -- and a
-    // stream capture of them -- consist of kernel launches only.
-    // The attribute belongs to the (device, kernel) pair: a thread that drives two GPUs must set it on each.
-    struct Done { int dev; const void* fn; size_t bytes; };
-    static thread_local std::vector<Done> done;
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    int dev = 0;
-    LFT_HIP_OK(hipGetDevice(&dev));
-    for (const auto& d : done)
-        if (d.dev == dev && d.fn == fn && d.bytes >= bytes) return 0;
-    LFT_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    done.push_back(Done{dev, fn, bytes});
-    return 0;
-}
 
-template <typename P> P* at(const void* base, size_t off) { return reinterpret_cast<P*>(const_cast<char*>(static_cast<const char*>(base)) + off); }
-inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
-// ---------------------------------------------------------------------------- packing plan
-PackOp lin_op(const float* src, int row0, int nrows, int ld, int k0, int ksteps, int kmap, float scale, int kmul = 1, int kadd = 0) {
-    PackOp p{};
-    p.src = src; p.kind = 0; p.row0 = row0; p.nrows = nrows; p.ntiles = (nrows + 31) / 32; p.ld = ld;
-    p.kmul = kmul; p.kadd = kadd; p.k0 = k0; p.ksteps = ksteps; p.kmap = kmap; p.scale = scale; p.s = 0; p.frag0 = 0;
-    return p;
-}
 void conv_ops(std::vector<PackOp>& v, const float* w, int nout) {   // [nout][64][3][3] == [nout][576], k index c*9 + tap
     for (int tap = 0; tap < 9; ++tap)
         for (int ks = 0; ks < 4; ++ks) v.push_back(lin_op(w, 0, nout, 576, 16 * ks, 1, 0, 1.0f, 9, tap));
-}
-
-// The packing plan, LFT_PACK_MAXOPS operations per launch: launch(a, nf, total) enqueues the kernel `name` for the nf fragments of
-// batch a, which follow the `total` fragments of the batches before it.
-template <typename Launch>
-int pack_batches(std::vector<PackOp>& ops, int expect_frags, const char* name, Launch&& launch) {
-    int total = 0;
-    size_t i = 0;
-    while (i < ops.size()) {
-        PackArgs a{};
-        int nf = 0;
-        while (i < ops.size() && a.nops < LFT_PACK_MAXOPS) {
-            a.op[a.nops] = ops[i];
-            a.op[a.nops].frag0 = nf;
-            nf += ops[i].ntiles * ops[i].ksteps;
-            ++a.nops; ++i;
-        }
-        if (int rc = launch(a, nf, total)) return rc;
-        LFT_LAUNCH_OK(name);
-        total += nf;
-    }
-    if (total != expect_frags) return fail(LFT_ERR_ARG, "internal: stream has %d fragments, expected %d", total, expect_frags);
-    return 0;
-}
-template <typename T>
-int run_pack(std::vector<PackOp>& ops, T* dst, int expect_frags, hipStream_t st) {
-    return pack_batches(ops, expect_frags, "k_pack", [&](const PackArgs& a, int nf, int total) {
-        k_pack<T><<<nf, 64, 0, st>>>(a, dst + (size_t)total * 512);
-        return 0;
-    });
 }
 
 // Lane-major hand-off of the spatial tokens from k_spa1 to part B: every workgroup tile of k_spa1 must be full, and the bf16
@@ -470,13 +265,6 @@ int pack_impl(const Fwd& c, const float* const* P, void* packed) {
         if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_up), frags_up(d), st))) return rc;
     }
     return 0;
-}
-
-void launch_assemble(const float* lr, const float* g, float* out, int B, int A, int h, int w, int s, hipStream_t st, int gld = 0, unsigned* status = nullptr) {
-    const dim3 tg((unsigned)((A * w + 7) / 8) * (unsigned)((A * h + 7) / 8) * (unsigned)B);    // 8 x 8 LR mosaic pixels per workgroup; tile order: k_assemble_t
-    if (!gld) gld = (s + 2) * (s + 2);
-    if (s == 2) k_assemble_t<2><<<tg, 256, 0, st>>>(lr, g, out, B, A, h, w, gld, status);
-    else k_assemble_t<4><<<tg, 256, 0, st>>>(lr, g, out, B, A, h, w, gld, status);
 }
 
 // ---------------------------------------------------------------------------- stages
@@ -712,7 +500,8 @@ int kernel_time_impl(const Fwd& c, const char* name, const void* packed, void* w
     *ms_out = ms / (float)reps;
     return 0;
 }
-#include "lft_train_host.cuh"
+
+
 
 // The tape fields lft_train_tape_offset knows: top level, and per layer behind "ang<l>." / "spa<l>."
 template <typename S> struct TapeField { const char* name; size_t S::*member; };
@@ -729,87 +518,13 @@ template <typename S, size_t N> bool tape_field(const TapeField<S> (&table)[N], 
     return false;
 }
 
-#if LFT_TU != 2
-// ---- the light field [U,V,H,W,C] with five strides (data preparation, colour path); nothing is launched when a check fails ----
-// The array itself: pointers, stored class, sizes, strides.  `shape` is the code of a bad size: lft_lf_prepare has always answered
-// LFT_ERR_ARG there, the colour path LFT_ERR_SHAPE.
-int lf_array_ok(const char* who, int shape, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides) {
-    if (!lf || !strides) return fail(LFT_ERR_ARG, "%s: null pointer", who);
-    if (lf_class != LFT_LF_UINT8 && lf_class != LFT_LF_FLOAT32 && lf_class != LFT_LF_FLOAT64)
-        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8, LFT_LF_FLOAT32 or LFT_LF_FLOAT64, got %d", who, lf_class);
-    if (U < 1 || V < 1 || H < 1 || W < 1 || C < 3)
-        return fail(shape, "%s: light field [%d,%d,%d,%d,%d] needs positive sizes and at least 3 channels", who, U, V, H, W, C);
-    for (int i = 0; i < 5; ++i)
-        if (strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, strides[i]);
-    return 0;
-}
-// Its centre A x A views.  `index`: what the message calls the centre-view index ("the scripts' centre-view index" for
-// lft_lf_prepare, which follows the MATLAB scripts).  A separate step because lft_lf_prepare checks its scale factor in between.
-int centre_views_ok(const char* who, int shape, const char* index, int U, int V, int A) {
-    if (A < 1 || A > U || A > V) return fail(shape, "%s: angRes %d outside the %d x %d views", who, A, U, V);
-    if ((U - A) % 2 || (V - A) % 2)
-        return fail(shape, "%s: U-A = %d and V-A = %d must be even (%s 0.5*(U-A+2) is not an integer)", who, U - A, V - A, index);
-    return 0;
-}
-// what lft_lf_luma and lft_colour_merge ask of the light field: both of the above, and a grid with one y block per view
-int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A) {
-    if (int rc = lf_array_ok(who, LFT_ERR_SHAPE, lf, lf_class, U, V, H, W, C, strides)) return rc;
-    if (int rc = centre_views_ok(who, LFT_ERR_SHAPE, "the centre-view index", U, V, A)) return rc;
-    if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
-    return 0;
-}
-// ---- B light fields [B,A,A,H,W,C] read in place through six strides, one 32 x 32 output tile per workgroup (refocus, disparity) ----
-struct WindowedLf {         // the arguments lft_refocus and lft_disparity share, and what windowed_lf_ok derives from them
-    const void* lf; int lf_class, B, A, H, W, C; const long long* strides; const void* table; int D, taps;
-    long long tiles_x, tiles;           // kRfTile tiles of a view; tiles == 0: an empty shape, no work and no error
-};
-int too_many_blocks(const char* who, const WindowedLf& l, const char* work) {
-    return fail(LFT_ERR_SHAPE, "%s: %d %s of %d slopes over views of %d x %d need more than 2^31 blocks", who, l.B, work, l.D, l.H, l.W);
-}
-// Every check the two entry points share, in the order they have always made them; nothing is launched when one fails.  The caller's
-// own arguments sit in between: `out_class` (called `out_name` in the message), `radius` (lft_disparity only; 0 for lft_refocus),
-// `own_null` (one of the caller's other pointers is null).  `work`: what too_many_blocks calls the B batches.
-int windowed_lf_ok(const char* who, WindowedLf& l, int out_class, const char* out_name, int radius, bool own_null, const char* work) {
-    if (l.lf_class != LFT_LF_UINT8 && l.lf_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "%s: light-field class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", who, l.lf_class);
-    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "%s: %s class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", who, out_name, out_class);
-    if (l.A < 1 || l.A > 4096) return fail(LFT_ERR_ARG, "%s: angRes %d outside 1 .. 4096", who, l.A);      // A*A records indexed in int
-    if (l.C < 1 || l.C > 4) return fail(LFT_ERR_ARG, "%s: %d channels (1 .. 4)", who, l.C);
-    if (l.taps != 1 && l.taps != 2 && l.taps != 4) return fail(LFT_ERR_ARG, "%s: %d taps (1, 2 or 4)", who, l.taps);
-    if (l.D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, l.D);
-    if (radius < 0 || radius > kDpMaxR) return fail(LFT_ERR_ARG, "%s: radius %d outside 0 .. %d", who, radius, kDpMaxR);
-    if (l.B < 0 || l.H < 0 || l.W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, views of %d x %d", who, l.B, l.H, l.W);
-    l.tiles_x = l.tiles = 0;
-    if (l.B == 0 || l.H == 0 || l.W == 0) return 0;                 // nothing to read or write
-    if (!l.lf || !l.strides || !l.table || own_null) return fail(LFT_ERR_ARG, "%s: null pointer", who);
-    for (int i = 0; i < 6; ++i)
-        if (l.strides[i] < 0) return fail(LFT_ERR_ARG, "%s: stride %d is negative (%lld)", who, i, l.strides[i]);
-    if ((double)(l.H - 1) * (double)l.strides[3] + (double)(l.W - 1) * (double)l.strides[4] + (double)(l.C - 1) * (double)l.strides[5] > 2147483647.0)
-        return fail(LFT_ERR_SHAPE, "%s: a view of %d x %d x %d with these strides spans more than 2^31 elements", who, l.H, l.W, l.C);
-    l.tiles_x = ((long long)l.W + kRfTile - 1) / kRfTile;
-    l.tiles = l.tiles_x * (((long long)l.H + kRfTile - 1) / kRfTile);
-    if (l.tiles * l.D * l.B > 0x7fffffffLL) return too_many_blocks(who, l, work);
-    return 0;
-}
-// the members RefocusArgs and SweepArgs have in common
-template <typename Args> void fill_windowed(Args& a, const WindowedLf& l) {
-    a.lf = l.lf;
-    for (int i = 0; i < 3; ++i) a.st[i] = l.strides[i];
-    a.sy = (int)l.strides[3]; a.sx = (int)l.strides[4]; a.sc = (int)l.strides[5];
-    a.A = l.A; a.H = l.H; a.W = l.W; a.D = l.D; a.tiles_x = (int)l.tiles_x; a.tiles = (int)l.tiles;
-    a.table = static_cast<const int*>(l.table);
-}
-#endif
-
 }  // namespace
 
 // ================================================================================ C ABI
 extern "C" {
 
-#if LFT_TU != 2
 int lft_version(void) { return LFT_ABI_VERSION; }
-const char* lft_last_error(void) { return g_err; }
+const char* lft_last_error(void) { return lft_err_buf(); }
 
 int lft_packed_bytes(int A, int h, int w, int s, int prec, size_t* out_bytes) {
     Fwd c;
@@ -1000,89 +715,6 @@ int lft_debug_clear_stamps(void) {
 }
 #endif
 
-static int scene_counts(int h0, int w0, int patch, int stride, int* nu, int* nv) {
-    if (h0 < 1 || w0 < 1 || patch < 1 || stride < 1 || stride > patch) return fail(LFT_ERR_SHAPE, "bad scene tiling (h0=%d w0=%d patch=%d stride=%d)", h0, w0, patch, stride);
-    const int bdr = (patch - stride) / 2, h = h0 + 2 * bdr, w = w0 + 2 * bdr;
-    if (h < patch || w < patch) return fail(LFT_ERR_SHAPE, "view %dx%d is smaller than one patch after extension", h0, w0);
-    *nu = (h - patch) / stride + ((h - patch) % stride ? 2 : 1);
-    *nv = (w - patch) / stride + ((w - patch) % stride ? 2 : 1);
-    return 0;
-}
-int lft_scene_counts(int h0, int w0, int patch, int stride, int* num_u, int* num_v) {
-    if (!num_u || !num_v) return fail(LFT_ERR_ARG, "null pointer");
-    return scene_counts(h0, w0, patch, stride, num_u, num_v);
-}
-int lft_scene_divide(const float* scene, float* patches, int A, int h0, int w0, int patch, int stride, void* stream) {
-    int nu, nv, rc;
-    if (!scene || !patches || A < 1) return fail(LFT_ERR_ARG, "bad argument");
-    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
-    const dim3 grid((unsigned)((A * patch + 255) / 256), (unsigned)(A * patch), (unsigned)(nu * nv));
-    k_scene_divide<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(scene, patches, A, h0, w0, patch, stride, nv);
-    LFT_LAUNCH_OK("k_scene_divide");
-    return 0;
-}
-int lft_scene_integrate(const float* sr_patches, float* sr_scene, int A, int h0, int w0, int patch, int stride, int s, void* stream) {
-    int nu, nv, rc;
-    if (!sr_patches || !sr_scene || A < 1 || s < 1) return fail(LFT_ERR_ARG, "bad argument");
-    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
-    const dim3 grid((unsigned)((A * w0 * s + 255) / 256), (unsigned)(A * h0 * s));
-    k_scene_integrate<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_patches, sr_scene, A, patch * s, stride * s, h0 * s, w0 * s, nv);
-    LFT_LAUNCH_OK("k_scene_integrate");
-    return 0;
-}
-
-// ---- dihedral transforms (lft_ensemble.cuh) ----
-static int dihedral_args(const void* in, const void* out, unsigned mask, int B, int H, int W, int* E, unsigned* blocks) {
-    if (!in || !out) return fail(LFT_ERR_ARG, "null pointer");
-    if (in == out) return fail(LFT_ERR_ARG, "the transforms do not work in place (in == out)");
-    if (mask == 0 || mask > 0xFFu) return fail(LFT_ERR_ARG, "mask 0x%x: one bit per dihedral code 0..7, at least one set", mask);
-    if (B < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "bad image batch (B=%d H=%d W=%d)", B, H, W);
-    *E = __builtin_popcount(mask);
-    const unsigned long long n = (unsigned long long)B * (unsigned long long)((H + DH_TILE - 1) / DH_TILE) * (unsigned long long)((W + DH_TILE - 1) / DH_TILE);
-    if (n * 8ull > 0x7fffffffull) return fail(LFT_ERR_SHAPE, "batch of %d images of %dx%d needs more than 2^31 blocks", B, H, W);
-    *blocks = (unsigned)n;
-    return 0;
-}
-int lft_dihedral_batch(const float* in, float* out, const int* codes, int B, int H, int W, void* stream) {
-    int E, rc; unsigned blocks;
-    if (!codes) return fail(LFT_ERR_ARG, "null pointer");
-    if ((rc = dihedral_args(in, out, 1u, B, H, W, &E, &blocks))) return rc;
-    k_dihedral<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, codes, 1u, 1, H, W);
-    LFT_LAUNCH_OK("k_dihedral");
-    return 0;
-}
-int lft_dihedral_expand(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream) {
-    int E, rc; unsigned blocks;
-    if ((rc = dihedral_args(in, out, mask, B, H, W, &E, &blocks))) return rc;
-    k_dihedral<<<blocks * (unsigned)E, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, nullptr, mask, E, H, W);
-    LFT_LAUNCH_OK("k_dihedral");
-    return 0;
-}
-int lft_dihedral_merge(const float* in, float* out, unsigned mask, int B, int H, int W, void* stream) {
-    int E, rc; unsigned blocks;
-    if ((rc = dihedral_args(in, out, mask, B, H, W, &E, &blocks))) return rc;
-    k_dihedral_merge<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(in, out, mask, E, H, W);
-    LFT_LAUNCH_OK("k_dihedral_merge");
-    return 0;
-}
-int lft_scene_integrate_ens(const float* sr_variants, float* sr_scene, unsigned mask, int A, int h0, int w0, int patch, int stride, int s,
-                            void* stream) {
-    int nu, nv, rc;
-    if (!sr_variants || !sr_scene) return fail(LFT_ERR_ARG, "null pointer");
-    if (sr_variants == sr_scene) return fail(LFT_ERR_ARG, "the merge does not work in place (in == out)");
-    if (mask == 0 || mask > 0xFFu) return fail(LFT_ERR_ARG, "mask 0x%x: one bit per dihedral code 0..7, at least one set", mask);
-    if (A < 1 || s < 1) return fail(LFT_ERR_SHAPE, "bad scene (A=%d s=%d)", A, s);
-    if ((rc = scene_counts(h0, w0, patch, stride, &nu, &nv))) return rc;
-    // the variants are A*patch*s square mosaics by construction, so a transposing code needs no further shape check
-    const int S = stride * s, ts = (S + DH_TILE - 1) / DH_TILE;
-    const unsigned long long n = (unsigned long long)nu * nv * A * A * ts * ts;
-    if (n > 0x7fffffffull) return fail(LFT_ERR_SHAPE, "scene needs more than 2^31 blocks");
-    k_scene_integrate_ens<<<(unsigned)n, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_variants, sr_scene, mask, __builtin_popcount(mask),
-                                                                                    A, patch * s, S, h0 * s, w0 * s, nv);
-    LFT_LAUNCH_OK("k_scene_integrate_ens");
-    return 0;
-}
-
 int lft_mfma_selftest(const float* Am, const float* Bm, const float* W2, float* C, float* D, int prec, void* stream) {
     if (!Am || !Bm || !W2 || !C || !D) return fail(LFT_ERR_ARG, "null pointer");
     if (prec != LFT_PREC_F32 && prec != LFT_PREC_BF16 && prec != LFT_PREC_F16) return fail(LFT_ERR_ARG, "bad prec %d", prec);
@@ -1091,173 +723,7 @@ int lft_mfma_selftest(const float* Am, const float* Bm, const float* W2, float* 
     return 0;
 }
 
-// ================================================================================ metrics
-int lft_view_metrics_scratch_bytes(int B, int A, int h, int w, size_t* out_bytes) {
-    if (!out_bytes || B < 1 || A < 1 || h < 1 || w < 1) return fail(LFT_ERR_ARG, "bad argument");
-    const size_t ntiles = (size_t)((h + kMetTile - 1) / kMetTile) * ((w + kMetTile - 1) / kMetTile);
-    *out_bytes = (size_t)B * A * A * ntiles * 3 * sizeof(double);
-    return 0;
-}
-int lft_view_metrics(const float* label, const float* out, int B, int A, int h, int w, float ssim_range, float* psnr, float* ssim,
-                     void* scratch, void* stream) {
-    if (!label || !out || !psnr || !ssim || !scratch || B < 1 || A < 1) return fail(LFT_ERR_ARG, "bad argument");
-    if (h < 11 || w < 11) return fail(LFT_ERR_SHAPE, "views of %dx%d are smaller than the 11x11 SSIM window", h, w);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int ntiles = ((h + kMetTile - 1) / kMetTile) * ((w + kMetTile - 1) / kMetTile), nviews = B * A * A;
-    const double C1 = (0.01 * ssim_range) * (0.01 * ssim_range), C2 = (0.03 * ssim_range) * (0.03 * ssim_range);
-    k_view_metrics<<<dim3((unsigned)ntiles, (unsigned)nviews), 256, 0, st>>>(label, out, static_cast<double*>(scratch), A, h, w, C1, C2);
-    LFT_LAUNCH_OK("k_view_metrics");
-    k_view_metrics_final<<<blocks_for(nviews, 64), 64, 0, st>>>(static_cast<const double*>(scratch), nviews, ntiles, h, w, psnr, ssim);
-    LFT_LAUNCH_OK("k_view_metrics_final");
-    return 0;
-}
-int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
-                   const int* crops, int n_crops, int crop_h, int crop_w, const double* weights_h, const int* indices_h, int taps_h,
-                   const double* weights_w, const int* indices_w, int taps_w, float* hr, float* lr, void* stream) {
-    if (!crops || !weights_h || !indices_h || !weights_w || !indices_w || !hr || !lr) return fail(LFT_ERR_ARG, "lft_lf_prepare: null pointer");
-    if (int rc = lf_array_ok("lft_lf_prepare", LFT_ERR_ARG, lf, lf_class, U, V, H, W, C, strides)) return rc;
-    if (s != 2 && s != 4) return fail(LFT_ERR_ARG, "lft_lf_prepare: scale factor must be 2 or 4, got %d", s);
-    if (int rc = centre_views_ok("lft_lf_prepare", LFT_ERR_ARG, "the scripts' centre-view index", U, V, A)) return rc;
-    if (n_crops < 0 || crop_h < 1 || crop_w < 1 || crop_h > H || crop_w > W)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d crops of %d x %d in views of %d x %d", n_crops, crop_h, crop_w, H, W);
-    for (int i = 0; i < n_crops; ++i) {
-        const int y0 = crops[2 * i], x0 = crops[2 * i + 1];
-        if (y0 < 0 || x0 < 0 || y0 > H - crop_h || x0 > W - crop_w)
-            return fail(LFT_ERR_ARG, "lft_lf_prepare: crop %d at (%d, %d) of %d x %d is outside the %d x %d view", i, y0, x0, crop_h, crop_w, H, W);
-    }
-    if (taps_h < 1 || taps_w < 1 || taps_h > kPrepMaxTaps || taps_w > kPrepMaxTaps)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kPrepMaxTaps);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    PrepArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
-    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s;
-    a.ch = crop_h; a.cw = crop_w; a.oh = (crop_h + s - 1) / s; a.ow = (crop_w + s - 1) / s; a.ph = taps_h; a.pw = taps_w;
-    a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w; a.hr = hr; a.lr = lr;
-    const int TO = kPrepTileHr / s;
-    const unsigned tiles = (unsigned)(((a.oh + TO - 1) / TO) * ((a.ow + TO - 1) / TO));
-    for (int n0 = 0; n0 < n_crops; n0 += kPrepCrops) {
-        const int nb = std::min(kPrepCrops, n_crops - n0);
-        PrepCrops c{};
-        for (int i = 0; i < nb; ++i) { c.y0[i] = crops[2 * (n0 + i)]; c.x0[i] = crops[2 * (n0 + i) + 1]; }
-        a.n0 = n0;
-        const dim3 grid(tiles, (unsigned)(A * A), (unsigned)nb);
-        by_lf_class(lf_class, [&](auto t) { k_lf_prepare<decltype(t)><<<grid, 256, 0, st>>>(a, c); return 0; });
-        LFT_LAUNCH_OK("k_lf_prepare");
-    }
-    return 0;
-}
 
-// ---- colour path (lft_colour.cuh) ----
-int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, float* y_out,
-                void* stream) {
-    if (!y_out) return fail(LFT_ERR_ARG, "lft_lf_luma: null pointer");
-    if (int rc = colour_lf_ok("lft_lf_luma", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
-    const long long blocks = ((long long)H * W + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "lft_lf_luma: views of %d x %d need more than 2^31 blocks", H, W);
-    LumaArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
-    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.H = H; a.W = W; a.y = y_out;
-    const dim3 grid((unsigned)blocks, (unsigned)(A * A));
-    by_lf_class(lf_class, [&](auto t) { k_lf_luma<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
-    LFT_LAUNCH_OK("k_lf_luma");
-    return 0;
-}
-
-int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, int C, const long long* strides, int A, int s,
-                     const float* sr_y, const double* weights_h, const int* indices_h, int taps_h, const double* weights_w,
-                     const int* indices_w, int taps_w, const double* minv, void* out, int out_class, void* stream) {
-    if (!weights_h || !indices_h || !weights_w || !indices_w || !minv || !out) return fail(LFT_ERR_ARG, "lft_colour_merge: null pointer");
-    if (int rc = colour_lf_ok("lft_colour_merge", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
-    if (s != 2 && s != 4) return fail(LFT_ERR_SHAPE, "lft_colour_merge: scale factor must be 2 or 4, got %d", s);
-    if (taps_h < 1 || taps_w < 1 || taps_h > kColMaxTaps || taps_w > kColMaxTaps)
-        return fail(LFT_ERR_ARG, "lft_colour_merge: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kColMaxTaps);
-    if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
-        return fail(LFT_ERR_ARG, "lft_colour_merge: output class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", out_class);
-    const long long tiles = (((long long)s * H + kColTile - 1) / kColTile) * (((long long)s * W + kColTile - 1) / kColTile);
-    if ((long long)s * H > 0x7fffffffLL || (long long)s * W > 0x7fffffffLL || tiles > 0x7fffffffLL)
-        return fail(LFT_ERR_SHAPE, "lft_colour_merge: views of %d x %d at %dx need more than 2^31 blocks", H, W, s);
-    ColourArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
-    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s; a.H = H; a.W = W; a.ph = taps_h; a.pw = taps_w;
-    a.sr_y = sr_y; a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w;
-    for (int i = 0; i < 9; ++i) a.minv[i] = minv[i];
-    a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
-    const dim3 grid((unsigned)tiles, (unsigned)(A * A));
-    by_lf_class(lf_class, [&](auto t) { k_colour_merge<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
-    LFT_LAUNCH_OK("k_colour_merge");
-    return 0;
-}
-
-// ---- synthetic refocus (lft_refocus.cuh) ----
-int lft_refocus(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
-                int taps, void* out, int out_class, void* stream) {
-    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
-    if (int rc = windowed_lf_ok("lft_refocus", l, out_class, "output", 0, !out, "stacks")) return rc;
-    if (!l.tiles) return 0;                                         // an empty stack
-    RefocusArgs a{};
-    fill_windowed(a, l);
-    a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;
-    const dim3 grid((unsigned)(l.tiles * D * B));
-    by_lf_class<false>(lf_class, [&](auto t) { refocus_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
-    LFT_LAUNCH_OK("k_refocus");
-    return 0;
-}
-
-// ---- disparity from a plane sweep (lft_disparity.cuh) ----
-// the floats of V [B, D, H, W] (and of m [B, D, H, W, C] behind it): 0 when they do not fit 2^40 bytes
-static size_t disparity_floats(int B, int D, int H, int W, int C, int flags, size_t* vol_floats) {
-    const double vol = (double)B * D * H * W, all = vol * (flags & LFT_DISPARITY_AIF ? 1 + C : 1);
-    if (all * 4.0 > 1099511627776.0) return 0;
-    *vol_floats = (size_t)B * D * H * W;
-    return *vol_floats * (size_t)(flags & LFT_DISPARITY_AIF ? 1 + C : 1);
-}
-int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_disparity: out_bytes is null");
-    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_disparity: %d channels (1 .. 4)", C);
-    if (D < 1) return fail(LFT_ERR_ARG, "lft_disparity: %d slopes", D);
-    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "lft_disparity: unknown flags 0x%x", flags);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_disparity: negative size in B = %d, views of %d x %d", B, H, W);
-    size_t vol = 0;
-    const size_t n = disparity_floats(B, D, H, W, C, flags, &vol);
-    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
-    *out_bytes = n * sizeof(float);
-    return 0;
-}
-int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
-                  const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
-                  float* cost, void* aif, int aif_class, void* stream) {
-    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
-    if (int rc = windowed_lf_ok("lft_disparity", l, aif_class, "all-in-focus", radius, !slopes || !scratch || !disparity || !confidence || !index, "sweeps"))
-        return rc;
-    if (!l.tiles) return 0;                                         // empty maps
-    const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
-    if (ptiles * B > 0x7fffffffLL) return too_many_blocks("lft_disparity", l, "sweeps");
-    size_t vol = 0;
-    if (!disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol))
-        return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
-    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_disparity: scratch must be 4-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    SweepArgs s{};
-    fill_windowed(s, l);
-    s.vol = static_cast<float*>(scratch); s.stack = aif ? s.vol + vol : nullptr;
-    const dim3 grid((unsigned)(l.tiles * D * B));
-    by_lf_class<false>(lf_class, [&](auto t) { sweep_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
-    LFT_LAUNCH_OK("k_sweep_cost");
-    PickArgs p{};
-    p.vol = s.vol; p.stack = s.stack; p.slopes = slopes;
-    p.H = H; p.W = W; p.D = D; p.C = C; p.r = radius; p.tiles_x = (int)ptiles_x; p.tiles = (int)ptiles;
-    p.disparity = disparity; p.confidence = confidence; p.index = index; p.cost = cost; p.aif = aif;
-    p.aif_f32 = aif_class == LFT_LF_FLOAT32;
-    k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
-    LFT_LAUNCH_OK("k_disparity_pick");
-    return 0;
-}
-
-#endif  // LFT_TU != 2
-#if LFT_TU != 1
 // ================================================================================ training (fp32)
 int lft_train_tape_bytes(int B, int A, int h, int w, int s, size_t* out_bytes) {
     Dims d; int rc;
@@ -1427,249 +893,6 @@ int lft_train_grad_bucket(int s, int bucket, size_t* first_float, size_t* n_floa
     grad_bucket_range(s, bucket, first_float, n_floats);
     return 0;
 }
-int lft_l1_loss(const float* sr, const float* hr, long long n, float* dsr, float gscale, float* loss, float* scratch1024, void* stream) {
-    if (!sr || !hr || !loss || !scratch1024 || n < 1) return fail(LFT_ERR_ARG, "bad argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nb = (int)std::min<long long>(1024, (n + 255) / 256);
-    k_l1_partial<<<nb, 256, 0, st>>>(sr, hr, dsr, gscale, n, scratch1024);
-    LFT_LAUNCH_OK("k_l1_partial");
-    k_l1_final<<<1, 64, 0, st>>>(scratch1024, nb, 1.0f / (float)n, loss);
-    LFT_LAUNCH_OK("k_l1_final");
-    return 0;
-}
-// ---- light-field loss (lft_loss.cuh) ----
-namespace {
-// do the n floats at a and the n floats at b share memory / does a gradient image (may be null) share memory with either input
-inline bool meets(const float* a, const float* b, long long n) { return (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n); }
-inline bool overlaps(const float* dsr, const float* sr, const float* hr, long long n) { return dsr && (meets(dsr, sr, n) || meets(dsr, hr, n)); }
-struct LossShape { long long n; int nblocks[2]; };     // stencil blocks of the scalar and of the 16-byte path
-int loss_shape(int B, int A, int H, int W, LossShape* s) {
-    if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "sizes must be positive, got B %d A %d H %d W %d", B, A, H, W);
-    if ((long long)A * A > 128) return fail(LFT_ERR_SHAPE, "A * A = %lld views, at most 128 are supported", (long long)A * A);
-    s->n = (long long)B * A * A * H * W;
-    for (int v = 0; v < 2; ++v)
-        s->nblocks[v] = (int)std::min<long long>(kLossMaxBlocks, (s->n / (v ? 4 : 1) + kLossThreads - 1) / kLossThreads);
-    return 0;
-}
-}  // namespace
-int lft_lf_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
-    LossShape s;
-    if (int rc = loss_shape(B, A, H, W, &s)) return rc;
-    *out_bytes = (size_t)s.nblocks[0] * kLossSums * sizeof(double);
-    return 0;
-}
-int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, int penalty, float eps, float w_pix, float w_epi,
-                float* dsr, float gscale, float* loss3, void* scratch, void* stream) {
-    if (!sr || !hr || !loss3 || !scratch) return fail(LFT_ERR_ARG, "null pointer");
-    if ((((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)dsr | (uintptr_t)loss3) & 3) || ((uintptr_t)scratch & 7))
-        return fail(LFT_ERR_ARG, "sr, hr, dsr and loss3 must be 4-byte aligned, scratch 8-byte aligned");
-    if (penalty != LFT_LOSS_L1 && penalty != LFT_LOSS_MSE && penalty != LFT_LOSS_CHARBONNIER) return fail(LFT_ERR_ARG, "unknown penalty %d", penalty);
-    if (penalty == LFT_LOSS_CHARBONNIER && !(eps > 0.0f)) return fail(LFT_ERR_ARG, "the Charbonnier eps must be positive, got %g", (double)eps);
-    if (!(w_pix >= 0.0f) || !(w_epi >= 0.0f)) return fail(LFT_ERR_ARG, "weights must not be negative or NaN, got %g and %g", (double)w_pix, (double)w_epi);
-    if (w_pix == 0.0f && w_epi == 0.0f) return fail(LFT_ERR_ARG, "both weights are zero");
-    if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "gscale is NaN");
-    LossShape s;
-    if (int rc = loss_shape(B, A, H, W, &s)) return rc;
-    if (overlaps(dsr, sr, hr, s.n)) return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the stencil reads neighbours, in place would race");
-    const double n = (double)s.n;
-    const double nt[4] = {n / W * (W - 1), n / H * (H - 1), n / A * (A - 1), n / A * (A - 1)};      // n_x, n_y, n_v, n_u: exact in double
-    int T = 0;
-    for (double c : nt) T += c > 0.0;
-    LossFoldArgs f = {};
-    f.inv_n = 1.0 / n; f.inv_T = T ? 1.0 / T : 0.0; f.w_pix = (double)w_pix; f.w_epi = (double)w_epi;
-    float ct[4];
-    for (int t = 0; t < 4; ++t) {
-        f.inv_nt[t] = nt[t] > 0.0 ? 1.0 / nt[t] : 0.0;
-        ct[t] = (float)((double)w_epi * f.inv_T * f.inv_nt[t]);
-    }
-    const LossArgs a = {B, A, H, W, eps * eps, (float)((double)w_pix * f.inv_n), ct[0], ct[1], ct[2], ct[3], gscale};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* part = static_cast<double*>(scratch);
-    const bool vec = ((long long)A * W) % 4 == 0 && !(((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)dsr) & 15);
-    const int nb = s.nblocks[vec];
-    const bool grad = dsr != nullptr;
-    if (int rc = dispatch<LFT_LOSS_L1, LFT_LOSS_MSE, LFT_LOSS_CHARBONNIER>(penalty, [&](auto PEN) {
-            return dispatch<true, false>(vec, [&](auto VEC4) {
-                return dispatch<true, false>(grad, [&](auto GRAD) {
-                    k_lf_loss<PEN, VEC4 ? 4 : 1, GRAD><<<nb, kLossThreads, 0, st>>>(sr, hr, dsr, a, part);
-                    return 0;
-                });
-            });
-        })) return rc;
-    LFT_LAUNCH_OK("k_lf_loss");
-    k_lf_loss_fold<<<1, kLossThreads, 0, st>>>(part, nb, f, loss3);
-    LFT_LAUNCH_OK("k_lf_loss_fold");
-    return 0;
-}
-// ---- structural loss term (lft_ssim_loss.cuh) ----
-namespace {
-struct SsimShape { long long n, nblocks, views; int tiles_x, ntiles; };
-int ssim_shape(int B, int A, int H, int W, SsimShape* s) {
-    if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "sizes must be positive, got B %d A %d H %d W %d", B, A, H, W);
-    if (H < 11 || W < 11) return fail(LFT_ERR_SHAPE, "views of %dx%d are smaller than the 11x11 SSIM window", H, W);
-    s->tiles_x = (W + kSsimTile - 1) / kSsimTile;
-    const long long ntiles = (long long)s->tiles_x * ((H + kSsimTile - 1) / kSsimTile);
-    s->views = (long long)B * A * A;
-    s->n = s->views * H * W;
-    s->nblocks = s->views * ntiles;
-    if (s->nblocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%lld tiles, more than one launch holds", s->nblocks);
-    s->ntiles = (int)ntiles;
-    return 0;
-}
-}  // namespace
-int lft_ssim_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
-    SsimShape s;
-    if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
-    *out_bytes = (size_t)s.nblocks * sizeof(double);
-    return 0;
-}
-int lft_ssim_loss(const float* sr, const float* hr, int B, int A, int H, int W, float ssim_range, float w_ssim,
-                  float* dsr, float gscale, int accumulate, float* total, float* ssim_out, void* scratch, void* stream) {
-    if (!sr || !hr || !total || !ssim_out || !scratch) return fail(LFT_ERR_ARG, "null pointer");
-    if ((((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)dsr | (uintptr_t)total | (uintptr_t)ssim_out) & 3) || ((uintptr_t)scratch & 7))
-        return fail(LFT_ERR_ARG, "sr, hr, dsr, total and ssim_out must be 4-byte aligned, scratch 8-byte aligned");
-    if (!(ssim_range > 0.0f) || !std::isfinite(ssim_range)) return fail(LFT_ERR_ARG, "ssim_range must be positive and finite, got %g", (double)ssim_range);
-    if (!(w_ssim > 0.0f) || !std::isfinite(w_ssim)) return fail(LFT_ERR_ARG, "w_ssim must be positive and finite, got %g", (double)w_ssim);
-    if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "gscale is NaN");
-    if (accumulate != 0 && accumulate != 1) return fail(LFT_ERR_ARG, "accumulate must be 0 or 1, got %d", accumulate);
-    SsimShape s;
-    if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
-    if (overlaps(dsr, sr, hr, s.n)) return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the windows read neighbours, in place would race");
-    const double R = (double)ssim_range, count = (double)s.views * (H - 2 * kSsimR) * (W - 2 * kSsimR);
-    SsimArgs a = {};
-    a.A = A; a.H = H; a.W = W; a.tiles_x = s.tiles_x; a.ntiles = s.ntiles; a.accumulate = accumulate;
-    a.C1 = (0.01 * R) * (0.01 * R); a.C2 = (0.03 * R) * (0.03 * R);                  // as lft_view_metrics forms them
-    a.k = -(double)gscale * (double)w_ssim / count;                                   // Q = 1 - S
-    const SsimFoldArgs f = {1.0 / count, (double)w_ssim, accumulate};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* part = static_cast<double*>(scratch);
-    if (dsr) k_ssim_loss<true><<<(unsigned)s.nblocks, kSsimThreads, 0, st>>>(sr, hr, dsr, a, part);
-    else k_ssim_loss<false><<<(unsigned)s.nblocks, kSsimThreads, 0, st>>>(sr, hr, dsr, a, part);
-    LFT_LAUNCH_OK("k_ssim_loss");
-    k_ssim_loss_fold<<<1, kSsimThreads, 0, st>>>(part, s.nblocks, f, total, ssim_out);
-    LFT_LAUNCH_OK("k_ssim_loss_fold");
-    return 0;
-}
-int lft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
-                  int step, float gscale, float weight_decay, void* stream) {
-    if (!p || !g || !m || !v || n < 1 || step < 1 || weight_decay < 0.0f) return fail(LFT_ERR_ARG, "bad argument");
-    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step)), bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));   // in double, as torch.optim.Adam
-    k_adam<<<blocks_for(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2, gscale, weight_decay);
-    LFT_LAUNCH_OK("k_adam");
-    return 0;
-}
 
-// ---- guarded Adam step (lft_optim.cuh) ----
-namespace {
-// Host memory of the guard blocks lft_guard_init wrote: what lft_adam_step_guarded needs to size its launches and to refuse a
-// foreign block or another n without reading device memory.  Bounded: the oldest entry goes when a 257th block is initialised.
-struct GuardHost { long long n; int nseg, nblocks; unsigned long long seq; };
-constexpr size_t kGuardHostMax = 256;
-std::mutex g_guard_mu;
-std::map<const void*, GuardHost> g_guards;
-unsigned long long g_guard_seq = 0;
-// what lft_guard_init remembered of the block at `guard` (to *h, which may be null), or the refusal of a block it never saw
-int find_guard(const void* guard, GuardHost* h) {
-    std::lock_guard<std::mutex> lock(g_guard_mu);
-    auto it = g_guards.find(guard);
-    if (it == g_guards.end()) return fail(LFT_ERR_ARG, "guard block %p was not initialised by lft_guard_init", guard);
-    if (h) *h = it->second;
-    return 0;
-}
-}  // namespace
 
-int lft_guard_bytes(int nseg, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
-    if (nseg < 1 || nseg > kGuardMaxSeg) return fail(LFT_ERR_ARG, "nseg %d outside 1..%d", nseg, kGuardMaxSeg);
-    *out_bytes = sizeof(GuardBlock) + (size_t)(kGuardMaxChunks + nseg) * sizeof(GuardPart);
-    return 0;
-}
-int lft_guard_init(void* guard, const lft_segment* segs, int nseg, long long n, long long steps_applied0, void* stream) {
-    if (!guard || !segs) return fail(LFT_ERR_ARG, "null pointer");
-    if ((uintptr_t)guard & 15) return fail(LFT_ERR_ARG, "the guard block must be 16-byte aligned");
-    if (nseg < 1 || nseg > kGuardMaxSeg) return fail(LFT_ERR_ARG, "nseg %d outside 1..%d", nseg, kGuardMaxSeg);
-    if (n < 1) return fail(LFT_ERR_SHAPE, "n must be positive, got %lld", n);
-    if (steps_applied0 < 0) return fail(LFT_ERR_ARG, "steps_applied0 must not be negative, got %lld", steps_applied0);
-    GuardInitArgs a = {};
-    long long off = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (segs[i].first != off || segs[i].count < 1 || segs[i].count > n - off)
-            return fail(LFT_ERR_SHAPE, "segment %d (first %lld, count %lld) does not continue the tiling of [0, %lld) at %lld", i,
-                        segs[i].first, segs[i].count, n, off);
-        a.count[i] = segs[i].count;
-        if (segs[i].trainable) a.trainable[i >> 5] |= 1u << (i & 31);
-        off += segs[i].count;
-    }
-    if (off != n) return fail(LFT_ERR_SHAPE, "the %d segments cover [0, %lld), not [0, %lld)", nseg, off, n);
-    a.n = n; a.steps0 = steps_applied0; a.nseg = nseg;
-    a.per = kGuardChunk;                                            // floats per block; larger only to bound the number of partials
-    if ((n + a.per - 1) / a.per > kGuardMaxChunks) a.per = ((n + kGuardMaxChunks - 1) / kGuardMaxChunks + 1023) / 1024 * 1024;
-    int nblocks = 0;
-    for (int i = 0; i < nseg; ++i) nblocks += (int)((a.count[i] + a.per - 1) / a.per);
-    if (nblocks > kGuardMaxChunks + nseg) return fail(LFT_ERR_SHAPE, "internal: %d blocks for %d segments", nblocks, nseg);
-    k_guard_init<<<1, kGuardMaxSeg, 0, static_cast<hipStream_t>(stream)>>>(static_cast<GuardBlock*>(guard), a);
-    LFT_LAUNCH_OK("k_guard_init");
-    std::lock_guard<std::mutex> lock(g_guard_mu);
-    g_guards[guard] = GuardHost{n, nseg, nblocks, ++g_guard_seq};
-    if (g_guards.size() > kGuardHostMax) {
-        auto oldest = g_guards.begin();
-        for (auto it = g_guards.begin(); it != g_guards.end(); ++it)
-            if (it->second.seq < oldest->second.seq) oldest = it;
-        g_guards.erase(oldest);
-    }
-    return 0;
-}
-int lft_adam_step_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
-                          float gscale, float weight_decay, float max_norm, void* guard, void* stream) {
-    if (!p || !g || !m || !v || !guard) return fail(LFT_ERR_ARG, "null pointer");
-    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) return fail(LFT_ERR_ARG, "p, g, m, v must be 4-byte aligned");
-    if (weight_decay < 0.0f) return fail(LFT_ERR_ARG, "weight decay must not be negative");
-    if (std::isnan(max_norm)) return fail(LFT_ERR_ARG, "max_norm is NaN (<= 0 or +inf switches clipping off)");
-    GuardHost h;
-    if (int rc = find_guard(guard, &h)) return rc;
-    if (n != h.n) return fail(LFT_ERR_SHAPE, "n = %lld, but the guard block was initialised for %lld", n, h.n);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    GuardBlock* gb = static_cast<GuardBlock*>(guard);
-    const int clip = max_norm > 0.0f && !std::isinf(max_norm);
-    k_grad_stats<<<h.nblocks, kGuardThreads, 0, st>>>(g, gb);
-    LFT_LAUNCH_OK("k_grad_stats");
-    k_guard_final<<<1, kGuardThreads, 0, st>>>(gb, gscale, max_norm, clip, beta1, beta2);
-    LFT_LAUNCH_OK("k_guard_final");
-    k_adam_guarded<<<h.nblocks, kGuardThreads, 0, st>>>(p, g, m, v, gb, lr, beta1, beta2, eps, gscale, weight_decay);
-    LFT_LAUNCH_OK("k_adam_guarded");
-    return 0;
-}
-int lft_guard_read(const void* guard, void* stream, lft_guard_report* host) {
-    if (!guard || !host) return fail(LFT_ERR_ARG, "null pointer");
-    if (int rc = find_guard(guard, nullptr)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    LFT_HIP_OK(hipMemcpyAsync(host, guard, sizeof(lft_guard_report), hipMemcpyDeviceToHost, st));   // the report is the block's first member
-    LFT_HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-int lft_ema_update(float* ema, const float* p, long long n, float decay, int warmup, long long step, const void* guard, void* stream) {
-    if (!ema || !p) return fail(LFT_ERR_ARG, "null pointer");
-    if (((uintptr_t)ema | (uintptr_t)p) & 3) return fail(LFT_ERR_ARG, "ema and p must be 4-byte aligned");
-    if (n < 1) return fail(LFT_ERR_ARG, "n must be positive, got %lld", n);
-    if (meets(ema, p, n)) return fail(LFT_ERR_ARG, "ema and p overlap");
-    if (!(decay >= 0.0f && decay < 1.0f)) return fail(LFT_ERR_ARG, "decay %g outside [0, 1)", (double)decay);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!guard) {
-        if (step < 1) return fail(LFT_ERR_ARG, "step counts from 1, got %lld", step);
-        const long long nchunks = (n + kGuardChunk - 1) / kGuardChunk;
-        k_ema_plain<<<(int)std::min<long long>(nchunks, 65536), kGuardThreads, 0, st>>>(ema, p, n, decay, warmup != 0, step);
-        LFT_LAUNCH_OK("k_ema_plain");
-        return 0;
-    }
-    GuardHost h;
-    if (int rc = find_guard(guard, &h)) return rc;
-    if (n != h.n) return fail(LFT_ERR_ARG, "n = %lld, but the guard block was initialised for %lld", n, h.n);
-    k_ema_guarded<<<h.nblocks, kGuardThreads, 0, st>>>(ema, p, static_cast<const GuardBlock*>(guard), decay, warmup != 0);
-    LFT_LAUNCH_OK("k_ema_guarded");
-    return 0;
-}
-
-#endif  // LFT_TU != 1
 }  // extern "C"

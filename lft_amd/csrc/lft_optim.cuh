@@ -1,3 +1,9 @@
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
+
 // lft_optim.cuh -- the guarded Adam step (lft_adam_step_guarded): gradient statistics, the skip / clip decision and the update,
 // three launches on one stream with no host round trip, so that a non-finite gradient or an exploding norm is dealt with on the
 // device and the call is graph-capturable (Adam's step counter lives in the guard block, not in a host scalar).
@@ -283,3 +289,19 @@ __global__ __launch_bounds__(kGuardThreads) void k_ema_plain(float* __restrict__
         ema_range(ema, p, lo, hi, a, threadIdx.x);
     }
 }
+
+// Adam (torch.optim.Adam defaults used by the reference, train.py:77-83: betas, eps, weight_decay 0), one flat
+// fp32 buffer of all parameters: p -= lr_t * m_hat / (sqrt(v_hat) + eps).  bc1 = 1 - b1^t, bc2 = 1 - b2^t.
+__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                       long long n, float lr, float b1, float b2, float eps, float bc1, float bc2, float gscale, float wd) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float gi = g[i] * gscale + wd * p[i];                        // torch.optim.Adam weight_decay: L2 term added to the gradient
+    const float mi = b1 * m[i] + (1.0f - b1) * gi;
+    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+    p[i] -= (lr / bc1) * (mi / denom);
+}
+
+}  // namespace

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+namespace {
+
 constexpr int kPrepCrops = 96;       // crop origins per launch, passed by value in the kernel arguments
 constexpr int kPrepSpan = 56;        // staged Y region: at most kPrepSpan rows x kPrepSpan columns (32 + 18 taps + slack)
 constexpr int kPrepTileHr = 32;      // HR extent of a tile; LR tile = 32 / s
@@ -127,3 +129,5 @@ __global__ __launch_bounds__(256) void k_lf_prepare(PrepArgs a, PrepCrops crops)
         a.hr[row * ((size_t)a.A * a.cw) + (size_t)v * a.cw + c] = (float)V.y(r, c);
     }
 }
+
+}  // namespace

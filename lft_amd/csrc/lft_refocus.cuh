@@ -25,6 +25,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "lft_common.cuh"
+
+namespace {
 
 constexpr int kRfTile = 32;          // output tile
 constexpr int kRfRec = 12;           // dwords per table record (lft_refocus_record of include/lft_hip.h)
@@ -189,3 +192,5 @@ inline void (*refocus_kernel(int C, int taps))(RefocusArgs) {
                                                  {k_refocus<T, 4, 1>, k_refocus<T, 4, 2>, k_refocus<T, 4, 4>}};
     return k[C - 1][taps == 4 ? 2 : taps - 1];
 }
+
+}  // namespace

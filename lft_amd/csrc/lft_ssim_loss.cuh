@@ -15,6 +15,10 @@
 // (3 x 26x16 fp64) reuse the moment rows.  Rows of 26 and 16 doubles are contiguous in a lane's neighbourhood: a wave's 8-byte reads
 // walk consecutive addresses, which the 64-bank 8-byte read path serves without conflicts.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
 
 constexpr int kSsimTile = 16, kSsimR = 5;
 constexpr int kSsimC = kSsimTile + 2 * kSsimR;      // 26 window centres per side reach the tile's pixels
@@ -151,3 +155,5 @@ __global__ __launch_bounds__(kSsimThreads) void k_ssim_loss_fold(const double* _
         *total = f.accumulate ? (float)((double)*total + term) : (float)term;
     }
 }
+
+}  // namespace

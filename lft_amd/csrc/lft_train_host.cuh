@@ -1,11 +1,14 @@
-// lft_train_host.cuh -- host orchestration of the fp32 training step (included inside lft_api.hip's anonymous
-// namespace): tape layout, forward with saved activations, backward into one flat gradient buffer.
+// lft_train_host.cuh -- host orchestration of the fp32 training step (its entry points: lft_network.hip): tape layout,
+// forward with saved activations, backward into one flat gradient buffer.
 //
 // Counterpart of autograd over reference model/LFT.py:52-83 as driven by train.py:89-107.  Parameter indices follow
 // lft_amd/params.py:param_table (the reference's registration order); the flat gradient buffer holds the 78 gradients
 // back to back in that order, so a data-parallel job needs ONE all-reduce per step.
 #pragma once
+#include "lft_pack_host.cuh"
 #include "lft_train.cuh"
+
+namespace {
 
 // ---- parameter indices ----
 constexpr int P_CONV0 = 0, P_CONV = 1, P_LAYER0 = 4, P_PER_LAYER = 18, P_UP0 = 76, P_UP3 = 77;
@@ -790,3 +793,5 @@ BwdSizes bwd_sizes(const Dims& d) {
     last = d; last_sz = sz;
     return sz;
 }
+
+}  // namespace

@@ -81,7 +81,7 @@ def resolve(policy: Policy) -> Dict[str, str]:
 
 
 def lane_major(h: int, w: int) -> bool:
-    """The 16-bit kernels' choice of the k_spa1 -> k_spa_b hand-off (lft_api.hip:tok_lane_major)."""
+    """The 16-bit kernels' choice of the k_spa1 -> k_spa_b hand-off (lft_network.hip:tok_lane_major)."""
     return (h * w) % 128 == 0 and w % 32 == 0
 
 

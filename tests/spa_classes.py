@@ -2,7 +2,7 @@
 
 The front-end convolutions, k_spa1, k_spa_b / k_win_attn_lds + k_spa2 and k_up choose tiles, hand-off layouts and LDS ring chunks
 from the view size (h, w) and the precision.  This module re-derives those choices from the constants of lft_amd/csrc
-(lft_api.hip: tok_lane_major, launch_spa1, lds_conv64, lds_conv64_lr, lds_spa1, allow_lds; lft_kernels_a.cuh: ConvIn, LrStage;
+(lft_network.hip: tok_lane_major, launch_spa1, lds_conv64, lds_conv64_lr, lds_spa1; lft_host.cuh: allow_lds; lft_kernels_a.cuh: ConvIn, LrStage;
 lft_common.cuh: WRing, TileIO), so that every view-size case of the parity tests can ASSERT the class it was chosen for: a later
 change of a constant then fails the case's table instead of silently moving it into a class another case already covers.
 tests/test_spa_classes.py pins the thresholds to values worked out by hand from the headers.

@@ -344,7 +344,7 @@ def test_forward_vs_oracle_big(big):
 
 
 # ---------------------------------------------------------------------------------------------------- the width limit
-# The conv input tile in LDS grows with the view width; allow_lds (lft_api.hip) refuses what no longer fits into the 160 KiB of a
+# The conv input tile in LDS grows with the view width; allow_lds (lft_host.cuh) refuses what no longer fits into the 160 KiB of a
 # CU, on the host, before anything is launched.  Widest accepted view: 75 columns in fp32 (k_conv64), 347 in the 16-bit precisions
 # (k_conv64_lr); k_spa1 accepts more (155 / 471: tests/test_spa_classes.py), so the weights still pack at these widths.
 WIDE_H = 3
@@ -395,7 +395,7 @@ def test_too_wide_view_is_refused(prec):
 
 # ---------------------------------------------------------------------------------------------------- beyond the grid cap
 def ang_positions_per_sweep(V, prec):
-    """Positions one launch of the angular block covers before its workgroups loop: lft_api.hip, ang_block / ang_multi and lds_ang
+    """Positions one launch of the angular block covers before its workgroups loop: lft_network.hip, ang_block / ang_multi and lds_ang
     re-derived -- grid = min(ceil(positions / per workgroup), 256 * max(1, 160 KiB / LDS per workgroup))."""
     esz = 4 if prec == "fp32" else 2
     fb = 1024 * (2 if prec == "fp32" else 1)                 # bytes of one weight / K / V fragment

@@ -70,7 +70,7 @@ def test_stale_library_and_changed_flags_are_noticed(monkeypatch):
     change of the compiler flags -- which live in _lib.py, not in a source file -- makes needs_build() true."""
     _lib.build()
     assert not _lib.needs_build()
-    monkeypatch.setitem(_lib.UNIT_FLAGS, 1, ["-fno-slp-vectorize", "-DSOMETHING_ELSE"])
+    monkeypatch.setattr(_lib, "COMMON_FLAGS", _lib.COMMON_FLAGS + ["-DSOMETHING_ELSE"])
     assert _lib.needs_build()
     monkeypatch.undo()
     assert not _lib.needs_build()
@@ -161,7 +161,7 @@ def isa_env(tmp_path_factory):
 
 
 def test_no_asm_loaded_register_is_read_before_its_wait(isa_env):
-    """Both units assembled with the product flags (no GPU needed): a register filled by an inline-asm global load must not be
+    """Every unit assembled with the product flags (no GPU needed): a register filled by an inline-asm global load must not be
     read -- hipcc copies such registers to set up tied asm operands -- before the counted s_waitcnt that guards it
     (tools/asm_load_hazards.py; the first k_linr did exactly that and passed every test in fp32)."""
     import subprocess
@@ -187,7 +187,7 @@ def test_lds_dma_pipelines_are_covered_by_counted_waits_and_barriers(isa_env):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "0 LDS-DMA protocol violation(s)" in r.stdout
     isa = isa_env["LFT_ISA_DIR"]
-    lines = open(os.path.join(isa, "hz1.s")).read().split("\n")
+    lines = open(os.path.join(isa, _lib.INFERENCE_UNIT + ".s")).read().split("\n")
     start = next(i for i, l in enumerate(lines) if l.startswith("_ZN12_GLOBAL__N_17k_spa_bIDF16bLb0ELb1ELb0E"))
     n = 0
     for i in range(start, len(lines)):
@@ -198,6 +198,24 @@ def test_lds_dma_pipelines_are_covered_by_counted_waits_and_barriers(isa_env):
             lines[i] = lines[i].replace(m.group(0), "vmcnt(%d)" % (int(m.group(1)) + 1))
             n += 1
     assert n >= 10
-    open(os.path.join(isa, "hz1_mut.s"), "w").write("\n".join(lines))
-    r = subprocess.run([sys.executable, tool, os.path.join(isa, "hz1_mut.s"), "k_spa_bIDF16bLb0ELb1ELb0E"], capture_output=True, text=True)
+    open(os.path.join(isa, "spa_b_mut.s"), "w").write("\n".join(lines))
+    r = subprocess.run([sys.executable, tool, os.path.join(isa, "spa_b_mut.s"), "k_spa_bIDF16bLb0ELb1ELb0E"], capture_output=True, text=True)
     assert r.returncode == 1 and "USE of" in r.stdout, r.stdout[-2000:]
+
+
+def test_every_kernel_is_emitted_by_one_unit_except_the_shared_ones(isa_env):
+    """A unit emits the kernels of the headers it includes, so each unit of the library includes only what it launches from (the
+    listings of the hazard tests above are re-used): the kernel symbols found in more than one unit's listing are exactly
+    _lib.SHARED_KERNELS, the kernels two units really launch -- and those are few."""
+    import re
+    found = {}
+    for unit, path in _lib.listings(isa_env["LFT_ISA_DIR"], reuse=True).items():
+        for sym in re.findall(r"^\s*\.amdhsa_kernel (\w+)", open(path, errors="replace").read(), flags=re.M):
+            found.setdefault(sym, []).append(unit)
+    assert {tuple(units) for units in found.values()} >= {(u,) for u in _lib.UNITS} and len(found) > 200, "the listings were not read"
+    twice = {sym: units for sym, units in found.items() if len(units) > 1}
+    unnamed = {sym: units for sym, units in twice.items() if not any(frag in sym for frag in _lib.SHARED_KERNELS)}
+    assert not unnamed, unnamed
+    unseen = [frag for frag in _lib.SHARED_KERNELS if sum(frag in sym for sym in twice) != 1]
+    assert not unseen, unseen
+    assert len(twice) == len(_lib.SHARED_KERNELS) <= 6

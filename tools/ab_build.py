@@ -21,7 +21,7 @@ for name, flags in variants:
     if os.path.exists(so) and not build_only:
         continue
     try:
-        _lib.compile_and_link("/opt/rocm/bin/hipcc", so, extra=[f for f in flags.split(",") if f])     # the library's own two-unit build + the variant's flags
+        _lib.compile_and_link("/opt/rocm/bin/hipcc", so, extra=[f for f in flags.split(",") if f])     # the library's own build (every unit) + the variant's flags
     except _lib.LftError as e:
         raise SystemExit(f"build of {name} failed\n{str(e)[-2000:]}")
 if build_only:

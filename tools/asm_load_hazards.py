@@ -9,10 +9,9 @@ the N youngest (vmcnt retires in issue order).  A register written by an ASM loa
 in the queue and appears as a source operand of any later instruction is reported.
 
   tools/asm_load_hazards.py file.s [kernel-name-substring ...]
-  tools/asm_load_hazards.py --build [substring ...]      both units of the library, product flags"""
+  tools/asm_load_hazards.py --build [substring ...]      every unit of the library, product flags (listings <unit>.s)"""
 import os
 import re
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,12 +98,8 @@ def main():
     if args and args[0] == "--build":
         sys.path.insert(0, ROOT)
         from lft_amd import _lib
-        os.makedirs(ISA_DIR, exist_ok=True)
         bad = []
-        for unit in (1, 2):
-            out = os.path.join(ISA_DIR, f"hz{unit}.s")
-            subprocess.run(["/opt/rocm/bin/hipcc", *_lib.COMMON_FLAGS, *_lib.UNIT_FLAGS[unit], f"-DLFT_TU={unit}", "--cuda-device-only", "-S",
-                            os.path.join(_lib.CSRC, "lft_api.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
+        for out in _lib.listings(ISA_DIR).values():
             bad += check(out, args[1:])
     else:
         bad = check(args[0], args[1:])

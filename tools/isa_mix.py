@@ -4,7 +4,8 @@ other VALU, SALU, LDS, vector-memory, waits and barriers between a kernel's labe
 which for these straight-line (fully unrolled) kernels is close to what one wave executes.
 
   tools/isa_mix.py file.s [substring ...]        kernels whose demangled name contains every substring
-  tools/isa_mix.py --build [substring ...]       compile the inference unit with the product flags first (to _build/isa/)
+  tools/isa_mix.py --build [substring ...]       compile the inference unit with the product flags first (to _build/isa/);
+                                                 --unit NAME: another unit of lft_amd/_lib.py UNITS;  -D... goes to hipcc
   tools/isa_mix.py --phases [substring ...]      the same build with -DLFT_EXPERIMENT -DLFT_ISA_MARKS: every LFT_STAMP(n) of a
                                                  kernel becomes a mark in the listing and the counts are given per phase
                                                  (the instructions between mark n and the next one; "pre" = before the first)
@@ -20,14 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ISA_DIR = os.environ.get("LFT_ISA_DIR") or os.path.join(ROOT, "_build", "isa")
 
 
-def build(extra=()):
+def build(unit, extra=()):
     sys.path.insert(0, ROOT)
     from lft_amd import _lib
     os.makedirs(ISA_DIR, exist_ok=True)
-    out = os.path.join(ISA_DIR, "tu1.s")
-    cmd = ["/opt/rocm/bin/hipcc", *_lib.COMMON_FLAGS, *_lib.UNIT_FLAGS[1], "-DLFT_TU=1", "--cuda-device-only", "-S",
-           os.path.join(_lib.CSRC, "lft_api.hip"), "-o", out] + [a for a in sys.argv[1:] if a.startswith("-D")] + list(extra)
-    subprocess.run(cmd, check=True)
+    out = os.path.join(ISA_DIR, f"mix_{unit or _lib.INFERENCE_UNIT}.s")
+    cmds = _lib.unit_commands("/opt/rocm/bin/hipcc", "listing", lambda u: out, [a for a in sys.argv[1:] if a.startswith("-D")] + list(extra))
+    subprocess.run(cmds[unit or _lib.INFERENCE_UNIT], check=True)
     return out
 
 
@@ -75,11 +75,16 @@ def classify(op):
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("-D")]
+    unit = None
+    if "--unit" in args:
+        i = args.index("--unit")
+        unit = args[i + 1]
+        del args[i:i + 2]
     phases = bool(args) and args[0] == "--phases"
     if phases:
-        path, subs = build(["-DLFT_EXPERIMENT", "-DLFT_ISA_MARKS", "-Wno-pass-failed"]), args[1:]
+        path, subs = build(unit, ["-DLFT_EXPERIMENT", "-DLFT_ISA_MARKS", "-Wno-pass-failed"]), args[1:]
     elif args and args[0] == "--build":
-        path, subs = build(), args[1:]
+        path, subs = build(unit), args[1:]
     else:
         path, subs = args[0], args[1:]
     names = {}

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Compile lft_api.hip for gfx950 and print per-kernel register / spill / occupancy / static LDS figures (extra arguments go to hipcc)."""
+"""Compile every unit of the library for gfx950 with the product flags (lft_amd/_lib.py) and print per-kernel register / spill /
+occupancy / static LDS figures (extra arguments go to hipcc)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
-                      os.path.join(ROOT, "lft_amd/csrc/lft_api.hip"), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:],
-                     capture_output=True, text=True).stderr
+sys.path.insert(0, ROOT)
+from lft_amd import _lib
+cmds = _lib.unit_commands("/opt/rocm/bin/hipcc", "device", lambda unit: "/dev/null", ["-c", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:])
+procs = [subprocess.Popen(c, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True) for c in cmds.values()]
+out = "".join(p.communicate()[1] for p in procs)
 cur = None
 rows = {}
 for line in out.splitlines():

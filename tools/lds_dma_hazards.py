@@ -18,10 +18,10 @@ Checked, for every slot:
 Reported per kernel as well: global_load_lds instructions outside any noted fill (run-time ring positions in loops: not modelled).
 
   tools/lds_dma_hazards.py file.s [kernel-name-substring ...]
-  tools/lds_dma_hazards.py --build [substring ...]      both units of the library, product flags"""
+  tools/lds_dma_hazards.py --build [substring ...]      every unit of the library, product flags (listings <unit>.s;
+                                                        LFT_HAZARD_REUSE=1: take the listings already there)"""
 import os
 import re
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,13 +136,7 @@ def main():
     if args and args[0] == "--build":
         sys.path.insert(0, ROOT)
         from lft_amd import _lib
-        os.makedirs(ISA_DIR, exist_ok=True)
-        for unit in (1, 2):
-            out = os.path.join(ISA_DIR, f"hz{unit}.s")
-            if not os.environ.get("LFT_HAZARD_REUSE") or not os.path.exists(out):
-                subprocess.run(["/opt/rocm/bin/hipcc", *_lib.COMMON_FLAGS, *_lib.UNIT_FLAGS[unit], f"-DLFT_TU={unit}", "--cuda-device-only", "-S",
-                                os.path.join(_lib.CSRC, "lft_api.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
-            paths.append(out)
+        paths = list(_lib.listings(ISA_DIR, reuse=bool(os.environ.get("LFT_HAZARD_REUSE"))).values())
         filters = args[1:]
     else:
         paths, filters = [args[0]], args[1:]

@@ -1,18 +1,18 @@
 #!/usr/bin/env python3
 """Diagnostic: build liblft_hip with -DLFT_EXPERIMENT, run one spatial block, print mean cycles between the
 LFT_STAMP() points of k_spa1 / k_spa2 (wave 0 of each workgroup).  GPU box only; never quote its run time."""
-import ctypes, os, subprocess, sys
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 # LFT_STAMPS_SO: a library built beforehand with the product flags + -DLFT_EXPERIMENT (hipcc cross-compiles in the build container:
-#   python tools/ab_build.py --build stamps:-DLFT_EXPERIMENT   ->  ab_so/liblft_stamps.so); otherwise it is built here, on GPU time.
+#   python tools/ab_build.py --build stamps:-DLFT_EXPERIMENT   ->  ab_so/liblft_stamps.so); otherwise it is built here, on GPU time,
+# the same way: every unit with the product flags and -DLFT_EXPERIMENT.
+from lft_amd import _lib
 so = os.environ.get("LFT_STAMPS_SO")
 if not so:
     so = os.path.join(ROOT, "gpurun_out", "liblft_hip_stamps.so")
     os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DLFT_EXPERIMENT",
-                           os.path.join(ROOT, "lft_amd", "csrc", "lft_api.hip"), "-o", so])
-from lft_amd import _lib
+    _lib.compile_and_link("/opt/rocm/bin/hipcc", so, ["-DLFT_EXPERIMENT"])
 _lib.LIB_PATH = so
 import numpy as np, torch
 from lft_amd.params import deterministic_state
