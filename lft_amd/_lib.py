@@ -170,18 +170,21 @@ def _ctype(ctype: str, where: str):
 
 
 def _prototypes(header: str) -> dict:
-    """{name: (restype, [argtypes])} of every `int lft_...(...);` and `const char* lft_...(...);` of a header (one parameter =
-    type + name, or `void` for none)."""
+    """{name: (restype, [argtypes], the last parameter's name)} of every `int lft_...(...);` and `const char* lft_...(...);` of a
+    header (one parameter = type + name, or `void` for none)."""
     sigs = {}
     for res, name, params in re.findall(r"^(int|const char\*)\s+(lft_\w+)\s*\(([^)]*)\)\s*;", _header_text(header), flags=re.M):
-        args = [] if params.strip() == "void" else [re.sub(r"\w+\s*$", "", p) for p in params.split(",")]
-        sigs[name] = (_ctype(res, name), [_ctype(a, name) for a in args])
+        args = [] if params.strip() == "void" else [re.match(r"(.*?)(\w+)\s*$", p, flags=re.S).groups() for p in params.split(",")]
+        sigs[name] = (_ctype(res, name), [_ctype(a, name) for a, _ in args], args[-1][1] if args else None)
     return sigs
 
 
 _SCALARS = {"int": c_int, "unsigned": ctypes.c_uint, "float": c_float, "double": ctypes.c_double, "long long": c_longlong, "size_t": c_size_t}
 TEST_EXPORTS = tuple(_prototypes("lft_hip_test.h"))             # declared in include/lft_hip_test.h, not in the product header
-_SIGS = {**_prototypes("lft_hip.h"), **_prototypes("lft_hip_test.h")}
+_PROTOTYPES = {**_prototypes("lft_hip.h"), **_prototypes("lft_hip_test.h")}
+_SIGS = {name: (res, args) for name, (res, args, _) in _PROTOTYPES.items()}
+# the entry points enqueue() serves: the last declared parameter is `void* stream`
+STREAM_LAST = frozenset(name for name, (_, args, last) in _PROTOTYPES.items() if last == "stream" and args[-1] is c_void_p)
 EXPORTS = tuple(_SIGS)
 GUARD_EXPORTS = ("lft_guard_bytes", "lft_guard_init", "lft_adam_step_guarded", "lft_guard_read")   # added to ABI 5 without a new version number
 EMA_EXPORTS = ("lft_ema_update",)                                                                  # likewise
@@ -221,13 +224,49 @@ def check(rc: int, what: str) -> None:
         raise LftError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
 
 
+def call(name: str, *args) -> None:
+    """The entry point `name` with `args`; a non-zero status raises LftError with the library's message."""
+    check(getattr(lib(), name)(*args), name)
+
+
+def query(name: str, *args):
+    """A size query: `args` without the trailing `size_t*` parameters of `name`, which come back as an int (several: a tuple)."""
+    types = _SIGS[name][1] if name in _SIGS else []
+    outs = [c_size_t(0) for t in types if t is POINTER(c_size_t)]
+    if not outs or types[-len(outs):] != [POINTER(c_size_t)] * len(outs):
+        raise LftError(f"{name} is no size query: its prototype does not end in a size_t* parameter")
+    call(name, *args, *[ctypes.byref(o) for o in outs])
+    return outs[0].value if len(outs) == 1 else tuple(o.value for o in outs)
+
+
+def stream_ptr(device) -> int:
+    """The handle of the current stream of `device` (a torch device), as the `void* stream` of an entry point."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def enqueue(name: str, device, *args) -> None:
+    """call(name, *args, stream_ptr(device)) with `device` current, for an entry point whose last parameter is `void* stream`."""
+    if name not in STREAM_LAST:
+        raise LftError(f"{name} does not take its stream last: use call() with stream_ptr(device)")
+    import torch
+    with torch.cuda.device(device):
+        call(name, *args, stream_ptr(device))
+
+
+def ptr_array(tensors):
+    return (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def strides_array(t):
+    """The element strides of a tensor, or the numbers of a sequence, as a C array of long long."""
+    strides = t.stride() if hasattr(t, "stride") else t
+    return (c_longlong * len(strides))(*strides)
+
+
 def packed_bytes(A, h, w, s, prec) -> int:
-    n = c_size_t(0)
-    check(lib().lft_packed_bytes(A, h, w, s, prec, ctypes.byref(n)), "lft_packed_bytes")
-    return n.value
+    return query("lft_packed_bytes", A, h, w, s, prec)
 
 
 def workspace_bytes(B, A, h, w, s, prec) -> int:
-    n = c_size_t(0)
-    check(lib().lft_workspace_bytes(B, A, h, w, s, prec, ctypes.byref(n)), "lft_workspace_bytes")
-    return n.value
+    return query("lft_workspace_bytes", B, A, h, w, s, prec)

@@ -17,7 +17,6 @@ There is no CPU fallback: the maps come from the HIP kernels or an :class:`~lft_
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -32,10 +31,7 @@ TAPE_BUDGET = 4 << 30          # bytes of tape attention_maps allows itself when
 
 def map_floats(block: int, per_head: bool, B: int, A: int, h: int, w: int) -> int:
     """Number of floats of one block's maps (lft_attn_maps_floats)."""
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_attn_maps_floats(block, _lib.MAPS_HEADS if per_head else _lib.MAPS_MEAN, B, A, h, w, ctypes.byref(n)),
-               "lft_attn_maps_floats")
-    return n.value
+    return _lib.query("lft_attn_maps_floats", block, _lib.MAPS_HEADS if per_head else _lib.MAPS_MEAN, B, A, h, w)
 
 
 def map_shape(block: int, per_head: bool, B: int, A: int, h: int, w: int):
@@ -55,10 +51,8 @@ def maps_from_tape(tape: torch.Tensor, block: int, layer: int, per_head: bool, B
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() != map_floats(block, per_head, B, A, h, w):
         raise _lib.LftError(f"out must be a contiguous float32 tensor of {shape} on {dev}")
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().lft_train_attn_maps(tape.data_ptr(), block, layer, _lib.MAPS_HEADS if per_head else _lib.MAPS_MEAN,
-                                                  out.data_ptr(), B, A, h, w, s, torch.cuda.current_stream(dev).cuda_stream),
-                   "lft_train_attn_maps")
+    _lib.enqueue("lft_train_attn_maps", dev, tape.data_ptr(), block, layer, _lib.MAPS_HEADS if per_head else _lib.MAPS_MEAN, out.data_ptr(),
+                 B, A, h, w, s)
     return out.view(shape)
 
 
@@ -102,15 +96,14 @@ def attention_maps(net, lr: torch.Tensor, blocks: Optional[Iterable[str]] = None
     dev = x.device
     ps = [p.detach() for p in net._params_in_order()]
     out = {name: torch.empty(map_shape(block, per_head, B, A, h, w), dtype=torch.float32, device=dev) for name, block, _ in sel}
-    with torch.cuda.device(dev):
-        tapes = {}
-        for b0 in range(0, B, nb):
-            n = min(nb, B - b0)
-            if n not in tapes:
-                tapes[n] = torch.empty(tape_bytes(n, A, h, w, s), dtype=torch.uint8, device=dev)
-            _, tape = train_forward(ps, x[b0:b0 + n], A, s, tape=tapes[n], math=math)
-            for name, block, layer in sel:
-                maps_from_tape(tape, block, layer, per_head, n, A, h, w, s, out=out[name][b0:b0 + n])
+    tapes = {}
+    for b0 in range(0, B, nb):
+        n = min(nb, B - b0)
+        if n not in tapes:
+            tapes[n] = torch.empty(tape_bytes(n, A, h, w, s), dtype=torch.uint8, device=dev)
+        _, tape = train_forward(ps, x[b0:b0 + n], A, s, tape=tapes[n], math=math)
+        for name, block, layer in sel:
+            maps_from_tape(tape, block, layer, per_head, n, A, h, w, s, out=out[name][b0:b0 + n])
     return out
 
 

@@ -21,7 +21,8 @@ the light field's device and current stream; there is no CPU path.
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Optional, Tuple
+from functools import partial
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -33,6 +34,7 @@ YCBCR_MATRIX = np.array([[65.481, 128.553, 24.966],
                          [-37.797, -74.203, 112.0],
                          [112.0, -93.786, -18.214]], dtype=np.float64)     # rgb2ycbcr, reference utils/utils.py:163-165
 _OUT_CLASS = {torch.uint8: _lib.LF_UINT8, torch.float32: _lib.LF_FLOAT32}
+_device_table = partial(prepare._device_table, up=True)         # (in_len, s, device): the up-scaling tables, in prepare's cache
 
 
 def inverse_matrix() -> np.ndarray:
@@ -42,35 +44,8 @@ def inverse_matrix() -> np.ndarray:
 
 def up_contributions(in_len: int, s: int) -> Tuple[np.ndarray, np.ndarray]:
     """The reference's ``contributions(L, L*s, s, cubic, 4.0)`` of one axis (utils/imresize.py:32-52, scale >= 1): (weights fp64
-    [L*s, P], indices int32 [L*s, P]), 0-based input indices.  The kernel is the plain cubic of width 4 (no antialiasing), 6 taps
-    per output before the all-zero tap columns are dropped, weights normalised per output, indices mirrored into [0, L)
-    symmetrically (period 2*L)."""
-    if in_len < 1 or s < 1:
-        raise ValueError(f"up_contributions: length {in_len}, scale factor {s}")
-    scale = float(s)
-    width = 4.0
-    x = np.arange(1, in_len * s + 1).astype(np.float64)
-    u = x / scale + 0.5 * (1 - 1 / scale)                        # the output sample's centre in 1-based input coordinates
-    left = np.floor(u - width / 2)
-    P = int(np.ceil(width)) + 2
-    ind = (left[:, None] + np.arange(P) - 1).astype(np.int32)   # 0-based
-    w = prepare._cubic(u[:, None] - ind - 1)
-    w = np.divide(w, np.sum(w, axis=1)[:, None])
-    mirror = np.concatenate((np.arange(in_len), np.arange(in_len - 1, -1, -1))).astype(np.int32)
-    ind = mirror[np.mod(ind, mirror.size)]
-    keep = np.nonzero(np.any(w, axis=0))[0]
-    return np.ascontiguousarray(w[:, keep]), np.ascontiguousarray(ind[:, keep])
-
-
-_tables: Dict[Tuple[int, int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
-
-
-def _device_table(in_len: int, s: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    key = (in_len, s, str(device))
-    if key not in _tables:
-        w, i = up_contributions(in_len, s)
-        _tables[key] = (torch.from_numpy(w).to(device), torch.from_numpy(i).to(device))
-    return _tables[key]
+    [L*s, P], indices int32 [L*s, P]); prepare.imresize_table without antialiasing, 6 taps before the all-zero columns are dropped."""
+    return prepare.imresize_table(in_len, s, up=True)
 
 
 def _field(lf, A: int, device=None) -> torch.Tensor:
@@ -91,15 +66,11 @@ def _field(lf, A: int, device=None) -> torch.Tensor:
 def luma(lf, A: int, device=None) -> torch.Tensor:
     """lft_lf_luma: single(Y) of the centre A x A views, scaled to [0, 1], as the mosaic [A*H, A*W] fp32.  Enqueue only."""
     t = _field(lf, A, device)
-    U, V, H, W, C = (int(d) for d in t.shape)
+    H, W = int(t.shape[2]), int(t.shape[3])
     if A < 1:
         raise LftError(f"angRes must be positive, got {A}")
     y = torch.empty(A * H, A * W, dtype=torch.float32, device=t.device)
-    strides = (ctypes.c_longlong * 5)(*t.stride())
-    with torch.cuda.device(t.device):
-        rc = _lib.lib().lft_lf_luma(t.data_ptr() if t.numel() else None, prepare._CLASS[t.dtype], U, V, H, W, C, strides, A,
-                                    y.data_ptr() or None, torch.cuda.current_stream(t.device).cuda_stream)
-    _lib.check(rc, "lft_lf_luma")
+    _lib.enqueue("lft_lf_luma", t.device, *prepare.lf_args(t), A, y.data_ptr() or None)
     return y
 
 
@@ -108,7 +79,7 @@ def merge(lf, sr_y: Optional[torch.Tensor], A: int, s: int, out_dtype=torch.uint
     [A*s*H, A*s*W] fp32 (None: the light field's own luma, up-scaled like the chroma).  out_dtype torch.uint8 gives the quantised
     image, torch.float32 the unquantised, unclipped rgb.  Enqueue only."""
     t = _field(lf, A, device)
-    U, V, H, W, C = (int(d) for d in t.shape)
+    H, W = int(t.shape[2]), int(t.shape[3])
     if out_dtype not in _OUT_CLASS:
         raise LftError(f"out_dtype must be torch.uint8 or torch.float32, got {out_dtype}")
     if A < 1:
@@ -124,14 +95,9 @@ def merge(lf, sr_y: Optional[torch.Tensor], A: int, s: int, out_dtype=torch.uint
     wh, ih = _device_table(H, s, t.device)
     ww, iw = _device_table(W, s, t.device)
     out = torch.empty(A, A, s * H, s * W, 3, dtype=out_dtype, device=t.device)
-    strides = (ctypes.c_longlong * 5)(*t.stride())
     minv = (ctypes.c_double * 9)(*inverse_matrix().reshape(-1))
-    with torch.cuda.device(t.device):
-        rc = _lib.lib().lft_colour_merge(t.data_ptr() if t.numel() else None, prepare._CLASS[t.dtype], U, V, H, W, C, strides, A, s,
-                                         sr_y.data_ptr() if sr_y is not None else None, wh.data_ptr(), ih.data_ptr(), wh.shape[1],
-                                         ww.data_ptr(), iw.data_ptr(), ww.shape[1], minv, out.data_ptr() or None,
-                                         _OUT_CLASS[out_dtype], torch.cuda.current_stream(t.device).cuda_stream)
-    _lib.check(rc, "lft_colour_merge")
+    _lib.enqueue("lft_colour_merge", t.device, *prepare.lf_args(t), A, s, sr_y.data_ptr() if sr_y is not None else None, wh.data_ptr(),
+                 ih.data_ptr(), wh.shape[1], ww.data_ptr(), iw.data_ptr(), ww.shape[1], minv, out.data_ptr() or None, _OUT_CLASS[out_dtype])
     return out
 
 

@@ -37,7 +37,6 @@ by their disparity maps: the figure for super-resolved views against ground-trut
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -45,7 +44,7 @@ import torch
 
 from . import _lib
 from ._lib import LftError
-from .refocus import TAPS, Aperture, _CLASS, _device_table, _layout
+from .refocus import TAPS, Aperture, _CLASS, _device_table, _field
 
 MAX_RADIUS = 8
 
@@ -73,9 +72,8 @@ def _device_scratch(B: int, D: int, H: int, W: int, C: int, flags: int, device) 
     """The sweep's volume (and stack), one buffer per shape and device: calls of one shape on different streams must not overlap."""
     key = (B, D, H, W, C, flags, str(device))
     if key not in _scratch:
-        n = ctypes.c_size_t(0)
-        _lib.check(_lib.lib().lft_disparity_scratch_bytes(B, D, H, W, C, flags, ctypes.byref(n)), "lft_disparity_scratch_bytes")
-        _scratch[key] = torch.empty(max(n.value // 4, 1), dtype=torch.float32, device=device)
+        n = _lib.query("lft_disparity_scratch_bytes", B, D, H, W, C, flags)
+        _scratch[key] = torch.empty(max(n // 4, 1), dtype=torch.float32, device=device)
     return _scratch[key]
 
 
@@ -106,23 +104,18 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     Layouts, strides, input classes, aperture and interp are ``refocus.refocus``'s.  radius: the aggregation window is
     (2 radius + 1)^2, 0 .. 8.  all_in_focus: also return the refocus stack gathered at the index, as aif_dtype (default: the
     input's; torch.float32 is the unclipped sum, torch.uint8 clips, scales and rounds half to even).  cost_volume: also return E."""
-    if not isinstance(lf, torch.Tensor):
-        raise LftError(f"the light field must be a torch tensor, got {type(lf).__name__}")
-    if lf.dtype not in _CLASS:
-        raise LftError(f"light field of class {lf.dtype}: uint8 and float32 are supported")
+    sl = ()
+
+    def sweep_arguments():                  # radius, interp and slopes are refused before a tensor off the GPU
+        nonlocal sl
+        if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= MAX_RADIUS:
+            raise LftError(f"radius must be an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
+        if interp not in TAPS:
+            raise LftError(f"interp must be nearest, linear or cubic, got {interp!r}")
+        sl = check_slopes(slopes)
+
+    B, A, H, W, C, strides, kind = _field(lf, angRes, "aif_dtype", aif_dtype, before_device=sweep_arguments)
     aif_dtype = lf.dtype if aif_dtype is None else aif_dtype
-    if aif_dtype not in _CLASS:
-        raise LftError(f"aif_dtype must be torch.uint8 or torch.float32, got {aif_dtype}")
-    if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= MAX_RADIUS:
-        raise LftError(f"radius must be an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
-    if interp not in TAPS:
-        raise LftError(f"interp must be nearest, linear or cubic, got {interp!r}")
-    sl = check_slopes(slopes)
-    if lf.device.type != "cuda":
-        raise LftError(f"the light field must be on the GPU, got a tensor on {lf.device} (there is no CPU path)")
-    B, A, H, W, C, strides, kind = _layout(lf, angRes)
-    if C < 1 or C > 4:
-        raise LftError(f"{C} channels: 1 to 4 are supported")
     table = _device_table(A, sl, aperture, interp, lf.device)
     D = len(sl)
     dev = lf.device
@@ -133,13 +126,9 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if all_in_focus else None
     if B and H and W:
         scratch = _device_scratch(B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0, dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().lft_disparity(lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, (ctypes.c_longlong * 6)(*strides),
-                                          table.data_ptr(), _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius),
-                                          scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(), index.data_ptr(),
-                                          cost.data_ptr() if cost_volume else None, aif.data_ptr() if all_in_focus else None,
-                                          _CLASS[aif_dtype], torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "lft_disparity")
+        _lib.enqueue("lft_disparity", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(),
+                     _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius), scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(),
+                     index.data_ptr(), cost.data_ptr() if cost_volume else None, aif.data_ptr() if all_in_focus else None, _CLASS[aif_dtype])
     if kind != "batch":
         disp, conf, index = disp[0], conf[0], index[0]
         cost = None if cost is None else cost[0]

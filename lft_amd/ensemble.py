@@ -49,10 +49,6 @@ def _one_shape(mask: int, H: int, W: int, what: str) -> None:
                          'and cannot share one batch; use "flips" (0x0F) for non-square mosaics')
 
 
-def _stream(x):
-    return torch.cuda.current_stream(x.device).cuda_stream
-
-
 def dihedral_batch(x: torch.Tensor, codes) -> torch.Tensor:
     """out[b] = T_(codes[b] & 7)(x[b]) for x [B,1,H,W]; codes: B ints (a sequence, or an int32 tensor, which may already be on the
     device).  Returns [B,1,H,W]; for H != W every code must transpose ([B,1,W,H]) or none."""
@@ -67,8 +63,7 @@ def dihedral_batch(x: torch.Tensor, codes) -> torch.Tensor:
                          'one batch (the "flips" codes 0..3 keep the shape)')
     c = c.to(x.device).contiguous()
     out = torch.empty((B, 1, W, H) if tr is not None and bool(tr.all()) else (B, 1, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().lft_dihedral_batch(x.data_ptr(), out.data_ptr(), c.data_ptr(), B, H, W, _stream(x)), "lft_dihedral_batch")
+    _lib.enqueue("lft_dihedral_batch", x.device, x.data_ptr(), out.data_ptr(), c.data_ptr(), B, H, W)
     return out
 
 
@@ -82,8 +77,7 @@ def expand(x: torch.Tensor, mask) -> torch.Tensor:
     E = len(codes_of(mask))
     shape = (B * E, 1, W, H) if not mask & ~TRANSPOSING & 0xFF else (B * E, 1, H, W)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().lft_dihedral_expand(x.data_ptr(), out.data_ptr(), mask, B, H, W, _stream(x)), "lft_dihedral_expand")
+    _lib.enqueue("lft_dihedral_expand", x.device, x.data_ptr(), out.data_ptr(), mask, B, H, W)
     return out
 
 
@@ -99,8 +93,7 @@ def merge(y: torch.Tensor, mask) -> torch.Tensor:
         raise ValueError(f"merge: {N} images are not a multiple of the {E} variants of mask {mask:#x}")
     H, W = (Wy, Hy) if not mask & ~TRANSPOSING & 0xFF else (Hy, Wy)
     out = torch.empty((N // E, 1, H, W), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(y.device):
-        _lib.check(_lib.lib().lft_dihedral_merge(y.data_ptr(), out.data_ptr(), mask, N // E, H, W, _stream(y)), "lft_dihedral_merge")
+    _lib.enqueue("lft_dihedral_merge", y.device, y.data_ptr(), out.data_ptr(), mask, N // E, H, W)
     return out
 
 

@@ -10,7 +10,6 @@ the reference's own loop; ``epi_error`` is the EPI term with the L1 penalty as a
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Optional
 
@@ -25,18 +24,13 @@ _SSIM_KEYS = ("ssim_weight", "ssim_range")
 
 
 def scratch_bytes(B: int, A: int, H: int, W: int) -> int:
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_lf_loss_scratch_bytes(B, A, H, W, ctypes.byref(n)), "lft_lf_loss_scratch_bytes")
-    return n.value
+    return _lib.query("lft_lf_loss_scratch_bytes", B, A, H, W)
 
 
-def lf_loss(sr: torch.Tensor, hr: torch.Tensor, angRes: int, penalty="l1", eps: float = 1e-3, pixel_weight: float = 1.0,
-            epi_weight: float = 0.0, dsr: Optional[torch.Tensor] = None, gscale: float = 1.0, loss3: Optional[torch.Tensor] = None,
-            scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """lft_lf_loss on contiguous float32 HIP tensors [B,1,A*H,A*W]: returns loss3 = (total, P, E) on the device and, if `dsr` is
-    given, writes gscale * d total / d sr there.  loss3 / scratch: buffers to use (a captured step owns its own).  Only enqueues."""
+def _mosaics(entry: str, sr, hr, dsr, angRes):
+    """What lf_loss and ssim_loss ask of their tensors; (B, A, H, W) of the mosaics [B,1,A*H,A*W]."""
     if not sr.is_cuda:
-        raise _lib.LftError("lft_lf_loss runs on a HIP device only")
+        raise _lib.LftError(f"{entry} runs on a HIP device only")
     for t in (sr, hr) + (() if dsr is None else (dsr,)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != sr.shape or t.device != sr.device or t.dim() != 4 or t.shape[1] != 1:
             raise _lib.LftError("sr, hr and dsr must be contiguous float32 tensors [B,1,A*H,A*W] on one device")
@@ -44,16 +38,20 @@ def lf_loss(sr: torch.Tensor, hr: torch.Tensor, angRes: int, penalty="l1", eps: 
     A = int(angRes)
     if A < 1 or R % A or C % A:
         raise _lib.LftError(f"a {R} x {C} mosaic does not divide into {A} x {A} views")
-    H, W = R // A, C // A
+    return B, A, R // A, C // A
+
+
+def lf_loss(sr: torch.Tensor, hr: torch.Tensor, angRes: int, penalty="l1", eps: float = 1e-3, pixel_weight: float = 1.0,
+            epi_weight: float = 0.0, dsr: Optional[torch.Tensor] = None, gscale: float = 1.0, loss3: Optional[torch.Tensor] = None,
+            scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lft_lf_loss on contiguous float32 HIP tensors [B,1,A*H,A*W]: returns loss3 = (total, P, E) on the device and, if `dsr` is
+    given, writes gscale * d total / d sr there.  loss3 / scratch: buffers to use (a captured step owns its own).  Only enqueues."""
+    B, A, H, W = _mosaics("lft_lf_loss", sr, hr, dsr, angRes)
     pen = PENALTIES[penalty] if isinstance(penalty, str) else int(penalty)
-    with torch.cuda.device(sr.device):
-        if loss3 is None:
-            loss3 = torch.empty(3, dtype=torch.float32, device=sr.device)
-        if scratch is None:
-            scratch = torch.empty(scratch_bytes(B, A, H, W), dtype=torch.uint8, device=sr.device)
-        _lib.check(_lib.lib().lft_lf_loss(sr.data_ptr(), hr.data_ptr(), B, A, H, W, pen, eps, pixel_weight, epi_weight,
-                                          None if dsr is None else dsr.data_ptr(), gscale, loss3.data_ptr(), scratch.data_ptr(),
-                                          torch.cuda.current_stream(sr.device).cuda_stream), "lft_lf_loss")
+    loss3 = torch.empty(3, dtype=torch.float32, device=sr.device) if loss3 is None else loss3
+    scratch = torch.empty(scratch_bytes(B, A, H, W), dtype=torch.uint8, device=sr.device) if scratch is None else scratch
+    _lib.enqueue("lft_lf_loss", sr.device, sr.data_ptr(), hr.data_ptr(), B, A, H, W, pen, eps, pixel_weight, epi_weight,
+                 None if dsr is None else dsr.data_ptr(), gscale, loss3.data_ptr(), scratch.data_ptr())
     return loss3
 
 
@@ -79,9 +77,7 @@ def lf_loss_torch(sr: torch.Tensor, hr: torch.Tensor, angRes: int, penalty="l1",
 
 
 def ssim_scratch_bytes(B: int, A: int, H: int, W: int) -> int:
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_ssim_loss_scratch_bytes(B, A, H, W, ctypes.byref(n)), "lft_ssim_loss_scratch_bytes")
-    return n.value
+    return _lib.query("lft_ssim_loss_scratch_bytes", B, A, H, W)
 
 
 def ssim_loss(sr: torch.Tensor, hr: torch.Tensor, angRes: int, ssim_range: float = 2.0, ssim_weight: float = 1.0,
@@ -90,32 +86,17 @@ def ssim_loss(sr: torch.Tensor, hr: torch.Tensor, angRes: int, ssim_range: float
     """lft_ssim_loss on contiguous float32 HIP tensors [B,1,A*H,A*W]: returns (total, ssim_out), one-element device tensors holding
     ssim_weight * (1 - S) and S, and, if `dsr` is given, writes gscale * ssim_weight * d(1 - S) / d sr there.  accumulate: total and
     dsr are added to instead (both must then be given).  total / ssim_out / scratch: buffers to use.  Only enqueues."""
-    if not sr.is_cuda:
-        raise _lib.LftError("lft_ssim_loss runs on a HIP device only")
-    for t in (sr, hr) + (() if dsr is None else (dsr,)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != sr.shape or t.device != sr.device or t.dim() != 4 or t.shape[1] != 1:
-            raise _lib.LftError("sr, hr and dsr must be contiguous float32 tensors [B,1,A*H,A*W] on one device")
-    B, _, R, C = sr.shape
-    A = int(angRes)
-    if A < 1 or R % A or C % A:
-        raise _lib.LftError(f"a {R} x {C} mosaic does not divide into {A} x {A} views")
-    H, W = R // A, C // A
+    B, A, H, W = _mosaics("lft_ssim_loss", sr, hr, dsr, angRes)
     if accumulate and total is None:
         raise _lib.LftError("accumulate adds to `total`: pass the tensor that holds the other terms")
     for t in (total, ssim_out):
         if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != sr.device):
             raise _lib.LftError("total and ssim_out are one-element float32 tensors on the device of sr")
-    with torch.cuda.device(sr.device):
-        if total is None:
-            total = torch.empty(1, dtype=torch.float32, device=sr.device)
-        if ssim_out is None:
-            ssim_out = torch.empty(1, dtype=torch.float32, device=sr.device)
-        if scratch is None:
-            scratch = torch.empty(ssim_scratch_bytes(B, A, H, W), dtype=torch.uint8, device=sr.device)
-        _lib.check(_lib.lib().lft_ssim_loss(sr.data_ptr(), hr.data_ptr(), B, A, H, W, ssim_range, ssim_weight,
-                                            None if dsr is None else dsr.data_ptr(), gscale, int(bool(accumulate)), total.data_ptr(),
-                                            ssim_out.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(sr.device).cuda_stream),
-                   "lft_ssim_loss")
+    total = torch.empty(1, dtype=torch.float32, device=sr.device) if total is None else total
+    ssim_out = torch.empty(1, dtype=torch.float32, device=sr.device) if ssim_out is None else ssim_out
+    scratch = torch.empty(ssim_scratch_bytes(B, A, H, W), dtype=torch.uint8, device=sr.device) if scratch is None else scratch
+    _lib.enqueue("lft_ssim_loss", sr.device, sr.data_ptr(), hr.data_ptr(), B, A, H, W, ssim_range, ssim_weight,
+                 None if dsr is None else dsr.data_ptr(), gscale, int(bool(accumulate)), total.data_ptr(), ssim_out.data_ptr(), scratch.data_ptr())
     return total, ssim_out
 
 

@@ -2,8 +2,6 @@
 means over the views whose metric is > 0."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -19,14 +17,11 @@ def view_metrics(label: torch.Tensor, out: torch.Tensor, angRes: int, ssim_range
     B, _, H, W = label.shape
     A = int(angRes)
     h, w = H // A, W // A
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_view_metrics_scratch_bytes(B, A, h, w, ctypes.byref(n)), "lft_view_metrics_scratch_bytes")
-    with torch.cuda.device(label.device):
-        scratch = torch.empty(n.value, dtype=torch.uint8, device=label.device)
-        psnr = torch.empty(B * A * A, dtype=torch.float32, device=label.device)
-        ssim = torch.empty_like(psnr)
-        _lib.check(_lib.lib().lft_view_metrics(label.data_ptr(), out.data_ptr(), B, A, h, w, float(ssim_range), psnr.data_ptr(), ssim.data_ptr(),
-                                               scratch.data_ptr(), torch.cuda.current_stream(label.device).cuda_stream), "lft_view_metrics")
+    scratch = torch.empty(_lib.query("lft_view_metrics_scratch_bytes", B, A, h, w), dtype=torch.uint8, device=label.device)
+    psnr = torch.empty(B * A * A, dtype=torch.float32, device=label.device)
+    ssim = torch.empty_like(psnr)
+    _lib.enqueue("lft_view_metrics", label.device, label.data_ptr(), out.data_ptr(), B, A, h, w, float(ssim_range), psnr.data_ptr(), ssim.data_ptr(),
+                 scratch.data_ptr())
     return psnr.view(B, A, A), ssim.view(B, A, A)
 
 

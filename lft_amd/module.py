@@ -22,6 +22,26 @@ _PREC = {"fp32": _lib.PREC_F32, "f32": _lib.PREC_F32, "float32": _lib.PREC_F32,
          "fp16": _lib.PREC_F16, "f16": _lib.PREC_F16, "float16": _lib.PREC_F16}
 
 
+def pack_weights(params, A, h, w, s, prec, stream) -> torch.Tensor:
+    """lft_pack_weights on `stream` (a handle): the 78 `params`, state-dict order, packed for this shape and precision as a new uint8 tensor."""
+    buf = torch.empty(_lib.packed_bytes(A, h, w, s, prec), dtype=torch.uint8, device=params[0].device)
+    _lib.call("lft_pack_weights", _lib.ptr_array(params), len(params), buf.data_ptr(), A, h, w, s, prec, stream)
+    return buf
+
+
+def status_reset(work: torch.Tensor, B, A, h, w, s, prec, stream) -> None:
+    """Clear the sticky status word of a workspace (lft_status_reset, ordered on `stream`)."""
+    _lib.call("lft_status_reset", work.data_ptr(), B, A, h, w, s, prec, stream)
+
+
+def status_read(work: torch.Tensor, B, A, h, w, s, prec, stream):
+    """(return code, flag word) of lft_status_read: (0, 0) unless a kernel saw a non-finite value since the reset.  The code is
+    the caller's to judge: STATUS_NONFINITE is an answer, not a failure."""
+    flags = ctypes.c_uint(0)
+    rc = _lib.lib().lft_status_read(work.data_ptr(), B, A, h, w, s, prec, stream, ctypes.byref(flags))
+    return rc, flags.value
+
+
 class _Node(nn.Module):
     """Parameter container; gives state-dict paths like ``altblock.0.spa_trans.MLP.weight``."""
 
@@ -102,12 +122,7 @@ class get_model(nn.Module):
                                     f"({dev}); call net.to(device) first")
         key = self._pack_key(ps, h, w, prec)
         if self._packed is None or self._packed[0] != key:
-            nbytes = _lib.packed_bytes(self.angRes, h, w, self.factor, prec)
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-            _lib.check(_lib.lib().lft_pack_weights(arr, len(ps), buf.data_ptr(), self.angRes, h, w, self.factor,
-                                                   prec, stream), "lft_pack_weights")
-            self._packed = (key, buf)
+            self._packed = (key, pack_weights(ps, self.angRes, h, w, self.factor, prec, stream))
         return self._packed[1]
 
     def _ensure_work(self, dev, B, h, w, prec, slot=0):
@@ -120,12 +135,10 @@ class get_model(nn.Module):
                 # replay since the last reset, include/lft_hip.h).  Allocation during capture is not wanted either.
                 raise _lib.LftError("a workspace would have to be created while a HIP graph is being captured: run one eager "
                                     "forward of this shape (same _slot_base) first (GraphedForward needs warmup >= 1)")
-            nbytes = _lib.workspace_bytes(B, self.angRes, h, w, self.factor, prec)
-            cur = (key, torch.empty(nbytes, dtype=torch.uint8, device=dev))
+            cur = (key, torch.empty(_lib.workspace_bytes(B, self.angRes, h, w, self.factor, prec), dtype=torch.uint8, device=dev))
             self._work[slot] = cur
             # the workspace's sticky status word starts clear (ordered on the current stream, like every later use)
-            _lib.check(_lib.lib().lft_status_reset(cur[1].data_ptr(), B, self.angRes, h, w, self.factor, prec,
-                                                   torch.cuda.current_stream(dev).cuda_stream), "lft_status_reset")
+            status_reset(cur[1], B, self.angRes, h, w, self.factor, prec, _lib.stream_ptr(dev))
         return cur[1]
 
     def check_status(self, reset: bool = True) -> None:
@@ -136,15 +149,15 @@ class get_model(nn.Module):
         bad = []
         for slot, (key, buf) in self._work.items():
             _, B, h, w, prec = key
+            dims = (B, self.angRes, h, w, self.factor, prec)
             with torch.cuda.device(buf.device):
-                stream = torch.cuda.current_stream(buf.device).cuda_stream
+                stream = _lib.stream_ptr(buf.device)
                 torch.cuda.synchronize(buf.device)              # forwards on side / pipeline streams included
-                flags = ctypes.c_uint(0)
-                rc = _lib.lib().lft_status_read(buf.data_ptr(), B, self.angRes, h, w, self.factor, prec, stream, ctypes.byref(flags))
+                rc, _ = status_read(buf, *dims, stream)
                 if rc == _lib.STATUS_NONFINITE:
                     bad.append((slot, _lib.lib().lft_last_error().decode()))
                     if reset:
-                        _lib.check(_lib.lib().lft_status_reset(buf.data_ptr(), B, self.angRes, h, w, self.factor, prec, stream), "lft_status_reset")
+                        status_reset(buf, *dims, stream)
                 else:
                     _lib.check(rc, "lft_status_read")
         if bad:
@@ -173,16 +186,14 @@ class get_model(nn.Module):
         h, w = H // A, W // A
         x = lr.contiguous().float()
         prec = _PREC[self.precision]
-        stream = torch.cuda.current_stream(x.device).cuda_stream
         with torch.cuda.device(x.device):
             main = torch.cuda.current_stream(x.device)
-            packed = self._ensure_packed(x.device, h, w, prec, stream)
+            packed = self._ensure_packed(x.device, h, w, prec, _lib.stream_ptr(x.device))
             out = torch.empty((B, 1, H * s, W * s), dtype=torch.float32, device=x.device)
             nsplit = max(1, min(self.streams, B))
             if nsplit == 1:
                 work = self._ensure_work(x.device, B, h, w, prec, slot=(_slot_base, 0))
-                _lib.check(_lib.lib().lft_forward(packed.data_ptr(), x.data_ptr(), out.data_ptr(), work.data_ptr(),
-                                                  B, A, h, w, s, prec, stream), "lft_forward")
+                _lib.enqueue("lft_forward", x.device, packed.data_ptr(), x.data_ptr(), out.data_ptr(), work.data_ptr(), B, A, h, w, s, prec)
             else:
                 side = self._side_streams.setdefault(x.device, [])
                 while len(side) < nsplit:
@@ -195,8 +206,8 @@ class get_model(nn.Module):
                 for i, (b0, b1) in enumerate(shards):
                     st = side[i]
                     st.wait_event(ready)
-                    _lib.check(_lib.lib().lft_forward(packed.data_ptr(), x[b0:b1].data_ptr(), out[b0:b1].data_ptr(), works[i].data_ptr(),
-                                                      b1 - b0, A, h, w, s, prec, st.cuda_stream), "lft_forward")
+                    _lib.call("lft_forward", packed.data_ptr(), x[b0:b1].data_ptr(), out[b0:b1].data_ptr(), works[i].data_ptr(),
+                              b1 - b0, A, h, w, s, prec, st.cuda_stream)
                     main.wait_stream(st)                # the caller's stream sees the finished sub-batch
             if self.check_finite and not torch.cuda.is_current_stream_capturing():
                 self.check_status()                     # fp16 by default: an overflow raises here (synchronises, like the .cpu() that follows in test.py)

@@ -46,21 +46,22 @@ def out_length(in_len: int, s: int) -> int:
     return int(math.ceil(in_len * (1.0 / s)))
 
 
-def contributions(in_len: int, s: int) -> Tuple[np.ndarray, np.ndarray]:
-    """MATLAB imresize's contribution table of one axis for the scale 1/s: (weights fp64 [out, P], indices int32 [out, P]),
-    out = ceil(in_len / s), 0-based input indices.  The antialiased kernel is scale * cubic(scale * x) with width 4 / scale;
+def imresize_table(in_len: int, s: int, up: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """imresize's contribution table of one axis (MATLAB's, and the reference's utils/imresize.py:32-52), down by s or up by s:
+    (weights fp64 [out, P], indices int32 [out, P]), 0-based input indices.  Down (scale = 1/s, out = ceil(in_len / s)) the kernel
+    is the antialiased scale * cubic(scale * x) of width 4 / scale; up (scale = s, out = in_len * s) the plain cubic of width 4.
     P = ceil(width) + 2 taps per output, weights normalised per output, indices mirrored into [0, in_len) symmetrically (period
     2 * in_len), tap columns that are zero for every output dropped."""
     if in_len < 1 or s < 1:
-        raise ValueError(f"contributions: length {in_len}, scale factor {s}")
-    scale = 1.0 / s
-    width = 4.0 / scale
-    x = np.arange(1, out_length(in_len, s) + 1, dtype=np.float64)
+        raise ValueError(f"{'up_contributions' if up else 'contributions'}: length {in_len}, scale factor {s}")
+    scale = float(s) if up else 1.0 / s
+    width = 4.0 if up else 4.0 / scale
+    x = np.arange(1, (in_len * s if up else out_length(in_len, s)) + 1, dtype=np.float64)
     u = x / scale + 0.5 * (1 - 1 / scale)                        # the output sample's centre in 1-based input coordinates
     left = np.floor(u - width / 2)
     P = int(math.ceil(width)) + 2
     ind = (left[:, None] + np.arange(P) - 1).astype(np.int32)   # 0-based
-    w = scale * _cubic(scale * (u[:, None] - ind - 1))
+    w = _cubic(u[:, None] - ind - 1) if up else scale * _cubic(scale * (u[:, None] - ind - 1))
     w = np.divide(w, np.sum(w, axis=1)[:, None])
     mirror = np.concatenate((np.arange(in_len), np.arange(in_len - 1, -1, -1))).astype(np.int32)
     ind = mirror[np.mod(ind, mirror.size)]
@@ -68,15 +69,26 @@ def contributions(in_len: int, s: int) -> Tuple[np.ndarray, np.ndarray]:
     return np.ascontiguousarray(w[:, keep]), np.ascontiguousarray(ind[:, keep])
 
 
-_tables: Dict[Tuple[int, int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
+def contributions(in_len: int, s: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The table of MATLAB's imresize(., 1/s): 4*s + 2 taps per output before the all-zero columns are dropped."""
+    return imresize_table(in_len, s, up=False)
 
 
-def _device_table(in_len: int, s: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    key = (in_len, s, str(device))
+_tables: Dict[Tuple[int, int, bool, str], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def _device_table(in_len: int, s: int, device, up: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    key = (in_len, s, bool(up), str(device))                     # one cache for both directions
     if key not in _tables:
-        w, i = contributions(in_len, s)
+        w, i = imresize_table(in_len, s, up)
         _tables[key] = (torch.from_numpy(w).to(device), torch.from_numpy(i).to(device))
     return _tables[key]
+
+
+def lf_args(lf: torch.Tensor) -> tuple:
+    """The leading arguments (lf, lf_class, U, V, H, W, C, strides) of the entry points that read a light field [U, V, H, W, C] in
+    place.  An empty tensor goes as a null pointer and an unknown class as -1: the library does the refusing."""
+    return (lf.data_ptr() if lf.numel() else None, _CLASS.get(lf.dtype, -1), *(int(d) for d in lf.shape), _lib.strides_array(lf))
 
 
 # ---------------------------------------------------------------------------------------------- the kernel
@@ -89,7 +101,6 @@ def lf_prepare(lf: torch.Tensor, A: int, s: int, crops: Sequence[Tuple[int, int]
         raise LftError(f"lft_lf_prepare: the light field must be [U, V, H, W, C], got shape {tuple(lf.shape)}")
     if lf.device.type != "cuda":
         raise LftError(f"lft_lf_prepare: the light field must be on the GPU, got a tensor on {lf.device}")
-    U, V, H, W, C = (int(d) for d in lf.shape)
     dev = lf.device
     cr = np.ascontiguousarray(np.asarray(crops, dtype=np.int32).reshape(-1, 2))
     n = cr.shape[0]
@@ -105,13 +116,9 @@ def lf_prepare(lf: torch.Tensor, A: int, s: int, crops: Sequence[Tuple[int, int]
         oh = ow = 1
     hr = torch.empty(n, A * crop_h, A * crop_w, dtype=torch.float32, device=dev) if A >= 1 else torch.empty(0, device=dev)
     lr = torch.empty(n, A * oh, A * ow, dtype=torch.float32, device=dev) if A >= 1 else torch.empty(0, device=dev)
-    strides = (ctypes.c_longlong * 5)(*lf.stride())
     cptr = cr.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = _lib.lib().lft_lf_prepare(lf.data_ptr() if lf.numel() else None, _CLASS.get(lf.dtype, -1), U, V, H, W, C, strides, A, s,
-                                   cptr, n, crop_h, crop_w, wh.data_ptr(), ih.data_ptr(), wh.shape[1],
-                                   ww.data_ptr(), iw.data_ptr(), ww.shape[1], hr.data_ptr() or None, lr.data_ptr() or None, stream)
-    _lib.check(rc, "lft_lf_prepare")
+    _lib.enqueue("lft_lf_prepare", dev, *lf_args(lf), A, s, cptr, n, crop_h, crop_w, wh.data_ptr(), ih.data_ptr(), wh.shape[1],
+                 ww.data_ptr(), iw.data_ptr(), ww.shape[1], hr.data_ptr() or None, lr.data_ptr() or None)
     return hr, lr
 
 

@@ -12,7 +12,6 @@ light field, as it lies in memory, to one launch of k_refocus (csrc/lft_refocus.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -148,6 +147,29 @@ def _layout(lf: torch.Tensor, angRes: Optional[int]):
         "batch" if lf.dim() == 4 else "mosaic"
 
 
+def _field(lf, angRes: Optional[int], out_name: str, out_dtype, before_device=None):
+    """What refocus and disparity ask of their input: (B, A, H, W, C, the six strides as a C array, kind of _layout).  out_dtype
+    (None: the input's), named out_name, is the class of the image they return.  A tensor off the GPU is refused first, or, with
+    before_device (disparity's further refusals), after the classes and those."""
+    if not isinstance(lf, torch.Tensor):
+        raise LftError(f"the light field must be a torch tensor, got {type(lf).__name__}")
+    off_gpu = LftError(f"the light field must be on the GPU, got a tensor on {lf.device} (there is no CPU path)")
+    if before_device is None and lf.device.type != "cuda":
+        raise off_gpu
+    if lf.dtype not in _CLASS:
+        raise LftError(f"light field of class {lf.dtype}: uint8 and float32 are supported")
+    if out_dtype is not None and out_dtype not in _CLASS:
+        raise LftError(f"{out_name} must be torch.uint8 or torch.float32, got {out_dtype}")
+    if before_device is not None:
+        before_device()
+        if lf.device.type != "cuda":
+            raise off_gpu
+    B, A, H, W, C, strides, kind = _layout(lf, angRes)
+    if C < 1 or C > 4:
+        raise LftError(f"{C} channels: 1 to 4 are supported")
+    return B, A, H, W, C, _lib.strides_array(strides), kind
+
+
 def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
             interp: str = "cubic", out_dtype=None) -> torch.Tensor:
     """The focal stack of a light field on the GPU, one slice per slope, on lf's device and current stream (enqueue only).
@@ -159,26 +181,13 @@ def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = N
     Any strides are read in place.  uint8 input enters as x / 255, float32 as stored.  out_dtype (default: the input's) is
     torch.float32, the unclipped sum, or torch.uint8: clip to [0, 1], * 255, round half to even.  aperture: "full", "disk",
     "gaussian" or an [A, A] array (``aperture_weights`` for a radius or sigma); views of weight 0 are not read."""
-    if not isinstance(lf, torch.Tensor):
-        raise LftError(f"the light field must be a torch tensor, got {type(lf).__name__}")
-    if lf.device.type != "cuda":
-        raise LftError(f"the light field must be on the GPU, got a tensor on {lf.device} (there is no CPU path)")
-    if lf.dtype not in _CLASS:
-        raise LftError(f"light field of class {lf.dtype}: uint8 and float32 are supported")
+    B, A, H, W, C, strides, kind = _field(lf, angRes, "out_dtype", out_dtype)
     out_dtype = lf.dtype if out_dtype is None else out_dtype
-    if out_dtype not in _CLASS:
-        raise LftError(f"out_dtype must be torch.uint8 or torch.float32, got {out_dtype}")
-    B, A, H, W, C, strides, kind = _layout(lf, angRes)
-    if C < 1 or C > 4:
-        raise LftError(f"{C} channels: 1 to 4 are supported")
     table = _device_table(A, slopes, aperture, interp, lf.device)
     D = int(table.shape[0])
     out = torch.empty(B, D, H, W, C, dtype=out_dtype, device=lf.device)
-    with torch.cuda.device(lf.device):
-        rc = _lib.lib().lft_refocus(lf.data_ptr() or None, _CLASS[lf.dtype], B, A, H, W, C, (ctypes.c_longlong * 6)(*strides),
-                                    table.data_ptr(), D, TAPS[interp], out.data_ptr() or None, _CLASS[out_dtype],
-                                    torch.cuda.current_stream(lf.device).cuda_stream)
-    _lib.check(rc, "lft_refocus")
+    _lib.enqueue("lft_refocus", lf.device, lf.data_ptr() or None, _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), D, TAPS[interp],
+                 out.data_ptr() or None, _CLASS[out_dtype])
     return {"views5": lambda: out[0], "views4": lambda: out[0, ..., 0], "mosaic": lambda: out[0, ..., 0],
             "batch": lambda: out[..., 0]}[kind]()
 

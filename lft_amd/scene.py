@@ -13,7 +13,7 @@ from . import _lib
 
 def scene_counts(h0: int, w0: int, patch: int = 32, stride: int = 16):
     nu, nv = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(_lib.lib().lft_scene_counts(h0, w0, patch, stride, ctypes.byref(nu), ctypes.byref(nv)), "lft_scene_counts")
+    _lib.call("lft_scene_counts", h0, w0, patch, stride, ctypes.byref(nu), ctypes.byref(nv))
     return nu.value, nv.value
 
 
@@ -26,9 +26,7 @@ def divide(scene: torch.Tensor, ang: int, patch: int = 32, stride: int = 16) -> 
     nu, nv = scene_counts(h0, w0, patch, stride)
     x = scene.contiguous().float()
     out = torch.empty((nu * nv, 1, ang * patch, ang * patch), dtype=torch.float32, device=scene.device)
-    with torch.cuda.device(scene.device):
-        _lib.check(_lib.lib().lft_scene_divide(x.data_ptr(), out.data_ptr(), ang, h0, w0, patch, stride,
-                                               torch.cuda.current_stream(scene.device).cuda_stream), "lft_scene_divide")
+    _lib.enqueue("lft_scene_divide", scene.device, x.data_ptr(), out.data_ptr(), ang, h0, w0, patch, stride)
     return out
 
 
@@ -36,9 +34,7 @@ def integrate(sr_patches: torch.Tensor, ang: int, h0: int, w0: int, scale: int, 
     """sr_patches: float32 [numU*numV, 1, A*patch*s, A*patch*s] -> SR scene mosaic [A*h0*s, A*w0*s]."""
     x = sr_patches.contiguous().float()
     out = torch.empty((ang * h0 * scale, ang * w0 * scale), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().lft_scene_integrate(x.data_ptr(), out.data_ptr(), ang, h0, w0, patch, stride, scale,
-                                                  torch.cuda.current_stream(x.device).cuda_stream), "lft_scene_integrate")
+    _lib.enqueue("lft_scene_integrate", x.device, x.data_ptr(), out.data_ptr(), ang, h0, w0, patch, stride, scale)
     return out
 
 
@@ -48,9 +44,7 @@ def integrate_ensemble(sr_variants: torch.Tensor, mask: int, ang: int, h0: int, 
     variants of a patch adjacent, as lft_amd.ensemble.expand lays them out) -> SR scene mosaic [A*h0*s, A*w0*s]."""
     x = sr_variants.contiguous().float()
     out = torch.empty((ang * h0 * scale, ang * w0 * scale), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().lft_scene_integrate_ens(x.data_ptr(), out.data_ptr(), mask, ang, h0, w0, patch, stride, scale,
-                                                      torch.cuda.current_stream(x.device).cuda_stream), "lft_scene_integrate_ens")
+    _lib.enqueue("lft_scene_integrate_ens", x.device, x.data_ptr(), out.data_ptr(), mask, ang, h0, w0, patch, stride, scale)
     return out
 
 

@@ -30,25 +30,18 @@ from .params import param_table
 
 
 def tape_bytes(B, A, h, w, s) -> int:
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_train_tape_bytes(B, A, h, w, s, ctypes.byref(n)), "lft_train_tape_bytes")
-    return n.value
+    return _lib.query("lft_train_tape_bytes", B, A, h, w, s)
 
 
 def grad_floats(s) -> int:
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_train_grad_floats(s, ctypes.byref(n)), "lft_train_grad_floats")
-    return n.value
+    return _lib.query("lft_train_grad_floats", s)
 
 
 def tape_view(tape: torch.Tensor, name: str, B, A, h, w, s, shape) -> torch.Tensor:
     """A saved activation of the last lft_train_forward as a tensor view (tests / debugging)."""
-    off = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_train_tape_offset(name.encode(), B, A, h, w, s, ctypes.byref(off)), "lft_train_tape_offset")
-    n = 1
-    for d in shape:
-        n *= d
-    return tape.view(torch.float32)[off.value:off.value + n].view(*shape)
+    off = _lib.query("lft_train_tape_offset", name.encode(), B, A, h, w, s)
+    n = torch.Size(shape).numel()
+    return tape.view(torch.float32)[off:off + n].view(*shape)
 
 
 def _check_params(ps: List[torch.Tensor], dev) -> None:
@@ -59,10 +52,7 @@ def _check_params(ps: List[torch.Tensor], dev) -> None:
             raise _lib.LftError(f"all parameters must be contiguous float32 tensors on {dev}; call net.to(device) first")
 
 
-def _ptr_array(ps):
-    return (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-
-
+_ptr_array = _lib.ptr_array
 MATH = {"fp32": _lib.MATH_F32, "bf16x3": _lib.MATH_BF16X3, "bf16x6": _lib.MATH_BF16X6}
 # HIP-graph captures use the thread-local error mode: with a process group alive, torch's NCCL watchdog THREAD polls its work
 # events (hipEventQuery) at any time; under the default global mode such a call from another thread while this thread captures
@@ -80,9 +70,7 @@ def train_forward(ps, lr, A, s, tape=None, math="fp32"):
     if tape is None:
         tape = torch.empty(tape_bytes(B, A, h, w, s), dtype=torch.uint8, device=dev)
     out = torch.empty((B, 1, H * s, W * s), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.lib().lft_train_forward(_ptr_array(ps), len(ps), lr.data_ptr(), out.data_ptr(), tape.data_ptr(),
-                                            B, A, h, w, s, MATH[math], stream), "lft_train_forward")
+    _lib.enqueue("lft_train_forward", dev, _ptr_array(ps), len(ps), lr.data_ptr(), out.data_ptr(), tape.data_ptr(), B, A, h, w, s, MATH[math])
     return out, tape
 
 
@@ -94,17 +82,14 @@ def train_backward(ps, lr, tape, dout, A, s, grads=None, math="fp32", d_lr=None)
     dev = lr.device
     if grads is None:
         grads = torch.empty(grad_floats(s), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     if d_lr is None:
-        _lib.check(_lib.lib().lft_train_backward(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(), grads.data_ptr(),
-                                                 B, A, h, w, s, MATH[math], stream),
-                   "lft_train_backward")
+        _lib.enqueue("lft_train_backward", dev, _ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(), grads.data_ptr(),
+                     B, A, h, w, s, MATH[math])
     else:
         if d_lr.shape != lr.shape or d_lr.dtype != torch.float32 or not d_lr.is_contiguous() or d_lr.device != dev:
             raise _lib.LftError(f"d_lr must be a contiguous float32 tensor of shape {tuple(lr.shape)} on {dev}")
-        _lib.check(_lib.lib().lft_train_backward_input(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(),
-                                                       grads.data_ptr(), d_lr.data_ptr(), B, A, h, w, s, MATH[math], stream),
-                   "lft_train_backward_input")
+        _lib.enqueue("lft_train_backward_input", dev, _ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(),
+                     grads.data_ptr(), d_lr.data_ptr(), B, A, h, w, s, MATH[math])
     return grads
 
 
@@ -113,9 +98,7 @@ def lr_grad_bwd(w0, dx0, dout, A, s, B, h, w):
     w0 = conv_init0.0.weight; dout [B,1,A*h*s,A*w*s] or None (the conv term alone)."""
     dev = dx0.device
     d_lr = torch.empty((B, 1, A * h, A * w), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.lib().lft_lr_grad_bwd(w0.data_ptr(), dx0.data_ptr(), None if dout is None else dout.data_ptr(), d_lr.data_ptr(),
-                                          B, A, h, w, s, stream), "lft_lr_grad_bwd")
+    _lib.enqueue("lft_lr_grad_bwd", dev, w0.data_ptr(), dx0.data_ptr(), None if dout is None else dout.data_ptr(), d_lr.data_ptr(), B, A, h, w, s)
     return d_lr
 
 
@@ -127,18 +110,14 @@ def block_backward(ps, lr, tape, block, layer, d_out, A, s, grads, math="fp32"):
     h, w = H // A, W // A
     dev = lr.device
     d_in = None if block == _lib.BLOCK_INIT else torch.empty((B, A * A, h, w, 64), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.lib().lft_train_block_backward(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), block, layer, d_out.data_ptr(),
-                                                   None if d_in is None else d_in.data_ptr(), grads.data_ptr(), B, A, h, w, s, MATH[math], stream),
-               "lft_train_block_backward")
+    _lib.enqueue("lft_train_block_backward", dev, _ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), block, layer, d_out.data_ptr(),
+                 None if d_in is None else d_in.data_ptr(), grads.data_ptr(), B, A, h, w, s, MATH[math])
     return d_in
 
 
 def grad_bucket(s: int, bucket: int):
     """(first_float, n_floats) of gradient bucket `bucket` in the flat buffer (include/lft_hip.h: lft_train_grad_bucket)."""
-    first, count = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_train_grad_bucket(s, bucket, ctypes.byref(first), ctypes.byref(count)), "lft_train_grad_bucket")
-    return first.value, count.value
+    return _lib.query("lft_train_grad_bucket", s, bucket)
 
 
 def train_backward_buckets(ps, lr, tape, dout, A, s, grads, on_bucket, math="fp32"):
@@ -148,8 +127,6 @@ def train_backward_buckets(ps, lr, tape, dout, A, s, grads, on_bucket, math="fp3
     LFT_ERR_CALLBACK) and is re-raised here."""
     B, _, H, W = lr.shape
     h, w = H // A, W // A
-    dev = lr.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
     err = []
 
     def trampoline(_user, bucket, first, count):
@@ -162,7 +139,7 @@ def train_backward_buckets(ps, lr, tape, dout, A, s, grads, on_bucket, math="fp3
 
     cb = _lib.BUCKET_FN(trampoline)
     rc = _lib.lib().lft_train_backward_buckets(_ptr_array(ps), len(ps), lr.data_ptr(), tape.data_ptr(), dout.data_ptr(), grads.data_ptr(),
-                                               B, A, h, w, s, MATH[math], stream,
+                                               B, A, h, w, s, MATH[math], _lib.stream_ptr(lr.device),
                                                ctypes.cast(cb, ctypes.c_void_p), None)
     if err:
         raise err[0]
@@ -172,33 +149,32 @@ def train_backward_buckets(ps, lr, tape, dout, A, s, grads, on_bucket, math="fp3
 
 # ---------------------------------------------------------------------------------------------- guarded Adam step
 def guard_bytes(nseg: int) -> int:
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_guard_bytes(nseg, ctypes.byref(n)), "lft_guard_bytes")
-    return n.value
+    return _lib.query("lft_guard_bytes", nseg)
+
+
+def guard_init(guard: torch.Tensor, segments, n: int, steps_applied0: int = 0) -> None:
+    """lft_guard_init on the current stream of the block's device; segments: (first, count, trainable) triples that tile [0, n) ascending."""
+    segs = (_lib.GuardSegment * len(segments))(*[_lib.GuardSegment(int(f), int(c), int(bool(t))) for f, c, t in segments])
+    _lib.enqueue("lft_guard_init", guard.device, guard.data_ptr(), segs, len(segments), n, steps_applied0)
 
 
 def guard_new(segments, n: int, device, steps_applied0: int = 0) -> torch.Tensor:
-    """A guard block (include/lft_hip.h: lft_guard_init) for a flat buffer of n floats; segments: (first, count, trainable) triples
-    that tile [0, n) in ascending order.  Enqueued on the current stream of `device`."""
-    segs = (_lib.GuardSegment * len(segments))(*[_lib.GuardSegment(int(f), int(c), int(bool(t))) for f, c, t in segments])
+    """A guard block (include/lft_hip.h: lft_guard_init) for a flat buffer of n floats.  Enqueued on the current stream of `device`."""
     guard = torch.empty(guard_bytes(len(segments)), dtype=torch.uint8, device=device)
-    _lib.check(_lib.lib().lft_guard_init(guard.data_ptr(), segs, len(segments), n, steps_applied0,
-                                         torch.cuda.current_stream(guard.device).cuda_stream), "lft_guard_init")
+    guard_init(guard, segments, n, steps_applied0)
     return guard
 
 
 def adam_step_guarded(p, g, m, v, guard, lr, beta1=0.9, beta2=0.999, eps=1e-8, gscale=1.0, weight_decay=0.0, max_norm=None):
     """lft_adam_step_guarded on flat fp32 tensors; max_norm None (or <= 0, or inf): no clipping.  Only enqueues."""
-    _lib.check(_lib.lib().lft_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
-                                                gscale, weight_decay, 0.0 if max_norm is None else max_norm, guard.data_ptr(),
-                                                torch.cuda.current_stream(p.device).cuda_stream), "lft_adam_step_guarded")
+    _lib.enqueue("lft_adam_step_guarded", p.device, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
+                 gscale, weight_decay, 0.0 if max_norm is None else max_norm, guard.data_ptr())
 
 
 def guard_read(guard: torch.Tensor) -> _lib.GuardReport:
     """lft_guard_read: the report of the last guarded step and the counters.  SYNCHRONISES the current stream."""
     rep = _lib.GuardReport()
-    _lib.check(_lib.lib().lft_guard_read(guard.data_ptr(), torch.cuda.current_stream(guard.device).cuda_stream, ctypes.byref(rep)),
-               "lft_guard_read")
+    _lib.call("lft_guard_read", guard.data_ptr(), _lib.stream_ptr(guard.device), ctypes.byref(rep))
     return rep
 
 
@@ -212,9 +188,8 @@ def ema_decay_at(decay: float, warmup: bool, t: int) -> float:
 def ema_update(ema, p, decay, warmup=True, step=0, guard=None):
     """lft_ema_update on flat fp32 tensors: ema += (1 - d_t) * (p - ema).  With a guard block t is its steps_applied and a skipped
     step or a frozen segment leaves ema alone; without one t = step.  Only enqueues."""
-    _lib.check(_lib.lib().lft_ema_update(ema.data_ptr(), p.data_ptr(), p.numel(), decay, int(bool(warmup)), int(step),
-                                         None if guard is None else guard.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream),
-               "lft_ema_update")
+    _lib.enqueue("lft_ema_update", p.device, ema.data_ptr(), p.data_ptr(), p.numel(), decay, int(bool(warmup)), int(step),
+                 None if guard is None else guard.data_ptr())
 
 
 # ---------------------------------------------------------------------------------------------- saved optimizer state
@@ -267,8 +242,7 @@ class LFTFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lr, A, s, math, *params):
         ps = [p.detach() for p in params]
-        with torch.cuda.device(lr.device):
-            out, tape = train_forward(ps, lr, A, s, math=math)
+        out, tape = train_forward(ps, lr, A, s, math=math)
         ctx.A, ctx.s, ctx.tape, ctx.lr, ctx.math = A, s, tape, lr, math
         ctx.save_for_backward(*params)
         return out
@@ -277,8 +251,7 @@ class LFTFunction(torch.autograd.Function):
     def backward(ctx, dout):
         ps = [p.detach() for p in ctx.saved_tensors]
         d_lr = torch.empty_like(ctx.lr) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(dout.device):
-            flat = train_backward(ps, ctx.lr, ctx.tape, dout.contiguous().float(), ctx.A, ctx.s, math=ctx.math, d_lr=d_lr)
+        flat = train_backward(ps, ctx.lr, ctx.tape, dout.contiguous().float(), ctx.A, ctx.s, math=ctx.math, d_lr=d_lr)
         ctx.tape = None
         grads, off = [], 0
         for i, p in enumerate(ps):
@@ -356,8 +329,7 @@ class TrainStep:
             table = param_table(net.channels, self.s)
             assert [tuple(p.shape) for p in ps] == [tuple(sh) for _, sh, _ in table]
             self.segment_names = [name for name, _, _ in table]
-            with torch.cuda.device(dev):
-                self._guard = guard_new(self._segments, n, dev)
+            self._guard = guard_new(self._segments, n, dev)
         # Replicas must start from the same weights (the reference has no DP; torch's DDP broadcasts rank 0's
         # parameters at construction): a network built from scratch draws its weights from this process's own RNG.
         from .dp import broadcast_
@@ -397,14 +369,11 @@ class TrainStep:
         return self._loss_scratch[key]
 
     def _fwd_loss_bwd(self, lr_in, hr, tape, dout, loss, on_bucket=None):
-        L = _lib.lib()
-        dev = lr_in.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
         out, _ = train_forward(self.params, lr_in, self.A, self.s, tape=tape, math=self.math)
         n = out.numel()
         if self.loss is None:
-            _lib.check(L.lft_l1_loss(out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, loss.data_ptr(),
-                                     self._scratch.data_ptr(), stream), "lft_l1_loss")
+            _lib.enqueue("lft_l1_loss", lr_in.device, out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, loss.data_ptr(),
+                         self._scratch.data_ptr())
         else:
             from .loss import lf_loss, ssim_loss
             lf = self.loss.has_lf_terms()
@@ -481,7 +450,6 @@ class TrainStep:
         dev = lr_in.device
         B, _, H, W = lr_in.shape
         h, w = H // self.A, W // self.A
-        L = _lib.lib()
         exchange = self.exchange and dp.dp_active(self.group)
         handles = []
 
@@ -509,12 +477,10 @@ class TrainStep:
                                                    on_bucket=start_bucket if exchange else None)
             dp.sum_gradients_finish(handles)                   # the Adam kernel is ordered after the collectives
             gscale = dp.grad_scale(self.group) if exchange else 1.0
-            stream = torch.cuda.current_stream(dev).cuda_stream
             self.t += 1                    # calls of step(); with the guard Adam's own counter is steps_applied in the guard block
             if self._guard is None:
-                _lib.check(L.lft_adam_step(self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                           self.flat_params.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.t,
-                                           gscale, self.weight_decay, stream), "lft_adam_step")
+                _lib.enqueue("lft_adam_step", dev, self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                             self.flat_params.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.t, gscale, self.weight_decay)
             else:
                 adam_step_guarded(self.flat_params, self.flat_grads, self.m, self.v, self._guard, self.lr, self.betas[0], self.betas[1],
                                   self.eps, gscale, self.weight_decay, self.max_grad_norm)
@@ -599,7 +565,6 @@ class TrainStep:
         own["ema"] = self.ema is not None
         for line in check_state(sd, own):
             log.warning("training state: %s", line)
-        dev = self.flat_params.device
         with torch.no_grad():
             self.m.copy_(sd["m"])
             self.v.copy_(sd["v"])
@@ -607,10 +572,7 @@ class TrainStep:
                 self.ema.copy_(sd["ema"])
         self.t = int(sd["t"])
         if self.guard:
-            with torch.cuda.device(dev):
-                segs = (_lib.GuardSegment * len(self._segments))(*[_lib.GuardSegment(int(f), int(c), int(t)) for f, c, t in self._segments])
-                _lib.check(_lib.lib().lft_guard_init(self._guard.data_ptr(), segs, len(segs), self.flat_params.numel(),
-                                                     int(sd["steps_applied"]), torch.cuda.current_stream(dev).cuda_stream), "lft_guard_init")
+            guard_init(self._guard, self._segments, self.flat_params.numel(), int(sd["steps_applied"]))
             self._counter0 = {k: int(sd[k]) for k in ("steps_skipped", "steps_clipped")}
 
 

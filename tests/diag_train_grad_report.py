@@ -24,8 +24,7 @@ for (A, s, B, h, w) in cases:
     out, tape = T.train_forward(ps, lr.cuda(), A, s)
     n = out.numel()
     dout = torch.empty_like(out); scr = torch.empty(1025, device="cuda")
-    _lib.check(_lib.lib().lft_l1_loss(out.data_ptr(), hr.cuda().data_ptr(), n, dout.data_ptr(), 1.0 / n, scr[1024:].data_ptr(), scr.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream), "l1")
+    _lib.enqueue("lft_l1_loss", "cuda", out.data_ptr(), hr.cuda().data_ptr(), n, dout.data_ptr(), 1.0 / n, scr[1024:].data_ptr(), scr.data_ptr())
     flat = T.train_backward(ps, lr.cuda(), tape, dout, A, s).cpu()
     off, rows = 0, []
     for name, p in zip(names, ps):

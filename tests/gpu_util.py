@@ -1,11 +1,9 @@
 """Helpers for the -m gpu parity tests: call liblft_hip.so's per-stage C-ABI entry points on torch
 device tensors and bring results back in the oracle's [B,C,V,h,w] layout."""
-import ctypes
-
 import numpy as np
 import torch
 
-from lft_amd import _lib
+from lft_amd import _lib, module
 from lft_amd.params import deterministic_state, param_table, synthetic_lr
 
 DEV = "cuda:0"
@@ -25,10 +23,7 @@ class Packed:
         self.prec_name, self.prec = prec, PRECS[prec]
         names = [n for n, _, _ in param_table(64, s)]
         self.params = [torch.from_numpy(sd_np[n]).to(DEV).contiguous() for n in names]
-        self.buf = torch.empty(_lib.packed_bytes(A, h, w, s, self.prec), dtype=torch.uint8, device=DEV)
-        arr = (ctypes.c_void_p * len(self.params))(*[p.data_ptr() for p in self.params])
-        _lib.check(_lib.lib().lft_pack_weights(arr, len(self.params), self.buf.data_ptr(), A, h, w, s, self.prec, stream()),
-                   "lft_pack_weights")
+        self.buf = module.pack_weights(self.params, A, h, w, s, self.prec, stream())
         # work=False: for the entry points that take no workspace (lft_ang_block_fwd) at sizes where it would be hundreds of MiB
         self.work = torch.empty(_lib.workspace_bytes(B, A, h, w, s, self.prec), dtype=torch.uint8, device=DEV) if work else None
         torch.cuda.synchronize()
@@ -77,14 +72,12 @@ def guard_intact(buf):
 
 
 def status_reset(pk):
-    _lib.check(_lib.lib().lft_status_reset(pk.work.data_ptr(), *pk.dims(), stream()), "lft_status_reset")
+    module.status_reset(pk.work, *pk.dims(), stream())
 
 
 def status_flags(pk):
     """(return code, flag word) of lft_status_read: (0, 0) unless a kernel saw a non-finite value since the reset."""
-    flags = ctypes.c_uint(0)
-    rc = _lib.lib().lft_status_read(pk.work.data_ptr(), *pk.dims(), stream(), ctypes.byref(flags))
-    return rc, flags.value
+    return module.status_read(pk.work, *pk.dims(), stream())
 
 
 def to_act(x_bcvhw: torch.Tensor, prec: str) -> torch.Tensor:

@@ -102,10 +102,8 @@ def _merge_raw(t, angres, scale, sr_t, wh_t, ih_t, ww_t, iw_t, out_t, **kw):
              minv=(ctypes.c_double * 9)(*colour.inverse_matrix().reshape(-1)), out=out_t.data_ptr(),
              out_cls=colour._OUT_CLASS[out_t.dtype])
     a.update(kw)
-    rc = _lib.lib().lft_colour_merge(a["lf"], a["cls"], a["U"], a["V"], a["H"], a["W"], a["C"], a["strides"], a["A"], a["s"], a["sr"],
-                                     a["wh"], a["ih"], a["ph"], a["ww"], a["iw"], a["pw"], a["minv"], a["out"], a["out_cls"],
-                                     torch.cuda.current_stream(DEV).cuda_stream)
-    _lib.check(rc, "lft_colour_merge")
+    _lib.enqueue("lft_colour_merge", DEV, a["lf"], a["cls"], a["U"], a["V"], a["H"], a["W"], a["C"], a["strides"], a["A"], a["s"], a["sr"],
+                 a["wh"], a["ih"], a["ph"], a["ww"], a["iw"], a["pw"], a["minv"], a["out"], a["out_cls"])
 
 
 def test_merge_fallback_path_gives_the_same_bits():
@@ -134,7 +132,6 @@ def test_merge_fallback_path_gives_the_same_bits():
 
 
 def test_refusals_enqueue_nothing_and_calls_repeat():
-    L = _lib.lib()
     A, s, H, W = 3, 2, 6, 5
     t = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (5, 5, H, W, 3)).astype(np.uint8)).to(DEV)
     sr = torch.rand(A * s * H, A * s * W, device=DEV)
@@ -145,7 +142,6 @@ def test_refusals_enqueue_nothing_and_calls_repeat():
     y = torch.full((A * H, A * W), -7.0, device=DEV)
     st = (ctypes.c_longlong * 5)(*t.stride())
     neg = (ctypes.c_longlong * 5)(*[-x if k == 2 else x for k, x in enumerate(t.stride())])
-    stream = torch.cuda.current_stream(DEV).cuda_stream
 
     bad_lf = [dict(cls=3), dict(cls=-1), dict(C=2), dict(C=0), dict(A=0), dict(A=-1), dict(A=7), dict(A=4), dict(U=6), dict(V=4),
               dict(U=2), dict(H=0), dict(W=-3), dict(U=0), dict(lf=None), dict(strides=None), dict(strides=neg)]
@@ -161,7 +157,7 @@ def test_refusals_enqueue_nothing_and_calls_repeat():
     def luma_raw(**kw):
         a = dict(lf=t.data_ptr(), cls=_lib.LF_UINT8, U=5, V=5, H=H, W=W, C=3, strides=st, A=A, y=y.data_ptr())
         a.update(kw)
-        _lib.check(L.lft_lf_luma(a["lf"], a["cls"], a["U"], a["V"], a["H"], a["W"], a["C"], a["strides"], a["A"], a["y"], stream), "lft_lf_luma")
+        _lib.enqueue("lft_lf_luma", DEV, a["lf"], a["cls"], a["U"], a["V"], a["H"], a["W"], a["C"], a["strides"], a["A"], a["y"])
 
     for kw in bad_lf + [dict(y=None)]:
         with pytest.raises(LftError, match="lft_lf_luma") as e:

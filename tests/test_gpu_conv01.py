@@ -65,7 +65,7 @@ def test_recomputed_x0_is_bit_identical_to_k_conv0(case, prec):
     lr = case["lr"].to(G.DEV)
     x0 = [pk.new_act().fill_(7.0) for _ in range(2)]
     for recomputed in (0, 1):
-        _lib.check(_lib.lib().lft_conv0_fwd(pk.buf.data_ptr(), lr.data_ptr(), x0[recomputed].data_ptr(), recomputed, *pk.dims(), G.stream()), "conv0")
+        _lib.call("lft_conv0_fwd", pk.buf.data_ptr(), lr.data_ptr(), x0[recomputed].data_ptr(), recomputed, *pk.dims(), G.stream())
     torch.cuda.synchronize()
     ref = G.from_act(x0[0])
     exact = O.conv_views(O.mosaic_to_views(case["lr"], case["A"]), case["sd"]["conv_init0.0.weight"])

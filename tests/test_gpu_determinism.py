@@ -23,8 +23,7 @@ def test_forward_is_bitwise_repeatable(prec):
     reps = {"bf16": 400, "fp16": 200, "fp32": 60}[prec]
     outs = []
     for _ in range(reps):
-        _lib.check(_lib.lib().lft_forward(pk.buf.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream()),
-                   "forward")
+        _lib.call("lft_forward", pk.buf.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
         torch.cuda.synchronize()
         outs.append(out.clone())
     ref = outs[-1]
@@ -40,8 +39,7 @@ def test_init_features_is_bitwise_repeatable():
     base, bad = None, 0
     for _ in range(1500):
         act = pk.new_act()
-        _lib.check(_lib.lib().lft_init_features_fwd(pk.buf.data_ptr(), lr.data_ptr(), act.data_ptr(), pk.work.data_ptr(), *pk.dims(),
-                                                    G.stream()), "init_features")
+        _lib.call("lft_init_features_fwd", pk.buf.data_ptr(), lr.data_ptr(), act.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
         torch.cuda.synchronize()
         if base is None:
             base = act.clone()

@@ -74,7 +74,7 @@ def rand(shape, *seed):
 
 
 def call(name, *args):
-    _lib.check(getattr(_lib.lib(), name)(*args, G.stream()), name)
+    _lib.call(name, *args, G.stream())
     torch.cuda.synchronize()
 
 

@@ -144,8 +144,8 @@ def test_clipped_step_matches_fp64_reference(step, wd, mode):
     U.check_step(b.pmv64(), ref, p.astype(np.float64), f"step {step} wd {wd} {mode}")
     if mode != "half":                                                        # reported, not gated: coef == 1 against the unguarded kernel
         u = Bufs(p, g, m, v)
-        _lib.check(_lib.lib().lft_adam_step(u.t[0].data_ptr(), u.t[1].data_ptr(), u.t[2].data_ptr(), u.t[3].data_ptr(), n, U.LR, U.B1, U.B2,
-                                            U.EPS, step, U.GSCALE, wd, G.stream()), "lft_adam_step")
+        _lib.call("lft_adam_step", u.t[0].data_ptr(), u.t[1].data_ptr(), u.t[2].data_ptr(), u.t[3].data_ptr(), n, U.LR, U.B1, U.B2, U.EPS, step,
+                  U.GSCALE, wd, G.stream())
         diff = [int((x.view(np.int32) != y.view(np.int32)).sum()) for x, y in zip(b.host(), u.host())]
         print(f"elements that differ from lft_adam_step on the same inputs (p, g, m, v): {diff} of {n}")
 

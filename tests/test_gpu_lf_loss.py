@@ -9,14 +9,13 @@ the restatement run in fp32 by torch on the CPU -- shows against fp64 on these v
 (test_gpu_tolerances_are_4x_fp32_torch) measures that level without a GPU: over every shape, weight pair and eps below, for MSE and
 Charbonnier, the worst gradient error is 1.99e-7 of the largest gradient element (the worst relative loss error 1.5e-7, held here to
 the project's LOSS_RTOL)."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-from lft_amd import _lib
+from lft_amd import _lib, loss
 
 import gpu_util as G
 import lf_loss_util as U
@@ -46,10 +45,9 @@ def padding_intact(buf, view_len, shift=0):
 
 
 def scratch_floats(B, A, H, W):
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_lf_loss_scratch_bytes(B, A, H, W, ctypes.byref(n)), "lft_lf_loss_scratch_bytes")
-    assert n.value % 8 == 0
-    return n.value // 4
+    n = loss.scratch_bytes(B, A, H, W)
+    assert n % 8 == 0
+    return n // 4
 
 
 class Call:

@@ -56,8 +56,8 @@ def test_l1_loss(n, with_dsr):
     dsr = torch.full((n + guard,), 7.0, device=G.DEV)
     loss = torch.full((1,), -1.0, device=G.DEV)
     scratch = torch.zeros(1024, device=G.DEV)
-    _lib.check(_lib.lib().lft_l1_loss(d_sr.data_ptr(), d_hr.data_ptr(), n, dsr.data_ptr() if with_dsr else None, float(gscale),
-                                      loss.data_ptr(), scratch.data_ptr(), G.stream()), "lft_l1_loss")
+    _lib.call("lft_l1_loss", d_sr.data_ptr(), d_hr.data_ptr(), n, dsr.data_ptr() if with_dsr else None, float(gscale), loss.data_ptr(),
+              scratch.data_ptr(), G.stream())
     torch.cuda.synchronize()
     got = float(loss.cpu())
     print(f"n={n}: loss {got:.9g} ref {ref_loss:.9g} rel {abs(got - ref_loss) / max(ref_loss, 1e-300):.2e}")
@@ -138,8 +138,8 @@ def test_adam_step(step, wd):
         b = torch.full((ADAM_N + guard,), 7.0, device=G.DEV)
         b[:ADAM_N] = a
         bufs.append(b)
-    _lib.check(_lib.lib().lft_adam_step(bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[3].data_ptr(), ADAM_N,
-                                        ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS, step, ADAM_GSCALE, wd, G.stream()), "lft_adam_step")
+    _lib.call("lft_adam_step", bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[3].data_ptr(), ADAM_N, ADAM_LR, ADAM_B1, ADAM_B2,
+              ADAM_EPS, step, ADAM_GSCALE, wd, G.stream())
     torch.cuda.synchronize()
     out = [b.cpu().double().numpy() for b in bufs]
     for b in out:

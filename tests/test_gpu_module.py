@@ -97,10 +97,8 @@ def test_full_size_properties_cfg4_cfg5(A, s, B, h, w):
     with torch.no_grad():
         dict(ref32.named_parameters())["upsampling.3.weight"].zero_()
         skip_only = ref32(lr[:1])
-    from lft_amd import _lib
     bic = torch.empty_like(skip_only)
-    _lib.check(_lib.lib().lft_bicubic_fwd(lr[:1].contiguous().data_ptr(), bic.data_ptr(), 1, A, h, w, s,
-                                          torch.cuda.current_stream().cuda_stream), "lft_bicubic_fwd")
+    _lib.enqueue("lft_bicubic_fwd", lr.device, lr[:1].contiguous().data_ptr(), bic.data_ptr(), 1, A, h, w, s)
     torch.cuda.synchronize()
     assert torch.equal(skip_only, bic)
 
@@ -278,24 +276,23 @@ def test_status_word_through_the_c_abi():
     params = [torch.from_numpy(sd[n]).to("cuda:0") for n, _, _ in param_table(64, s)]
     L = _lib.lib()
     st = torch.cuda.current_stream().cuda_stream
-    packed = torch.empty(_lib.packed_bytes(A, h, w, s, prec), dtype=torch.uint8, device="cuda:0")
-    arr = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-    _lib.check(L.lft_pack_weights(arr, len(params), packed.data_ptr(), A, h, w, s, prec, st), "pack")
+    from lft_amd.module import pack_weights
+    packed = pack_weights(params, A, h, w, s, prec, st)
     work = torch.empty(_lib.workspace_bytes(B, A, h, w, s, prec), dtype=torch.uint8, device="cuda:0")
     work.fill_(0xFF)                                              # garbage, as a fresh allocation may hold
     dims = (B, A, h, w, s, prec)
-    _lib.check(L.lft_status_reset(work.data_ptr(), *dims, st), "reset")
+    _lib.call("lft_status_reset", work.data_ptr(), *dims, st)
     lr = torch.from_numpy(synthetic_lr(B, A, h, w, seed=0)).to("cuda:0")
     out = torch.empty(B, 1, A * h * s, A * w * s, device="cuda:0")
     flags = ctypes.c_uint(7)
-    _lib.check(L.lft_forward(packed.data_ptr(), lr.data_ptr(), out.data_ptr(), work.data_ptr(), *dims, st), "forward")
+    _lib.call("lft_forward", packed.data_ptr(), lr.data_ptr(), out.data_ptr(), work.data_ptr(), *dims, st)
     assert L.lft_status_read(work.data_ptr(), *dims, st, ctypes.byref(flags)) == 0 and flags.value == 0
     lr[0, 0, 5, 5] = float("inf")
-    _lib.check(L.lft_forward(packed.data_ptr(), lr.data_ptr(), out.data_ptr(), work.data_ptr(), *dims, st), "forward")
+    _lib.call("lft_forward", packed.data_ptr(), lr.data_ptr(), out.data_ptr(), work.data_ptr(), *dims, st)
     assert L.lft_status_read(work.data_ptr(), *dims, st, ctypes.byref(flags)) == _lib.STATUS_NONFINITE and flags.value == 1
     assert b"non-finite" in L.lft_last_error()
     assert L.lft_status_read(work.data_ptr(), *dims, st, None) == _lib.STATUS_NONFINITE      # sticky until reset
-    _lib.check(L.lft_status_reset(work.data_ptr(), *dims, st), "reset")
+    _lib.call("lft_status_reset", work.data_ptr(), *dims, st)
     assert L.lft_status_read(work.data_ptr(), *dims, st, ctypes.byref(flags)) == 0 and flags.value == 0
     assert L.lft_status_read(None, *dims, st, None) == -1
 

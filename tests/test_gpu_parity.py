@@ -96,8 +96,7 @@ def test_mfma_fragment_layout(prec):
     C = torch.zeros(32, 32, device=G.DEV)
     D = torch.zeros(32, 32, device=G.DEV)
     a, b, w2 = Am.to(G.DEV), Bm.to(G.DEV), W2.to(G.DEV)
-    _lib.check(_lib.lib().lft_mfma_selftest(a.data_ptr(), b.data_ptr(), w2.data_ptr(), C.data_ptr(), D.data_ptr(),
-                                            G.PRECS[prec], G.stream()), "selftest")
+    _lib.call("lft_mfma_selftest", a.data_ptr(), b.data_ptr(), w2.data_ptr(), C.data_ptr(), D.data_ptr(), G.PRECS[prec], G.stream())
     torch.cuda.synchronize()
     Cref = Am @ Bm
     assert torch.equal(C.cpu(), Cref), "C = A*B layout wrong"
@@ -112,7 +111,7 @@ def test_bicubic(A, h, w, s):
     lr = torch.from_numpy(synthetic_lr(2, A, h, w, seed=3))
     out = torch.empty(2, 1, A * h * s, A * w * s, device=G.DEV)
     x = lr.to(G.DEV)
-    _lib.check(_lib.lib().lft_bicubic_fwd(x.data_ptr(), out.data_ptr(), 2, A, h, w, s, G.stream()), "bicubic")
+    _lib.call("lft_bicubic_fwd", x.data_ptr(), out.data_ptr(), 2, A, h, w, s, G.stream())
     torch.cuda.synchronize()
     ref = O.bicubic_skip(lr, A, s)
     assert (out.cpu() - ref).abs().max() <= 2e-6, G.err_report(out.cpu(), ref)
@@ -225,8 +224,7 @@ def run_init_features(case, prec):
     pk = begin(case, prec)
     lr = case["lr"].to(G.DEV)
     buf, act = G.guarded(pk.new_act().shape, G.ACT_DTYPE[prec])
-    _lib.check(_lib.lib().lft_init_features_fwd(pk.buf.data_ptr(), lr.data_ptr(), act.data_ptr(), pk.work.data_ptr(),
-                                                *pk.dims(), G.stream()), "init_features")
+    _lib.call("lft_init_features_fwd", pk.buf.data_ptr(), lr.data_ptr(), act.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
     end(case, pk, buf, "init_features")
     check(G.from_act(act), case["taps"]["feat"], prec, "init_features",
           lambda: LP.init_features(case["sd"], O.mosaic_to_views(case["lr"], case["A"]), prec), per_view=case["per_view"])
@@ -240,8 +238,8 @@ def run_spa_block(case, prec, layer, with_skip):
     if with_skip:
         ref = ref + G.from_act(skip)
     buf, act = G.guarded(pk.new_act().shape, G.ACT_DTYPE[prec])
-    _lib.check(_lib.lib().lft_spa_block_fwd(pk.buf.data_ptr(), layer, xin.data_ptr(), skip.data_ptr() if with_skip else None,
-                                            act.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream()), "spa_block")
+    _lib.call("lft_spa_block_fwd", pk.buf.data_ptr(), layer, xin.data_ptr(), skip.data_ptr() if with_skip else None, act.data_ptr(),
+              pk.work.data_ptr(), *pk.dims(), G.stream())
     end(case, pk, buf, f"spa_block{layer}")
     check(G.from_act(act), ref, prec, f"spa_block{layer}",
           lambda: LP.spa_block(case["sd"], layer, G.from_act(xin), prec, case["mask"], G.from_act(skip) if with_skip else None),
@@ -254,8 +252,7 @@ def run_upsample(case, prec):
     lr = case["lr"].to(G.DEV)
     A, s, B, h, w = case["shape"]
     buf, out = G.guarded((B, 1, A * h * s, A * w * s), torch.float32)
-    _lib.check(_lib.lib().lft_upsample_fwd(pk.buf.data_ptr(), xin.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(),
-                                           *pk.dims(), G.stream()), "upsample")
+    _lib.call("lft_upsample_fwd", pk.buf.data_ptr(), xin.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
     end(case, pk, buf, "upsample")
     ref = O.upsample(case["sd"], O.views_to_mosaic(G.from_act(xin), A), s)
     skip = case["taps"]["skip"]
@@ -268,8 +265,7 @@ def run_forward(case, prec):
     lr = case["lr"].to(G.DEV)
     A, s, B, h, w = case["shape"]
     buf, out = G.guarded((B, 1, A * h * s, A * w * s), torch.float32)
-    _lib.check(_lib.lib().lft_forward(pk.buf.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream()),
-               "forward")
+    _lib.call("lft_forward", pk.buf.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
     end(case, pk, buf, "forward")
     got, ref = out.cpu(), case["out"]
     msg = f"forward [{prec}] " + G.err_report(got, ref) + f" psnr={O.psnr(got, ref):.2f}dB"
@@ -301,8 +297,7 @@ def test_ang_block(case, prec, layer):
     xin = G.to_act(x, prec)
     ref = O.ang_block(case["sd"], layer, G.from_act(xin))       # oracle sees the same (possibly bf16-rounded) input
     buf, act = G.guarded(pk.new_act().shape, G.ACT_DTYPE[prec])
-    _lib.check(_lib.lib().lft_ang_block_fwd(pk.buf.data_ptr(), layer, xin.data_ptr(), act.data_ptr(), *pk.dims(), G.stream()),
-               "ang_block")
+    _lib.call("lft_ang_block_fwd", pk.buf.data_ptr(), layer, xin.data_ptr(), act.data_ptr(), *pk.dims(), G.stream())
     torch.cuda.synchronize()
     assert G.guard_intact(buf), "ang_block: the elements behind the output were written"
     check(G.from_act(act), ref, prec, f"ang_block{layer}", lambda: LP.ang_block(case["sd"], layer, G.from_act(xin), prec),
@@ -364,8 +359,7 @@ def test_init_features_widest_view(prec):
     pk = G.Packed(sd_np, A, h, w, s, prec, B)
     x = lr.to(G.DEV)
     buf, act = G.guarded(pk.new_act().shape, G.ACT_DTYPE[prec])
-    _lib.check(_lib.lib().lft_init_features_fwd(pk.buf.data_ptr(), x.data_ptr(), act.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream()),
-               "init_features")
+    _lib.call("lft_init_features_fwd", pk.buf.data_ptr(), x.data_ptr(), act.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
     torch.cuda.synchronize()
     assert G.guard_intact(buf), "init_features: the elements behind the output were written"
     check(G.from_act(act), ref, prec, f"init_features {h}x{w}", lambda: LP.init_features(sd, views, prec), per_view=True)
@@ -390,7 +384,7 @@ def test_too_wide_view_is_refused(prec):
     assert bool(torch.isnan(act).all()) and bool(torch.isnan(out).all()), "a refused call wrote to its output"
     assert G.guard_intact(buf) and G.guard_intact(obuf)
     with pytest.raises(_lib.LftError, match="width"):
-        _lib.check(L.lft_forward(pk.buf.data_ptr(), x.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream()), "forward")
+        _lib.call("lft_forward", pk.buf.data_ptr(), x.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), G.stream())
 
 
 # ---------------------------------------------------------------------------------------------------- beyond the grid cap
@@ -459,7 +453,7 @@ def test_ang_block_many_positions(A, prec):
     act = buf[:n].view(B, V, h, w, 64)
     with torch.no_grad():
         ref = O.ang_block(sd, 0, G.from_act(xin))
-    _lib.check(_lib.lib().lft_ang_block_fwd(pk.buf.data_ptr(), 0, xin.data_ptr(), act.data_ptr(), *pk.dims(), G.stream()), "ang_block")
+    _lib.call("lft_ang_block_fwd", pk.buf.data_ptr(), 0, xin.data_ptr(), act.data_ptr(), *pk.dims(), G.stream())
     torch.cuda.synchronize()
     assert bool((buf[n:].float() == -7.0).all()), "the 64 elements behind the output were written"
     check(G.from_act(act), ref, prec, f"ang_block0 A{A} {B}x{h}x{w}", lambda: LP.ang_block(sd, 0, G.from_act(xin), prec), per_view=True)

@@ -101,19 +101,16 @@ def test_large_cases_match_restatement():
 
 
 def test_argument_errors_enqueue_nothing():
-    L = _lib.lib()
     lf = torch.zeros(5, 5, 8, 8, 3, dtype=torch.uint8, device=DEV)
     w, i = prepare._device_table(8, 2, DEV)
     hr = torch.full((1, 3 * 8, 3 * 8), -7.0, device=DEV)
     lr = torch.full((1, 3 * 4, 3 * 4), -7.0, device=DEV)
-    st = (ctypes.c_longlong * 5)(*lf.stride())
-    stream = torch.cuda.current_stream(DEV).cuda_stream
+    st = _lib.strides_array(lf)
 
     def call(lfp=lf.data_ptr(), cls=_lib.LF_UINT8, U=5, V=5, A=3, s=2, crops=((0, 0),), ch=8, cw=8, hrp=hr.data_ptr(), strides=st):
         c = np.ascontiguousarray(np.asarray(crops, dtype=np.int32).reshape(-1, 2))
-        rc = L.lft_lf_prepare(lfp, cls, U, V, 8, 8, 3, strides, A, s, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), c.shape[0], ch, cw,
-                              w.data_ptr(), i.data_ptr(), w.shape[1], w.data_ptr(), i.data_ptr(), w.shape[1], hrp, lr.data_ptr(), stream)
-        _lib.check(rc, "lft_lf_prepare")
+        _lib.enqueue("lft_lf_prepare", DEV, lfp, cls, U, V, 8, 8, 3, strides, A, s, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), c.shape[0], ch, cw,
+                     w.data_ptr(), i.data_ptr(), w.shape[1], w.data_ptr(), i.data_ptr(), w.shape[1], hrp, lr.data_ptr())
 
     bad = [dict(U=6, A=3), dict(V=4, A=3), dict(A=7), dict(s=3), dict(s=1), dict(crops=((1, 0),)), dict(crops=((0, -1),)),
            dict(crops=((0, 0), (0, 4)), ch=8, cw=5), dict(cls=3), dict(cls=-1), dict(lfp=None), dict(hrp=None), dict(strides=None)]

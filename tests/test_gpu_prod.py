@@ -74,8 +74,7 @@ def test_prod_exact(mode, case):
     w, x = (torch.from_numpy(a.astype(np.float32)).to(G.DEV) for a in (W, X))
     assert torch.equal(w.cpu().long(), torch.from_numpy(W)) and torch.equal(x.cpu().long(), torch.from_numpy(X))   # exact as fp32
     Y, Yl, Yr = (torch.full((32, 32), float("nan"), device=G.DEV) for _ in range(3))
-    _lib.check(_lib.lib().lft_prod_selftest(w.data_ptr(), x.data_ptr(), Y.data_ptr(), Yl.data_ptr(), Yr.data_ptr(), MODES[mode], G.stream()),
-               "lft_prod_selftest")
+    _lib.call("lft_prod_selftest", w.data_ptr(), x.data_ptr(), Y.data_ptr(), Yl.data_ptr(), Yr.data_ptr(), MODES[mode], G.stream())
     torch.cuda.synchronize()
     zero = np.zeros((1, 16), dtype=np.int64)
     for name, got, Xs in (("Y", Y, X), ("Yl", Yl, np.concatenate([zero, X[:-1]])), ("Yr", Yr, np.concatenate([X[1:], zero]))):

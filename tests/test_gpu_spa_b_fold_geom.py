@@ -81,8 +81,8 @@ def test_last_layer_into_the_upsampler(shape, prec):
     xin, skip, lr = G.to_act(taps["ang3"], prec), G.to_act(taps["feat"], prec), c["lr"].to(G.DEV)
     G.status_reset(pk)
     buf, out = G.guarded((B, 1, A * h * s, A * w * s), torch.float32)
-    _lib.check(_lib.lib().lft_tail_fwd(pk.buf.data_ptr(), xin.data_ptr(), skip.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(),
-                                       *pk.dims(), 1, G.stream()), "lft_tail_fwd")
+    _lib.call("lft_tail_fwd", pk.buf.data_ptr(), xin.data_ptr(), skip.data_ptr(), lr.data_ptr(), out.data_ptr(), pk.work.data_ptr(), *pk.dims(), 1,
+              G.stream())
     torch.cuda.synchronize()
     assert G.guard_intact(buf), "the elements behind the output were written"
     assert G.status_flags(pk) == (0, 0), f"status word {G.status_flags(pk)}"

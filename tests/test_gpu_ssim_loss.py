@@ -5,13 +5,11 @@ reproducibility, graph capture, and every refusal.  Every buffer the call is han
 The gradient bound: the kernel is fp64 between its fp32 loads and its one fp32 store, so an element is off by the store's rounding,
 2^-24 of itself, plus fp64 noise; the gate is four times that unit, 2^-22 of the largest reference element (an exact evaluation
 measures 3.6e-8).  An fp32 moment pass misses it by two to three orders of magnitude (1e-5 ... 6.5e-5), which is the point."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-from lft_amd import _lib, metrics
+from lft_amd import _lib, loss, metrics
 
 import gpu_util as G
 import lf_loss_util as LU
@@ -24,10 +22,9 @@ W_SSIM = 0.2
 
 
 def scratch_floats(B, A, H, W):
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_ssim_loss_scratch_bytes(B, A, H, W, ctypes.byref(n)), "lft_ssim_loss_scratch_bytes")
-    assert n.value % 8 == 0
-    return n.value // 4
+    n = loss.ssim_scratch_bytes(B, A, H, W)
+    assert n % 8 == 0
+    return n // 4
 
 
 class Call:
@@ -122,12 +119,10 @@ def test_accumulate_adds_to_what_lf_loss_left(shape):
     B, A, H, W = shape
     sr, hr, S, g = U.case(shape)
     c = Call(sr, hr, shape)
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lft_lf_loss_scratch_bytes(B, A, H, W, ctypes.byref(n)), "lft_lf_loss_scratch_bytes")
-    lf_scratch = torch.empty(n.value, dtype=torch.uint8, device=G.DEV)
+    lf_scratch = torch.empty(loss.scratch_bytes(B, A, H, W), dtype=torch.uint8, device=G.DEV)
     loss3 = torch.empty(3, dtype=torch.float32, device=G.DEV)
-    _lib.check(_lib.lib().lft_lf_loss(c.sr.data_ptr(), c.hr.data_ptr(), B, A, H, W, LU.PEN_ENUM["charbonnier"], 1e-3, 1.0, 0.5,
-                                      c.dsr.data_ptr(), 1.0, loss3.data_ptr(), lf_scratch.data_ptr(), G.stream()), "lft_lf_loss")
+    _lib.call("lft_lf_loss", c.sr.data_ptr(), c.hr.data_ptr(), B, A, H, W, LU.PEN_ENUM["charbonnier"], 1e-3, 1.0, 0.5, c.dsr.data_ptr(), 1.0,
+              loss3.data_ptr(), lf_scratch.data_ptr(), G.stream())
     c.total.copy_(loss3[:1])
     pre_g, pre_t = c.grad(), float(loss3[0])
     c.run(accumulate=1)

@@ -64,8 +64,7 @@ def build_case(param):
     n = out.numel()
     dout = torch.empty_like(out)
     scratch = torch.empty(1025, device=G.DEV)
-    _lib.check(_lib.lib().lft_l1_loss(out.data_ptr(), hr_d.data_ptr(), n, dout.data_ptr(), 1.0 / n, scratch[1024:].data_ptr(),
-                                      scratch.data_ptr(), G.stream()), "lft_l1_loss")
+    _lib.call("lft_l1_loss", out.data_ptr(), hr_d.data_ptr(), n, dout.data_ptr(), 1.0 / n, scratch[1024:].data_ptr(), scratch.data_ptr(), G.stream())
     flat = T.train_backward(ps, lr_d, tape, dout, A, s, math=math)
     torch.cuda.synchronize()
     return dict(math=math, sd=sd, A=A, s=s, B=B, h=h, w=w, names=names, ps=ps, lr=lr_d, hr=hr_d, out=out, tape=tape, flat=flat, loss=float(scratch[1024]),
@@ -325,8 +324,7 @@ def test_gradients_on_unscreened_inputs_with_aligned_kinks(fixture, math, golden
     n = out.numel()
     dout = torch.empty_like(out)
     scratch = torch.empty(1025, device=G.DEV)
-    _lib.check(_lib.lib().lft_l1_loss(out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, scratch[1024:].data_ptr(),
-                                      scratch.data_ptr(), G.stream()), "lft_l1_loss")
+    _lib.call("lft_l1_loss", out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, scratch[1024:].data_ptr(), scratch.data_ptr(), G.stream())
     # the loss's own kink, sign(sr - hr): every pixel away from it must have the reference's sign (hash of the bitmap); at the listed
     # near-zero pixels ours may differ only where the reference's |sr - hr| is at rounding level, and d loss / d out takes the
     # reference's sign there

@@ -33,6 +33,19 @@ def test_contributions_bit_identical(g):
         assert i.min() >= 0 and i.max() < L
 
 
+def test_contributions_of_axes_shorter_than_the_kernel(golden_dir):
+    """Lengths 1, 2, 3 and 5, down and up by 2 and 4: the mirror period 2 * L is shorter than the tap count, so an index wraps more
+    than once.  Against tables recorded when prepare.contributions and colour.up_contributions were two separate functions."""
+    from lft_amd import colour
+    t = np.load(os.path.join(golden_dir, "contributions_short.npz"))
+    for L, s, way in ((L, s, way) for L in (1, 2, 3, 5) for s in (2, 4) for way in ("down", "up")):
+        w, i = (prepare.contributions if way == "down" else colour.up_contributions)(L, s)
+        rw, ri = t[f"{way}_w_{L}_{s}"], t[f"{way}_i_{L}_{s}"]
+        assert w.dtype == np.float64 and i.dtype == np.int32 and w.shape == rw.shape and i.shape == ri.shape, (way, L, s)
+        assert np.array_equal(w.view(np.uint64), rw.view(np.uint64)) and np.array_equal(i, ri), (way, L, s)
+        assert w.shape[0] == (L * s if way == "up" else -(-L // s)) and i.min() >= 0 and i.max() < L
+
+
 def test_restatement_matches_reference_views(g):
     v = g["views"]
     names = sorted({k[:-5] for k in v.files if k.endswith("_meta")})

@@ -25,9 +25,8 @@ BLOCKS = [("up", _lib.BLOCK_UPSAMPLE, 0)] + [(f"{n}{l}", b, l) for n, b in (("sp
 def profiled_names(math, tape):
     out, grads, n_max = torch.empty_like(dout), torch.empty(T.grad_floats(s), device=dev), 4096
     ms, names, cnt = (ctypes.c_float * n_max)(), (ctypes.c_char_p * n_max)(), ctypes.c_int(0)
-    _lib.check(_lib.lib().lft_train_step_profiled(T._ptr_array(ps), len(ps), lr.data_ptr(), out.data_ptr(), tape.data_ptr(), dout.data_ptr(),
-                                                  grads.data_ptr(), B, A, h, w, s, T.MATH[math], torch.cuda.current_stream().cuda_stream,
-                                                  n_max, ms, names, ctypes.byref(cnt)), "lft_train_step_profiled")
+    _lib.call("lft_train_step_profiled", _lib.ptr_array(ps), len(ps), lr.data_ptr(), out.data_ptr(), tape.data_ptr(), dout.data_ptr(),
+              grads.data_ptr(), B, A, h, w, s, T.MATH[math], _lib.stream_ptr(dev), n_max, ms, names, ctypes.byref(cnt))
     return [names[i].decode() for i in range(cnt.value)]
 
 

@@ -18,29 +18,26 @@ def child(args):
     import ctypes
     sys.path.insert(0, ROOT)
     import torch
-    from lft_amd import _lib
+    from lft_amd import _lib, module
     from lft_amd.params import deterministic_state, param_table, synthetic_lr
     A, s, B, h, w = args.ang, args.scale, args.batch, args.lr, args.lr
     prec = {"bf16": _lib.PREC_BF16, "fp16": _lib.PREC_F16, "fp32": _lib.PREC_F32}[args.precision]
-    L = _lib.lib()
-    st = torch.cuda.current_stream().cuda_stream
+    st = _lib.stream_ptr("cuda")
     sd = deterministic_state(64, s, seed=1)
     params = [torch.from_numpy(sd[n]).cuda() for n, _, _ in param_table(64, s)]
-    packed = torch.empty(_lib.packed_bytes(A, h, w, s, prec), dtype=torch.uint8, device="cuda")
-    arr = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-    _lib.check(L.lft_pack_weights(arr, len(params), packed.data_ptr(), A, h, w, s, prec, st), "pack")
+    packed = module.pack_weights(params, A, h, w, s, prec, st)
     work = torch.empty(_lib.workspace_bytes(B, A, h, w, s, prec), dtype=torch.uint8, device="cuda")
     lr = torch.from_numpy(synthetic_lr(B, A, h, w, seed=0)).cuda()
     out = torch.empty(B, 1, A * h * s, A * w * s, device="cuda")
     for _ in range(3):
-        _lib.check(L.lft_forward(packed.data_ptr(), lr.data_ptr(), out.data_ptr(), work.data_ptr(), B, A, h, w, s, prec, st), "forward")
+        _lib.enqueue("lft_forward", "cuda", packed.data_ptr(), lr.data_ptr(), out.data_ptr(), work.data_ptr(), B, A, h, w, s, prec)
     torch.cuda.synchronize()
     res = {}
     for k in args.kernels.split(","):
         ms = ctypes.c_float(0)
         best = []
         for _ in range(3):
-            _lib.check(L.lft_kernel_time(k.encode(), packed.data_ptr(), work.data_ptr(), B, A, h, w, s, prec, args.reps, st, ctypes.byref(ms)), k)
+            _lib.call("lft_kernel_time", k.encode(), packed.data_ptr(), work.data_ptr(), B, A, h, w, s, prec, args.reps, st, ctypes.byref(ms))
             best.append(ms.value * 1e3)
         res[k] = sorted(best)[1]                     # median of three
     print(json.dumps(res))

@@ -32,7 +32,6 @@ def time_loss_launches(ts, hr, calls=50):
     from lft_amd.loss import lf_loss, ssim_loss
     sr, dout = ts.last_out, torch.empty_like(hr)
     n = sr.numel()
-    stream = torch.cuda.current_stream(hr.device).cuda_stream
     scratch = ts._loss_scratch_for(hr)
 
     def run_lf():
@@ -40,8 +39,8 @@ def time_loss_launches(ts, hr, calls=50):
                 scratch=scratch)
 
     def run_l1():
-        _lib.check(_lib.lib().lft_l1_loss(sr.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, ts._scratch[1024:].data_ptr(),
-                                          ts._scratch.data_ptr(), stream), "lft_l1_loss")
+        _lib.enqueue("lft_l1_loss", hr.device, sr.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, ts._scratch[1024:].data_ptr(),
+                     ts._scratch.data_ptr())
 
     def run_ssim():
         ssim_loss(sr, hr, ts.A, ts.loss.ssim_range, ts.loss.ssim_weight, dsr=dout, accumulate=ts.loss.has_lf_terms(),
