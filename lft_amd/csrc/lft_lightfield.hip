@@ -1,6 +1,8 @@
 // lft_lightfield.hip -- what handles light fields around the network, in the C ABI of liblft_hip.so (include/lft_hip.h): scene
-// tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus and disparity.
+// tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity and view
+// synthesis (the last declared in include/lft_hip_views.h).
 #include "lft_host.cuh"
+#include "../../include/lft_hip_views.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
@@ -8,6 +10,7 @@
 #include "lft_colour.cuh"    // colour path: RGB light field -> Y mosaic; SR Y + up-scaled chroma -> RGB views
 #include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
 #include "lft_disparity.cuh" // disparity: plane-sweep cost volume, windowed aggregation, winner-take-all (lft_disparity)
+#include "lft_views.cuh"     // view synthesis: splat the disparity to the target, fill, gather the views (lft_view_render)
 
 namespace {
 
@@ -39,8 +42,9 @@ int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, in
     if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
     return 0;
 }
-// ---- B light fields [B,A,A,H,W,C] read in place through six strides, one 32 x 32 output tile per workgroup (refocus, disparity) ----
-struct WindowedLf {         // the arguments lft_refocus and lft_disparity share, and what windowed_lf_ok derives from them
+// ---- B light fields [B,A,A,H,W,C] read in place through six strides, one 32 x 32 output tile per workgroup (refocus, disparity,
+// view synthesis with its targets in the place of the slopes) ----
+struct WindowedLf {         // the arguments lft_refocus, lft_disparity and lft_view_render share, and what windowed_lf_ok derives from them
     const void* lf; int lf_class, B, A, H, W, C; const long long* strides; const void* table; int D, taps;
     long long tiles_x, tiles;           // kRfTile tiles of a view; tiles == 0: an empty shape, no work and no error
 };
@@ -332,6 +336,55 @@ int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int 
     p.aif_f32 = aif_class == LFT_LF_FLOAT32;
     k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
     LFT_LAUNCH_OK("k_disparity_pick");
+    return 0;
+}
+
+// ---- view synthesis (lft_views.cuh; declared in include/lft_hip_views.h) ----
+int lft_view_render_scratch_bytes(int B, int T, int H, int W, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_view_render: out_bytes is null");
+    if (T < 1) return fail(LFT_ERR_ARG, "lft_view_render: %d targets", T);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_view_render: negative size in B = %d, views of %d x %d", B, H, W);
+    const double n = (double)B * T * H * W * 4.0;
+    if (n > 1099511627776.0) return fail(LFT_ERR_SHAPE, "lft_view_render: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", B, T, H, W);
+    *out_bytes = (size_t)B * T * H * W * sizeof(uint32_t);
+    return 0;
+}
+int lft_view_render(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const float* disparity,
+                    const float* deltas, float max_delta, const void* records, int T, int taps, float lo, float hi, int near, int fill,
+                    void* scratch, void* views, int views_class, float* target_disparity, unsigned char* holes, void* stream) {
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, records, T, taps, 0, 0};
+    if (int rc = windowed_lf_ok("lft_view_render", l, views_class, "output", 0, !disparity || !deltas || !scratch || !views || !target_disparity || !holes, "renders"))
+        return rc;
+    if (taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "lft_view_render: %d taps (2 or 4: nearest is not offered)", taps);
+    if (fill < 0 || fill > kVwMaxFill) return fail(LFT_ERR_ARG, "lft_view_render: fill %d outside 0 .. %d", fill, kVwMaxFill);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi) return fail(LFT_ERR_ARG, "lft_view_render: d_range (%g, %g) must be finite with lo <= hi", lo, hi);
+    if (near != LFT_VIEW_NEAR_LARGER && near != LFT_VIEW_NEAR_SMALLER) return fail(LFT_ERR_ARG, "lft_view_render: near must be LFT_VIEW_NEAR_LARGER or LFT_VIEW_NEAR_SMALLER, got %d", near);
+    if (!std::isfinite(max_delta) || max_delta < 0.0f) return fail(LFT_ERR_ARG, "lft_view_render: max_delta %g must be finite and >= 0", max_delta);
+    // exact in double; an integer bound of the exact product also bounds its fp32 rounding
+    const double reach = std::ceil(std::max(std::fabs((double)lo), std::fabs((double)hi)) * (double)max_delta) + 1.0;
+    if (reach > (double)kVwMaxReach) return fail(LFT_ERR_SHAPE, "lft_view_render: reach %.0f pixels (d_range times the largest target offset) above %d", reach, kVwMaxReach);
+    if (H > (1 << 24) || W > (1 << 24)) return fail(LFT_ERR_SHAPE, "lft_view_render: views of %d x %d: pixel coordinates are fp32, at most 2^24", H, W);
+    if (!l.tiles) return 0;                                         // nothing to render
+    const long long rtiles_x = l.tiles_x, rtiles = rtiles_x * (((long long)H + kVwRows - 1) / kVwRows);
+    if (rtiles * T * B > 0x7fffffffLL) return too_many_blocks("lft_view_render", l, "renders");
+    if ((double)B * T * H * W * 4.0 > 1099511627776.0)
+        return fail(LFT_ERR_SHAPE, "lft_view_render: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", B, T, H, W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_view_render: scratch must be 4-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SplatArgs s{};
+    s.dr = disparity; s.deltas = deltas; s.keys = static_cast<uint32_t*>(scratch); s.lo = lo; s.hi = hi;
+    s.neg = near == LFT_VIEW_NEAR_SMALLER; s.reach = (int)reach;
+    s.H = H; s.W = W; s.T = T; s.tiles_x = (int)l.tiles_x; s.tiles = (int)l.tiles;
+    k_view_splat<<<dim3((unsigned)(l.tiles * T * B)), 256, 0, st>>>(s);
+    LFT_LAUNCH_OK("k_view_splat");
+    RenderArgs r{};
+    fill_windowed(r, l);
+    r.dr = disparity; r.keys = s.keys; r.lo = lo; r.hi = hi; r.neg = s.neg; r.fill = fill;
+    r.rtiles_x = (int)rtiles_x; r.rtiles = (int)rtiles;
+    r.out = views; r.out_f32 = views_class == LFT_LF_FLOAT32; r.dt = target_disparity; r.holes = holes;
+    const dim3 grid((unsigned)(rtiles * T * B));
+    by_lf_class<false>(lf_class, [&](auto t) { render_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(r); return 0; });
+    LFT_LAUNCH_OK("k_view_render");
     return 0;
 }
 

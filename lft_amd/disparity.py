@@ -94,7 +94,7 @@ def check_slopes(slopes) -> Tuple[float, ...]:
 
 def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
               interp: str = "linear", radius: int = 2, all_in_focus: bool = False, cost_volume: bool = False,
-              aif_dtype=None) -> DisparityResult:
+              aif_dtype=None, centre=None) -> DisparityResult:
     """The disparity map of a light field on the GPU, on lf's device and current stream (enqueue only).
 
       views  [A, A, H, W, C] (C <= 4) or [A, A, H, W]   ->  maps [H, W], all_in_focus [H, W, C] or [H, W], cost [D, H, W]
@@ -103,7 +103,9 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
 
     Layouts, strides, input classes, aperture and interp are ``refocus.refocus``'s.  radius: the aggregation window is
     (2 radius + 1)^2, 0 .. 8.  all_in_focus: also return the refocus stack gathered at the index, as aif_dtype (default: the
-    input's; torch.float32 is the unclipped sum, torch.uint8 clips, scales and rounds half to even).  cost_volume: also return E."""
+    input's; torch.float32 is the unclipped sum, torch.uint8 clips, scales and rounds half to even).  cost_volume: also return E.
+    centre: the angular position (cu, cv) the sweep is seen from (``refocus.shift_table``), default the centre of the views: the
+    map then belongs to that position, and all_in_focus is the plane-sweep rendering of a view there."""
     sl = ()
 
     def sweep_arguments():                  # radius, interp and slopes are refused before a tensor off the GPU
@@ -116,7 +118,7 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
 
     B, A, H, W, C, strides, kind = _field(lf, angRes, "aif_dtype", aif_dtype, before_device=sweep_arguments)
     aif_dtype = lf.dtype if aif_dtype is None else aif_dtype
-    table = _device_table(A, sl, aperture, interp, lf.device)
+    table = _device_table(A, sl, aperture, interp, lf.device, centre)
     D = len(sl)
     dev = lf.device
     disp = torch.empty(B, H, W, dtype=torch.float32, device=dev)

@@ -84,8 +84,20 @@ def _axis(off: float, interp: str) -> Tuple[int, np.ndarray]:
     return base, w
 
 
-def shift_table(A: int, slopes: Sequence[float], aperture: Aperture = "full", interp: str = "cubic") -> np.ndarray:
-    """The host table [D, A*A] of RECORD, slope-major, views in (u, v) order."""
+def _centre(A: int, centre) -> Tuple[float, float]:
+    """(cu, cv) of a `centre` argument: None is (uc, uc); else two finite numbers in view-index units."""
+    uc = (A - 1) / 2
+    if centre is None:
+        return uc, uc
+    c = np.array(centre, dtype=np.float64).reshape(-1)
+    if c.size != 2 or not np.all(np.isfinite(c)):
+        raise LftError(f"centre must be two finite view coordinates (cu, cv), got {centre!r}")
+    return float(c[0]), float(c[1])
+
+
+def shift_table(A: int, slopes: Sequence[float], aperture: Aperture = "full", interp: str = "cubic", centre=None) -> np.ndarray:
+    """The host table [D, A*A] of RECORD, slope-major, views in (u, v) order.  centre (default (uc, uc)): the angular position
+    (cu, cv) the stack is seen from; the offsets are d*(u-cu), d*(v-cv)."""
     if interp not in TAPS:
         raise LftError(f"interp must be nearest, linear or cubic, got {interp!r}")
     if A < 1:
@@ -94,17 +106,17 @@ def shift_table(A: int, slopes: Sequence[float], aperture: Aperture = "full", in
     if sl.size < 1 or not np.all(np.isfinite(sl)):
         raise LftError(f"slopes must be a non-empty sequence of finite numbers, got {slopes!r}")
     a = _aperture(A, aperture)
-    uc = (A - 1) / 2
-    if np.abs(sl).max() * uc > MAX_OFFSET:
+    cu, cv = _centre(A, centre)
+    if np.abs(sl).max() * max(abs(i - c) for c in (cu, cv) for i in (0, A - 1)) > MAX_OFFSET:
         raise LftError(f"slope {np.abs(sl).max()} shifts the outer views by more than 2^30 pixels")
     tab = np.zeros((sl.size, A * A), dtype=RECORD)
     for k, d in enumerate(sl):
-        axis = [_axis(d * (i - uc), interp) for i in range(A)]
+        rows, cols = [_axis(d * (i - cu), interp) for i in range(A)], [_axis(d * (i - cv), interp) for i in range(A)]
         for u in range(A):
             for v in range(A):
                 r = tab[k, u * A + v]
-                r["oy"], r["ox"] = axis[u][0], axis[v][0]
-                r["wy"], r["wx"] = axis[u][1], axis[v][1]                # rounded once, here
+                r["oy"], r["ox"] = rows[u][0], cols[v][0]
+                r["wy"], r["wx"] = rows[u][1], cols[v][1]                # rounded once, here
                 r["a"] = a[u, v]
                 r["skip"] = int(r["a"] == 0)
     return tab
@@ -113,12 +125,12 @@ def shift_table(A: int, slopes: Sequence[float], aperture: Aperture = "full", in
 _tables: Dict[tuple, torch.Tensor] = {}
 
 
-def _device_table(A: int, slopes, aperture: Aperture, interp: str, device) -> torch.Tensor:
+def _device_table(A: int, slopes, aperture: Aperture, interp: str, device, centre=None) -> torch.Tensor:
     sl = tuple(float(s) for s in np.array(slopes, dtype=np.float64).reshape(-1))
     ap = aperture if isinstance(aperture, str) else _aperture(A, aperture).tobytes()
-    key = (A, sl, ap, interp, str(device))
+    key = (A, sl, ap, interp, str(device), None if centre is None else _centre(A, centre))
     if key not in _tables:
-        tab = shift_table(A, sl, aperture, interp)
+        tab = shift_table(A, sl, aperture, interp, centre)
         _tables[key] = torch.from_numpy(tab.view(np.int32).reshape(tab.shape[0], A * A, RECORD.itemsize // 4).copy()).to(device)
     return _tables[key]
 
@@ -171,7 +183,7 @@ def _field(lf, angRes: Optional[int], out_name: str, out_dtype, before_device=No
 
 
 def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
-            interp: str = "cubic", out_dtype=None) -> torch.Tensor:
+            interp: str = "cubic", out_dtype=None, centre=None) -> torch.Tensor:
     """The focal stack of a light field on the GPU, one slice per slope, on lf's device and current stream (enqueue only).
 
       views  [A, A, H, W, C] (C <= 4) or [A, A, H, W]   ->  [D, H, W, C] or [D, H, W]
@@ -180,10 +192,11 @@ def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = N
 
     Any strides are read in place.  uint8 input enters as x / 255, float32 as stored.  out_dtype (default: the input's) is
     torch.float32, the unclipped sum, or torch.uint8: clip to [0, 1], * 255, round half to even.  aperture: "full", "disk",
-    "gaussian" or an [A, A] array (``aperture_weights`` for a radius or sigma); views of weight 0 are not read."""
+    "gaussian" or an [A, A] array (``aperture_weights`` for a radius or sigma); views of weight 0 are not read.  centre: the
+    angular position (cu, cv) the stack is seen from (``shift_table``), default the centre of the views."""
     B, A, H, W, C, strides, kind = _field(lf, angRes, "out_dtype", out_dtype)
     out_dtype = lf.dtype if out_dtype is None else out_dtype
-    table = _device_table(A, slopes, aperture, interp, lf.device)
+    table = _device_table(A, slopes, aperture, interp, lf.device, centre)
     D = int(table.shape[0])
     out = torch.empty(B, D, H, W, C, dtype=out_dtype, device=lf.device)
     _lib.enqueue("lft_refocus", lf.device, lf.data_ptr() or None, _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), D, TAPS[interp],

@@ -1,0 +1,143 @@
+"""The view-synthesis definition (lft_amd/views.py) restated in numpy: splat and fill in float32, operation for operation, so that
+the target map and the holes compare bit for bit; the render in fp64 from the float32 coordinates, so that only the GPU's fp32
+filtering and accumulation separate the two; and the tolerance the GPU tests hold the rendered views to."""
+import numpy as np
+
+from lft_amd import prepare
+
+import disparity_util as DU
+
+F = np.float32
+
+
+def clamp_np(Dr, lo, hi):
+    """(finite mask, Dr clamped into [lo, hi] in float32 with one zero); non-finite pixels come back as 0 and are masked."""
+    fin = np.isfinite(Dr)
+    d = np.minimum(np.maximum(np.where(fin, Dr, F(0)).astype(F), F(lo)), F(hi))
+    return fin, np.where(d == 0, F(0), d).astype(F)
+
+
+def splat_np(Dr, delta, d_range, near="larger"):
+    """Dr fp32 [H, W], delta = (Δu, Δv) fp32 -> Dt0 fp32 [H, W], NaN where no source covers the pixel."""
+    H, W = Dr.shape
+    fin, d = clamp_np(Dr, *d_range)
+    y, x = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
+    py = (y + (d * F(delta[0])).astype(F)).astype(F)
+    px = (x + (d * F(delta[1])).astype(F)).astype(F)
+    fy, fx = np.floor(py), np.floor(px)
+    val = d if near == "larger" else -d                      # the min of d is the max of -d
+    best = np.full((H, W), -np.inf, dtype=F)
+    for a in (0, 1):
+        for b in (0, 1):
+            ty, tx = fy.astype(np.int64) + a, fx.astype(np.int64) + b
+            ok = fin & ((a == 0) | (py != fy)) & ((b == 0) | (px != fx)) & (ty >= 0) & (ty < H) & (tx >= 0) & (tx < W)
+            np.maximum.at(best, (ty[ok], tx[ok]), val[ok])
+    hole = np.isneginf(best)
+    out = best if near == "larger" else -best
+    return np.where(hole, F(np.nan), np.where(out == 0, F(0), out)).astype(F)
+
+
+def fill_np(Dt0, Dr, d_range, near="larger", fill=32):
+    """(Dt fp32 [H, W], holes uint8 [H, W]): every hole of Dt0 from pre-fill values only."""
+    H, W = Dt0.shape
+    fin, d = clamp_np(Dr, *d_range)
+    far = min if near == "larger" else max
+    Dt, holes = Dt0.copy(), np.isnan(Dt0)
+
+    def first(line, at, step):
+        for s in range(1, fill + 1):
+            i = at + step * s
+            if i < 0 or i >= len(line):
+                return None
+            if not np.isnan(line[i]):
+                return line[i]
+        return None
+
+    for y, x in zip(*np.nonzero(holes)):
+        found = [v for v in (first(Dt0[y], x, -1), first(Dt0[y], x, +1)) if v is not None]
+        if not found:
+            found = [v for v in (first(Dt0[:, x], y, -1), first(Dt0[:, x], y, +1)) if v is not None]
+        if found:
+            Dt[y, x] = far(found)
+        else:
+            Dt[y, x] = d[y, x] if fin[y, x] else F(d_range[0] if near == "larger" else d_range[1])
+    return np.where(Dt == 0, F(0), Dt).astype(F), holes.astype(np.uint8)
+
+
+def axis_np(s, n, taps):
+    """s: float32 sample positions.  (tap indices [taps, ...] clamped into 0 .. n-1, fp64 weights [taps, ...]): the float32
+    coordinates, f and the linear weights as the definition rounds them, the cubic weights from fp64."""
+    fl = np.floor(s)
+    f = (s - fl).astype(F)                                   # exact
+    i0 = np.clip(fl, -4, n + 4).astype(np.int64) - (1 if taps == 4 else 0)
+    idx = np.stack([np.clip(i0 + k, 0, n - 1) for k in range(taps)])
+    if taps == 2:
+        w = np.stack([(F(1) - f).astype(F).astype(np.float64), f.astype(np.float64)])
+    else:
+        g = f.astype(np.float64)
+        w = np.stack([prepare._cubic(g + 1.0), prepare._cubic(g), prepare._cubic(1.0 - g), prepare._cubic(2.0 - g)])
+    return idx, w
+
+
+def render_np(views, Dt, records, taps):
+    """views [A, A, H, W, C] (uint8: scaled by / 255), Dt fp32 [H, W], records [A*A] of lft_amd.views.RECORD -> fp64 [H, W, C]."""
+    A, _, H, W, C = views.shape
+    X = views.astype(np.float64) / 255.0 if views.dtype == np.uint8 else views.astype(np.float64)
+    y, x = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
+    num_in, num_all = np.zeros((H, W, C)), np.zeros((H, W, C))
+    den_in, den_all = np.zeros((H, W)), np.zeros((H, W))
+    for n, r in enumerate(records):
+        if r["skip"]:
+            continue
+        sy = (y + (Dt * F(r["du"])).astype(F)).astype(F)
+        sx = (x + (Dt * F(r["dv"])).astype(F)).astype(F)
+        inside = (sy >= 0) & (sy <= F(H - 1)) & (sx >= 0) & (sx <= F(W - 1))
+        iy, wy = axis_np(sy, H, taps)
+        ix, wx = axis_np(sx, W, taps)
+        v = X[n // A, n % A]
+        s = np.zeros((H, W, C))
+        for k in range(taps):
+            rows = np.zeros((H, W, C))
+            for j in range(taps):
+                rows += wy[j][..., None] * v[iy[j], ix[k]]
+            s += wx[k][..., None] * rows
+        w = float(r["w"])
+        num_all += w * s
+        den_all += w
+        num_in += np.where(inside[..., None], w * s, 0.0)
+        den_in += np.where(inside, w, 0.0)
+    some = den_in > 0
+    return np.where(some[..., None], num_in / np.where(some, den_in, 1.0)[..., None], num_all / den_all[..., None])
+
+
+def tol_render(n_views, taps, max_abs):
+    """(2 V + 2 taps + 2) * u * S^2 * max|x|, plus 38 * u * S * max|x| for cubic; u = 2^-24 the unit roundoff of fp32, V the views
+    of non-zero weight, S the largest 1-D sum |tap weight| (1 linear, 1.25 cubic).  A first-order worst-case bound, every rounding
+    step counted once at the magnitude it acts on:
+
+    - Accumulation depth: V fused multiply-adds of w*s into the numerator, on magnitude S^2 max|x| since the weights sum to 1; 2 taps
+      rounding steps in a sample (taps in the row pass, taps in the column pass); the quotient: V additions in the denominator
+      (relative, so the same magnitude), the division, and the x / 255 of uint8 input.
+    - S^2 * max|x| bounds a sample and the quotient.
+    - Cubic: the fp32 evaluation of Keys' weights (k_view_render's factored forms, g = fl(1 - f)) against the fp64 ones.
+      k(f) = 1 - f^2 (2.5 - 1.5 f): 1.5 f within 1.5 u, the bracket (<= 2.5) within 3.5 u, f^2 within u, their product (<= 1) within
+      3.5 u + 2.5 u + u = 7 u, the difference within 8 u.  k(1 - f): the same from g, whose own rounding (u / 2, slope <= 1.4) adds
+      0.7 u: 8.7 u.  k(1 + f) = -0.5 f g^2 and k(2 - f) = -0.5 g f^2, at most 0.0741: three roundings and g's: 0.35 u and 0.47 u.
+      In sum 18 u <= 19 u an axis; a sample is a product of the two axes' sums, so the two axes give 2 * 19 u * S * max|x|.
+      The linear weights fl(1 - f), f enter the reference as rounded.
+    3.2e-6 for 24 views, linear, and 8.4e-6 for 25 views, cubic, on [0, 1] data.  Not fitted to any output of the kernels."""
+    S, u = (1.25 if taps == 4 else 1.0), 2.0 ** -24
+    t = (2 * n_views + 2 * taps + 2) * u * S * S * max_abs
+    return t + (38 * u * S * max_abs if taps == 4 else 0.0)
+
+
+def occlusion_masks(t, H=72, W=64):
+    """(analytic Dt of the two-layer scene at the integer target t, the pixels >= 5 from the border, the pixels the render is held
+    to: >= 9 from the border and not in the 9-pixel ring around the foreground box's image)."""
+    y0, y1, x0, x1 = DU.FG_BOX
+    oy, ox = t[0] - 2, t[1] - 2                                   # the foreground (d = +1) moves by the target's offset from the centre
+    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    fg = (yy >= y0 + oy) & (yy < y1 + oy) & (xx >= x0 + ox) & (xx < x1 + ox)
+    near = (yy >= y0 + oy - 9) & (yy < y1 + oy + 9) & (xx >= x0 + ox - 9) & (xx < x1 + ox + 9)
+    border = lambda m: (yy >= m) & (yy < H - m) & (xx >= m) & (xx < W - m)
+    return np.where(fg, np.float32(1), np.float32(-1)), border(5), border(9) & (fg | ~near), fg
