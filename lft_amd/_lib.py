@@ -27,8 +27,11 @@ def _header_text(header: str) -> str:
 # reports another one), STATUS_NONFINITE, NUM_PARAMS, PREC_*, MATH_*, ERR_*, LOSS_*, BLOCK_*, LF_*, MAPS_*, GRAD_BUCKETS,
 # DISPARITY_AIF, GUARD_MAX_SEGMENTS.
 globals().update({k: int(v) for k, v in re.findall(r"^#define LFT_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", _header_text("lft_hip.h"), flags=re.M)})
-# likewise those of include/lft_hip_views.h (added beside ABI 5): VIEW_NEAR_LARGER, VIEW_NEAR_SMALLER, VIEW_MAX_REACH, VIEW_MAX_FILL
-globals().update({k: int(v) for k, v in re.findall(r"^#define LFT_(VIEW_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", _header_text("lft_hip_views.h"), flags=re.M)})
+# The headers added beside ABI 5 (lft_version unchanged), each with the prefix of its constants: VIEW_NEAR_LARGER, VIEW_NEAR_SMALLER,
+# VIEW_MAX_REACH, VIEW_MAX_FILL; SGM_MAX_D.
+ADDON_HEADERS = {"lft_hip_views.h": "VIEW_", "lft_hip_sgm.h": "SGM_"}
+for _header, _prefix in ADDON_HEADERS.items():
+    globals().update({k: int(v) for k, v in re.findall(r"^#define LFT_(%s\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$" % _prefix, _header_text(_header), flags=re.M)})
 
 _lib = None
 
@@ -52,7 +55,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(HERE, "..", "include", h) for h in ("lft_hip.h", "lft_hip_test.h", "lft_hip_views.h")]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(HERE, "..", "include", h) for h in ("lft_hip.h", "lft_hip_test.h", *ADDON_HEADERS)]
     if any(os.path.getmtime(d) > t for d in deps):
         return True
     # a change of compiler flags must rebuild too; a shipped library without a stamp (the GPU box gets the .so, not the
@@ -78,7 +81,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
 # The library's translation units, in build order (csrc/<unit>.hip; the longest compile first, they run in parallel):
 #   lft_network      the network: the inference path with its per-stage test entry points, the fp32 training step and the
 #                    attention maps from its tape; lft_version / lft_last_error.  One unit, not two: see the file's header
-#   lft_lightfield   scene tiling, dihedral transforms, view metrics, data preparation, colour, refocus, disparity, view synthesis
+#   lft_lightfield   scene tiling, dihedral transforms, view metrics, data preparation, colour, refocus, disparity, view synthesis,
+#                    semi-global aggregation
 #   lft_objective    losses, Adam, the guarded step, the EMA
 # A unit emits the kernels of the headers it includes, so each includes only what it launches from.
 UNITS = ("lft_network", "lft_lightfield", "lft_objective")
@@ -194,14 +198,18 @@ LOSS_EXPORTS = ("lft_lf_loss_scratch_bytes", "lft_lf_loss")                     
 SSIM_LOSS_EXPORTS = ("lft_ssim_loss_scratch_bytes", "lft_ssim_loss")                                 # likewise
 REFOCUS_EXPORTS = ("lft_refocus",)                                                                   # likewise
 DISPARITY_EXPORTS = ("lft_disparity_scratch_bytes", "lft_disparity")                                 # likewise
-# View synthesis is declared in a header of its own, include/lft_hip_views.h (added beside ABI 5, lft_version unchanged), and bound
-# from a table of its own: _SIGS, EXPORTS, STREAM_LAST and TEST_EXPORTS are the two older headers' and keep their contents.
-_VIEW_PROTOTYPES = _prototypes("lft_hip_views.h")
-_VIEW_SIGS = {name: (res, args) for name, (res, args, _) in _VIEW_PROTOTYPES.items()}
-VIEW_STREAM_LAST = frozenset(name for name, (_, args, last) in _VIEW_PROTOTYPES.items() if last == "stream" and args[-1] is c_void_p)
-VIEW_EXPORTS = tuple(_VIEW_SIGS)                                                                    # lft_view_render_scratch_bytes, lft_view_render
+# View synthesis and semi-global aggregation are declared in headers of their own (ADDON_HEADERS) and bound from a table of their
+# own: _SIGS, EXPORTS, STREAM_LAST and TEST_EXPORTS are the two older headers' and keep their contents.
+_ADDON_PROTOTYPES = {h: _prototypes(h) for h in ADDON_HEADERS}
+_ADDON_SIGS = {name: (res, args) for protos in _ADDON_PROTOTYPES.values() for name, (res, args, _) in protos.items()}
+ADDON_STREAM_LAST = frozenset(name for protos in _ADDON_PROTOTYPES.values() for name, (_, args, last) in protos.items()
+                              if last == "stream" and args[-1] is c_void_p)
+VIEW_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_views.h"])                                          # lft_view_render_scratch_bytes, lft_view_render
+VIEW_STREAM_LAST = ADDON_STREAM_LAST & frozenset(VIEW_EXPORTS)
+SGM_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_sgm.h"])                                             # lft_sgm_scratch_bytes, lft_sgm
 # what an older LFT_LIB_PATH build of the same ABI version (A/B runs) may lack: lib() binds everything else unconditionally
-OPTIONAL_EXPORTS = frozenset(TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS + DISPARITY_EXPORTS + VIEW_EXPORTS)
+OPTIONAL_EXPORTS = frozenset(TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS + DISPARITY_EXPORTS + VIEW_EXPORTS
+                             + SGM_EXPORTS)
 BUCKET_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_size_t, c_size_t)     # lft_bucket_fn of include/lft_hip.h: 0 = go on, else stop
 
 
@@ -217,7 +225,7 @@ def lib() -> ctypes.CDLL:
         got = L.lft_version()
         if got != ABI_VERSION:              # a stale or foreign LFT_LIB_PATH build: its entry points may take other arguments
             raise LftError(f"{LIB_PATH} reports ABI version {got}, this binding needs {ABI_VERSION}: rebuild it (__graft_entry__.build())")
-        for name, (res, args) in {**_SIGS, **_VIEW_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_ADDON_SIGS}.items():
             if name in OPTIONAL_EXPORTS and not hasattr(L, name):
                 continue        # everything else is there, and asking the library for a missing entry point raises
             fn = getattr(L, name)
@@ -239,7 +247,7 @@ def call(name: str, *args) -> None:
 
 def query(name: str, *args):
     """A size query: `args` without the trailing `size_t*` parameters of `name`, which come back as an int (several: a tuple)."""
-    types = _SIGS[name][1] if name in _SIGS else _VIEW_SIGS[name][1] if name in _VIEW_SIGS else []
+    types = {**_SIGS, **_ADDON_SIGS}.get(name, (None, []))[1]
     outs = [c_size_t(0) for t in types if t is POINTER(c_size_t)]
     if not outs or types[-len(outs):] != [POINTER(c_size_t)] * len(outs):
         raise LftError(f"{name} is no size query: its prototype does not end in a size_t* parameter")
@@ -255,7 +263,7 @@ def stream_ptr(device) -> int:
 
 def enqueue(name: str, device, *args) -> None:
     """call(name, *args, stream_ptr(device)) with `device` current, for an entry point whose last parameter is `void* stream`."""
-    if name not in STREAM_LAST and name not in VIEW_STREAM_LAST:
+    if name not in STREAM_LAST and name not in ADDON_STREAM_LAST:
         raise LftError(f"{name} does not take its stream last: use call() with stream_ptr(device)")
     import torch
     with torch.cuda.device(device):

@@ -1,8 +1,9 @@
 // lft_lightfield.hip -- what handles light fields around the network, in the C ABI of liblft_hip.so (include/lft_hip.h): scene
-// tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity and view
-// synthesis (the last declared in include/lft_hip_views.h).
+// tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity, view
+// synthesis (declared in include/lft_hip_views.h) and semi-global aggregation (declared in include/lft_hip_sgm.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
+#include "../../include/lft_hip_sgm.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
@@ -11,6 +12,7 @@
 #include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
 #include "lft_disparity.cuh" // disparity: plane-sweep cost volume, windowed aggregation, winner-take-all (lft_disparity)
 #include "lft_views.cuh"     // view synthesis: splat the disparity to the target, fill, gather the views (lft_view_render)
+#include "lft_sgm.cuh"       // semi-global aggregation of a cost volume: the path scans, the sum and the selection (lft_sgm)
 
 namespace {
 
@@ -385,6 +387,81 @@ int lft_view_render(const void* lf, int lf_class, int B, int A, int H, int W, in
     const dim3 grid((unsigned)(rtiles * T * B));
     by_lf_class<false>(lf_class, [&](auto t) { render_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(r); return 0; });
     LFT_LAUNCH_OK("k_view_render");
+    return 0;
+}
+
+// ---- semi-global aggregation (lft_sgm.cuh; declared in include/lft_hip_sgm.h) ----
+static_assert(kSgMaxD == LFT_SGM_MAX_D && kSgMaxD <= 4 * 64 && kSgMaxD <= kSgSegs * 64,
+              "a row's wave holds four slopes per lane, a line's wave a segment of at most 64");
+// What the size query and the call both judge; *vol: the floats of one volume [B, D, H, W], 0 for an empty shape.
+static int sgm_shape_ok(int B, int D, int H, int W, int paths, size_t* vol) {
+    if (paths != 4 && paths != 8) return fail(LFT_ERR_ARG, "lft_sgm: %d paths (4 or 8)", paths);
+    if (D < 1 || D > LFT_SGM_MAX_D) return fail(LFT_ERR_ARG, "lft_sgm: %d slopes outside 1 .. %d", D, LFT_SGM_MAX_D);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_sgm: negative size in B = %d, maps of %d x %d", B, H, W);
+    if ((double)H * W > 2147483647.0) return fail(LFT_ERR_SHAPE, "lft_sgm: maps of %d x %d have more than 2^31 pixels", H, W);
+    if ((double)paths * B * D * H * W * 4.0 > 1099511627776.0)
+        return fail(LFT_ERR_SHAPE, "lft_sgm: %d path volumes of %d x %d x %d x %d need more than 2^40 bytes", paths, B, D, H, W);
+    *vol = (size_t)B * D * H * W;
+    return 0;
+}
+int lft_sgm_scratch_bytes(int B, int D, int H, int W, int paths, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_sgm: out_bytes is null");
+    size_t vol = 0;
+    if (int rc = sgm_shape_ok(B, D, H, W, paths, &vol)) return rc;
+    *out_bytes = (size_t)paths * vol * sizeof(float);
+    return 0;
+}
+int lft_sgm(const float* cost, int B, int D, int H, int W, int C, const float* slopes, int paths, float p1, float p2,
+            const float* guide, float gain, const float* stack, void* scratch, float* disparity, float* confidence, int* index,
+            float* aggregated, void* aif, int aif_class, void* stream) {
+    size_t vol = 0;
+    if (int rc = sgm_shape_ok(B, D, H, W, paths, &vol)) return rc;
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_sgm: %d channels (1 .. 4)", C);
+    if (!std::isfinite(p1) || !std::isfinite(p2) || !std::isfinite(gain) || p1 < 0.0f || p2 < 0.0f || gain < 0.0f)
+        return fail(LFT_ERR_ARG, "lft_sgm: p1 %g, p2 %g and gain %g must be finite and >= 0", p1, p2, gain);
+    if (p2 < p1) return fail(LFT_ERR_ARG, "lft_sgm: p2 %g below p1 %g", p2, p1);
+    if (gain > 0.0f && !guide) return fail(LFT_ERR_ARG, "lft_sgm: gain %g without a guide", gain);
+    if (aif && !stack) return fail(LFT_ERR_ARG, "lft_sgm: all-in-focus output without a stack");
+    if (aif_class != LFT_LF_UINT8 && aif_class != LFT_LF_FLOAT32)
+        return fail(LFT_ERR_ARG, "lft_sgm: all-in-focus class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", aif_class);
+    if (!vol) return 0;                                             // empty maps
+    if (!cost || !slopes || !scratch || !disparity || !confidence || !index) return fail(LFT_ERR_ARG, "lft_sgm: null pointer");
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_sgm: scratch must be 4-byte aligned");
+    SgmScanArgs s{};
+    s.cost = cost; s.guide = guide; s.paths = static_cast<float*>(scratch);
+    s.B = B; s.D = D; s.H = H; s.W = W; s.R = paths; s.kc = (D + kSgSegs - 1) / kSgSegs;
+    s.p1 = p1; s.p2 = p2; s.gain = gain;
+    long long at = 0;
+    for (int i = 0; i < paths; ++i) {                               // the grid's order: r2 .. r7 (r2, r3 of four paths), then r0, r1
+        s.start[i] = (int)at;
+        const bool rows = i >= paths - 2, diagonal = !rows && i >= 2;
+        at += rows ? ((long long)H + kSgRows - 1) / kSgRows : ((long long)W + (diagonal ? H - 1 : 0) + kSgLines - 1) / kSgLines;
+    }
+    s.start[paths] = (int)at;
+    const long long per = ((long long)H * W + 255) / 256;
+    if (at * B > 0x7fffffffLL || per * B > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "lft_sgm: %d maps of %d x %d need more than 2^31 blocks", B, H, W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(at * B));
+    // the registers a lane keeps for its segment of the slopes, and the rows it loads ahead
+    auto scan = [&](auto kc, auto pf) {
+        if (guide) k_sgm_scan<decltype(kc)::value, decltype(pf)::value, true><<<grid, 256, 0, st>>>(s);
+        else k_sgm_scan<decltype(kc)::value, decltype(pf)::value, false><<<grid, 256, 0, st>>>(s);
+    };
+    if (s.kc <= 4) scan(int_c<4>{}, int_c<4>{});
+    else if (s.kc <= 8) scan(int_c<8>{}, int_c<4>{});
+    else if (s.kc <= 12) scan(int_c<12>{}, int_c<4>{});
+    else if (s.kc <= 16) scan(int_c<16>{}, int_c<4>{});
+    else if (s.kc <= 32) scan(int_c<32>{}, int_c<2>{});
+    else scan(int_c<64>{}, int_c<2>{});
+    LFT_LAUNCH_OK("k_sgm_scan");
+    SgmPickArgs p{};
+    p.paths = s.paths; p.stack = stack; p.slopes = slopes;
+    p.H = H; p.W = W; p.D = D; p.C = C; p.R = paths; p.per = (int)per; p.vol = vol;
+    p.disparity = disparity; p.confidence = confidence; p.index = index; p.aggregated = aggregated; p.aif = aif;
+    p.aif_f32 = aif_class == LFT_LF_FLOAT32;
+    k_sgm_pick<<<dim3((unsigned)(per * B)), 256, 0, st>>>(p);
+    LFT_LAUNCH_OK("k_sgm_pick");
     return 0;
 }
 

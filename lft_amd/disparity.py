@@ -34,6 +34,46 @@ That requires a fixed aggregation order, dy then dx.
 ``disparity`` hands the light field as it lies in memory, refocus's table and the fp32 slopes to one call of lft_disparity
 (csrc/lft_disparity.cuh: k_sweep_cost, then k_disparity_pick); there is no CPU path.  ``disparity_error`` compares two light fields
 by their disparity maps: the figure for super-resolved views against ground-truth views.
+
+Semi-global aggregation
+-----------------------
+Winner-take-all decides each pixel from its own window; where the window sees no texture every slope costs the same and the lowest
+k wins.  ``regularize`` (lft_sgm, csrc/lft_sgm.cuh: k_sgm_scan, then k_sgm_pick; declared in include/lft_hip_sgm.h) aggregates a
+cost volume along 4 or 8 paths before the selection, and ``disparity(..., regularize=dict(p1=, p2=, ...))`` sweeps and then does so.
+
+**Inputs**
+- `E`: fp32 `[B, D, H, W]`, the aggregated cost of `lft_disparity` or any other cost. It must be finite. The bit-for-bit promise is
+  for costs ≥ +0.
+- Slopes: as for `lft_disparity`.
+- Host floats `P1`, `P2` with `0 ≤ P1 ≤ P2`, and `gain ≥ 0`, each rounded once to fp32.
+- An optional guide `g`: fp32 `[B, H, W]`.
+- `paths` R ∈ {4, 8}.
+- `1 ≤ D ≤ LFT_SGM_MAX_D = 256`.
+
+**Directions**, in this order; `paths = 4` takes the first four. Here `q = p − r` is the predecessor of `p` on the path.
+- `r0 = (0,+1)`, `r1 = (0,−1)`, `r2 = (+1,0)`, `r3 = (−1,0)`
+- `r4 = (+1,+1)`, `r5 = (−1,−1)`, `r6 = (+1,−1)`, `r7 = (−1,+1)`, each written (dy, dx).
+
+**Recurrence.** All of it is fp32, one rounded operation per step, contraction off.
+- If `q` lies outside the image: `L_r(p,k) = E(p,k)`.
+- Otherwise:
+  - `M = min_j L_r(q,j)`.
+  - `P2' = P2` without a guide.
+  - With a guide: `P2' = max(P1, P2 − fl(gain·|fl(g(p) − g(q))|))`.
+  - `c = fl(M + P2')`.
+  - `b_k = fl(min(L_r(q,k−1), L_r(q,k+1)) + P1)` over the neighbours that exist. With `D = 1` there is none and `b` is absent.
+  - `t_k = min(L_r(q,k), b_k, c)`.
+  - `L_r(p,k) = fl(E(p,k) + fl(t_k − M))`.
+
+**Sum.** `S = fl(…fl(fl(L_0 + L_1) + L_2)… + L_{R−1}) · fl(1/R)`. The scaling is exact for R = 4 and 8.
+
+**Selection.** Steps 4–7 of `lft_disparity`, word for word, applied to `S` in the place of `E`:
+- index: the lowest k on a tie,
+- the parabola refinement,
+- `conf = 1 − S_{k*}/S̄`,
+- `aif` gathered from a stack at `k*`.
+
+Nothing may depend on launch shape, tile or arrival order. Every sum has a fixed order, and `min` has none to fix.
 """
 from __future__ import annotations
 
@@ -77,8 +117,18 @@ def _device_scratch(B: int, D: int, H: int, W: int, C: int, flags: int, device) 
     return _scratch[key]
 
 
+def _device_sgm_scratch(B: int, D: int, H: int, W: int, paths: int, device) -> torch.Tensor:
+    """The path volumes of ``regularize``, one buffer per shape and device, as ``_device_scratch``."""
+    key = ("sgm", B, D, H, W, paths, str(device))
+    if key not in _scratch:
+        n = _lib.query("lft_sgm_scratch_bytes", B, D, H, W, paths)
+        _scratch[key] = torch.empty(max(n // 4, 1), dtype=torch.float32, device=device)
+    return _scratch[key]
+
+
 def clear_cache() -> None:
-    """Drop the cached scratch buffers and slope arrays (the volume of a large sweep is D*H*W*(1 + C) floats)."""
+    """Drop the cached scratch buffers and slope arrays (the volume of a large sweep is D*H*W*(1 + C) floats, the path volumes
+    of ``regularize`` paths*D*H*W)."""
     _scratch.clear()
     _slopes.clear()
 
@@ -94,7 +144,7 @@ def check_slopes(slopes) -> Tuple[float, ...]:
 
 def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
               interp: str = "linear", radius: int = 2, all_in_focus: bool = False, cost_volume: bool = False,
-              aif_dtype=None, centre=None) -> DisparityResult:
+              aif_dtype=None, centre=None, regularize: Optional[dict] = None) -> DisparityResult:
     """The disparity map of a light field on the GPU, on lf's device and current stream (enqueue only).
 
       views  [A, A, H, W, C] (C <= 4) or [A, A, H, W]   ->  maps [H, W], all_in_focus [H, W, C] or [H, W], cost [D, H, W]
@@ -105,7 +155,12 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     (2 radius + 1)^2, 0 .. 8.  all_in_focus: also return the refocus stack gathered at the index, as aif_dtype (default: the
     input's; torch.float32 is the unclipped sum, torch.uint8 clips, scales and rounds half to even).  cost_volume: also return E.
     centre: the angular position (cu, cv) the sweep is seen from (``refocus.shift_table``), default the centre of the views: the
-    map then belongs to that position, and all_in_focus is the plane-sweep rendering of a view there."""
+    map then belongs to that position, and all_in_focus is the plane-sweep rendering of a view there.
+    regularize: None, or dict(p1=, p2=, paths=8, guide=None, edge_gain=0.0): sweep with the cost volume, then ``regularize`` it with
+    these arguments and select from S (cost is then S); all_in_focus gathers from ``refocus.refocus``'s fp32 stack, which is the
+    sweep's m bit for bit."""
+    if regularize is not None:
+        return _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, regularize)
     sl = ()
 
     def sweep_arguments():                  # radius, interp and slopes are refused before a tensor off the GPU
@@ -138,6 +193,114 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     elif aif is not None:
         aif = aif[..., 0]
     return DisparityResult(disp, conf, index, aif, cost)
+
+
+def penalties_from_cost(cost: torch.Tensor, p1_rel: float = 0.1, p2_rel: float = 1.0) -> Tuple[float, float]:
+    """(p1, p2) for ``regularize`` as multiples of the mean of `cost`.  It reads the mean back from the device: it synchronises.
+    The defaults are a starting point, nobody has tuned them."""
+    if not isinstance(cost, torch.Tensor):
+        raise LftError(f"the cost must be a torch tensor, got {type(cost).__name__}")
+    if not (np.isfinite(p1_rel) and np.isfinite(p2_rel) and 0 <= p1_rel <= p2_rel):
+        raise LftError(f"p1_rel and p2_rel must be finite with 0 <= p1_rel <= p2_rel, got {p1_rel!r}, {p2_rel!r}")
+    mean = float(cost.mean(dtype=torch.float64)) if cost.numel() else 0.0
+    return float(p1_rel) * mean, float(p2_rel) * mean
+
+
+def _sgm_arguments(D: Optional[int], slopes, p1, p2, paths, edge_gain, has_guide: bool, aif_dtype, has_stack: bool) -> Tuple[float, ...]:
+    """The refusals of ``regularize`` that need no tensor (D: the slices of the cost volume, None before it exists); returns the
+    checked slopes."""
+    if isinstance(paths, bool) or paths not in (4, 8):
+        raise LftError(f"paths must be 4 or 8, got {paths!r}")
+    for name, v in (("p1", p1), ("p2", p2), ("edge_gain", edge_gain)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v <= float(np.finfo(np.float32).max):
+            raise LftError(f"{name} must be a finite number >= 0 (as float32), got {v!r}")
+    if np.float32(p2) < np.float32(p1):
+        raise LftError(f"p2 must not be below p1, got p1 = {p1!r}, p2 = {p2!r}")
+    if np.float32(edge_gain) > 0 and not has_guide:
+        raise LftError(f"edge_gain {edge_gain!r} needs a guide")
+    if aif_dtype is not None and aif_dtype not in _CLASS:
+        raise LftError(f"aif_dtype must be torch.uint8 or torch.float32, got {aif_dtype}")
+    if aif_dtype is not None and not has_stack:
+        raise LftError("aif_dtype without a stack: the all-in-focus image is gathered from one")
+    sl = check_slopes(slopes)
+    if D is not None and len(sl) != D:
+        raise LftError(f"{len(sl)} slopes for a cost volume of {D} slices")
+    if len(sl) > _lib.SGM_MAX_D:
+        raise LftError(f"{len(sl)} slopes: regularize takes at most {_lib.SGM_MAX_D}")
+    return sl
+
+
+def regularize(cost: torch.Tensor, slopes: Sequence[float], p1: float, p2: float, paths: int = 8, guide: Optional[torch.Tensor] = None,
+               edge_gain: float = 0.0, stack: Optional[torch.Tensor] = None, aif_dtype=None, aggregated: bool = False) -> DisparityResult:
+    """Semi-global aggregation of a cost volume and the selection from it (the module docstring has the definition), on cost's
+    device and current stream (enqueue only).
+
+      cost [D, H, W]     ->  maps [H, W];     guide [H, W];     stack [D, H, W] or [D, H, W, C]        ->  all_in_focus [H, W] or [H, W, C]
+      cost [B, D, H, W]  ->  maps [B, H, W];  guide [B, H, W];  stack [B, D, H, W] or [B, D, H, W, C]  ->  all_in_focus [B, H, W(, C)]
+
+    cost, guide and stack are float32.  p1 <= p2 are the penalties of a step of one slope and of a larger jump along a path
+    (``penalties_from_cost``); with a guide, p2 falls by edge_gain times the guide's step, not below p1.  paths: 4 or 8.  stack:
+    what all_in_focus is gathered from at the index (``refocus.refocus``'s fp32 stack), as aif_dtype (default torch.float32).
+    aggregated: DisparityResult.cost holds S."""
+    if not isinstance(cost, torch.Tensor):
+        raise LftError(f"the cost must be a torch tensor, got {type(cost).__name__}")
+    if cost.dtype != torch.float32 or cost.dim() not in (3, 4):
+        raise LftError(f"the cost must be float32 [D, H, W] or [B, D, H, W], got {cost.dtype} {tuple(cost.shape)}")
+    batch = cost.dim() == 4
+    B, D, H, W = (int(n) for n in (cost.shape if batch else (1,) + tuple(cost.shape)))
+    if D < 1:
+        raise LftError(f"a cost volume of {D} slices")
+    sl = _sgm_arguments(D, slopes, p1, p2, paths, edge_gain, guide is not None, aif_dtype, stack is not None)
+    lead = (B,) if batch else ()
+    for name, t, shapes in (("guide", guide, [lead + (H, W)]), ("stack", stack, [lead + (D, H, W)] + [lead + (D, H, W, c) for c in (1, 2, 3, 4)])):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) not in shapes:
+            raise LftError(f"the {name} must be a float32 tensor of shape {' or '.join(str(list(x)) for x in shapes[:2])}, got "
+                           f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != cost.device:
+            raise LftError(f"the {name} is on {t.device}, the cost on {cost.device}")
+    if cost.device.type != "cuda":
+        raise LftError(f"the cost must be on the GPU, got a tensor on {cost.device} (there is no CPU path)")
+    dev = cost.device
+    channels = stack is not None and stack.dim() == cost.dim() + 1
+    C = int(stack.shape[-1]) if channels else 1
+    aif_dtype = torch.float32 if aif_dtype is None else aif_dtype
+    disp = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    conf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    index = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    S = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if aggregated else None
+    aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if stack is not None else None
+    if B and H and W:
+        cost, guide, stack = (None if t is None else t.contiguous() for t in (cost, guide, stack))
+        scratch = _device_sgm_scratch(B, D, H, W, int(paths), dev)
+        _lib.enqueue("lft_sgm", dev, cost.data_ptr(), B, D, H, W, C, _device_slopes(sl, dev).data_ptr(), int(paths), float(p1), float(p2),
+                     None if guide is None else guide.data_ptr(), float(edge_gain), None if stack is None else stack.data_ptr(),
+                     scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(), index.data_ptr(), None if S is None else S.data_ptr(),
+                     None if aif is None else aif.data_ptr(), _CLASS[aif_dtype])
+    if aif is not None and not channels:
+        aif = aif[..., 0]
+    if not batch:
+        disp, conf, index = disp[0], conf[0], index[0]
+        S = None if S is None else S[0]
+        aif = None if aif is None else aif[0]
+    return DisparityResult(disp, conf, index, aif, S)
+
+
+_SGM_KEYS = ("p1", "p2", "paths", "guide", "edge_gain")
+
+
+def _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, how) -> DisparityResult:
+    """``disparity`` with regularize=how: the sweep's E, refocus's stack when all_in_focus, then ``regularize``."""
+    from . import refocus as Rf
+    if not isinstance(how, dict) or set(how) - set(_SGM_KEYS) or not {"p1", "p2"} <= set(how):
+        raise LftError(f"regularize must be None or a dict with p1, p2 and any of paths, guide, edge_gain, got {how!r}")
+    if aif_dtype is not None and aif_dtype not in _CLASS:
+        raise LftError(f"aif_dtype must be torch.uint8 or torch.float32, got {aif_dtype}")
+    _sgm_arguments(None, slopes, how["p1"], how["p2"], how.get("paths", 8), how.get("edge_gain", 0.0), how.get("guide") is not None, None, False)
+    swept = disparity(lf, slopes, angRes, aperture, interp, radius, cost_volume=True, centre=centre)
+    stack = Rf.refocus(lf, slopes, angRes, aperture, interp, out_dtype=torch.float32, centre=centre) if all_in_focus else None
+    return regularize(swept.cost, slopes, stack=stack, aif_dtype=(aif_dtype or lf.dtype) if all_in_focus else None, aggregated=cost_volume, **how)
 
 
 def disparity_error(a: torch.Tensor, b: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None,

@@ -1,7 +1,7 @@
 """Disparity map, confidence and all-in-focus image of one light field (GPU box): angular consistency as a number.
 
   python tools/disparity.py --lf scene.mat --angRes 5 --out_dir out/ --slopes=-2:2:33 --radius 2 [--aperture full|disk|gaussian]
-                            [--interp nearest|linear|cubic]
+                            [--interp nearest|linear|cubic] [--regularize [--p1 P1 --p2 P2] [--paths 4|8] [--edge_gain G]]
                             [--path_pre_pth LFT_5x5_4x.pth.tar --scale_factor 4 [--precision ..] [--self_ensemble ..]] [--bicubic]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C]; its centre angRes x angRes views are used.  Without
@@ -11,7 +11,10 @@ far).  Slopes are in pixels of the views being swept per view step, LO:HI:N or a
 <out_dir>/disparity.png (the slope range mapped to 0 .. 255, grey as RGB), confidence.png (0 .. 1 mapped to 0 .. 255, grey as RGB),
 all_in_focus.png and disparity.npy (fp32 [H, W], slope units) from one lft_amd.disparity.disparity call.  With both
 --path_pre_pth and --bicubic it prints one JSON line with lft_amd.disparity.disparity_error of the super-resolved views against
-the bicubic ones: the mean absolute disparity difference over the pixels where the bicubic sweep is confident, and their share."""
+the bicubic ones: the mean absolute disparity difference over the pixels where the bicubic sweep is confident, and their share.
+--regularize aggregates the cost volume along --paths paths before the selection (lft_amd.disparity.regularize): the penalties
+default to lft_amd.disparity.penalties_from_cost of the winner-take-all sweep, and with --edge_gain the guide is the channel mean of
+that sweep's all-in-focus image.  Without these flags the files keep their bytes."""
 import argparse
 import json
 import os
@@ -34,10 +37,26 @@ def grey(x: torch.Tensor, lo: float, hi: float) -> np.ndarray:
     return g[..., None].expand(-1, -1, 3).contiguous().cpu().numpy()
 
 
+def regularize_arguments(views, slopes, args, guided=True):
+    """The `regularize` dict of lft_amd.disparity.disparity for --regularize, or None without it.  Penalties not given on the
+    command line come from ``penalties_from_cost`` on the winner-take-all sweep's cost (this synchronises); with --edge_gain > 0 and
+    `guided` the guide is the channel mean of that sweep's fp32 all-in-focus image."""
+    if not args.regularize:
+        return None
+    want_guide = guided and args.edge_gain > 0
+    wta = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus=want_guide,
+                              aif_dtype=torch.float32, cost_volume=True)
+    p1, p2 = disparity.penalties_from_cost(wta.cost)
+    how = dict(p1=p1 if args.p1 is None else args.p1, p2=p2 if args.p2 is None else args.p2, paths=args.paths)
+    if want_guide:
+        how.update(guide=wta.all_in_focus.mean(-1), edge_gain=args.edge_gain)
+    return how
+
+
 def write_maps(out_dir, views, slopes, args, prefix=""):
     """views: [A, A, H, W, 3] on the GPU (uint8, or float32 in [0, 1]).  Returns the paths written."""
     r = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus=True,
-                            aif_dtype=torch.uint8)
+                            aif_dtype=torch.uint8, regularize=regularize_arguments(views, slopes, args))
     paths = [os.path.join(out_dir, prefix + name) for name in ("disparity.png", "confidence.png", "all_in_focus.png", "disparity.npy")]
     png.write_png(paths[0], grey(r.disparity, min(slopes), max(slopes)))
     png.write_png(paths[1], grey(r.confidence, 0.0, 1.0))
@@ -55,6 +74,11 @@ def main(argv=None):
     ap.add_argument("--radius", type=int, default=2, help="the cost is averaged over (2 radius + 1)^2 pixels, 0 .. 8")
     ap.add_argument("--aperture", default="full", choices=("full", "disk", "gaussian"))
     ap.add_argument("--interp", default="linear", choices=tuple(disparity.TAPS))
+    ap.add_argument("--regularize", action="store_true", help="semi-global aggregation of the cost volume before the selection")
+    ap.add_argument("--p1", type=float, default=None, help="penalty of a step of one slope (default: 0.1 x the mean cost)")
+    ap.add_argument("--p2", type=float, default=None, help="penalty of a larger jump (default: the mean cost)")
+    ap.add_argument("--paths", type=int, default=8, choices=(4, 8))
+    ap.add_argument("--edge_gain", type=float, default=0.0, help="p2 falls by this times the step of the guide, not below p1")
     ap.add_argument("--min_confidence", type=float, default=0.5, help="pixels counted by the printed disparity_error")
     ap.add_argument("--path_pre_pth", default=None, help="checkpoint in the reference's format: sweep the super-resolved views")
     ap.add_argument("--scale_factor", type=int, default=4)
@@ -82,8 +106,9 @@ def main(argv=None):
         raw = lf if lf.dtype in (torch.uint8, torch.float32) else lf.float()
         paths += write_maps(args.out_dir, raw, slopes, args)
     if sr is not None and base is not None:
+        # one set of penalties for both sides: the bicubic (trusted) side's, and no guide
         err, share = disparity.disparity_error(sr, base, slopes, min_confidence=args.min_confidence, aperture=args.aperture,
-                                               interp=args.interp, radius=args.radius)
+                                               interp=args.interp, radius=args.radius, **({"regularize": regularize_arguments(base, slopes, args, guided=False)} if args.regularize else {}))
         print(json.dumps({"disparity_error": err, "confident_share": share, "min_confidence": args.min_confidence,
                           "against": "bicubic", "slopes": [min(slopes), max(slopes), len(slopes)], "radius": args.radius}))
     print(f"{args.out_dir}: {len(paths)} files, {len(slopes)} slopes from {min(slopes):g} to {max(slopes):g}")

@@ -12,7 +12,10 @@ The three are timed in the same process, alternating, in `--rounds` rounds (HIP 
 a warm-up); ``kernels_faster_in_every_round`` is the condition the design rests on.  ``index_agreement`` is the share of pixels
 where the two pick the same slope (their costs differ by fp32 rounding and the composition's fp32 grid coordinates).
 
-  python tools/disparity_bench.py [--rounds 3] [--reps 200] [--torch_reps 10] [--warmup 3] [--out profiles/disparity_bench.txt]"""
+  python tools/disparity_bench.py [--rounds 3] [--reps 200] [--torch_reps 10] [--warmup 3] [--out profiles/disparity_bench.txt]
+  python tools/disparity_bench.py --regularize [--rounds 3] [--reps 200] [--warmup 3] [--out profiles/sgm_bench.txt]
+
+--regularize times the semi-global aggregation of that workload's cost volume instead (``regularize_bench``)."""
 import argparse
 import json
 import os
@@ -45,8 +48,40 @@ def torch_index(planes, grids, weights):
     return E.argmin(0), E
 
 
+HBM_PEAK = 8.0e12                                                       # bytes per second, the MI355X's specified peak
+
+
+def regularize_bench(args, lf, slopes):
+    """--regularize: one JSON line per path count.  ``sgm_ms`` is `disparity.regularize` alone (k_sgm_scan + k_sgm_pick) on the
+    sweep's E, ``maps_ms`` the unchanged `disparity.disparity` at the same shape, alternating in the same rounds.  The byte
+    contract follows the decomposition: every direction reads E once and writes its volume L_r once, the selection reads the R
+    volumes once and writes three maps; ``hbm_peak_share`` is that contract over the best time over the specified 8.0 TB/s."""
+    E = disparity.disparity(lf, slopes, interp="linear", radius=RADIUS, cost_volume=True).cost
+    p1, p2 = disparity.penalties_from_cost(E)
+    lines = []
+    for paths in (8, 4):
+        def sgm():
+            return disparity.regularize(E, slopes, p1, p2, paths=paths)
+
+        def maps():
+            return disparity.disparity(lf, slopes, interp="linear", radius=RADIUS)
+
+        for _ in range(args.warmup):
+            sgm(), maps()
+        torch.cuda.synchronize()
+        rounds = [{"sgm_ms": round(timed(sgm, args.reps), 4), "maps_ms": round(timed(maps, args.reps), 4)} for _ in range(args.rounds)]
+        best = min(r["sgm_ms"] for r in rounds)
+        nbytes = 3 * paths * D * H * W * 4 + 3 * H * W * 4
+        lines.append(json.dumps({"bench": "sgm", "device": torch.cuda.get_device_name(0), "A": A, "view": [H, W, C], "D": D, "paths": paths,
+                                 "p1": p1, "p2": p2, "reps": args.reps, "rounds": rounds, "sgm_ms_best": best,
+                                 "maps_ms_best": min(r["maps_ms"] for r in rounds), "contract_bytes": nbytes,
+                                 "sgm_GBps": round(nbytes / (best * 1e-3) / 1e9, 1), "hbm_peak_share": round(nbytes / (best * 1e-3) / HBM_PEAK, 4)}))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--regularize", action="store_true", help="time the semi-global aggregation beside the sweep instead (one line per path count)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--torch_reps", type=int, default=10)
@@ -56,6 +91,14 @@ def main():
     dev = torch.device("cuda", 0)
     slopes = [float(x) for x in np.linspace(-2.0, 2.0, D)]
     lf = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (A, A, H, W, C)).astype(np.uint8)).to(dev)
+    if args.regularize:
+        lines = regularize_bench(args, lf, slopes)
+        print("\n".join(lines))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     planes = (lf.float() / 255).permute(0, 1, 4, 2, 3).reshape(A * A, C, H, W).contiguous()
     grids = torch_grids(slopes, dev)
     weights = [1.0 / (A * A)] * (A * A)
