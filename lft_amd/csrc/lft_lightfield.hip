@@ -4,6 +4,7 @@
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
+#include "../../include/lft_hip_visibility.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
@@ -12,6 +13,7 @@
 #include "lft_refocus.cuh"   // synthetic refocus: focal stack by shift-and-add over the views (lft_refocus)
 #include "lft_disparity.cuh" // disparity: plane-sweep cost volume, windowed aggregation, winner-take-all (lft_disparity)
 #include "lft_views.cuh"     // view synthesis: splat the disparity to the target, fill, gather the views (lft_view_render)
+#include "lft_visibility.cuh" // view synthesis with a per-view visibility test, the warp of a map to other positions (lft_view_render_visible)
 #include "lft_sgm.cuh"       // semi-global aggregation of a cost volume: the path scans, the sum and the selection (lft_sgm)
 
 namespace {
@@ -351,42 +353,133 @@ int lft_view_render_scratch_bytes(int B, int T, int H, int W, size_t* out_bytes)
     *out_bytes = (size_t)B * T * H * W * sizeof(uint32_t);
     return 0;
 }
+// What lft_view_render and lft_view_render_visible check after windowed_lf_ok, in lft_view_render's order, and the launch shape
+// they share.  `who` starts every message.  rtiles == 0: an empty shape, no work and no error.
+struct ViewLaunch { int reach; long long rtiles_x, rtiles; };
+static int view_values_ok(const char* who, int H, int W, float max_delta, float lo, float hi, int near, int fill, ViewLaunch& v) {
+    if (fill < 0 || fill > kVwMaxFill) return fail(LFT_ERR_ARG, "%s: fill %d outside 0 .. %d", who, fill, kVwMaxFill);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi) return fail(LFT_ERR_ARG, "%s: d_range (%g, %g) must be finite with lo <= hi", who, lo, hi);
+    if (near != LFT_VIEW_NEAR_LARGER && near != LFT_VIEW_NEAR_SMALLER) return fail(LFT_ERR_ARG, "%s: near must be LFT_VIEW_NEAR_LARGER or LFT_VIEW_NEAR_SMALLER, got %d", who, near);
+    if (!std::isfinite(max_delta) || max_delta < 0.0f) return fail(LFT_ERR_ARG, "%s: max_delta %g must be finite and >= 0", who, max_delta);
+    // exact in double; an integer bound of the exact product also bounds its fp32 rounding
+    const double reach = std::ceil(std::max(std::fabs((double)lo), std::fabs((double)hi)) * (double)max_delta) + 1.0;
+    if (reach > (double)kVwMaxReach) return fail(LFT_ERR_SHAPE, "%s: reach %.0f pixels (d_range times the largest target offset) above %d", who, reach, kVwMaxReach);
+    if (H > (1 << 24) || W > (1 << 24)) return fail(LFT_ERR_SHAPE, "%s: views of %d x %d: pixel coordinates are fp32, at most 2^24", who, H, W);
+    v.reach = (int)reach;
+    return 0;
+}
+static int view_render_ok(const char* who, WindowedLf& l, int views_class, bool own_null, float max_delta, float lo, float hi, int near, int fill,
+                          float tau, const void* scratch, ViewLaunch& v) {
+    v = ViewLaunch{0, 0, 0};
+    if (int rc = windowed_lf_ok(who, l, views_class, "output", 0, own_null, "renders")) return rc;
+    if (l.taps != 2 && l.taps != 4) return fail(LFT_ERR_ARG, "%s: %d taps (2 or 4: nearest is not offered)", who, l.taps);
+    if (int rc = view_values_ok(who, l.H, l.W, max_delta, lo, hi, near, fill, v)) return rc;
+    if (!std::isfinite(tau) || tau < 0.0f) return fail(LFT_ERR_ARG, "%s: tau %g must be finite and >= 0", who, tau);
+    if (!l.tiles) return 0;                                         // nothing to render
+    const long long rtiles = l.tiles_x * (((long long)l.H + kVwRows - 1) / kVwRows);
+    if (rtiles * l.D * l.B > 0x7fffffffLL) return too_many_blocks(who, l, "renders");
+    if ((double)l.B * l.D * l.H * l.W * 4.0 > 1099511627776.0)
+        return fail(LFT_ERR_SHAPE, "%s: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", who, l.B, l.D, l.H, l.W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
+    v.rtiles_x = l.tiles_x; v.rtiles = rtiles;
+    return 0;
+}
+static SplatArgs splat_args(const float* disparity, const float* deltas, void* scratch, float lo, float hi, int near, int reach, int H, int W, int T,
+                            long long tiles_x, long long tiles) {
+    SplatArgs s{};
+    s.dr = disparity; s.deltas = deltas; s.keys = static_cast<uint32_t*>(scratch); s.lo = lo; s.hi = hi;
+    s.neg = near == LFT_VIEW_NEAR_SMALLER; s.reach = reach;
+    s.H = H; s.W = W; s.T = T; s.tiles_x = (int)tiles_x; s.tiles = (int)tiles;
+    return s;
+}
+static RenderArgs render_args(const WindowedLf& l, const SplatArgs& s, const ViewLaunch& v, int fill, void* views, int views_class, float* target_disparity,
+                              unsigned char* holes) {
+    RenderArgs r{};
+    fill_windowed(r, l);
+    r.dr = s.dr; r.keys = s.keys; r.lo = s.lo; r.hi = s.hi; r.neg = s.neg; r.fill = fill;
+    r.rtiles_x = (int)v.rtiles_x; r.rtiles = (int)v.rtiles;
+    r.out = views; r.out_f32 = views_class == LFT_LF_FLOAT32; r.dt = target_disparity; r.holes = holes;
+    return r;
+}
 int lft_view_render(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const float* disparity,
                     const float* deltas, float max_delta, const void* records, int T, int taps, float lo, float hi, int near, int fill,
                     void* scratch, void* views, int views_class, float* target_disparity, unsigned char* holes, void* stream) {
     WindowedLf l{lf, lf_class, B, A, H, W, C, strides, records, T, taps, 0, 0};
-    if (int rc = windowed_lf_ok("lft_view_render", l, views_class, "output", 0, !disparity || !deltas || !scratch || !views || !target_disparity || !holes, "renders"))
+    ViewLaunch v;
+    if (int rc = view_render_ok("lft_view_render", l, views_class, !disparity || !deltas || !scratch || !views || !target_disparity || !holes, max_delta, lo, hi,
+                                near, fill, 0.0f, scratch, v))
         return rc;
-    if (taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "lft_view_render: %d taps (2 or 4: nearest is not offered)", taps);
-    if (fill < 0 || fill > kVwMaxFill) return fail(LFT_ERR_ARG, "lft_view_render: fill %d outside 0 .. %d", fill, kVwMaxFill);
-    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi) return fail(LFT_ERR_ARG, "lft_view_render: d_range (%g, %g) must be finite with lo <= hi", lo, hi);
-    if (near != LFT_VIEW_NEAR_LARGER && near != LFT_VIEW_NEAR_SMALLER) return fail(LFT_ERR_ARG, "lft_view_render: near must be LFT_VIEW_NEAR_LARGER or LFT_VIEW_NEAR_SMALLER, got %d", near);
-    if (!std::isfinite(max_delta) || max_delta < 0.0f) return fail(LFT_ERR_ARG, "lft_view_render: max_delta %g must be finite and >= 0", max_delta);
-    // exact in double; an integer bound of the exact product also bounds its fp32 rounding
-    const double reach = std::ceil(std::max(std::fabs((double)lo), std::fabs((double)hi)) * (double)max_delta) + 1.0;
-    if (reach > (double)kVwMaxReach) return fail(LFT_ERR_SHAPE, "lft_view_render: reach %.0f pixels (d_range times the largest target offset) above %d", reach, kVwMaxReach);
-    if (H > (1 << 24) || W > (1 << 24)) return fail(LFT_ERR_SHAPE, "lft_view_render: views of %d x %d: pixel coordinates are fp32, at most 2^24", H, W);
-    if (!l.tiles) return 0;                                         // nothing to render
-    const long long rtiles_x = l.tiles_x, rtiles = rtiles_x * (((long long)H + kVwRows - 1) / kVwRows);
-    if (rtiles * T * B > 0x7fffffffLL) return too_many_blocks("lft_view_render", l, "renders");
-    if ((double)B * T * H * W * 4.0 > 1099511627776.0)
-        return fail(LFT_ERR_SHAPE, "lft_view_render: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", B, T, H, W);
-    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_view_render: scratch must be 4-byte aligned");
+    if (!v.rtiles) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SplatArgs s{};
-    s.dr = disparity; s.deltas = deltas; s.keys = static_cast<uint32_t*>(scratch); s.lo = lo; s.hi = hi;
-    s.neg = near == LFT_VIEW_NEAR_SMALLER; s.reach = (int)reach;
-    s.H = H; s.W = W; s.T = T; s.tiles_x = (int)l.tiles_x; s.tiles = (int)l.tiles;
+    const SplatArgs s = splat_args(disparity, deltas, scratch, lo, hi, near, v.reach, H, W, T, l.tiles_x, l.tiles);
     k_view_splat<<<dim3((unsigned)(l.tiles * T * B)), 256, 0, st>>>(s);
     LFT_LAUNCH_OK("k_view_splat");
-    RenderArgs r{};
-    fill_windowed(r, l);
-    r.dr = disparity; r.keys = s.keys; r.lo = lo; r.hi = hi; r.neg = s.neg; r.fill = fill;
-    r.rtiles_x = (int)rtiles_x; r.rtiles = (int)rtiles;
-    r.out = views; r.out_f32 = views_class == LFT_LF_FLOAT32; r.dt = target_disparity; r.holes = holes;
-    const dim3 grid((unsigned)(rtiles * T * B));
+    const RenderArgs r = render_args(l, s, v, fill, views, views_class, target_disparity, holes);
+    const dim3 grid((unsigned)(v.rtiles * T * B));
     by_lf_class<false>(lf_class, [&](auto t) { render_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(r); return 0; });
     LFT_LAUNCH_OK("k_view_render");
+    return 0;
+}
+
+// ---- view synthesis with the per-view visibility test (lft_visibility.cuh; declared in include/lft_hip_visibility.h) ----
+static_assert(kVsMask == LFT_VIS_MASK_VIEWS, "the header states the views whose visible bit stays in registers");
+int lft_view_visible_scratch_bytes(int B, int N, int H, int W, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_view_visible_scratch_bytes: out_bytes is null");
+    if (N < 1) return fail(LFT_ERR_ARG, "lft_view_visible_scratch_bytes: %d positions", N);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_view_visible_scratch_bytes: negative size in B = %d, maps of %d x %d", B, H, W);
+    if ((double)B * N * H * W * 4.0 > 1099511627776.0)
+        return fail(LFT_ERR_SHAPE, "lft_view_visible_scratch_bytes: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", B, N, H, W);
+    *out_bytes = (size_t)B * N * H * W * sizeof(uint32_t);
+    return 0;
+}
+int lft_view_warp_disparity(const float* disparity, int B, int H, int W, const float* deltas, float max_delta, int N, float lo, float hi,
+                            int near, int fill, void* scratch, float* maps, unsigned char* holes, void* stream) {
+    const char* who = "lft_view_warp_disparity";
+    if (N < 1) return fail(LFT_ERR_ARG, "%s: %d positions", who, N);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, maps of %d x %d", who, B, H, W);
+    ViewLaunch v{0, 0, 0};
+    if (int rc = view_values_ok(who, H, W, max_delta, lo, hi, near, fill, v)) return rc;
+    if (B == 0 || H == 0 || W == 0) return 0;                       // nothing to read or write
+    if (!disparity || !deltas || !scratch || !maps || !holes) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, tiles = tiles_x * (((long long)H + kRfTile - 1) / kRfTile);
+    const long long rtiles = tiles_x * (((long long)H + kVwRows - 1) / kVwRows);
+    if (rtiles * N * B > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: %d warps to %d positions over maps of %d x %d need more than 2^31 blocks", who, B, N, H, W);
+    if ((double)B * N * H * W * 4.0 > 1099511627776.0)
+        return fail(LFT_ERR_SHAPE, "%s: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", who, B, N, H, W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SplatArgs s = splat_args(disparity, deltas, scratch, lo, hi, near, v.reach, H, W, N, tiles_x, tiles);
+    k_view_splat<<<dim3((unsigned)(tiles * N * B)), 256, 0, st>>>(s);
+    LFT_LAUNCH_OK("k_view_splat");
+    FillArgs f{};
+    f.keys = s.keys; f.dr = disparity; f.lo = lo; f.hi = hi; f.neg = s.neg; f.fill = fill;
+    f.H = H; f.W = W; f.N = N; f.rtiles_x = (int)tiles_x; f.rtiles = (int)rtiles;
+    f.maps = maps; f.holes = holes;
+    k_view_fill<<<dim3((unsigned)(rtiles * N * B)), 256, 0, st>>>(f);
+    LFT_LAUNCH_OK("k_view_fill");
+    return 0;
+}
+int lft_view_render_visible(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const float* disparity,
+                            const float* view_disparity, float tau, const float* deltas, float max_delta, const void* records, int T, int taps,
+                            float lo, float hi, int near, int fill, void* scratch, void* views, int views_class, float* target_disparity,
+                            unsigned char* holes, unsigned char* visible, void* stream) {
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, records, T, taps, 0, 0};
+    ViewLaunch v;
+    if (int rc = view_render_ok("lft_view_render_visible", l, views_class,
+                                !disparity || !view_disparity || !deltas || !scratch || !views || !target_disparity || !holes || !visible, max_delta, lo, hi,
+                                near, fill, tau, scratch, v))
+        return rc;
+    if (!v.rtiles) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SplatArgs s = splat_args(disparity, deltas, scratch, lo, hi, near, v.reach, H, W, T, l.tiles_x, l.tiles);
+    k_view_splat<<<dim3((unsigned)(l.tiles * T * B)), 256, 0, st>>>(s);
+    LFT_LAUNCH_OK("k_view_splat");
+    VisArgs r{};
+    r.r = render_args(l, s, v, fill, views, views_class, target_disparity, holes);
+    r.dv = view_disparity; r.tau = tau; r.visible = visible;
+    const dim3 grid((unsigned)(v.rtiles * T * B));
+    by_lf_class<false>(lf_class, [&](auto t) { render_vis_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(r); return 0; });
+    LFT_LAUNCH_OK("k_view_render_vis");
     return 0;
 }
 

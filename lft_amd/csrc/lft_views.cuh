@@ -162,6 +162,36 @@ __device__ __forceinline__ void vw_axis(float s, int n, int st, int (&off)[TAPS]
     }
 }
 
+// The fill of one pixel from the pre-fill keys of its target (step 2): Dt[y,x], and whether the pixel was a hole.  The farther of
+// two found values has the smaller key for either `near`.  Shared by k_view_render and k_view_fill (lft_visibility.cuh).
+__device__ __forceinline__ float vw_fill(const uint32_t* keys, const float* dr, int y, int x, int H, int W, int fill, int neg, float lo, float hi,
+                                         bool& hole) {
+    uint32_t key = keys[(size_t)y * W + x];
+    hole = key == 0u;
+    float d;
+    if (hole) {
+        uint32_t k0 = 0u, k1 = 0u;
+        for (int s = 1; s <= fill && x - s >= 0 && !k0; ++s) k0 = keys[(size_t)y * W + x - s];
+        for (int s = 1; s <= fill && x + s < W && !k1; ++s) k1 = keys[(size_t)y * W + x + s];
+        if (!k0 && !k1) {
+            for (int s = 1; s <= fill && y - s >= 0 && !k0; ++s) k0 = keys[(size_t)(y - s) * W + x];
+            for (int s = 1; s <= fill && y + s < H && !k1; ++s) k1 = keys[(size_t)(y + s) * W + x];
+        }
+        if (k0 || k1) {
+            key = k0 && k1 ? min(k0, k1) : (k0 | k1);
+            d = vw_unkey(key);
+            if (neg) d = -d;
+        } else {
+            const float r = dr[(size_t)y * W + x];
+            d = vw_finite(r) ? fminf(fmaxf(r, lo), hi) : (neg ? hi : lo);
+        }
+    } else {
+        d = vw_unkey(key);
+        if (neg) d = -d;
+    }
+    return d == 0.0f ? 0.0f : d;                                     // one zero
+}
+
 template <typename T, int C, int TAPS>
 __global__ __launch_bounds__(256) void k_view_render(RenderArgs a) {
 #pragma clang fp contract(off)
@@ -173,31 +203,8 @@ __global__ __launch_bounds__(256) void k_view_render(RenderArgs a) {
     const size_t plane = (size_t)a.H * a.W;
     const uint32_t* keys = a.keys + ((size_t)b * a.D + t) * plane;
 
-    // ---- fill: pre-fill keys only; the farther of two found values has the smaller key for either `near`
-    uint32_t key = keys[(size_t)y * a.W + x];
-    const bool hole = key == 0u;
-    float d;
-    if (hole) {
-        uint32_t k0 = 0u, k1 = 0u;
-        for (int s = 1; s <= a.fill && x - s >= 0 && !k0; ++s) k0 = keys[(size_t)y * a.W + x - s];
-        for (int s = 1; s <= a.fill && x + s < a.W && !k1; ++s) k1 = keys[(size_t)y * a.W + x + s];
-        if (!k0 && !k1) {
-            for (int s = 1; s <= a.fill && y - s >= 0 && !k0; ++s) k0 = keys[(size_t)(y - s) * a.W + x];
-            for (int s = 1; s <= a.fill && y + s < a.H && !k1; ++s) k1 = keys[(size_t)(y + s) * a.W + x];
-        }
-        if (k0 || k1) {
-            key = k0 && k1 ? min(k0, k1) : (k0 | k1);
-            d = vw_unkey(key);
-            if (a.neg) d = -d;
-        } else {
-            const float r = a.dr[(size_t)b * plane + (size_t)y * a.W + x];
-            d = vw_finite(r) ? fminf(fmaxf(r, a.lo), a.hi) : (a.neg ? a.hi : a.lo);
-        }
-    } else {
-        d = vw_unkey(key);
-        if (a.neg) d = -d;
-    }
-    if (d == 0.0f) d = 0.0f;                                         // one zero
+    bool hole;
+    const float d = vw_fill(keys, a.dr + (size_t)b * plane, y, x, a.H, a.W, a.fill, a.neg, a.lo, a.hi, hole);
     const size_t o = ((size_t)b * a.D + t) * plane + (size_t)y * a.W + x;
     a.dt[o] = d;
     a.holes[o] = hole ? 1 : 0;

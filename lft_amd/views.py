@@ -45,11 +45,34 @@ out all zero is an `LftError`.
 At an integer target with `quad` the taps are `(1,0)` / `(0,1,0,0)` exactly, so the output equals the input view bit for bit, for
 fp32 and for uint8.
 
-Per-view visibility is not tested: in a disocclusion band the views that see the foreground there are blended with those that see
-the background.
+**Visibility** (``render(..., visibility=dict(tau=...))``). Inputs are those of `lft_view_render`, plus:
+
+- `Dv`: the per-view disparity maps, fp32 `[B, A, A, H, W]`. `Dv[u,v]` is the map at integer view position `(u,v)`.
+- `tau`: a threshold, finite, ≥ 0, rounded once to fp32.
+
+Steps 1 (splat) and 2 (fill) are unchanged. `Dt` and `holes` carry the same bits as the plain call.
+
+Step 3 gains a test per view of non-zero weight. Use the same `sy`, `sx`, `inside` as now. Then:
+
+- **Footprint.** `iy = floor(sy)`, `ix = floor(sx)`. The footprint is `(iy+a, ix+b)` for `a, b ∈ {0,1}`.
+  - `a = 1` is dropped when `sy` is integral. `b = 1` is dropped when `sx` is integral. Indices are clamped into the image.
+  - The footprint is the same for linear and cubic.
+- **Occluded.** For `near = larger`: some finite footprint value `q = Dv[u,v,·,·]` satisfies `q > fl(d + tau)`. For `near = smaller`:
+  `q < fl(d − tau)`. Non-finite `q` never occludes. All comparisons are fp32, so a numpy float32 restatement gives the same booleans.
+- **Three classes.** `visible` = inside and not occluded. `inside`. `all`: every view with `w > 0`.
+- **Output.** `out = Σ w·s / Σ w` over the first non-empty class in that order. Accumulate in `(u,v)` order with the same FMAs as
+  now. Views outside the chosen class contribute nothing. So when nothing is occluded, the bits equal `lft_view_render`'s.
+- **New output** `visible`: uint8 `[B,T,H,W]`, the number of views in the `visible` class, saturated at 255.
+
+By default `Dv` is made from `Dr` itself: splat and fill (steps 1–2) to the A×A integer positions (``warp_disparity``). The hole fill
+already takes the farther neighbour, which is what a disocclusion needs. A caller may pass their own maps instead, for example from
+per-view sweeps with ``disparity(centre=(u,v))``. Rendered at the reference position with nothing excluded, `visible` is an occlusion
+map: how many views see the surface at each pixel.
 
 ``render`` hands the light field as it lies in memory, the map, the record table and the target offsets to one call of
-lft_view_render (csrc/lft_views.cuh: k_view_splat, then k_view_render; declared in include/lft_hip_views.h); there is no CPU path.
+lft_view_render (csrc/lft_views.cuh: k_view_splat, then k_view_render; declared in include/lft_hip_views.h); with `visibility`, to
+one call of lft_view_render_visible (csrc/lft_visibility.cuh: k_view_splat, then k_view_render_vis; include/lft_hip_visibility.h),
+after one of lft_view_warp_disparity (k_view_splat, then k_view_fill) where the maps are not given.  There is no CPU path.
 ``densify`` renders the views between the given ones, ``leave_one_out`` scores how well the other views predict each view.
 """
 from __future__ import annotations
@@ -76,6 +99,13 @@ class RenderResult(NamedTuple):
     views: torch.Tensor          # [T, H, W, C] for views with channels, [T, H, W] for views without and mosaics, [B, T, H, W] for a batch
     disparity: torch.Tensor      # fp32 [T, H, W] ([B, T, H, W]): Dt, the map at each target after the fill
     holes: torch.Tensor          # uint8, the same shape: 1 where Dt was filled
+
+
+class VisibleRenderResult(NamedTuple):
+    views: torch.Tensor          # as RenderResult's
+    disparity: torch.Tensor
+    holes: torch.Tensor
+    visible: torch.Tensor        # uint8, the shape of holes: the views of non-zero weight that see the pixel's surface, at most 255
 
 
 def check_targets(targets) -> np.ndarray:
@@ -178,7 +208,7 @@ def record_table(A: int, targets, weights: np.ndarray) -> np.ndarray:
     return tab
 
 
-_tables: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+_tables: Dict[tuple, Tuple[torch.Tensor, ...]] = {}
 _scratch: Dict[tuple, torch.Tensor] = {}
 
 
@@ -192,11 +222,11 @@ def _device_tables(A: int, t: np.ndarray, deltas: np.ndarray, weights: np.ndarra
     return _tables[key]
 
 
-def _device_scratch(B: int, T: int, H: int, W: int, device) -> torch.Tensor:
-    """The pre-fill map, one buffer per shape and device: calls of one shape on different streams must not overlap."""
-    key = (B, T, H, W, str(device))
+def _device_scratch(B: int, T: int, H: int, W: int, device, query: str = "lft_view_render_scratch_bytes") -> torch.Tensor:
+    """The pre-fill map, one buffer per size query, shape and device: calls of one shape on different streams must not overlap."""
+    key = (query, B, T, H, W, str(device))
     if key not in _scratch:
-        n = _lib.query("lft_view_render_scratch_bytes", B, T, H, W)
+        n = _lib.query(query, B, T, H, W)
         _scratch[key] = torch.empty(max(n // 4, 1), dtype=torch.int32, device=device)
     return _scratch[key]
 
@@ -207,9 +237,78 @@ def clear_cache() -> None:
     _scratch.clear()
 
 
+def _check_fill(near, fill) -> None:
+    if near not in NEAR:
+        raise LftError(f"near must be larger or smaller, got {near!r}")
+    if isinstance(fill, bool) or int(fill) != fill or not 0 <= int(fill) <= MAX_FILL:
+        raise LftError(f"fill must be an integer in 0 .. {MAX_FILL}, got {fill!r}")
+
+
+def _check_reach(lo: float, hi: float, deltas_h: np.ndarray) -> None:
+    reach = splat_reach((lo, hi), deltas_h)
+    if reach > MAX_REACH:
+        raise LftError(f"reach {reach} pixels (d_range {lo:g} .. {hi:g} times the largest target offset "
+                       f"{float(np.abs(deltas_h).max()):g}) above {MAX_REACH}: a shape error")
+
+
+def _warp(dr: torch.Tensor, B: int, H: int, W: int, deltas_h: np.ndarray, lo: float, hi: float, near: str, fill: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(maps fp32 [B, N, H, W], holes uint8 [B, N, H, W]) of the contiguous map dr [B, H, W] at the N offsets deltas_h: one enqueue."""
+    dev, N = dr.device, len(deltas_h)
+    key = ("deltas", deltas_h.tobytes(), str(dev))
+    if key not in _tables:
+        _tables[key] = (torch.from_numpy(deltas_h.copy()).to(dev),)
+    maps = torch.empty(B, N, H, W, dtype=torch.float32, device=dev)
+    holes = torch.empty(B, N, H, W, dtype=torch.uint8, device=dev)
+    if B and H and W:
+        scratch = _device_scratch(B, N, H, W, dev, "lft_view_visible_scratch_bytes")
+        _lib.enqueue("lft_view_warp_disparity", dev, dr.data_ptr(), B, H, W, _tables[key][0].data_ptr(), float(np.abs(deltas_h).max()), N, lo, hi,
+                     NEAR[near], int(fill), scratch.data_ptr(), maps.data_ptr(), holes.data_ptr())
+    return maps, holes
+
+
+def warp_disparity(disparity: torch.Tensor, positions, d_range, reference, near: str = "larger", fill: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(maps, holes): the disparity map, given at the angular position `reference` = (ur, vr), at each of the N `positions` (u, v) --
+    steps 1 and 2 of the module's definition alone, on the map's device and current stream (enqueue only).
+
+      disparity [H, W]     ->  maps fp32 [N, H, W],    holes uint8 [N, H, W]
+      disparity [B, H, W]  ->  maps fp32 [B, N, H, W], holes uint8 [B, N, H, W]
+
+    With the A×A integer positions in (u, v) order, maps reshaped to [A, A, H, W] is what ``render(visibility=...)`` uses by default."""
+    _check_fill(near, fill)
+    lo, hi = check_range(d_range)
+    t = check_targets(positions)
+    if reference is None:
+        raise LftError("warp_disparity: reference (ur, vr), the position the map is given at, is required")
+    if not isinstance(disparity, torch.Tensor) or disparity.dtype != torch.float32 or disparity.dim() not in (2, 3):
+        raise LftError("the disparity map must be a float32 torch tensor [H, W] or [B, H, W]")
+    deltas_h = (t - np.array(_reference(1, reference), dtype=np.float64)).astype(np.float32)
+    _check_reach(lo, hi, deltas_h)
+    if disparity.device.type != "cuda":
+        raise LftError("warp_disparity runs on the GPU only (no CPU path): the disparity map is on " + str(disparity.device))
+    dr = disparity.contiguous()
+    maps, holes = _warp(dr if dr.dim() == 3 else dr[None], 1 if dr.dim() == 2 else int(dr.shape[0]), int(dr.shape[-2]), int(dr.shape[-1]), deltas_h, lo, hi, near, fill)
+    return (maps, holes) if disparity.dim() == 3 else (maps[0], holes[0])
+
+
+def _check_visibility(visibility) -> Tuple[float, Optional[torch.Tensor]]:
+    """(tau as the fp32 value the kernel adds, the caller's maps or None) of ``render``'s `visibility`."""
+    if not isinstance(visibility, dict) or "tau" not in visibility or set(visibility) - {"tau", "view_disparity"}:
+        raise LftError(f"visibility must be a dict with tau and, optionally, view_disparity, got {visibility!r}")
+    try:
+        tau = float(np.float32(visibility["tau"]))
+    except (TypeError, ValueError):
+        raise LftError(f"visibility: tau must be a number, got {visibility['tau']!r}") from None
+    if not (math.isfinite(tau) and tau >= 0):
+        raise LftError(f"visibility: tau must be finite and >= 0, got {visibility['tau']!r}")
+    dv = visibility.get("view_disparity")
+    if dv is not None and (not isinstance(dv, torch.Tensor) or dv.dtype != torch.float32):
+        raise LftError("visibility: view_disparity must be a float32 torch tensor")
+    return tau, dv
+
+
 def render(lf: torch.Tensor, disparity: torch.Tensor, targets, d_range, angRes: Optional[int] = None, reference=None,
            blend: Blend = "quad", sigma: float = 0.75, exclude=None, interp: str = "linear", near: str = "larger", fill: int = 32,
-           out_dtype=None) -> RenderResult:
+           out_dtype=None, visibility: Optional[dict] = None) -> Union[RenderResult, VisibleRenderResult]:
     """The views of a light field at the angular positions `targets`, on lf's device and current stream (enqueue only).
 
       views  [A, A, H, W, C] (C <= 4) or [A, A, H, W], disparity [H, W]   ->  views [T, H, W, C] or [T, H, W], maps [T, H, W]
@@ -218,17 +317,21 @@ def render(lf: torch.Tensor, disparity: torch.Tensor, targets, d_range, angRes: 
 
     Layouts, strides and input classes are ``refocus.refocus``'s; out_dtype (default: the input's) is torch.float32, the quotient
     itself, or torch.uint8.  disparity: fp32, on lf's device, at `reference` (default the centre, where ``disparity.disparity``
-    gives it; with its ``centre=`` anywhere else).  d_range: the ends of the sweep the map came from."""
-    t = lo = hi = weights = deltas_h = None
+    gives it; with its ``centre=`` anywhere else).  d_range: the ends of the sweep the map came from.
+
+    visibility: None, or dict(tau=..., view_disparity=None) for the per-view visibility test of the module's definition; the result
+    is then a VisibleRenderResult, whose fourth field counts the views that see each pixel.  view_disparity: the per-view maps
+    [A, A, H, W] ([B, A, A, H, W] for a batch), fp32 on lf's device; None: `disparity` warped to the A×A views first, one more
+    enqueue (``warp_disparity``; its reach, to the farthest view from `reference`, falls under the same limit as the targets')."""
+    t = lo = hi = weights = deltas_h = tau = dv = None
 
     def own_arguments():                   # refused before a tensor off the GPU
-        nonlocal t, lo, hi, weights, deltas_h
+        nonlocal t, lo, hi, weights, deltas_h, tau, dv
         if interp not in TAPS:
             raise LftError(f"interp must be linear or cubic (nearest is discontinuous in the disparity), got {interp!r}")
-        if near not in NEAR:
-            raise LftError(f"near must be larger or smaller, got {near!r}")
-        if isinstance(fill, bool) or int(fill) != fill or not 0 <= int(fill) <= MAX_FILL:
-            raise LftError(f"fill must be an integer in 0 .. {MAX_FILL}, got {fill!r}")
+        _check_fill(near, fill)
+        if visibility is not None:
+            tau, dv = _check_visibility(visibility)
         lo, hi = check_range(d_range)
         t = check_targets(targets)
         if not isinstance(disparity, torch.Tensor) or disparity.dtype != torch.float32:
@@ -236,10 +339,7 @@ def render(lf: torch.Tensor, disparity: torch.Tensor, targets, d_range, angRes: 
         A = _layout(lf, angRes)[1]
         weights = blend_weights(A, t, blend, sigma, exclude)
         deltas_h = target_deltas(A, t, reference)
-        reach = splat_reach((lo, hi), deltas_h)
-        if reach > MAX_REACH:
-            raise LftError(f"reach {reach} pixels (d_range {lo:g} .. {hi:g} times the largest target offset "
-                           f"{float(np.abs(deltas_h).max()):g}) above {MAX_REACH}: a shape error")
+        _check_reach(lo, hi, deltas_h)
 
     B, A, H, W, C, strides, kind = _field(lf, angRes, "out_dtype", out_dtype, before_device=own_arguments)
     out_dtype = lf.dtype if out_dtype is None else out_dtype
@@ -255,6 +355,27 @@ def render(lf: torch.Tensor, disparity: torch.Tensor, targets, d_range, angRes: 
     out = torch.empty(B, T, H, W, C, dtype=out_dtype, device=dev)
     dt = torch.empty(B, T, H, W, dtype=torch.float32, device=dev)
     holes = torch.empty(B, T, H, W, dtype=torch.uint8, device=dev)
+    if visibility is not None:
+        if dv is None:
+            views_at = target_deltas(A, [(u, v) for u in range(A) for v in range(A)], reference)
+            _check_reach(lo, hi, views_at)
+            dv = _warp(dr if dr.dim() == 3 else dr[None], B, H, W, views_at, lo, hi, near, fill)[0]
+        else:
+            if dv.device != dev:
+                raise LftError(f"visibility: view_disparity is on {dv.device}, the light field on {dev}")
+            if tuple(dv.shape) not in ((B, A, A, H, W),) + (((A, A, H, W),) if B == 1 else ()):
+                raise LftError(f"visibility: view_disparity must be {[A, A, H, W] if kind != 'batch' else [B, A, A, H, W]} for this light field, "
+                               f"got shape {tuple(dv.shape)}")
+            dv = dv.contiguous()
+        seen = torch.empty(B, T, H, W, dtype=torch.uint8, device=dev)
+        if B and H and W:
+            scratch = _device_scratch(B, T, H, W, dev, "lft_view_visible_scratch_bytes")
+            _lib.enqueue("lft_view_render_visible", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, dr.data_ptr(), dv.data_ptr(), tau,
+                         deltas.data_ptr(), float(np.abs(deltas_h).max()), records.data_ptr(), T, TAPS[interp], lo, hi, NEAR[near], int(fill),
+                         scratch.data_ptr(), out.data_ptr(), _CLASS[out_dtype], dt.data_ptr(), holes.data_ptr(), seen.data_ptr())
+        if kind == "batch":
+            return VisibleRenderResult(out[..., 0], dt, holes, seen)
+        return VisibleRenderResult(out[0] if kind == "views5" else out[0, ..., 0], dt[0], holes[0], seen[0])
     if B and H and W:
         scratch = _device_scratch(B, T, H, W, dev)
         _lib.enqueue("lft_view_render", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, dr.data_ptr(), deltas.data_ptr(),
@@ -276,7 +397,8 @@ def grid_targets(A: int, factor: int) -> np.ndarray:
 
 def densify(lf: torch.Tensor, disparity: torch.Tensor, factor: int, d_range, angRes: Optional[int] = None, **kw) -> torch.Tensor:
     """The light field with `factor` times as many view steps: [A', A', H, W(, C)], A' = factor·(A−1)+1.  The given views are
-    copied to their places, the ones between them rendered in one ``render`` call (kw goes there).  Views and mosaics, not batches."""
+    copied to their places, the ones between them rendered in one ``render`` call (kw goes there, `visibility` included).  Views and
+    mosaics, not batches."""
     if not isinstance(lf, torch.Tensor):
         raise LftError(f"the light field must be a torch tensor, got {type(lf).__name__}")
     if lf.dim() == 4 and not (angRes is None or (lf.shape[0] == lf.shape[1] == angRes and lf.shape[1] != 1)):
@@ -317,7 +439,8 @@ def leave_one_out(lf: torch.Tensor, slopes: Sequence[float], positions=None, ang
     step, ceil(max|slope|) + 1 pixels: the nearest views carry the gaussian's weight.  With `disparity` (a map [H, W] at
     `reference`, default the centre) nothing is swept: every held-out view is rendered from that map, the slopes give d_range, and
     the interior is left by the splat's reach where that is larger.  regularize goes to the sweeps (``disparity.disparity``: None, or
-    the arguments of the semi-global aggregation).  kw goes to ``render``.  An angularly inconsistent field scores
+    the arguments of the semi-global aggregation).  kw goes to ``render``, `visibility` included: with it the views that do not see a
+    pixel's surface leave its blend.  An angularly inconsistent field scores
     low however good its single views are.  A view reproduced exactly scores inf."""
     from . import disparity as Dm
     from .refocus import _views

@@ -1,7 +1,7 @@
 """Views along a camera path, or the densified array of views, of one light field (GPU box): what the disparity map is for.
 
   python tools/view_path.py --lf scene.mat --angRes 5 --out_dir out/ --slopes=-2:2:33 --path circle|line|grid:<factor> --frames 24
-                            [--radius 2] [--interp linear|cubic] [--blend quad|gaussian|nearest]
+                            [--radius 2] [--interp linear|cubic] [--blend quad|gaussian|nearest] [--visibility [TAU]]
                             [--path_pre_pth LFT_5x5_4x.pth.tar --scale_factor 4 [--precision ..] [--self_ensemble ..]] [--bicubic]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C]; its centre angRes x angRes views are used.  Without
@@ -12,7 +12,11 @@ view step), the views from one lft_amd.views.render call.  circle: --frames targ
 centre view; line: --frames targets from the left-most to the right-most view of the centre row; both write frame_<i>.png.
 grid:<factor>: lft_amd.views.densify, written as view_<i>_<j>.png, i and j counting the factor * (A-1) + 1 positions a side.
 With both --path_pre_pth and --bicubic it prints one JSON line with the leave-one-out PSNR (lft_amd.views.leave_one_out, mean
-over the views) of the super-resolved and of the bicubic views: how well each field's other views predict a held-out one."""
+over the views) of the super-resolved and of the bicubic views: how well each field's other views predict a held-out one.
+--visibility [TAU]: render with the per-view visibility test (lft_amd.views, "Visibility"), the per-view maps warped from the swept
+one.  TAU defaults to the largest step between adjacent slopes of the sweep -- a choice, not a measurement: two surfaces the sweep
+cannot tell apart do not occlude one another.  The JSON line then also carries the leave-one-out PSNR with the test
+(leave_one_out_psnr_visible), beside the one without."""
 import argparse
 import json
 import math
@@ -42,12 +46,20 @@ def path_targets(kind: str, A: int, frames: int):
     raise SystemExit(f"--path must be circle, line or grid:<factor>, got {kind!r}")
 
 
+def visibility_of(args, slopes):
+    """None, or the `visibility` argument of lft_amd.views.render for --visibility [TAU]."""
+    if args.visibility is None:
+        return None
+    tau = max(np.diff(np.array(slopes, dtype=np.float64)), default=0.0) if args.visibility == "auto" else float(args.visibility)
+    return dict(tau=float(tau))
+
+
 def write_frames(out_dir, field, slopes, args, prefix=""):
     """field: [A, A, H, W, 3] on the GPU (uint8, or float32 in [0, 1]).  Returns the paths written."""
     A = int(field.shape[0])
     d_range = (min(slopes), max(slopes))
     dr = disparity.disparity(field, slopes, interp=args.interp, radius=args.radius).disparity
-    kw = dict(blend=args.blend, interp=args.interp, out_dtype=torch.uint8)
+    kw = dict(blend=args.blend, interp=args.interp, out_dtype=torch.uint8, visibility=visibility_of(args, slopes))
     if args.path.startswith("grid:"):
         dense = views.densify(field, dr, int(args.path[5:]), d_range, **kw).cpu().numpy()
         named = [(f"view_{i}_{j}.png", dense[i, j]) for i in range(dense.shape[0]) for j in range(dense.shape[1])]
@@ -72,6 +84,8 @@ def main(argv=None):
     ap.add_argument("--radius", type=int, default=2, help="aggregation radius of the disparity sweep, 0 .. 8")
     ap.add_argument("--interp", default="linear", choices=tuple(views.TAPS))
     ap.add_argument("--blend", default="quad", choices=("quad", "gaussian", "nearest"))
+    ap.add_argument("--visibility", nargs="?", const="auto", default=None, metavar="TAU",
+                    help="per-view visibility test; TAU defaults to the largest step between adjacent slopes")
     ap.add_argument("--path_pre_pth", default=None, help="checkpoint in the reference's format: render the super-resolved views")
     ap.add_argument("--scale_factor", type=int, default=4)
     ap.add_argument("--bicubic", action="store_true", help="render the bicubic baseline (prefix bicubic_)")
@@ -99,9 +113,15 @@ def main(argv=None):
         paths += write_frames(args.out_dir, raw, slopes, args)
     if sr is not None and base is not None:
         loo = {name: views.leave_one_out(field, slopes, interp=args.interp, radius=args.radius) for name, field in (("sr", sr), ("bicubic", base))}
-        print(json.dumps({"leave_one_out_psnr": {k: float(np.mean(v)) for k, v in loo.items()},
-                          "leave_one_out_psnr_min": {k: float(np.min(v)) for k, v in loo.items()}, "views": len(loo["sr"]),
-                          "slopes": [min(slopes), max(slopes), len(slopes)], "radius": args.radius, "interp": args.interp}))
+        rec = {"leave_one_out_psnr": {k: float(np.mean(v)) for k, v in loo.items()},
+               "leave_one_out_psnr_min": {k: float(np.min(v)) for k, v in loo.items()}, "views": len(loo["sr"]),
+               "slopes": [min(slopes), max(slopes), len(slopes)], "radius": args.radius, "interp": args.interp}
+        vis = visibility_of(args, slopes)
+        if vis is not None:
+            seen = {name: views.leave_one_out(field, slopes, interp=args.interp, radius=args.radius, visibility=vis) for name, field in (("sr", sr), ("bicubic", base))}
+            rec["leave_one_out_psnr_visible"] = {k: float(np.mean(v)) for k, v in seen.items()}
+            rec["visibility_tau"] = vis["tau"]
+        print(json.dumps(rec))
     print(f"{args.out_dir}: {len(paths)} files, path {args.path}")
     return paths
 
