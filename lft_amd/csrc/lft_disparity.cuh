@@ -47,6 +47,8 @@
 //                     best E and its k, the E before it, the E after it (caught by a pending flag), the last E and the running
 //                     sum; after the last slope it refines and writes disparity, confidence, index, and gathers aif from the
 //                     stack.  E goes out per slope when the caller asks for it.
+//   DpSelect, dp_gather_aif   steps 4-7 for one pixel, written once here: the state a lane keeps (step(k, E) per slope, finish
+//                     after the last) and the gather.  k_disparity_pick and k_sgm_pick (lft_sgm.cuh) both run them.
 // Nothing here depends on which tile a pixel falls in: every sum has a fixed order and a fixed set of terms per pixel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -201,6 +203,51 @@ __global__ __launch_bounds__(256) void k_sweep_cost(SweepArgs a) {
     }
 }
 
+// The selection (steps 4-7) of one pixel, written once: k_disparity_pick feeds it E_k, k_sgm_pick (lft_sgm.cuh) S_k, in k order.
+// It keeps the best value and its k, the value before it, the value after it (caught by the pending flag), the last value and the
+// running sum.
+struct DpSelect {
+    float best = 0.0f, before = 0.0f, after = 0.0f, last = 0.0f, sum = 0.0f;
+    int bk = 0;
+    bool pending = true;
+
+    __device__ __forceinline__ void step(int k, float E) {
+#pragma clang fp contract(off)
+        sum = k ? sum + E : E;
+        if (k == 0 || E < best) {                                    // strict: the lowest k wins an exact tie
+            before = last; best = E; bk = k; pending = true;
+        } else if (pending) {
+            after = E; pending = false;
+        }
+        last = E;
+    }
+    // after the last of the D values: refines, writes disparity, confidence and index at pixel o of [B, H, W]; returns k*
+    __device__ __forceinline__ int finish(const float* slopes, int D, float* disparity, float* confidence, int* index, size_t o) const {
+#pragma clang fp contract(off)
+        float delta = 0.0f;
+        if (bk > 0 && !pending) {                                    // pending: no slope after the best one, bk == D - 1
+            const float den = (before - best) + (after - best);
+            if (den > 0.0f) delta = fminf(fmaxf((0.5f * (before - after)) / den, -0.5f), 0.5f);
+        }
+        const float dk = slopes[bk];
+        float disp = dk;
+        if (delta > 0.0f) disp = dk + delta * (slopes[bk + 1] - dk);
+        else if (delta < 0.0f) disp = dk + delta * (dk - slopes[bk - 1]);
+        const float mean = sum / (float)D;
+        disparity[o] = disp;
+        confidence[o] = mean > 0.0f ? 1.0f - best / mean : 0.0f;
+        index[o] = bk;
+        return bk;
+    }
+};
+// step 7 at pixel o of [B, H, W]: mk, the pixel's C channels of the stack at k*, to aif as fp32 or as bytes (rf_byte)
+__device__ __forceinline__ void dp_gather_aif(const float* mk, int C, void* aif, int aif_f32, size_t o) {
+    for (int c = 0; c < C; ++c) {
+        if (aif_f32) static_cast<float*>(aif)[o * C + c] = mk[c];
+        else static_cast<uint8_t*>(aif)[o * C + c] = rf_byte(mk[c]);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_disparity_pick(PickArgs a) {
 #pragma clang fp contract(off)
     __shared__ float vt[kDpCols * kDpPitch];                         // V_k of the tile and its halo
@@ -217,9 +264,7 @@ __global__ __launch_bounds__(256) void k_disparity_pick(PickArgs a) {
     const size_t plane = (size_t)a.H * a.W;
     const int gx = min(max(x0 - r + lx, 0), a.W - 1);                // this lane's column of the halo, clamped into the image
 
-    float best = 0.0f, before = 0.0f, after = 0.0f, last = 0.0f, sum = 0.0f;
-    int bk = 0;
-    bool pending = true;
+    DpSelect sel;
     for (int k = 0; k < a.D; ++k) {
         const float* v = a.vol + ((size_t)b * a.D + k) * plane;
         if (lx < pw)
@@ -236,37 +281,13 @@ __global__ __launch_bounds__(256) void k_disparity_pick(PickArgs a) {
         for (int dx = 1; dx < n; ++dx) s += cs[py * kDpPitch + px + dx];
         const float E = s * inv;
         if (a.cost && live) a.cost[((size_t)b * a.D + k) * plane + (size_t)(y0 + py) * a.W + x0 + px] = E;
-        sum = k ? sum + E : E;
-        if (k == 0 || E < best) {                                    // strict: the lowest k wins an exact tie
-            before = last; best = E; bk = k; pending = true;
-        } else if (pending) {
-            after = E; pending = false;
-        }
-        last = E;
+        sel.step(k, E);
     }
     if (!live) return;
 
-    float delta = 0.0f;
-    if (bk > 0 && !pending) {                                        // pending: no slope after the best one, bk == D - 1
-        const float den = (before - best) + (after - best);
-        if (den > 0.0f) delta = fminf(fmaxf((0.5f * (before - after)) / den, -0.5f), 0.5f);
-    }
-    const float dk = a.slopes[bk];
-    float disp = dk;
-    if (delta > 0.0f) disp = dk + delta * (a.slopes[bk + 1] - dk);
-    else if (delta < 0.0f) disp = dk + delta * (dk - a.slopes[bk - 1]);
-    const float mean = sum / (float)a.D;
-    const size_t o = (size_t)b * plane + (size_t)(y0 + py) * a.W + x0 + px;
-    a.disparity[o] = disp;
-    a.confidence[o] = mean > 0.0f ? 1.0f - best / mean : 0.0f;
-    a.index[o] = bk;
-    if (a.aif) {
-        const float* mk = a.stack + (((size_t)b * a.D + bk) * plane + (size_t)(y0 + py) * a.W + x0 + px) * a.C;
-        for (int c = 0; c < a.C; ++c) {
-            if (a.aif_f32) static_cast<float*>(a.aif)[o * a.C + c] = mk[c];
-            else static_cast<uint8_t*>(a.aif)[o * a.C + c] = (uint8_t)(int)rintf(255.0f * fminf(fmaxf(mk[c], 0.0f), 1.0f));
-        }
-    }
+    const size_t at = (size_t)(y0 + py) * a.W + x0 + px, o = (size_t)b * plane + at;
+    const int bk = sel.finish(a.slopes, a.D, a.disparity, a.confidence, a.index, o);
+    if (a.aif) dp_gather_aif(a.stack + (((size_t)b * a.D + bk) * plane + at) * a.C, a.C, a.aif, a.aif_f32, o);
 }
 
 // the instantiation for an input type, channel count (1 .. 4) and tap count (1, 2, 4)

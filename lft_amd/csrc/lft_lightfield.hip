@@ -344,14 +344,23 @@ int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int 
 }
 
 // ---- view synthesis (lft_views.cuh; declared in include/lft_hip_views.h) ----
-int lft_view_render_scratch_bytes(int B, int T, int H, int W, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_view_render: out_bytes is null");
-    if (T < 1) return fail(LFT_ERR_ARG, "lft_view_render: %d targets", T);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_view_render: negative size in B = %d, views of %d x %d", B, H, W);
-    const double n = (double)B * T * H * W * 4.0;
-    if (n > 1099511627776.0) return fail(LFT_ERR_SHAPE, "lft_view_render: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", B, T, H, W);
-    *out_bytes = (size_t)B * T * H * W * sizeof(uint32_t);
+// The pre-fill map [B, N, H, W] of keys, one dword each, must fit 2^40 bytes.  `who` starts the message.
+static int prefill_map_ok(const char* who, int B, int N, int H, int W) {
+    if ((double)B * N * H * W * 4.0 > 1099511627776.0)
+        return fail(LFT_ERR_SHAPE, "%s: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", who, B, N, H, W);
     return 0;
+}
+// The body of the two scratch-size queries: the bytes of the pre-fill map.  The messages call the N planes `what`, of `planes`.
+static int prefill_map_bytes(const char* who, const char* what, const char* planes, int B, int N, int H, int W, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "%s: out_bytes is null", who);
+    if (N < 1) return fail(LFT_ERR_ARG, "%s: %d %s", who, N, what);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, %s of %d x %d", who, B, planes, H, W);
+    if (int rc = prefill_map_ok(who, B, N, H, W)) return rc;
+    *out_bytes = (size_t)B * N * H * W * sizeof(uint32_t);
+    return 0;
+}
+int lft_view_render_scratch_bytes(int B, int T, int H, int W, size_t* out_bytes) {
+    return prefill_map_bytes("lft_view_render", "targets", "views", B, T, H, W, out_bytes);
 }
 // What lft_view_render and lft_view_render_visible check after windowed_lf_ok, in lft_view_render's order, and the launch shape
 // they share.  `who` starts every message.  rtiles == 0: an empty shape, no work and no error.
@@ -378,8 +387,7 @@ static int view_render_ok(const char* who, WindowedLf& l, int views_class, bool 
     if (!l.tiles) return 0;                                         // nothing to render
     const long long rtiles = l.tiles_x * (((long long)l.H + kVwRows - 1) / kVwRows);
     if (rtiles * l.D * l.B > 0x7fffffffLL) return too_many_blocks(who, l, "renders");
-    if ((double)l.B * l.D * l.H * l.W * 4.0 > 1099511627776.0)
-        return fail(LFT_ERR_SHAPE, "%s: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", who, l.B, l.D, l.H, l.W);
+    if (int rc = prefill_map_ok(who, l.B, l.D, l.H, l.W)) return rc;
     if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
     v.rtiles_x = l.tiles_x; v.rtiles = rtiles;
     return 0;
@@ -391,6 +399,12 @@ static SplatArgs splat_args(const float* disparity, const float* deltas, void* s
     s.neg = near == LFT_VIEW_NEAR_SMALLER; s.reach = reach;
     s.H = H; s.W = W; s.T = T; s.tiles_x = (int)tiles_x; s.tiles = (int)tiles;
     return s;
+}
+// step 1 of the three entry points: k_view_splat over (batch element, kRfTile tile, target)
+static int enqueue_splat(const SplatArgs& s, int B, hipStream_t st) {
+    k_view_splat<<<dim3((unsigned)((long long)s.tiles * s.T * B)), 256, 0, st>>>(s);
+    LFT_LAUNCH_OK("k_view_splat");
+    return 0;
 }
 static RenderArgs render_args(const WindowedLf& l, const SplatArgs& s, const ViewLaunch& v, int fill, void* views, int views_class, float* target_disparity,
                               unsigned char* holes) {
@@ -412,8 +426,7 @@ int lft_view_render(const void* lf, int lf_class, int B, int A, int H, int W, in
     if (!v.rtiles) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SplatArgs s = splat_args(disparity, deltas, scratch, lo, hi, near, v.reach, H, W, T, l.tiles_x, l.tiles);
-    k_view_splat<<<dim3((unsigned)(l.tiles * T * B)), 256, 0, st>>>(s);
-    LFT_LAUNCH_OK("k_view_splat");
+    if (int rc = enqueue_splat(s, B, st)) return rc;
     const RenderArgs r = render_args(l, s, v, fill, views, views_class, target_disparity, holes);
     const dim3 grid((unsigned)(v.rtiles * T * B));
     by_lf_class<false>(lf_class, [&](auto t) { render_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(r); return 0; });
@@ -424,13 +437,7 @@ int lft_view_render(const void* lf, int lf_class, int B, int A, int H, int W, in
 // ---- view synthesis with the per-view visibility test (lft_visibility.cuh; declared in include/lft_hip_visibility.h) ----
 static_assert(kVsMask == LFT_VIS_MASK_VIEWS, "the header states the views whose visible bit stays in registers");
 int lft_view_visible_scratch_bytes(int B, int N, int H, int W, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_view_visible_scratch_bytes: out_bytes is null");
-    if (N < 1) return fail(LFT_ERR_ARG, "lft_view_visible_scratch_bytes: %d positions", N);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_view_visible_scratch_bytes: negative size in B = %d, maps of %d x %d", B, H, W);
-    if ((double)B * N * H * W * 4.0 > 1099511627776.0)
-        return fail(LFT_ERR_SHAPE, "lft_view_visible_scratch_bytes: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", B, N, H, W);
-    *out_bytes = (size_t)B * N * H * W * sizeof(uint32_t);
-    return 0;
+    return prefill_map_bytes("lft_view_visible_scratch_bytes", "positions", "maps", B, N, H, W, out_bytes);
 }
 int lft_view_warp_disparity(const float* disparity, int B, int H, int W, const float* deltas, float max_delta, int N, float lo, float hi,
                             int near, int fill, void* scratch, float* maps, unsigned char* holes, void* stream) {
@@ -444,13 +451,11 @@ int lft_view_warp_disparity(const float* disparity, int B, int H, int W, const f
     const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, tiles = tiles_x * (((long long)H + kRfTile - 1) / kRfTile);
     const long long rtiles = tiles_x * (((long long)H + kVwRows - 1) / kVwRows);
     if (rtiles * N * B > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: %d warps to %d positions over maps of %d x %d need more than 2^31 blocks", who, B, N, H, W);
-    if ((double)B * N * H * W * 4.0 > 1099511627776.0)
-        return fail(LFT_ERR_SHAPE, "%s: the pre-fill map of %d x %d x %d x %d needs more than 2^40 bytes", who, B, N, H, W);
+    if (int rc = prefill_map_ok(who, B, N, H, W)) return rc;
     if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SplatArgs s = splat_args(disparity, deltas, scratch, lo, hi, near, v.reach, H, W, N, tiles_x, tiles);
-    k_view_splat<<<dim3((unsigned)(tiles * N * B)), 256, 0, st>>>(s);
-    LFT_LAUNCH_OK("k_view_splat");
+    if (int rc = enqueue_splat(s, B, st)) return rc;
     FillArgs f{};
     f.keys = s.keys; f.dr = disparity; f.lo = lo; f.hi = hi; f.neg = s.neg; f.fill = fill;
     f.H = H; f.W = W; f.N = N; f.rtiles_x = (int)tiles_x; f.rtiles = (int)rtiles;
@@ -472,8 +477,7 @@ int lft_view_render_visible(const void* lf, int lf_class, int B, int A, int H, i
     if (!v.rtiles) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SplatArgs s = splat_args(disparity, deltas, scratch, lo, hi, near, v.reach, H, W, T, l.tiles_x, l.tiles);
-    k_view_splat<<<dim3((unsigned)(l.tiles * T * B)), 256, 0, st>>>(s);
-    LFT_LAUNCH_OK("k_view_splat");
+    if (int rc = enqueue_splat(s, B, st)) return rc;
     VisArgs r{};
     r.r = render_args(l, s, v, fill, views, views_class, target_disparity, holes);
     r.dv = view_disparity; r.tau = tau; r.visible = visible;

@@ -22,6 +22,9 @@
 // Sums run over the views in (u, v) order and over the taps in table order, every step after a sum's first product one explicit
 // fused multiply-add (the compiler's own contraction is off): a pixel's bits do not depend on the tile, the image size around it
 // or the launch shape.
+// Shared with the other light-field kernels from here: rf_x (an input element as fp32) and rf_byte (the uint8 output rule), each
+// written once.  The window pipeline of k_refocus is not shared: k_sweep_cost (lft_disparity.cuh) holds a copy, on a measurement
+// (DESIGN.md section 10).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,6 +54,9 @@ template <> __device__ __forceinline__ float rf_x<uint8_t>(uint8_t v) {
     const float b = (float)v, r = 1.0f / 255.0f, q = b * r;
     return __fmaf_rn(__fmaf_rn(-q, 255.0f, b), r, q);
 }
+// the byte of a value: convertDouble2Byte's rule in fp32 -- clip to [0, 1], * 255, round half to even.  The one place it is written:
+// refocus, the all-in-focus gather of both picks and both renders store their uint8 output through it
+__device__ __forceinline__ uint8_t rf_byte(float v) { return (uint8_t)(int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f)); }
 
 template <typename T, int C, int TAPS>
 __global__ __launch_bounds__(256) void k_refocus(RefocusArgs a) {
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(256) void k_refocus(RefocusArgs a) {
 #pragma unroll
     for (int r = 0; r < NACC; ++r) {
         const int i = tid + 256 * r, y = i / OW, e = i % OW;
-        if (y < ny && e < nb) ob8[y * nb + e] = (uint8_t)(int)rintf(255.0f * fminf(fmaxf(acc[r], 0.0f), 1.0f));
+        if (y < ny && e < nb) ob8[y * nb + e] = rf_byte(acc[r]);
     }
     __syncthreads();
     // the 4-byte-aligned middle of every row goes out as whole dwords, the up to 3 bytes before and after it one by one

@@ -51,12 +51,14 @@
 //                  (odd pitch: no bank conflict), overwritten in place with L_r and leave with lanes along x again.  k-1 and k+1
 //                  come from the neighbouring lanes by shuffles, M from a cross-lane minimum (DPP within rows of 16 lanes, then
 //                  the four rows).
-//   k_sgm_pick   one pixel per lane: per slope the R volumes added in direction order and scaled, then the selection of
-//                k_disparity_pick statement for statement (best, before, after, running sum), no box sum and no LDS.  S goes out
+//   k_sgm_pick   one pixel per lane: per slope the R volumes added in direction order and scaled and fed to the selection that
+//                k_disparity_pick uses (DpSelect and dp_gather_aif of lft_disparity.cuh), no box sum and no LDS.  S goes out
 //                per slope when the caller asks for it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "lft_disparity.cuh"   // the selection: DpSelect, dp_gather_aif
 
 namespace {
 
@@ -331,45 +333,19 @@ __global__ __launch_bounds__(256) void k_sgm_pick(SgmPickArgs a) {
     if (px >= plane) return;
     const float inv = 1.0f / (float)a.R;
 
-    float best = 0.0f, before = 0.0f, after = 0.0f, last = 0.0f, sum = 0.0f;
-    int bk = 0;
-    bool pending = true;
+    DpSelect sel;
     for (int k = 0; k < a.D; ++k) {
         const size_t at = ((size_t)b * a.D + k) * plane + px;
         float s = a.paths[at];
         for (int r = 1; r < a.R; ++r) s = s + a.paths[(size_t)r * a.vol + at];
         const float E = s * inv;
         if (a.aggregated) a.aggregated[at] = E;
-        sum = k ? sum + E : E;
-        if (k == 0 || E < best) {                                    // strict: the lowest k wins an exact tie
-            before = last; best = E; bk = k; pending = true;
-        } else if (pending) {
-            after = E; pending = false;
-        }
-        last = E;
+        sel.step(k, E);
     }
 
-    float delta = 0.0f;
-    if (bk > 0 && !pending) {                                        // pending: no slope after the best one, bk == D - 1
-        const float den = (before - best) + (after - best);
-        if (den > 0.0f) delta = fminf(fmaxf((0.5f * (before - after)) / den, -0.5f), 0.5f);
-    }
-    const float dk = a.slopes[bk];
-    float disp = dk;
-    if (delta > 0.0f) disp = dk + delta * (a.slopes[bk + 1] - dk);
-    else if (delta < 0.0f) disp = dk + delta * (dk - a.slopes[bk - 1]);
-    const float mean = sum / (float)a.D;
     const size_t o = (size_t)b * plane + px;
-    a.disparity[o] = disp;
-    a.confidence[o] = mean > 0.0f ? 1.0f - best / mean : 0.0f;
-    a.index[o] = bk;
-    if (a.aif) {
-        const float* mk = a.stack + (((size_t)b * a.D + bk) * plane + px) * a.C;
-        for (int c = 0; c < a.C; ++c) {
-            if (a.aif_f32) static_cast<float*>(a.aif)[o * a.C + c] = mk[c];
-            else static_cast<uint8_t*>(a.aif)[o * a.C + c] = (uint8_t)(int)rintf(255.0f * fminf(fmaxf(mk[c], 0.0f), 1.0f));
-        }
-    }
+    const int bk = sel.finish(a.slopes, a.D, a.disparity, a.confidence, a.index, o);
+    if (a.aif) dp_gather_aif(a.stack + (((size_t)b * a.D + bk) * plane + px) * a.C, a.C, a.aif, a.aif_f32, o);
 }
 
 }  // namespace

@@ -41,6 +41,11 @@
 //                  walks the records of its target: per view of non-zero weight TAPS^2 * C plain loads at the lane's own offset
 //                  -- neighbouring lanes at neighbouring addresses except across depth edges --, the row pass, the column pass
 //                  and the two pairs of sums in registers.  No LDS, no barrier.
+// The steps shared with k_view_render_vis and k_view_fill (lft_visibility.cuh) are device functions here, each written once:
+// vw_fill (the fill search of step 2) and vw_sample (one view at (sy, sx): vw_axis twice, the view's base, the TAPS^2 * C gather, rows
+// then columns) for all of them; vw_pixel (the workgroup's id and the lane to batch element, target and pixel of a 32 x 8 tile) and
+// vw_fill_store (vw_fill, then Dt and holes written) for those two.  k_view_render keeps its own pixel decode, stores and quotient:
+// through the helpers it measured slower.  The two render algorithms stay two kernels.
 // A pixel's bits do not depend on the tile, on the image beyond its splat sources, fill search and taps, or on the launch shape.
 // They do depend on its coordinates: fl(y + fl(d*du)) rounds by the magnitude of y, so a crop away from the origin agrees with the
 // whole image to a few 1e-6, not to the bit (tests/test_gpu_views.py::test_tile_independence).
@@ -163,7 +168,7 @@ __device__ __forceinline__ void vw_axis(float s, int n, int st, int (&off)[TAPS]
 }
 
 // The fill of one pixel from the pre-fill keys of its target (step 2): Dt[y,x], and whether the pixel was a hole.  The farther of
-// two found values has the smaller key for either `near`.  Shared by k_view_render and k_view_fill (lft_visibility.cuh).
+// two found values has the smaller key for either `near`.  keys points at the target's plane, dr at the batch element's.
 __device__ __forceinline__ float vw_fill(const uint32_t* keys, const float* dr, int y, int x, int H, int W, int fill, int neg, float lo, float hi,
                                          bool& hole) {
     uint32_t key = keys[(size_t)y * W + x];
@@ -190,6 +195,51 @@ __device__ __forceinline__ float vw_fill(const uint32_t* keys, const float* dr, 
         if (neg) d = -d;
     }
     return d == 0.0f ? 0.0f : d;                                     // one zero
+}
+// Step 2 as k_view_fill and k_view_render_vis (lft_visibility.cuh) run it: vw_fill, then the two stores; dt and holes point at
+// the target's plane too.  Returns Dt[y,x].
+__device__ __forceinline__ float vw_fill_store(const uint32_t* keys, const float* dr, int y, int x, int H, int W, int fill, int neg, float lo, float hi,
+                                               float* dt, uint8_t* holes) {
+    bool hole;
+    const float d = vw_fill(keys, dr, y, x, H, W, fill, neg, lo, hi, hole);
+    dt[(size_t)y * W + x] = d;
+    holes[(size_t)y * W + x] = hole ? 1 : 0;
+    return d;
+}
+
+// This lane's pixel of a kRfTile x kVwRows tile: the workgroup's id, dealt XCD-aware, is (batch element b, tile, target t of n), the
+// target fastest.  False for a lane past the image's edge.
+__device__ __forceinline__ bool vw_pixel(int n, int rtiles_x, int rtiles, int H, int W, int& b, int& t, int& y, int& x) {
+    const int tid = threadIdx.x;
+    const int bid = xcd_tile(blockIdx.x, gridDim.x);
+    const int tile = (bid / n) % rtiles;
+    t = bid % n;
+    b = bid / (n * rtiles);
+    y = (tile / rtiles_x) * kVwRows + tid / kRfTile;
+    x = (tile % rtiles_x) * kRfTile + tid % kRfTile;
+    return y < H && x < W;
+}
+
+// The sample of step 3: view n of the batch element at lfb, at the position (sy, sx), into s[c].  TAPS^2 * C plain loads; per
+// column tap its row pass, then its term of the column pass, every step after a sum's first product one explicit FMA.
+template <typename T, int C, int TAPS>
+__device__ __forceinline__ void vw_sample(const RenderArgs& a, const T* lfb, int n, float sy, float sx, float (&s)[C]) {
+#pragma clang fp contract(off)
+    int oy[TAPS], ox[TAPS];
+    float wy[TAPS], wx[TAPS];
+    vw_axis<TAPS>(sy, a.H, a.sy, oy, wy);
+    vw_axis<TAPS>(sx, a.W, a.sx, ox, wx);
+    const T* vb = lfb + (n / a.A) * a.st[1] + (n % a.A) * a.st[2];
+#pragma unroll
+    for (int k = 0; k < TAPS; ++k) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float r = wy[0] * rf_x<T>(vb[oy[0] + ox[k] + c * a.sc]);
+#pragma unroll
+            for (int j = 1; j < TAPS; ++j) r = __fmaf_rn(wy[j], rf_x<T>(vb[oy[j] + ox[k] + c * a.sc]), r);
+            s[c] = k ? __fmaf_rn(wx[k], r, s[c]) : wx[0] * r;
+        }
+    }
 }
 
 template <typename T, int C, int TAPS>
@@ -223,22 +273,8 @@ __global__ __launch_bounds__(256) void k_view_render(RenderArgs a) {
         const float w = rf[2];
         const float sy = fy + d * rf[0], sx = fx + d * rf[1];
         const bool inside = sy >= 0.0f && sy <= ymax && sx >= 0.0f && sx <= xmax;
-        int oy[TAPS], ox[TAPS];
-        float wy[TAPS], wx[TAPS];
-        vw_axis<TAPS>(sy, a.H, a.sy, oy, wy);
-        vw_axis<TAPS>(sx, a.W, a.sx, ox, wx);
-        const T* vb = lfb + (n / a.A) * a.st[1] + (n % a.A) * a.st[2];
         float s[C];
-#pragma unroll
-        for (int k = 0; k < TAPS; ++k) {                             // column tap k: its row pass, then its term of the column pass
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                float r = wy[0] * rf_x<T>(vb[oy[0] + ox[k] + c * a.sc]);
-#pragma unroll
-                for (int j = 1; j < TAPS; ++j) r = __fmaf_rn(wy[j], rf_x<T>(vb[oy[j] + ox[k] + c * a.sc]), r);
-                s[c] = k ? __fmaf_rn(wx[k], r, s[c]) : wx[0] * r;
-            }
-        }
+        vw_sample<T, C, TAPS>(a, lfb, n, sy, sx, s);
         den_all = den_all + w;
 #pragma unroll
         for (int c = 0; c < C; ++c) num_all[c] = __fmaf_rn(w, s[c], num_all[c]);
@@ -253,7 +289,7 @@ __global__ __launch_bounds__(256) void k_view_render(RenderArgs a) {
     for (int c = 0; c < C; ++c) {
         const float v = any ? num_in[c] / den_in : num_all[c] / den_all;
         if (a.out_f32) static_cast<float*>(a.out)[o * C + c] = v;
-        else static_cast<uint8_t*>(a.out)[o * C + c] = (uint8_t)(int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f));
+        else static_cast<uint8_t*>(a.out)[o * C + c] = rf_byte(v);
     }
 }
 

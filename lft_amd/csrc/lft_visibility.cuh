@@ -22,9 +22,10 @@
 // By default Dv is made from Dr itself: splat and fill (steps 1-2) to the A x A integer positions. The hole fill already takes the
 // farther neighbour, which is what a disocclusion needs.
 //
-//   k_view_fill        one pixel per lane over (batch element, 32 x 8 tile, target): the fill search of k_view_render (vw_fill) on the
-//                      keys k_view_splat left, written to the maps and the holes, with no render.
-//   k_view_render_vis  the launch shape, the fill and the sample arithmetic of k_view_render.  Two passes over the records of the
+//   k_view_fill        one pixel per lane over (batch element, 32 x 8 tile, target): vw_pixel and vw_fill_store of lft_views.cuh --
+//                      the fill on the keys k_view_splat left, written to the maps and the holes -- with no render.
+//   k_view_render_vis  k_view_render's launch shape (vw_pixel), its fill (vw_fill_store: k_view_render's vw_fill and stores) and its
+//                      sample (vw_sample, the one k_view_render calls).  Two passes over the records of the
 //                      target.  The first needs only Dt, the record and four dwords of Dv per view -- the footprint's dropped
 //                      members repeat a kept one, so the four loads are unconditional --; it counts the visible and the inside
 //                      views, which fixes the class, and keeps the visible bits of the first 64 views in a register pair.  The
@@ -56,16 +57,10 @@ struct VisArgs {
 };
 
 __global__ __launch_bounds__(256) void k_view_fill(FillArgs a) {
-    const int tid = threadIdx.x;
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);
-    const int t = bid % a.N, tile = (bid / a.N) % a.rtiles, b = bid / (a.N * a.rtiles);
-    const int y = (tile / a.rtiles_x) * kVwRows + tid / kRfTile, x = (tile % a.rtiles_x) * kRfTile + tid % kRfTile;
-    if (y >= a.H || x >= a.W) return;
-    const size_t plane = (size_t)a.H * a.W, o = ((size_t)b * a.N + t) * plane;
-    bool hole;
-    const float d = vw_fill(a.keys + o, a.dr + (size_t)b * plane, y, x, a.H, a.W, a.fill, a.neg, a.lo, a.hi, hole);
-    a.maps[o + (size_t)y * a.W + x] = d;
-    a.holes[o + (size_t)y * a.W + x] = hole ? 1 : 0;
+    int b, t, y, x;
+    if (!vw_pixel(a.N, a.rtiles_x, a.rtiles, a.H, a.W, b, t, y, x)) return;
+    const size_t plane = (size_t)a.H * a.W, tp = ((size_t)b * a.N + t) * plane;
+    vw_fill_store(a.keys + tp, a.dr + (size_t)b * plane, y, x, a.H, a.W, a.fill, a.neg, a.lo, a.hi, a.maps + tp, a.holes + tp);
 }
 
 // the two clamped indices of one axis of the footprint at the sample position s: floor(s), and floor(s) + 1 unless s is integral
@@ -95,19 +90,10 @@ template <typename T, int C, int TAPS>
 __global__ __launch_bounds__(256) void k_view_render_vis(VisArgs va) {
 #pragma clang fp contract(off)
     const RenderArgs& a = va.r;
-    const int tid = threadIdx.x;
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);
-    const int t = bid % a.D, tile = (bid / a.D) % a.rtiles, b = bid / (a.D * a.rtiles);
-    const int y = (tile / a.rtiles_x) * kVwRows + tid / kRfTile, x = (tile % a.rtiles_x) * kRfTile + tid % kRfTile;
-    if (y >= a.H || x >= a.W) return;                                // no barrier below
-    const size_t plane = (size_t)a.H * a.W;
-
-    // ---- fill: as k_view_render
-    bool hole;
-    const float d = vw_fill(a.keys + ((size_t)b * a.D + t) * plane, a.dr + (size_t)b * plane, y, x, a.H, a.W, a.fill, a.neg, a.lo, a.hi, hole);
-    const size_t o = ((size_t)b * a.D + t) * plane + (size_t)y * a.W + x;
-    a.dt[o] = d;
-    a.holes[o] = hole ? 1 : 0;
+    int b, t, y, x;
+    if (!vw_pixel(a.D, a.rtiles_x, a.rtiles, a.H, a.W, b, t, y, x)) return;          // no barrier below
+    const size_t plane = (size_t)a.H * a.W, tp = ((size_t)b * a.D + t) * plane, o = tp + (size_t)y * a.W + x;
+    const float d = vw_fill_store(a.keys + tp, a.dr + (size_t)b * plane, y, x, a.H, a.W, a.fill, a.neg, a.lo, a.hi, a.dt + tp, a.holes + tp);
 
     // ---- first pass: the classes
     const int nv = a.A * a.A;
@@ -148,22 +134,8 @@ __global__ __launch_bounds__(256) void k_view_render_vis(VisArgs va) {
             else member = sy >= 0.0f && sy <= ymax && sx >= 0.0f && sx <= xmax && !vs_occluded(dvb + (size_t)n * plane, sy, sx, a.H, a.W, thr, a.neg);
         }
         if (!member) continue;
-        int oy[TAPS], ox[TAPS];
-        float wy[TAPS], wx[TAPS];
-        vw_axis<TAPS>(sy, a.H, a.sy, oy, wy);
-        vw_axis<TAPS>(sx, a.W, a.sx, ox, wx);
-        const T* vb = lfb + (n / a.A) * a.st[1] + (n % a.A) * a.st[2];
         float s[C];
-#pragma unroll
-        for (int k = 0; k < TAPS; ++k) {                             // column tap k: its row pass, then its term of the column pass
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                float r = wy[0] * rf_x<T>(vb[oy[0] + ox[k] + c * a.sc]);
-#pragma unroll
-                for (int j = 1; j < TAPS; ++j) r = __fmaf_rn(wy[j], rf_x<T>(vb[oy[j] + ox[k] + c * a.sc]), r);
-                s[c] = k ? __fmaf_rn(wx[k], r, s[c]) : wx[0] * r;
-            }
-        }
+        vw_sample<T, C, TAPS>(a, lfb, n, sy, sx, s);
         den = den + w;
 #pragma unroll
         for (int c = 0; c < C; ++c) num[c] = __fmaf_rn(w, s[c], num[c]);
@@ -172,7 +144,7 @@ __global__ __launch_bounds__(256) void k_view_render_vis(VisArgs va) {
     for (int c = 0; c < C; ++c) {
         const float v = num[c] / den;
         if (a.out_f32) static_cast<float*>(a.out)[o * C + c] = v;
-        else static_cast<uint8_t*>(a.out)[o * C + c] = (uint8_t)(int)rintf(255.0f * fminf(fmaxf(v, 0.0f), 1.0f));
+        else static_cast<uint8_t*>(a.out)[o * C + c] = rf_byte(v);
     }
 }
 

@@ -84,7 +84,7 @@ import torch
 
 from . import _lib
 from ._lib import LftError
-from .refocus import TAPS, Aperture, _CLASS, _device_table, _field
+from .refocus import TAPS, Aperture, _CLASS, _as_given, _device_scratch, _device_table, _field
 
 MAX_RADIUS = 8
 
@@ -98,7 +98,7 @@ class DisparityResult(NamedTuple):
 
 
 _slopes: Dict[tuple, torch.Tensor] = {}
-_scratch: Dict[tuple, torch.Tensor] = {}
+_scratch: Dict[tuple, torch.Tensor] = {}      # the sweep's volume (and stack); the path volumes of ``regularize``
 
 
 def _device_slopes(sl: Tuple[float, ...], device) -> torch.Tensor:
@@ -106,24 +106,6 @@ def _device_slopes(sl: Tuple[float, ...], device) -> torch.Tensor:
     if key not in _slopes:
         _slopes[key] = torch.from_numpy(np.array(sl, dtype=np.float64).astype(np.float32)).to(device)     # rounded once, here
     return _slopes[key]
-
-
-def _device_scratch(B: int, D: int, H: int, W: int, C: int, flags: int, device) -> torch.Tensor:
-    """The sweep's volume (and stack), one buffer per shape and device: calls of one shape on different streams must not overlap."""
-    key = (B, D, H, W, C, flags, str(device))
-    if key not in _scratch:
-        n = _lib.query("lft_disparity_scratch_bytes", B, D, H, W, C, flags)
-        _scratch[key] = torch.empty(max(n // 4, 1), dtype=torch.float32, device=device)
-    return _scratch[key]
-
-
-def _device_sgm_scratch(B: int, D: int, H: int, W: int, paths: int, device) -> torch.Tensor:
-    """The path volumes of ``regularize``, one buffer per shape and device, as ``_device_scratch``."""
-    key = ("sgm", B, D, H, W, paths, str(device))
-    if key not in _scratch:
-        n = _lib.query("lft_sgm_scratch_bytes", B, D, H, W, paths)
-        _scratch[key] = torch.empty(max(n // 4, 1), dtype=torch.float32, device=device)
-    return _scratch[key]
 
 
 def clear_cache() -> None:
@@ -182,17 +164,11 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     cost = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if cost_volume else None
     aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if all_in_focus else None
     if B and H and W:
-        scratch = _device_scratch(B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0, dev)
+        scratch = _device_scratch(_scratch, "lft_disparity_scratch_bytes", (B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0), dev)
         _lib.enqueue("lft_disparity", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(),
                      _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius), scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(),
                      index.data_ptr(), cost.data_ptr() if cost_volume else None, aif.data_ptr() if all_in_focus else None, _CLASS[aif_dtype])
-    if kind != "batch":
-        disp, conf, index = disp[0], conf[0], index[0]
-        cost = None if cost is None else cost[0]
-        aif = None if aif is None else (aif[0] if kind == "views5" else aif[0, ..., 0])
-    elif aif is not None:
-        aif = aif[..., 0]
-    return DisparityResult(disp, conf, index, aif, cost)
+    return DisparityResult(*(_as_given(kind, t) for t in (disp, conf, index)), _as_given(kind, aif, image=True), _as_given(kind, cost))
 
 
 def penalties_from_cost(cost: torch.Tensor, p1_rel: float = 0.1, p2_rel: float = 1.0) -> Tuple[float, float]:
@@ -273,18 +249,13 @@ def regularize(cost: torch.Tensor, slopes: Sequence[float], p1: float, p2: float
     aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if stack is not None else None
     if B and H and W:
         cost, guide, stack = (None if t is None else t.contiguous() for t in (cost, guide, stack))
-        scratch = _device_sgm_scratch(B, D, H, W, int(paths), dev)
+        scratch = _device_scratch(_scratch, "lft_sgm_scratch_bytes", (B, D, H, W, int(paths)), dev)
         _lib.enqueue("lft_sgm", dev, cost.data_ptr(), B, D, H, W, C, _device_slopes(sl, dev).data_ptr(), int(paths), float(p1), float(p2),
                      None if guide is None else guide.data_ptr(), float(edge_gain), None if stack is None else stack.data_ptr(),
                      scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(), index.data_ptr(), None if S is None else S.data_ptr(),
                      None if aif is None else aif.data_ptr(), _CLASS[aif_dtype])
-    if aif is not None and not channels:
-        aif = aif[..., 0]
-    if not batch:
-        disp, conf, index = disp[0], conf[0], index[0]
-        S = None if S is None else S[0]
-        aif = None if aif is None else aif[0]
-    return DisparityResult(disp, conf, index, aif, S)
+    kind = ("batch" if batch else "views") + ("5" if channels else "4")
+    return DisparityResult(*(_as_given(kind, t) for t in (disp, conf, index)), _as_given(kind, aif, image=True), _as_given(kind, S))
 
 
 _SGM_KEYS = ("p1", "p2", "paths", "guide", "edge_gain")

@@ -182,6 +182,26 @@ def _field(lf, angRes: Optional[int], out_name: str, out_dtype, before_device=No
     return B, A, H, W, C, _lib.strides_array(strides), kind
 
 
+def _as_given(kind: str, t, image: bool = False):
+    """A result [B, ...] (image: [B, ..., C]) in the layout of the caller's input, by the kind of _layout: the batch axis stays for
+    a kind that starts with "batch", the channel axis for one that ends in "5" (views5; ``disparity.regularize`` also has batch5).
+    None stays None."""
+    if t is None:
+        return None
+    if image and not kind.endswith("5"):
+        t = t[..., 0]
+    return t if kind.startswith("batch") else t[0]
+
+
+def _device_scratch(cache: Dict[tuple, torch.Tensor], query: str, args: tuple, device) -> torch.Tensor:
+    """The scratch of an entry point, as many bytes as its size query `query` answers for `args`: one buffer in `cache` per query,
+    arguments and device, so calls of one shape on different streams must not overlap."""
+    key = (query, *args, str(device))
+    if key not in cache:
+        cache[key] = torch.empty(max(_lib.query(query, *args) // 4, 1), dtype=torch.int32, device=device)
+    return cache[key]
+
+
 def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
             interp: str = "cubic", out_dtype=None, centre=None) -> torch.Tensor:
     """The focal stack of a light field on the GPU, one slice per slope, on lf's device and current stream (enqueue only).
@@ -201,8 +221,7 @@ def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = N
     out = torch.empty(B, D, H, W, C, dtype=out_dtype, device=lf.device)
     _lib.enqueue("lft_refocus", lf.device, lf.data_ptr() or None, _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), D, TAPS[interp],
                  out.data_ptr() or None, _CLASS[out_dtype])
-    return {"views5": lambda: out[0], "views4": lambda: out[0, ..., 0], "mosaic": lambda: out[0, ..., 0],
-            "batch": lambda: out[..., 0]}[kind]()
+    return _as_given(kind, out, image=True)
 
 
 def _views(lf, angRes: Optional[int]):

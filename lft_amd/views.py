@@ -85,7 +85,7 @@ import torch
 
 from . import _lib
 from ._lib import LftError
-from .refocus import _CLASS, _field, _layout
+from .refocus import _CLASS, _as_given, _device_scratch, _field, _layout
 
 TAPS = {"linear": 2, "cubic": 4}
 NEAR = {"larger": _lib.VIEW_NEAR_LARGER, "smaller": _lib.VIEW_NEAR_SMALLER}
@@ -209,7 +209,7 @@ def record_table(A: int, targets, weights: np.ndarray) -> np.ndarray:
 
 
 _tables: Dict[tuple, Tuple[torch.Tensor, ...]] = {}
-_scratch: Dict[tuple, torch.Tensor] = {}
+_scratch: Dict[tuple, torch.Tensor] = {}      # the pre-fill maps
 
 
 def _device_tables(A: int, t: np.ndarray, deltas: np.ndarray, weights: np.ndarray, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -220,15 +220,6 @@ def _device_tables(A: int, t: np.ndarray, deltas: np.ndarray, weights: np.ndarra
         _tables[key] = (torch.from_numpy(tab.view(np.int32).reshape(len(t), A * A, RECORD.itemsize // 4).copy()).to(device),
                         torch.from_numpy(deltas.copy()).to(device))
     return _tables[key]
-
-
-def _device_scratch(B: int, T: int, H: int, W: int, device, query: str = "lft_view_render_scratch_bytes") -> torch.Tensor:
-    """The pre-fill map, one buffer per size query, shape and device: calls of one shape on different streams must not overlap."""
-    key = (query, B, T, H, W, str(device))
-    if key not in _scratch:
-        n = _lib.query(query, B, T, H, W)
-        _scratch[key] = torch.empty(max(n // 4, 1), dtype=torch.int32, device=device)
-    return _scratch[key]
 
 
 def clear_cache() -> None:
@@ -260,7 +251,7 @@ def _warp(dr: torch.Tensor, B: int, H: int, W: int, deltas_h: np.ndarray, lo: fl
     maps = torch.empty(B, N, H, W, dtype=torch.float32, device=dev)
     holes = torch.empty(B, N, H, W, dtype=torch.uint8, device=dev)
     if B and H and W:
-        scratch = _device_scratch(B, N, H, W, dev, "lft_view_visible_scratch_bytes")
+        scratch = _device_scratch(_scratch, "lft_view_visible_scratch_bytes", (B, N, H, W), dev)
         _lib.enqueue("lft_view_warp_disparity", dev, dr.data_ptr(), B, H, W, _tables[key][0].data_ptr(), float(np.abs(deltas_h).max()), N, lo, hi,
                      NEAR[near], int(fill), scratch.data_ptr(), maps.data_ptr(), holes.data_ptr())
     return maps, holes
@@ -355,6 +346,7 @@ def render(lf: torch.Tensor, disparity: torch.Tensor, targets, d_range, angRes: 
     out = torch.empty(B, T, H, W, C, dtype=out_dtype, device=dev)
     dt = torch.empty(B, T, H, W, dtype=torch.float32, device=dev)
     holes = torch.empty(B, T, H, W, dtype=torch.uint8, device=dev)
+    seen = None
     if visibility is not None:
         if dv is None:
             views_at = target_deltas(A, [(u, v) for u in range(A) for v in range(A)], reference)
@@ -368,22 +360,15 @@ def render(lf: torch.Tensor, disparity: torch.Tensor, targets, d_range, angRes: 
                                f"got shape {tuple(dv.shape)}")
             dv = dv.contiguous()
         seen = torch.empty(B, T, H, W, dtype=torch.uint8, device=dev)
-        if B and H and W:
-            scratch = _device_scratch(B, T, H, W, dev, "lft_view_visible_scratch_bytes")
-            _lib.enqueue("lft_view_render_visible", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, dr.data_ptr(), dv.data_ptr(), tau,
-                         deltas.data_ptr(), float(np.abs(deltas_h).max()), records.data_ptr(), T, TAPS[interp], lo, hi, NEAR[near], int(fill),
-                         scratch.data_ptr(), out.data_ptr(), _CLASS[out_dtype], dt.data_ptr(), holes.data_ptr(), seen.data_ptr())
-        if kind == "batch":
-            return VisibleRenderResult(out[..., 0], dt, holes, seen)
-        return VisibleRenderResult(out[0] if kind == "views5" else out[0, ..., 0], dt[0], holes[0], seen[0])
+    # lft_view_render_visible takes lft_view_render's arguments with (Dv, tau) after the map and `visible` after the holes
+    name, with_map, with_holes = ("lft_view_render", (), ()) if seen is None else ("lft_view_render_visible", (dv.data_ptr(), tau), (seen.data_ptr(),))
     if B and H and W:
-        scratch = _device_scratch(B, T, H, W, dev)
-        _lib.enqueue("lft_view_render", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, dr.data_ptr(), deltas.data_ptr(),
+        scratch = _device_scratch(_scratch, "lft_view_render_scratch_bytes" if seen is None else "lft_view_visible_scratch_bytes", (B, T, H, W), dev)
+        _lib.enqueue(name, dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, dr.data_ptr(), *with_map, deltas.data_ptr(),
                      float(np.abs(deltas_h).max()), records.data_ptr(), T, TAPS[interp], lo, hi, NEAR[near], int(fill),
-                     scratch.data_ptr(), out.data_ptr(), _CLASS[out_dtype], dt.data_ptr(), holes.data_ptr())
-    if kind == "batch":
-        return RenderResult(out[..., 0], dt, holes)
-    return RenderResult(out[0] if kind == "views5" else out[0, ..., 0], dt[0], holes[0])
+                     scratch.data_ptr(), out.data_ptr(), _CLASS[out_dtype], dt.data_ptr(), holes.data_ptr(), *with_holes)
+    results = [_as_given(kind, out, image=True)] + [_as_given(kind, t) for t in (dt, holes, seen) if t is not None]
+    return RenderResult(*results) if seen is None else VisibleRenderResult(*results)
 
 
 def grid_targets(A: int, factor: int) -> np.ndarray:

@@ -79,28 +79,46 @@ def axis_np(s, n, taps):
     return idx, w
 
 
+def coords_np(Dt, r):
+    """(sy, sx float32 [H, W], inside bool [H, W]) of the view of record r at every pixel of Dt fp32 [H, W], in float32, operation
+    for operation."""
+    H, W = Dt.shape
+    y, x = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
+    sy = (y + (Dt * F(r["du"])).astype(F)).astype(F)
+    sx = (x + (Dt * F(r["dv"])).astype(F)).astype(F)
+    return sy, sx, (sy >= 0) & (sy <= F(H - 1)) & (sx >= 0) & (sx <= F(W - 1))
+
+
+def as_fp64(views):
+    """The views as the sample reads them: uint8 scaled by / 255, in fp64."""
+    return views.astype(np.float64) / 255.0 if views.dtype == np.uint8 else views.astype(np.float64)
+
+
+def sample_np(v, sy, sx, taps):
+    """One view v fp64 [H, W, C] sampled at the float32 positions (sy, sx) -> fp64 [H, W, C]: rows first, then columns."""
+    H, W, C = v.shape
+    iy, wy = axis_np(sy, H, taps)
+    ix, wx = axis_np(sx, W, taps)
+    s = np.zeros(sy.shape + (C,))
+    for k in range(taps):
+        rows = np.zeros(sy.shape + (C,))
+        for j in range(taps):
+            rows += wy[j][..., None] * v[iy[j], ix[k]]
+        s += wx[k][..., None] * rows
+    return s
+
+
 def render_np(views, Dt, records, taps):
     """views [A, A, H, W, C] (uint8: scaled by / 255), Dt fp32 [H, W], records [A*A] of lft_amd.views.RECORD -> fp64 [H, W, C]."""
     A, _, H, W, C = views.shape
-    X = views.astype(np.float64) / 255.0 if views.dtype == np.uint8 else views.astype(np.float64)
-    y, x = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
+    X = as_fp64(views)
     num_in, num_all = np.zeros((H, W, C)), np.zeros((H, W, C))
     den_in, den_all = np.zeros((H, W)), np.zeros((H, W))
     for n, r in enumerate(records):
         if r["skip"]:
             continue
-        sy = (y + (Dt * F(r["du"])).astype(F)).astype(F)
-        sx = (x + (Dt * F(r["dv"])).astype(F)).astype(F)
-        inside = (sy >= 0) & (sy <= F(H - 1)) & (sx >= 0) & (sx <= F(W - 1))
-        iy, wy = axis_np(sy, H, taps)
-        ix, wx = axis_np(sx, W, taps)
-        v = X[n // A, n % A]
-        s = np.zeros((H, W, C))
-        for k in range(taps):
-            rows = np.zeros((H, W, C))
-            for j in range(taps):
-                rows += wy[j][..., None] * v[iy[j], ix[k]]
-            s += wx[k][..., None] * rows
+        sy, sx, inside = coords_np(Dt, r)
+        s = sample_np(X[n // A, n % A], sy, sx, taps)
         w = float(r["w"])
         num_all += w * s
         den_all += w

@@ -28,15 +28,12 @@ def classes_np(Dt, records, Dv, tau, near="larger"):
     """Dt fp32 [H, W], records [A*A], Dv fp32 [A, A, H, W] -> (used [V] view numbers of non-zero weight, inside bool [V, H, W],
     visible bool [V, H, W], count uint8 [H, W])."""
     A, _, H, W = Dv.shape
-    y, x = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
     thr = (Dt + F(tau)).astype(F) if near == "larger" else (Dt - F(tau)).astype(F)
     used, inside, visible = [], [], []
     for n, r in enumerate(records):
         if r["skip"]:
             continue
-        sy = (y + (Dt * F(r["du"])).astype(F)).astype(F)
-        sx = (x + (Dt * F(r["dv"])).astype(F)).astype(F)
-        ins = (sy >= 0) & (sy <= F(H - 1)) & (sx >= 0) & (sx <= F(W - 1))
+        sy, sx, ins = VU.coords_np(Dt, r)
         q = Dv[n // A, n % A]
         occ = np.zeros((H, W), bool)
         for iy in _footprint(sy, H):
@@ -55,24 +52,14 @@ def render_np(views, Dt, records, taps, Dv, tau, near="larger"):
     """(fp64 [H, W, C], count uint8 [H, W], class int [H, W]: 0 visible, 1 inside, 2 all): views_util.render_np over the first
     non-empty class."""
     A, _, H, W, C = views.shape
-    X = views.astype(np.float64) / 255.0 if views.dtype == np.uint8 else views.astype(np.float64)
+    X = VU.as_fp64(views)
     used, inside, visible, count = classes_np(Dt, records, Dv, tau, near)
     cls = np.where(visible.any(0), 0, np.where(inside.any(0), 1, 2))
-    y, x = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
     num, den = np.zeros((H, W, C)), np.zeros((H, W))
     for k, n in enumerate(used):
         r = records[n]
-        sy = (y + (Dt * F(r["du"])).astype(F)).astype(F)
-        sx = (x + (Dt * F(r["dv"])).astype(F)).astype(F)
-        iy, wy = VU.axis_np(sy, H, taps)
-        ix, wx = VU.axis_np(sx, W, taps)
-        v = X[n // A, n % A]
-        s = np.zeros((H, W, C))
-        for b in range(taps):
-            rows = np.zeros((H, W, C))
-            for a in range(taps):
-                rows += wy[a][..., None] * v[iy[a], ix[b]]
-            s += wx[b][..., None] * rows
+        sy, sx, _ = VU.coords_np(Dt, r)
+        s = VU.sample_np(X[n // A, n % A], sy, sx, taps)
         member = np.where(cls == 0, visible[k], np.where(cls == 1, inside[k], True))
         w = float(r["w"])
         num += np.where(member[..., None], w * s, 0.0)
