@@ -1018,4 +1018,28 @@ LFT_DEV void linear_acc(const T* __restrict__ w, int f0, int lane, const Frag<T>
         for (int ks = 0; ks < KS; ++ks) mma(load_wfrag(w, f0 + nt * KS + ks, lane), x[ks], y[nt]);
 }
 
+// The fixed-order sum over a workgroup: a wave64 __shfl_xor butterfly, lane 0 of each wave to LDS, then the waves added in index
+// order; no atomics, the same bits every run.  Written once for k_lf_loss, k_lf_loss_fold, k_ssim_loss, k_ssim_loss_fold,
+// k_grad_stats (its count of non-finite elements too) and, wave_sum alone, k_guard_final.  BlockSum: N sums of a workgroup of
+// WAVES waves, in LDS: every thread put()s its N terms, __syncthreads(), then get(k) is sum k.
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+template <typename T, int N, int WAVES>
+struct BlockSum {
+    T red[WAVES][N];
+    __device__ __forceinline__ void put(T* s, int tid) {            // s[k] becomes its wave's sum
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] = wave_sum(s[k]);
+        if ((tid & 63) == 0)
+            for (int k = 0; k < N; ++k) red[tid >> 6][k] = s[k];
+    }
+    __device__ __forceinline__ T get(int k) const {
+        T t = 0;
+        for (int w = 0; w < WAVES; ++w) t += red[w][k];
+        return t;
+    }
+};
+
 }  // namespace

@@ -46,6 +46,13 @@ int colour_lf_ok(const char* who, const void* lf, int lf_class, int U, int V, in
     if (A > 255) return fail(LFT_ERR_SHAPE, "%s: angRes %d needs more than 65535 blocks in the grid's y", who, A);
     return 0;
 }
+template <typename Args> void fill_centre_views(Args& a, const void* lf, const long long* strides, int U, int V, int A) {   // Prep-, Luma-, ColourArgs
+    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
+    a.lf = lf; a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A;
+}
+int taps_ok(const char* who, int taps_h, int taps_w, int limit) {       // the taps per output of the caller's two tables
+    return taps_h < 1 || taps_w < 1 || taps_h > limit || taps_w > limit ? fail(LFT_ERR_ARG, "%s: %d / %d taps per output (1 .. %d)", who, taps_h, taps_w, limit) : 0;
+}
 // ---- B light fields [B,A,A,H,W,C] read in place through six strides, one 32 x 32 output tile per workgroup (refocus, disparity,
 // view synthesis with its targets in the place of the slopes) ----
 struct WindowedLf {         // the arguments lft_refocus, lft_disparity and lft_view_render share, and what windowed_lf_ok derives from them
@@ -181,18 +188,17 @@ int lft_scene_integrate_ens(const float* sr_variants, float* sr_scene, unsigned 
 // ================================================================================ metrics
 int lft_view_metrics_scratch_bytes(int B, int A, int h, int w, size_t* out_bytes) {
     if (!out_bytes || B < 1 || A < 1 || h < 1 || w < 1) return fail(LFT_ERR_ARG, "bad argument");
-    const size_t ntiles = (size_t)((h + kMetTile - 1) / kMetTile) * ((w + kMetTile - 1) / kMetTile);
-    *out_bytes = (size_t)B * A * A * ntiles * 3 * sizeof(double);
+    *out_bytes = (size_t)B * A * A * (size_t)ssim_window(h, w, kMetTile, 1.0f).ntiles * 3 * sizeof(double);
     return 0;
 }
 int lft_view_metrics(const float* label, const float* out, int B, int A, int h, int w, float ssim_range, float* psnr, float* ssim,
                      void* scratch, void* stream) {
     if (!label || !out || !psnr || !ssim || !scratch || B < 1 || A < 1) return fail(LFT_ERR_ARG, "bad argument");
-    if (h < 11 || w < 11) return fail(LFT_ERR_SHAPE, "views of %dx%d are smaller than the 11x11 SSIM window", h, w);
+    if (int rc = ssim_views_ok(h, w)) return rc;
+    const SsimWindow win = ssim_window(h, w, kMetTile, ssim_range);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int ntiles = ((h + kMetTile - 1) / kMetTile) * ((w + kMetTile - 1) / kMetTile), nviews = B * A * A;
-    const double C1 = (0.01 * ssim_range) * (0.01 * ssim_range), C2 = (0.03 * ssim_range) * (0.03 * ssim_range);
-    k_view_metrics<<<dim3((unsigned)ntiles, (unsigned)nviews), 256, 0, st>>>(label, out, static_cast<double*>(scratch), A, h, w, C1, C2);
+    const int ntiles = (int)win.ntiles, nviews = B * A * A;
+    k_view_metrics<<<dim3((unsigned)ntiles, (unsigned)nviews), 256, 0, st>>>(label, out, static_cast<double*>(scratch), A, h, w, win.C1, win.C2);
     LFT_LAUNCH_OK("k_view_metrics");
     k_view_metrics_final<<<blocks_for(nviews, 64), 64, 0, st>>>(static_cast<const double*>(scratch), nviews, ntiles, h, w, psnr, ssim);
     LFT_LAUNCH_OK("k_view_metrics_final");
@@ -212,14 +218,11 @@ int lft_lf_prepare(const void* lf, int lf_class, int U, int V, int H, int W, int
         if (y0 < 0 || x0 < 0 || y0 > H - crop_h || x0 > W - crop_w)
             return fail(LFT_ERR_ARG, "lft_lf_prepare: crop %d at (%d, %d) of %d x %d is outside the %d x %d view", i, y0, x0, crop_h, crop_w, H, W);
     }
-    if (taps_h < 1 || taps_w < 1 || taps_h > kPrepMaxTaps || taps_w > kPrepMaxTaps)
-        return fail(LFT_ERR_ARG, "lft_lf_prepare: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kPrepMaxTaps);
+    if (int rc = taps_ok("lft_lf_prepare", taps_h, taps_w, kPrepMaxTaps)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     PrepArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
-    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s;
-    a.ch = crop_h; a.cw = crop_w; a.oh = (crop_h + s - 1) / s; a.ow = (crop_w + s - 1) / s; a.ph = taps_h; a.pw = taps_w;
+    fill_centre_views(a, lf, strides, U, V, A);
+    a.s = s; a.ch = crop_h; a.cw = crop_w; a.oh = (crop_h + s - 1) / s; a.ow = (crop_w + s - 1) / s; a.ph = taps_h; a.pw = taps_w;
     a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w; a.hr = hr; a.lr = lr;
     const int TO = kPrepTileHr / s;
     const unsigned tiles = (unsigned)(((a.oh + TO - 1) / TO) * ((a.ow + TO - 1) / TO));
@@ -243,9 +246,8 @@ int lft_lf_luma(const void* lf, int lf_class, int U, int V, int H, int W, int C,
     const long long blocks = ((long long)H * W + 255) / 256;
     if (blocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "lft_lf_luma: views of %d x %d need more than 2^31 blocks", H, W);
     LumaArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
-    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.H = H; a.W = W; a.y = y_out;
+    fill_centre_views(a, lf, strides, U, V, A);
+    a.H = H; a.W = W; a.y = y_out;
     const dim3 grid((unsigned)blocks, (unsigned)(A * A));
     by_lf_class(lf_class, [&](auto t) { k_lf_luma<decltype(t)><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
     LFT_LAUNCH_OK("k_lf_luma");
@@ -258,17 +260,15 @@ int lft_colour_merge(const void* lf, int lf_class, int U, int V, int H, int W, i
     if (!weights_h || !indices_h || !weights_w || !indices_w || !minv || !out) return fail(LFT_ERR_ARG, "lft_colour_merge: null pointer");
     if (int rc = colour_lf_ok("lft_colour_merge", lf, lf_class, U, V, H, W, C, strides, A)) return rc;
     if (s != 2 && s != 4) return fail(LFT_ERR_SHAPE, "lft_colour_merge: scale factor must be 2 or 4, got %d", s);
-    if (taps_h < 1 || taps_w < 1 || taps_h > kColMaxTaps || taps_w > kColMaxTaps)
-        return fail(LFT_ERR_ARG, "lft_colour_merge: %d / %d taps per output (1 .. %d)", taps_h, taps_w, kColMaxTaps);
+    if (int rc = taps_ok("lft_colour_merge", taps_h, taps_w, kColMaxTaps)) return rc;
     if (out_class != LFT_LF_UINT8 && out_class != LFT_LF_FLOAT32)
         return fail(LFT_ERR_ARG, "lft_colour_merge: output class must be LFT_LF_UINT8 or LFT_LF_FLOAT32, got %d", out_class);
     const long long tiles = (((long long)s * H + kColTile - 1) / kColTile) * (((long long)s * W + kColTile - 1) / kColTile);
     if ((long long)s * H > 0x7fffffffLL || (long long)s * W > 0x7fffffffLL || tiles > 0x7fffffffLL)
         return fail(LFT_ERR_SHAPE, "lft_colour_merge: views of %d x %d at %dx need more than 2^31 blocks", H, W, s);
     ColourArgs a{};
-    a.lf = lf;
-    for (int i = 0; i < 5; ++i) a.st[i] = strides[i];
-    a.u0 = (U - A) / 2; a.v0 = (V - A) / 2; a.A = A; a.s = s; a.H = H; a.W = W; a.ph = taps_h; a.pw = taps_w;
+    fill_centre_views(a, lf, strides, U, V, A);
+    a.s = s; a.H = H; a.W = W; a.ph = taps_h; a.pw = taps_w;
     a.sr_y = sr_y; a.wh = weights_h; a.ih = indices_h; a.ww = weights_w; a.iw = indices_w;
     for (int i = 0; i < 9; ++i) a.minv[i] = minv[i];
     a.out = out; a.out_f32 = out_class == LFT_LF_FLOAT32;

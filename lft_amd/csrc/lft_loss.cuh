@@ -6,7 +6,7 @@
 //                               x +- 1 and y +- 1 inside the view, the same pixel of views a2 +- 1 (W columns away) and a1 +- 1 (H rows
 //                               away) --, writes dsr and adds rho(d) and rho of the four forward differences that START at its pixels
 //                               to five double sums.  GRAD = false (dsr == NULL): only the forward neighbours are read.  The sums are
-//                               folded by wave butterfly, then through LDS, into five doubles per block.
+//                               folded into five doubles per block by BlockSum (lft_common.cuh).
 //   k_lf_loss_fold            : one workgroup adds the per-block partials in a fixed order and writes {total, P, E}.
 // No atomics: the same bits every run.  Every element offset is formed in 64 bits.
 #pragma once
@@ -52,7 +52,7 @@ template <int VEC> __device__ inline void loss_load(const float* __restrict__ sr
 template <int PEN, int VEC, bool GRAD>
 __global__ __launch_bounds__(kLossThreads) void k_lf_loss(const float* __restrict__ sr, const float* __restrict__ hr, float* __restrict__ dsr,
                                                           LossArgs p, double* __restrict__ part) {
-    __shared__ double red[kLossThreads / 64][kLossSums];
+    __shared__ BlockSum<double, kLossSums, kLossThreads / 64> red;
     const int H = p.H, W = p.W, A = p.A;
     const long long R = (long long)A * H, C = (long long)A * W;           // rows and columns of one mosaic
     const long long cpr = C / VEC, nchunk = (long long)p.B * R * cpr;     // VEC = 4 only when C is a multiple of 4
@@ -152,39 +152,24 @@ __global__ __launch_bounds__(kLossThreads) void k_lf_loss(const float* __restric
             else dsr[i0] = g[0] * p.gscale;
         }
     }
-#pragma unroll
-    for (int k = 0; k < kLossSums; ++k)
-        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);            // wave64 butterfly: the same order every run
     const int tid = threadIdx.x;
-    if ((tid & 63) == 0)
-        for (int k = 0; k < kLossSums; ++k) red[tid >> 6][k] = s[k];
+    red.put(s, tid);
     __syncthreads();
-    if (tid < kLossSums) {
-        double t = 0.0;
-        for (int w = 0; w < kLossThreads / 64; ++w) t += red[w][tid];
-        part[(long long)blockIdx.x * kLossSums + tid] = t;
-    }
+    if (tid < kLossSums) part[(long long)blockIdx.x * kLossSums + tid] = red.get(tid);
 }
 
 __global__ __launch_bounds__(kLossThreads) void k_lf_loss_fold(const double* __restrict__ part, int nb, LossFoldArgs f, float* __restrict__ loss3) {
-    __shared__ double red[kLossThreads / 64][kLossSums];
+    __shared__ BlockSum<double, kLossSums, kLossThreads / 64> red;
     if (blockIdx.x != 0) return;
     const int tid = threadIdx.x;
     double s[kLossSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int b = tid; b < nb; b += kLossThreads)
         for (int k = 0; k < kLossSums; ++k) s[k] += part[(long long)b * kLossSums + k];
-#pragma unroll
-    for (int k = 0; k < kLossSums; ++k)
-        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);
-    if ((tid & 63) == 0)
-        for (int k = 0; k < kLossSums; ++k) red[tid >> 6][k] = s[k];
+    red.put(s, tid);
     __syncthreads();
     if (tid == 0) {
         double t[kLossSums];
-        for (int k = 0; k < kLossSums; ++k) {
-            t[k] = 0.0;
-            for (int w = 0; w < kLossThreads / 64; ++w) t[k] += red[w][k];
-        }
+        for (int k = 0; k < kLossSums; ++k) t[k] = red.get(k);
         const double P = t[0] * f.inv_n;
         const double E = (t[1] * f.inv_nt[0] + t[2] * f.inv_nt[1] + t[3] * f.inv_nt[2] + t[4] * f.inv_nt[3]) * f.inv_T;
         loss3[0] = (float)(f.w_pix * P + f.w_epi * E);

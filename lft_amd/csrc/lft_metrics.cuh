@@ -1,12 +1,14 @@
 // lft_metrics.cuh -- per-view PSNR and Gaussian-window SSIM of SR mosaics on the GPU: the numbers the reference logs
 // through scikit-image (utils/utils.py:56-88 cal_metrics; oracle/metrics_oracle.py restates the algorithm).
-// Mosaics are [B,1,A*h,A*w] fp32, view (u,v) = rows u*h.., cols v*w.. .  All sums in fp64 as scikit-image does.
+// Mosaics are [B,1,A*h,A*w] fp32, view (u,v) = rows u*h.., cols v*w.. .  All sums in fp64 as scikit-image does.  The window (weights,
+// moments, quotient) is lft_ssim_window.cuh's, shared with k_ssim_loss.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "lft_ssim_window.cuh"
 
 namespace {
 
-constexpr int kMetTile = 16, kMetR = 5, kMetIn = kMetTile + 2 * kMetR;       // 16x16 outputs need a 26x26 input tile
+constexpr int kMetTile = 16, kMetR = kSsimR, kMetIn = kMetTile + 2 * kMetR;  // 16x16 outputs need a 26x26 input tile
 
 // part[(view*ntiles + tile)*3 + {0,1,2}] = sum of the SSIM map over the tile's interior pixels, sum of squared error
 // over the tile's pixels, min of the label over the tile's pixels.
@@ -20,12 +22,8 @@ __global__ __launch_bounds__(256) void k_view_metrics(const float* __restrict__ 
     const int ty0 = (tile / tiles_x) * kMetTile, tx0 = (tile % tiles_x) * kMetTile;
     const int v = view % A, u = (view / A) % A, b = view / (A * A);
     const size_t base = ((size_t)b * A * h + (size_t)u * h) * (A * w) + (size_t)v * w;
-    double g[11];
-    {
-        double s = 0.0;
-        for (int k = -kMetR; k <= kMetR; ++k) { g[k + kMetR] = exp(-0.5 * k * k / (1.5 * 1.5)); s += g[k + kMetR]; }
-        for (int k = 0; k < 11; ++k) g[k] /= s;
-    }
+    double g[kSsimTaps];
+    ssim_gauss(g, [](int i) { return ssim_gauss_raw(i - kSsimR); });
     for (int i = threadIdx.x; i < kMetIn * kMetIn; i += 256) {
         const int yy = ty0 - kMetR + i / kMetIn, xx = tx0 - kMetR + i % kMetIn;
         const bool in = yy >= 0 && yy < h && xx >= 0 && xx < w;                      // outside values are never used by an interior pixel
@@ -33,15 +31,7 @@ __global__ __launch_bounds__(256) void k_view_metrics(const float* __restrict__ 
         ty[i / kMetIn][i % kMetIn] = in ? out[base + (size_t)yy * (A * w) + xx] : 0.0f;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < kMetIn * kMetTile; i += 256) {                    // horizontal pass of the 5 maps
-        const int rr = i / kMetTile, cc = i % kMetTile;
-        double sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
-        for (int k = 0; k < 11; ++k) {
-            const double a = tx[rr][cc + k], c = ty[rr][cc + k];
-            sx += g[k] * a; sy += g[k] * c; sxx += g[k] * a * a; syy += g[k] * c * c; sxy += g[k] * a * c;
-        }
-        hz[0][rr][cc] = sx; hz[1][rr][cc] = sy; hz[2][rr][cc] = sxx; hz[3][rr][cc] = syy; hz[4][rr][cc] = sxy;
-    }
+    ssim_moment_rows<kMetIn, kMetTile, kMetIn + 1, 256>(tx, ty, hz, g, threadIdx.x);
     __syncthreads();
     const int ly = threadIdx.x / kMetTile, lx = threadIdx.x % kMetTile, y = ty0 + ly, x = tx0 + lx;
     double ssim = 0.0, se = 0.0, tmin = 1e300;
@@ -49,14 +39,7 @@ __global__ __launch_bounds__(256) void k_view_metrics(const float* __restrict__ 
         const double a = tx[ly + kMetR][lx + kMetR], c = ty[ly + kMetR][lx + kMetR];
         se = (a - c) * (a - c);
         tmin = a;
-        if (y >= kMetR && y < h - kMetR && x >= kMetR && x < w - kMetR) {
-            double m[5] = {0, 0, 0, 0, 0};
-            for (int k = 0; k < 11; ++k)
-                for (int q = 0; q < 5; ++q) m[q] += g[k] * hz[q][ly + k][lx];
-            const double cov = 121.0 / 120.0;
-            const double vx = cov * (m[2] - m[0] * m[0]), vy = cov * (m[3] - m[1] * m[1]), vxy = cov * (m[4] - m[0] * m[1]);
-            ssim = ((2 * m[0] * m[1] + C1) * (2 * vxy + C2)) / ((m[0] * m[0] + m[1] * m[1] + C1) * (vx + vy + C2));
-        }
+        if (y >= kMetR && y < h - kMetR && x >= kMetR && x < w - kMetR) ssim = ssim_at(hz, ly, lx, g, C1, C2).S;
     }
     red[0][threadIdx.x] = ssim; red[1][threadIdx.x] = se; red[2][threadIdx.x] = tmin;
     __syncthreads();

@@ -85,24 +85,22 @@ int lft_lf_loss(const float* sr, const float* hr, int B, int A, int H, int W, in
 }
 // ---- structural loss term (lft_ssim_loss.cuh) ----
 namespace {
-struct SsimShape { long long n, nblocks, views; int tiles_x, ntiles; };
-int ssim_shape(int B, int A, int H, int W, SsimShape* s) {
+struct SsimShape { long long n, nblocks, views; SsimWindow win; };
+int ssim_shape(int B, int A, int H, int W, float ssim_range, SsimShape* s) {
     if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "sizes must be positive, got B %d A %d H %d W %d", B, A, H, W);
-    if (H < 11 || W < 11) return fail(LFT_ERR_SHAPE, "views of %dx%d are smaller than the 11x11 SSIM window", H, W);
-    s->tiles_x = (W + kSsimTile - 1) / kSsimTile;
-    const long long ntiles = (long long)s->tiles_x * ((H + kSsimTile - 1) / kSsimTile);
+    if (int rc = ssim_views_ok(H, W)) return rc;
+    s->win = ssim_window(H, W, kSsimTile, ssim_range);
     s->views = (long long)B * A * A;
     s->n = s->views * H * W;
-    s->nblocks = s->views * ntiles;
+    s->nblocks = s->views * s->win.ntiles;
     if (s->nblocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%lld tiles, more than one launch holds", s->nblocks);
-    s->ntiles = (int)ntiles;
     return 0;
 }
 }  // namespace
 int lft_ssim_loss_scratch_bytes(int B, int A, int H, int W, size_t* out_bytes) {
     if (!out_bytes) return fail(LFT_ERR_ARG, "null pointer");
     SsimShape s;
-    if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
+    if (int rc = ssim_shape(B, A, H, W, 1.0f, &s)) return rc;
     *out_bytes = (size_t)s.nblocks * sizeof(double);
     return 0;
 }
@@ -116,12 +114,12 @@ int lft_ssim_loss(const float* sr, const float* hr, int B, int A, int H, int W, 
     if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "gscale is NaN");
     if (accumulate != 0 && accumulate != 1) return fail(LFT_ERR_ARG, "accumulate must be 0 or 1, got %d", accumulate);
     SsimShape s;
-    if (int rc = ssim_shape(B, A, H, W, &s)) return rc;
+    if (int rc = ssim_shape(B, A, H, W, ssim_range, &s)) return rc;
     if (overlaps(dsr, sr, hr, s.n)) return fail(LFT_ERR_ARG, "dsr overlaps sr or hr: the windows read neighbours, in place would race");
-    const double R = (double)ssim_range, count = (double)s.views * (H - 2 * kSsimR) * (W - 2 * kSsimR);
+    const double count = (double)s.views * (H - 2 * kSsimR) * (W - 2 * kSsimR);
     SsimArgs a = {};
-    a.A = A; a.H = H; a.W = W; a.tiles_x = s.tiles_x; a.ntiles = s.ntiles; a.accumulate = accumulate;
-    a.C1 = (0.01 * R) * (0.01 * R); a.C2 = (0.03 * R) * (0.03 * R);                  // as lft_view_metrics forms them
+    a.A = A; a.H = H; a.W = W; a.tiles_x = s.win.tiles_x; a.ntiles = (int)s.win.ntiles; a.accumulate = accumulate;
+    a.C1 = s.win.C1; a.C2 = s.win.C2;                                                 // ssim_window's, as lft_view_metrics takes them
     a.k = -(double)gscale * (double)w_ssim / count;                                   // Q = 1 - S
     const SsimFoldArgs f = {1.0 / count, (double)w_ssim, accumulate};
     hipStream_t st = static_cast<hipStream_t>(stream);

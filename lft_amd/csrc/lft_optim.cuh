@@ -30,7 +30,7 @@ namespace {
 // Block map: a block works on at most `per` consecutive floats of ONE segment (per = kGuardChunk, larger only for buffers beyond
 // kGuardChunk * kGuardMaxChunks floats, so that the number of partials is bounded by the segment count alone); segment i owns
 // blocks bstart[i] .. bstart[i + 1] - 1.  Segments begin at arbitrary float offsets: a block's range is split into a scalar head
-// up to the first 16-byte boundary, 16-byte loads / stores, and a scalar tail.
+// up to the first 16-byte boundary, 16-byte loads / stores, and a scalar tail (guard_walk); sums fold through BlockSum (lft_common.cuh).
 
 constexpr int kGuardMaxSeg = 128;          // seg_norm[128] of lft_guard_report
 constexpr int kGuardChunk = 2048;          // floats per block: 256 threads x two 16-byte accesses per array
@@ -109,40 +109,55 @@ __device__ inline long long guard_head(uintptr_t base, long long lo, long long h
     return head < hi - lo ? head : hi - lo;
 }
 
-__device__ inline void stats_add(float x, double& sum, unsigned long long& bad) {
-    if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) { ++bad; return; }      // inf or NaN: counted, not summed
-    const double d = (double)x;
-    sum += d * d;
+// One block's walk over [lo, hi) of NRW arrays it updates and one it reads: f(x, r) at every element, x the NRW values there, r the
+// value read.  Scalar head to the first 16-byte boundary, 16-byte accesses, scalar tail; all scalar when the alignments differ.
+template <int NRW, typename F>
+__device__ __forceinline__ void guard_walk(float* const* rw, const float* __restrict__ ro, long long lo, long long hi, int tid, F f) {
+    bool same = true;
+    for (int j = 0; j < NRW; ++j) same = same && (((uintptr_t)rw[j] >> 2) & 3) == (((uintptr_t)ro >> 2) & 3);
+    const long long a = same ? lo + guard_head((uintptr_t)ro, lo, hi) : hi;
+    const long long nvec = (hi - a) >> 2, vend = a + 4 * nvec;
+    auto one = [&](long long i) {
+        float x[NRW + 1];
+        for (int j = 0; j < NRW; ++j) x[j] = rw[j][i];
+        f(x, ro[i]);
+        for (int j = 0; j < NRW; ++j) rw[j][i] = x[j];
+    };
+    for (long long i = lo + tid; i < a; i += kGuardThreads) one(i);
+    for (long long q = tid; q < nvec; q += kGuardThreads) {
+        const long long i = a + 4 * q;
+        float4 x4[NRW + 1];
+        for (int j = 0; j < NRW; ++j) x4[j] = *reinterpret_cast<const float4*>(rw[j] + i);
+        const float4 r4 = *reinterpret_cast<const float4*>(ro + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float x[NRW + 1];
+            for (int j = 0; j < NRW; ++j) x[j] = reinterpret_cast<const float*>(&x4[j])[e];
+            f(x, reinterpret_cast<const float*>(&r4)[e]);
+            for (int j = 0; j < NRW; ++j) reinterpret_cast<float*>(&x4[j])[e] = x[j];
+        }
+        for (int j = 0; j < NRW; ++j) *reinterpret_cast<float4*>(rw[j] + i) = x4[j];
+    }
+    if (vend + tid < hi) one(vend + tid);
 }
 
 __global__ __launch_bounds__(kGuardThreads) void k_grad_stats(const float* __restrict__ g, GuardBlock* __restrict__ gb) {
-    __shared__ double s_sum[kGuardThreads / 64];
-    __shared__ unsigned long long s_bad[kGuardThreads / 64];
+    __shared__ BlockSum<double, 1, kGuardThreads / 64> s_sum;
+    __shared__ BlockSum<unsigned long long, 1, kGuardThreads / 64> s_bad;
     const int b = blockIdx.x, tid = threadIdx.x;
     if (b >= gb->nblocks) return;
     long long lo, hi;
     guard_range(gb, b, &lo, &hi);
-    const long long a = lo + guard_head((uintptr_t)g, lo, hi);
-    const long long nvec = (hi - a) >> 2, vend = a + 4 * nvec;
     double sum = 0.0;
     unsigned long long bad = 0;
-    if (lo + tid < a) stats_add(g[lo + tid], sum, bad);                             // head: at most 3 floats
-    for (long long q = tid; q < nvec; q += kGuardThreads) {
-        const float4 x = *reinterpret_cast<const float4*>(g + a + 4 * q);
-        stats_add(x.x, sum, bad); stats_add(x.y, sum, bad); stats_add(x.z, sum, bad); stats_add(x.w, sum, bad);
-    }
-    if (vend + tid < hi) stats_add(g[vend + tid], sum, bad);                        // tail: at most 3 floats
-    for (int off = 32; off > 0; off >>= 1) {                                        // wave64 butterfly: the same order every run
-        sum += __shfl_xor(sum, off);
-        bad += __shfl_xor(bad, off);
-    }
-    if ((tid & 63) == 0) { s_sum[tid >> 6] = sum; s_bad[tid >> 6] = bad; }
+    guard_walk<0>(nullptr, g, lo, hi, tid, [&](float*, float x) {
+        if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) { ++bad; return; }  // inf or NaN: counted, not summed
+        const double d = (double)x;
+        sum += d * d;
+    });
+    s_sum.put(&sum, tid); s_bad.put(&bad, tid);
     __syncthreads();
-    if (tid == 0) {
-        GuardPart r = {0.0, 0};
-        for (int w = 0; w < kGuardThreads / 64; ++w) { r.sumsq += s_sum[w]; r.bad += s_bad[w]; }
-        guard_parts(gb)[b] = r;
-    }
+    if (tid == 0) guard_parts(gb)[b] = GuardPart{s_sum.get(0), s_bad.get(0)};
 }
 
 __global__ __launch_bounds__(kGuardThreads) void k_guard_final(GuardBlock* __restrict__ gb, float gscale, float max_norm, int clip,
@@ -156,10 +171,7 @@ __global__ __launch_bounds__(kGuardThreads) void k_guard_final(GuardBlock* __res
         double sum = 0.0;
         unsigned long long bad = 0;
         for (int j = gb->bstart[s] + lane; j < gb->bstart[s + 1]; j += 64) { sum += part[j].sumsq; bad += part[j].bad; }
-        for (int off = 32; off > 0; off >>= 1) {
-            sum += __shfl_xor(sum, off);
-            bad += __shfl_xor(bad, off);
-        }
+        sum = wave_sum(sum); bad = wave_sum(bad);
         if (lane == 0) {
             s_sum[s] = sum; s_bad[s] = bad;
             gb->rep.seg_norm[s] = (float)((double)gscale * sqrt(sum));
@@ -202,7 +214,8 @@ __global__ __launch_bounds__(kGuardThreads) void k_guard_final(GuardBlock* __res
 }
 
 struct AdamHyper { float lr, b1, b2, eps, bc1, bc2, gscale, coef, wd; };
-__device__ inline void adam_guarded_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
+// Adam at one element (weight_decay: torch.optim.Adam's L2 term), written once: k_adam passes coef = 1, k_adam_guarded the guard's
+__device__ inline void adam_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
     const float gi = g * h.gscale * h.coef + h.wd * p;                              // the clip is folded in here; g is not written
     const float mi = h.b1 * m + (1.0f - h.b1) * gi;
     const float vi = h.b2 * v + (1.0f - h.b2) * gi * gi;
@@ -220,25 +233,8 @@ __global__ __launch_bounds__(kGuardThreads) void k_adam_guarded(float* __restric
     const int s = guard_range(gb, b, &lo, &hi);
     if (!gb->trainable[s]) return;
     const AdamHyper h = {lr, b1, b2, eps, gb->bc1, gb->bc2, gscale, gb->rep.clip_coef, wd};
-    // 16-byte accesses need the four arrays to share their alignment; otherwise the whole range takes the scalar path
-    const unsigned ph = (unsigned)(((uintptr_t)p >> 2) & 3);
-    const bool same = ph == (((uintptr_t)g >> 2) & 3) && ph == (((uintptr_t)m >> 2) & 3) && ph == (((uintptr_t)v >> 2) & 3);
-    const long long a = same ? lo + guard_head((uintptr_t)p, lo, hi) : hi;
-    const long long nvec = (hi - a) >> 2, vend = a + 4 * nvec;
-    for (long long i = lo + tid; i < a; i += kGuardThreads) adam_guarded_one(p[i], g[i], m[i], v[i], h);
-    for (long long q = tid; q < nvec; q += kGuardThreads) {
-        const long long i = a + 4 * q;
-        float4 pp = *reinterpret_cast<float4*>(p + i), mm = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);
-        const float4 gg = *reinterpret_cast<const float4*>(g + i);
-        adam_guarded_one(pp.x, gg.x, mm.x, vv.x, h);
-        adam_guarded_one(pp.y, gg.y, mm.y, vv.y, h);
-        adam_guarded_one(pp.z, gg.z, mm.z, vv.z, h);
-        adam_guarded_one(pp.w, gg.w, mm.w, vv.w, h);
-        *reinterpret_cast<float4*>(p + i) = pp;
-        *reinterpret_cast<float4*>(m + i) = mm;
-        *reinterpret_cast<float4*>(v + i) = vv;
-    }
-    if (vend + tid < hi) adam_guarded_one(p[vend + tid], g[vend + tid], m[vend + tid], v[vend + tid], h);
+    float* const pmv[3] = {p, m, v};
+    guard_walk<3>(pmv, g, lo, hi, tid, [&](float* x, float gi) { adam_one(x[0], gi, x[1], x[2], h); });
 }
 
 // ---- exponential moving average of the weights (lft_ema_update) ----
@@ -253,21 +249,9 @@ __device__ inline float ema_alpha(float decay, int warmup, long long t) {
     return (float)(1.0 - d);
 }
 __device__ inline void ema_one(float& e, float p, float a) { e += a * (p - e); }
-// [lo, hi) of one block: scalar head up to ema's first 16-byte boundary, 16-byte accesses, scalar tail; all scalar when ema and p
-// do not share their alignment.
 __device__ inline void ema_range(float* __restrict__ ema, const float* __restrict__ p, long long lo, long long hi, float a, int tid) {
-    const bool same = (((uintptr_t)ema >> 2) & 3) == (((uintptr_t)p >> 2) & 3);
-    const long long h = same ? lo + guard_head((uintptr_t)ema, lo, hi) : hi;
-    const long long nvec = (hi - h) >> 2, vend = h + 4 * nvec;
-    for (long long i = lo + tid; i < h; i += kGuardThreads) ema_one(ema[i], p[i], a);
-    for (long long q = tid; q < nvec; q += kGuardThreads) {
-        const long long i = h + 4 * q;
-        float4 ee = *reinterpret_cast<float4*>(ema + i);
-        const float4 pp = *reinterpret_cast<const float4*>(p + i);
-        ema_one(ee.x, pp.x, a); ema_one(ee.y, pp.y, a); ema_one(ee.z, pp.z, a); ema_one(ee.w, pp.w, a);
-        *reinterpret_cast<float4*>(ema + i) = ee;
-    }
-    if (vend + tid < hi) ema_one(ema[vend + tid], p[vend + tid], a);
+    float* const e1[1] = {ema};
+    guard_walk<1>(e1, p, lo, hi, tid, [&](float* e, float pi) { ema_one(e[0], pi, a); });
 }
 
 __global__ __launch_bounds__(kGuardThreads) void k_ema_guarded(float* __restrict__ ema, const float* __restrict__ p,
@@ -296,12 +280,7 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
                        long long n, float lr, float b1, float b2, float eps, float bc1, float bc2, float gscale, float wd) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i] * gscale + wd * p[i];                        // torch.optim.Adam weight_decay: L2 term added to the gradient
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
+    adam_one(p[i], g[i], m[i], v[i], AdamHyper{lr, b1, b2, eps, bc1, bc2, gscale, 1.0f, wd});
 }
 
 }  // namespace

@@ -100,6 +100,49 @@ def test_large_cases_match_restatement():
     assert torch.equal(lr4, lr) and torch.equal(hr4, hr)
 
 
+def test_prepare_fallback_path_gives_the_same_bits():
+    """The true tables never span more than the staged region (kPrepSpan = 56 rows / columns per 32 x 32 HR tile), so the
+    fall-back is forced through the C ABI, as test_gpu_colour.py::test_merge_fallback_path_gives_the_same_bits does for the colour
+    path: one more tap of weight 0 that points to the far end of the crop widens every tile's span past the region and adds
+    0 * y = 0 to each sum (Y is at least 16/255, so no partial sum changes).  The far end is the end farther from the output's
+    own taps: with 'the last column for taps that start below 56, else column 0' the middle tile of 80 columns at s = 4 would
+    span 54 and stay staged.  A = 2 needs an even number of spare views, so the centre 2 x 2 of 4 x 4 views are taken."""
+    SPAN, MAX_TAPS, TILE_HR = 56, 18, 32                                    # kPrepSpan, kPrepMaxTaps, kPrepTileHr of lft_prepare.cuh
+    A, H, W = 2, 96, 80
+    lf = torch.from_numpy(np.random.default_rng(12).integers(0, 256, (4, 4, H, W, 3)).astype(np.uint8)).to(DEV)
+    crop = np.zeros((1, 2), dtype=np.int32)
+
+    def tables(L, s, far):
+        w, i = prepare.contributions(L, s)                                  # all-zero columns already dropped
+        if far:
+            end = np.where(L - 1 - i.min(axis=1) >= i.max(axis=1), L - 1, 0).astype(np.int32)
+            w = np.concatenate([w, np.zeros((w.shape[0], 1))], axis=1)
+            i = np.concatenate([i, end[:, None]], axis=1)
+            assert w.shape[1] <= MAX_TAPS
+            TO = TILE_HR // s
+            spans = [int(i[o:o + TO].max() - i[o:o + TO].min() + 1) for o in range(0, i.shape[0], TO)]
+            assert min(spans) > SPAN, (L, s, spans)                         # every tile leaves the staged region
+        return torch.from_numpy(np.ascontiguousarray(w)).to(DEV), torch.from_numpy(np.ascontiguousarray(i)).to(DEV)
+
+    def run(s, far_h, far_w):
+        (wh, ih), (ww, iw) = tables(H, s, far_h), tables(W, s, far_w)
+        hr = torch.zeros(1, A * H, A * W, device=DEV)
+        lr = torch.zeros(1, A * wh.shape[0], A * ww.shape[0], device=DEV)
+        _lib.enqueue("lft_lf_prepare", DEV, *prepare.lf_args(lf), A, s, crop.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 1, H, W,
+                     wh.data_ptr(), ih.data_ptr(), wh.shape[1], ww.data_ptr(), iw.data_ptr(), ww.shape[1], hr.data_ptr(), lr.data_ptr())
+        torch.cuda.synchronize()
+        return hr, lr
+
+    for s in (2, 4):
+        want_hr, want_lr = run(s, False, False)
+        got = prepare.lf_prepare(lf, A, s, [(0, 0)], H, W)
+        assert torch.equal(got[0], want_hr) and torch.equal(got[1], want_lr)
+        assert float(want_hr.min()) >= 0.0627 and float(want_lr.std()) > 0.0    # Y >= 16/255; the call computed something
+        for far_h, far_w in ((True, True), (True, False), (False, True)):      # neither stage fits | rows only | columns only
+            hr, lr = run(s, far_h, far_w)
+            assert torch.equal(hr, want_hr) and torch.equal(lr, want_lr), (s, far_h, far_w)
+
+
 def test_argument_errors_enqueue_nothing():
     lf = torch.zeros(5, 5, 8, 8, 3, dtype=torch.uint8, device=DEV)
     w, i = prepare._device_table(8, 2, DEV)

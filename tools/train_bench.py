@@ -5,8 +5,9 @@
 
 One process per GPU, each with its own --batch patches (weak scaling); a step = forward-with-tape, L1 loss + its
 gradient, backward, ONE all-reduce of the flat gradient buffer (RCCL), fused Adam.  Same timing protocol as bench.py
-(barrier + synchronize on both sides, max over ranks).  Prints one JSON line on rank 0.  --phases adds a per-phase
-breakdown from HIP events on the step's stream (forward / loss / backward / all-reduce / adam).
+(barrier + synchronize on both sides, max over ranks).  Prints one JSON line on rank 0.  --phases adds "adam_ms": the
+event-timed milliseconds of the optimizer launches alone, as step() enqueues them (lft_adam_step or lft_adam_step_guarded, then
+lft_ema_update with --ema_decay), the median over 50 groups of 10 updates.
 --ema_decay D keeps the EMA of the weights (lft_ema_update after the Adam kernel); with --alternate R a second TrainStep WITHOUT the
 EMA is built beside it and R rounds of --steps steps alternate between the two in this one process: "ms_per_step_rounds" then holds
 both series, the only fair way to see a difference of this size.
@@ -60,6 +61,36 @@ def time_loss_launches(ts, hr, calls=50):
             if i >= 5:
                 ms[name].append(e0.elapsed_time(e1))
     return {k: float(np.median(v)) for k, v in ms.items()}
+
+
+def time_optimizer_launches(ts, groups=50, per=10):
+    """Median event-timed milliseconds of one optimizer update of the step, on the step's own buffers (run after the timed steps:
+    it moves the weights)."""
+    from lft_amd import _lib, train as T
+    dev = ts.flat_params.device
+
+    def update():
+        ts.t += 1
+        if ts._guard is None:
+            _lib.enqueue("lft_adam_step", dev, ts.flat_params.data_ptr(), ts.flat_grads.data_ptr(), ts.m.data_ptr(), ts.v.data_ptr(),
+                         ts.flat_params.numel(), ts.lr, ts.betas[0], ts.betas[1], ts.eps, ts.t, 1.0, ts.weight_decay)
+        else:
+            T.adam_step_guarded(ts.flat_params, ts.flat_grads, ts.m, ts.v, ts._guard, ts.lr, ts.betas[0], ts.betas[1], ts.eps, 1.0,
+                                ts.weight_decay, ts.max_grad_norm)
+        if ts.ema is not None:
+            T.ema_update(ts.ema, ts.flat_params, ts.ema_decay, ts.ema_warmup, ts.t, ts._guard)
+
+    ms = []
+    for i in range(groups + 5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(per):
+            update()
+        e1.record()
+        e1.synchronize()
+        if i >= 5:
+            ms.append(e0.elapsed_time(e1) / per)
+    return float(np.median(ms))
 
 
 def main():
@@ -157,6 +188,8 @@ def main():
         if loss_ms:
             out["loss"] = ts.loss.spec()
             out["loss_ms"] = loss_ms
+        if args.phases:
+            out["adam_ms"] = time_optimizer_launches(ts)
         if args.guard:
             rep = ts.guard_report()
             out["guard_report"] = {k: rep[k] for k in ("grad_norm", "steps_applied", "steps_skipped", "steps_clipped")}
