@@ -1,10 +1,12 @@
 // lft_lightfield.hip -- what handles light fields around the network, in the C ABI of liblft_hip.so (include/lft_hip.h): scene
 // tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity, view
-// synthesis (declared in include/lft_hip_views.h) and semi-global aggregation (declared in include/lft_hip_sgm.h).
+// synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h) and the sweep's
+// occlusion-aware cost (declared in include/lft_hip_occlusion.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
 #include "../../include/lft_hip_visibility.h"
+#include "../../include/lft_hip_occlusion.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
@@ -15,6 +17,7 @@
 #include "lft_views.cuh"     // view synthesis: splat the disparity to the target, fill, gather the views (lft_view_render)
 #include "lft_visibility.cuh" // view synthesis with a per-view visibility test, the warp of a map to other positions (lft_view_render_visible)
 #include "lft_sgm.cuh"       // semi-global aggregation of a cost volume: the path scans, the sum and the selection (lft_sgm)
+#include "lft_occlusion.cuh" // the sweep's cost from partial apertures: min over the whole aperture and up to four subsets (lft_disparity_occ)
 
 namespace {
 
@@ -559,6 +562,77 @@ int lft_sgm(const float* cost, int B, int D, int H, int W, int C, const float* s
     p.aif_f32 = aif_class == LFT_LF_FLOAT32;
     k_sgm_pick<<<dim3((unsigned)(per * B)), 256, 0, st>>>(p);
     LFT_LAUNCH_OK("k_sgm_pick");
+    return 0;
+}
+
+// ---- the sweep's occlusion-aware cost (lft_occlusion.cuh; declared in include/lft_hip_occlusion.h) ----
+static_assert(kOccMaxP == LFT_OCC_MAX_SUBSETS, "the header states how many subsets the kernel keeps accumulators for");
+// the bytes of the choice volume [B, D, H, W] behind lft_disparity's floats, rounded up to whole dwords
+int lft_disparity_occ_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
+    const char* who = "lft_disparity_occ";
+    if (!out_bytes) return fail(LFT_ERR_ARG, "%s: out_bytes is null", who);
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "%s: %d channels (1 .. 4)", who, C);
+    if (D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, D);
+    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, views of %d x %d", who, B, H, W);
+    size_t vol = 0;
+    const size_t n = disparity_floats(B, D, H, W, C, flags, &vol);
+    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "%s: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", who, B, D, H, W);
+    *out_bytes = n * sizeof(float) + (n ? (vol + 3) / 4 * 4 : 0);
+    return 0;
+}
+int lft_disparity_occ(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
+                      const float* subsets, int P, float beta, const float* slopes, int D, int taps, int radius, void* scratch,
+                      float* disparity, float* confidence, int* index, unsigned char* subset, unsigned char* choice, float* cost,
+                      void* aif, int aif_class, void* stream) {
+    const char* who = "lft_disparity_occ";
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
+    if (int rc = windowed_lf_ok(who, l, aif_class, "all-in-focus", radius, !subsets || !slopes || !scratch || !disparity || !confidence || !index, "sweeps"))
+        return rc;
+    if (P < 1 || P > LFT_OCC_MAX_SUBSETS) return fail(LFT_ERR_ARG, "%s: %d subsets outside 1 .. %d", who, P, LFT_OCC_MAX_SUBSETS);
+    if (!std::isfinite(beta) || beta < 1.0f) return fail(LFT_ERR_ARG, "%s: margin %g must be finite and >= 1", who, beta);
+    if (!l.tiles) return 0;                                         // empty maps
+    const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
+    const long long gblocks = ((long long)B * H * W + 255) / 256;
+    if (ptiles * B > 0x7fffffffLL || gblocks > 0x7fffffffLL) return too_many_blocks(who, l, "sweeps");
+    size_t vol = 0;
+    const size_t floats = disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol);
+    if (!floats) return fail(LFT_ERR_SHAPE, "%s: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", who, B, D, H, W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SweepOccArgs s{};
+    fill_windowed(s.s, l);
+    s.s.vol = static_cast<float*>(scratch); s.s.stack = aif ? s.s.vol + vol : nullptr;
+    s.subsets = subsets; s.P = P; s.beta = beta;
+    s.choice = choice ? choice : subset ? reinterpret_cast<uint8_t*>(s.s.vol + floats) : nullptr;
+    const dim3 grid((unsigned)(l.tiles * D * B));
+    by_lf_class<false>(lf_class, [&](auto t) { sweep_occ_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
+    LFT_LAUNCH_OK("k_sweep_cost_occ");
+    PickArgs p{};
+    p.vol = s.s.vol; p.stack = s.s.stack; p.slopes = slopes;
+    p.H = H; p.W = W; p.D = D; p.C = C; p.r = radius; p.tiles_x = (int)ptiles_x; p.tiles = (int)ptiles;
+    p.disparity = disparity; p.confidence = confidence; p.index = index; p.cost = cost; p.aif = aif;
+    p.aif_f32 = aif_class == LFT_LF_FLOAT32;
+    k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
+    LFT_LAUNCH_OK("k_disparity_pick");
+    if (subset) {
+        const OccGatherArgs g{index, s.choice, subset, D, (size_t)H * W, (size_t)B * H * W};
+        k_occ_gather<<<dim3((unsigned)gblocks), 256, 0, st>>>(g);
+        LFT_LAUNCH_OK("k_occ_gather");
+    }
+    return 0;
+}
+int lft_occ_gather(const int* index, const unsigned char* choice, int B, int D, int H, int W, unsigned char* subset, void* stream) {
+    const char* who = "lft_occ_gather";
+    if (D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, D);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, maps of %d x %d", who, B, H, W);
+    if (B == 0 || H == 0 || W == 0) return 0;                       // nothing to read or write
+    const double blocks = std::ceil((double)B * H * W / 256.0);
+    if (blocks > 2147483647.0) return fail(LFT_ERR_SHAPE, "%s: %d maps of %d x %d need more than 2^31 blocks", who, B, H, W);
+    if (!index || !choice || !subset) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    const OccGatherArgs g{index, choice, subset, D, (size_t)H * W, (size_t)B * H * W};
+    k_occ_gather<<<dim3((unsigned)blocks), 256, 0, static_cast<hipStream_t>(stream)>>>(g);
+    LFT_LAUNCH_OK("k_occ_gather");
     return 0;
 }
 

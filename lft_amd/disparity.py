@@ -74,9 +74,56 @@ cost volume along 4 or 8 paths before the selection, and ``disparity(..., regula
 - `aif` gathered from a stack at `k*`.
 
 Nothing may depend on launch shape, tile or arrival order. Every sum has a fixed order, and `min` has none to fix.
+
+Occlusion-aware cost from partial apertures
+-------------------------------------------
+Next to a foreground edge the views on the far side of the edge see the foreground at the background's true slope: the variance of
+all views is large there and a wrong slope wins.  ``disparity(..., occlusion="halves" | "quadrants" | dict(subsets=, margin=2.0,
+min_views=2))`` also scores each slope by the variance of up to four subsets of the views (lft_disparity_occ,
+csrc/lft_occlusion.cuh: k_sweep_cost_occ, then the unchanged k_disparity_pick, then k_occ_gather; declared in
+include/lft_hip_occlusion.h).
+
+The inputs, the table, the samples `s`, the aperture `a` (fp64 on the host, sum 1) and the centre `(cu, cv)` are those of
+`lft_disparity`. Everything below is fp32, one rounded operation per step, with contraction off.
+
+**Subsets (host only).** Let `δu = u − cu` and `δv = v − cv` in fp64.
+- `"halves"`: the four subsets `δu ≤ 0`, `δu ≥ 0`, `δv ≤ 0`, `δv ≥ 0`.
+- `"quadrants"`: `(≤,≤)`, `(≤,≥)`, `(≥,≤)`, `(≥,≥)` in `(δu, δv)`.
+- A boolean array `[P, A, A]` with 1 ≤ P ≤ 4.
+- A subset is *kept* iff at least `min_views` of its views have `a > 0`. `min_views` is an integer ≥ 2, default 2. One view has
+  variance 0 at every slope and would win everywhere.
+- Dropped subsets never reach the kernel. Subset ids in the outputs are positions in the kept list.
+- If no subset is kept, raise `LftError`.
+- For a kept subset `p`: `W_p = Σ_{p} a` in fp64. The row `b_p[u,v] = fl32(a/W_p)` for members and 0 for the rest.
+- The table `[P', A·A]` fp32, views in (u, v) order, is the only place these weights are rounded.
+
+**Moments.**
+- The full aperture is unchanged: `m`, `q`, `V_full` exactly as today, the same FMAs in the same order. `m` stays refocus's stack
+  bit for bit, and `aif` is still gathered from it.
+- Per kept subset, over its members in (u, v) order:
+  - `m_p = fma(b_p, s, m_p)`
+  - `q_p = fma(fl(b_p·s), s, q_p)`
+  - `V_p = Σ_c max(q_p − fl(m_p·m_p), 0)`, with c = 0 first.
+
+**Combination.**
+- `t = min_p V_p` and `U = fl(β·t)`.
+- `V = min(V_full, U)`.
+- `choice = 0` if `V_full ≤ U`, else the lowest `p` (1-based) with `V_p = t`.
+- `β` is the margin: finite, ≥ 1, rounded once to fp32. A subset wins only where it is β times better than the whole aperture.
+- Default β = 2. This is a choice and nobody has tuned it.
+
+**After that.** Steps 3 to 7 of `lft_disparity` run word for word on this `V`, through the existing `k_disparity_pick` unchanged.
+
+**New outputs.**
+- `subset`: uint8 `[B, H, W]`, equal to `choice` at `(k*, y, x)`.
+- Optionally the whole `choice` volume, uint8 `[B, D, H, W]` (``occlusion_volume``).
+- Read together with `index`, `subset` is an occlusion-edge map: 0 where all views agree.
+
+No result may depend on the tile, the launch shape or the arrival order.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -84,7 +131,7 @@ import torch
 
 from . import _lib
 from ._lib import LftError
-from .refocus import TAPS, Aperture, _CLASS, _as_given, _device_scratch, _device_table, _field
+from .refocus import TAPS, Aperture, _CLASS, _aperture, _as_given, _centre, _device_scratch, _device_table, _field
 
 MAX_RADIUS = 8
 
@@ -95,10 +142,25 @@ class DisparityResult(NamedTuple):
     index: torch.Tensor                        # int32, the same shape: k*
     all_in_focus: Optional[torch.Tensor]       # [H, W, C] for views with channels, else the shape of disparity; None unless asked for
     cost: Optional[torch.Tensor]               # fp32 [D, H, W] ([B, D, H, W]): E; None unless asked for
+    subset = None                              # these two are set on an OcclusionDisparityResult only: the plain tuple keeps its five
+    subsets_kept = None
+
+
+class OcclusionDisparityResult(NamedTuple):
+    """DisparityResult with `occlusion`: its fields in their order, then the two new ones."""
+    disparity: torch.Tensor
+    confidence: torch.Tensor
+    index: torch.Tensor
+    all_in_focus: Optional[torch.Tensor]
+    cost: Optional[torch.Tensor]
+    subset: torch.Tensor                       # uint8, the shape of index: 0 where the whole aperture set the cost at k*, else the
+    #                                            kept subset (1-based) that did
+    subsets_kept: Tuple[int, ...]              # which of the given subsets (0-based) the ids of `subset` stand for
 
 
 _slopes: Dict[tuple, torch.Tensor] = {}
 _scratch: Dict[tuple, torch.Tensor] = {}      # the sweep's volume (and stack); the path volumes of ``regularize``
+_subset_tables: Dict[tuple, tuple] = {}       # (device table [P', A*A], kept ids) of ``subset_table``
 
 
 def _device_slopes(sl: Tuple[float, ...], device) -> torch.Tensor:
@@ -113,6 +175,7 @@ def clear_cache() -> None:
     of ``regularize`` paths*D*H*W)."""
     _scratch.clear()
     _slopes.clear()
+    _subset_tables.clear()
 
 
 def check_slopes(slopes) -> Tuple[float, ...]:
@@ -124,9 +187,120 @@ def check_slopes(slopes) -> Tuple[float, ...]:
     return tuple(float(s) for s in sl)
 
 
+SUBSET_MODES = ("halves", "quadrants")
+_OCC_KEYS = ("subsets", "margin", "min_views")
+
+
+def _occlusion_arguments(occlusion) -> Tuple[object, float, int]:
+    """(subsets, margin, min_views) of an `occlusion` argument, with the refusals that need no light field: the shape of an array
+    against A is ``subset_table``'s."""
+    if isinstance(occlusion, str):
+        occlusion = dict(subsets=occlusion)
+    if not isinstance(occlusion, dict) or set(occlusion) - set(_OCC_KEYS):
+        raise LftError(f"occlusion must be None, halves, quadrants or a dict with any of subsets, margin, min_views, got {occlusion!r}")
+    subsets, margin, min_views = occlusion.get("subsets", "halves"), occlusion.get("margin", 2.0), occlusion.get("min_views", 2)
+    if isinstance(subsets, str) and subsets not in SUBSET_MODES:
+        raise LftError(f"subsets must be halves, quadrants or a boolean array [P, A, A], got {subsets!r}")
+    if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) or not 1 <= margin <= float(np.finfo(np.float32).max):
+        raise LftError(f"margin must be a finite number >= 1 (as float32), got {margin!r}")
+    if isinstance(min_views, bool) or not isinstance(min_views, (int, np.integer)) or min_views < 2:
+        raise LftError(f"min_views must be an integer >= 2, got {min_views!r}")
+    return subsets, float(margin), int(min_views)
+
+
+def subset_table(A: int, aperture: Aperture = "full", centre=None, subsets="halves", min_views: int = 2) -> Tuple[np.ndarray, Tuple[int, ...]]:
+    """(the host table fp32 [P', A*A] of the kept subsets' weights b_p, views in (u, v) order; the kept subsets' positions in the
+    given list).  The module docstring has the definition; this is the only place these weights are computed and rounded."""
+    subsets, _, min_views = _occlusion_arguments(dict(subsets=subsets, min_views=min_views))
+    a = _aperture(A, aperture)
+    cu, cv = _centre(A, centre)
+    du = np.broadcast_to((np.arange(A, dtype=np.float64) - cu)[:, None], (A, A))
+    dv = np.broadcast_to((np.arange(A, dtype=np.float64) - cv)[None, :], (A, A))
+    if isinstance(subsets, str):
+        lo_u, hi_u, lo_v, hi_v = du <= 0, du >= 0, dv <= 0, dv >= 0
+        masks = np.stack([lo_u, hi_u, lo_v, hi_v] if subsets == "halves" else [lo_u & lo_v, lo_u & hi_v, hi_u & lo_v, hi_u & hi_v])
+    else:
+        masks = np.asarray(subsets.detach().cpu().numpy() if isinstance(subsets, torch.Tensor) else subsets)
+        if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1:] != (A, A) or not 1 <= masks.shape[0] <= _lib.OCC_MAX_SUBSETS:
+            raise LftError(f"subsets must be a boolean array [P, {A}, {A}] with 1 <= P <= {_lib.OCC_MAX_SUBSETS}, got {masks.dtype} {masks.shape}")
+    kept = tuple(p for p in range(masks.shape[0]) if int((masks[p] & (a > 0)).sum()) >= min_views)
+    if not kept:
+        raise LftError(f"none of the {masks.shape[0]} subsets has {min_views} views of non-zero aperture weight")
+    table = np.zeros((len(kept), A * A), dtype=np.float32)
+    for row, p in enumerate(kept):
+        member = masks[p].reshape(-1)
+        W = math.fsum(a.reshape(-1)[member])                        # the exactly rounded fp64 sum: no order to fix
+        table[row, member] = (a.reshape(-1)[member] / W).astype(np.float32)      # rounded once, here
+    return table, kept
+
+
+def _device_subsets(A: int, aperture: Aperture, centre, subsets, min_views: int, device) -> Tuple[torch.Tensor, Tuple[int, ...]]:
+    ap = aperture if isinstance(aperture, str) else _aperture(A, aperture).tobytes()
+    how = subsets if isinstance(subsets, str) else (np.asarray(subsets.cpu() if isinstance(subsets, torch.Tensor) else subsets).shape,
+                                                    np.asarray(subsets.cpu() if isinstance(subsets, torch.Tensor) else subsets).tobytes())
+    key = (A, ap, None if centre is None else _centre(A, centre), how, min_views, str(device))
+    if key not in _subset_tables:
+        table, kept = subset_table(A, aperture, centre, subsets, min_views)
+        _subset_tables[key] = (torch.from_numpy(table).to(device), kept)
+    return _subset_tables[key]
+
+
+def _sweep_arguments(radius, interp, slopes) -> Tuple[float, ...]:
+    """The refusals of a sweep that need no tensor; returns the checked slopes."""
+    if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= MAX_RADIUS:
+        raise LftError(f"radius must be an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
+    if interp not in TAPS:
+        raise LftError(f"interp must be nearest, linear or cubic, got {interp!r}")
+    return check_slopes(slopes)
+
+
+def _disparity_occ(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion,
+                   choice_volume: bool = False) -> Tuple[OcclusionDisparityResult, Optional[torch.Tensor]]:
+    """``disparity`` with `occlusion`: one call of lft_disparity_occ.  Also returns the choice volume, uint8 [D, H, W] ([B, D, H, W]
+    for a batch), when asked for."""
+    sl, how = (), ()
+
+    def sweep_arguments():
+        nonlocal sl, how
+        sl = _sweep_arguments(radius, interp, slopes)
+        how = _occlusion_arguments(occlusion)
+
+    B, A, H, W, C, strides, kind = _field(lf, angRes, "aif_dtype", aif_dtype, before_device=sweep_arguments)
+    aif_dtype = lf.dtype if aif_dtype is None else aif_dtype
+    subsets, margin, min_views = how
+    dev = lf.device
+    table = _device_table(A, sl, aperture, interp, dev, centre)
+    btable, kept = _device_subsets(A, aperture, centre, subsets, min_views, dev)
+    D = len(sl)
+    disp = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    conf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    index = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    subset = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    choice = torch.empty(B, D, H, W, dtype=torch.uint8, device=dev) if choice_volume else None
+    cost = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if cost_volume else None
+    aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if all_in_focus else None
+    if B and H and W:
+        scratch = _device_scratch(_scratch, "lft_disparity_occ_scratch_bytes", (B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0), dev)
+        _lib.enqueue("lft_disparity_occ", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), btable.data_ptr(),
+                     len(kept), margin, _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius), scratch.data_ptr(), disp.data_ptr(),
+                     conf.data_ptr(), index.data_ptr(), subset.data_ptr(), choice.data_ptr() if choice_volume else None,
+                     cost.data_ptr() if cost_volume else None, aif.data_ptr() if all_in_focus else None, _CLASS[aif_dtype])
+    return OcclusionDisparityResult(*(_as_given(kind, t) for t in (disp, conf, index)), _as_given(kind, aif, image=True), _as_given(kind, cost),
+                                    _as_given(kind, subset), kept), _as_given(kind, choice)
+
+
+def occlusion_volume(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
+                     interp: str = "linear", centre=None, occlusion="halves") -> torch.Tensor:
+    """The whole `choice` volume of ``disparity(..., occlusion=occlusion)``, uint8 [D, H, W] ([B, D, H, W] for a batch): per pixel
+    and slope 0 where the whole aperture set the raw cost V, else the kept subset (1-based) that did.  It does not depend on the
+    aggregation radius."""
+    _, choice = _disparity_occ(lf, slopes, angRes, aperture, interp, 0, False, False, None, centre, occlusion, choice_volume=True)
+    return choice
+
+
 def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
               interp: str = "linear", radius: int = 2, all_in_focus: bool = False, cost_volume: bool = False,
-              aif_dtype=None, centre=None, regularize: Optional[dict] = None) -> DisparityResult:
+              aif_dtype=None, centre=None, regularize: Optional[dict] = None, occlusion=None) -> DisparityResult:
     """The disparity map of a light field on the GPU, on lf's device and current stream (enqueue only).
 
       views  [A, A, H, W, C] (C <= 4) or [A, A, H, W]   ->  maps [H, W], all_in_focus [H, W, C] or [H, W], cost [D, H, W]
@@ -140,18 +314,22 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     map then belongs to that position, and all_in_focus is the plane-sweep rendering of a view there.
     regularize: None, or dict(p1=, p2=, paths=8, guide=None, edge_gain=0.0): sweep with the cost volume, then ``regularize`` it with
     these arguments and select from S (cost is then S); all_in_focus gathers from ``refocus.refocus``'s fp32 stack, which is the
-    sweep's m bit for bit."""
+    sweep's m bit for bit.
+    occlusion: None, "halves", "quadrants" or dict(subsets="halves" | "quadrants" | a boolean array [P, A, A], margin=2.0,
+    min_views=2): the occlusion-aware cost of the module docstring (one call of lft_disparity_occ in the sweep's place).  The
+    result is then an ``OcclusionDisparityResult``, DisparityResult's fields and then `subset` and `subsets_kept`: `subset` is 0
+    where the whole aperture set the cost at the index and else the kept subset (1-based) that did, `subsets_kept` says which of
+    the given subsets those ids stand for; with regularize, SGM runs on the new E and `subset` is the choice volume gathered at
+    SGM's index.  Without it nothing changes (the five-field result answers None for both names): the same launches, the same bits."""
     if regularize is not None:
-        return _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, regularize)
+        return _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, regularize, occlusion)
+    if occlusion is not None:
+        return _disparity_occ(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion)[0]
     sl = ()
 
     def sweep_arguments():                  # radius, interp and slopes are refused before a tensor off the GPU
         nonlocal sl
-        if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= MAX_RADIUS:
-            raise LftError(f"radius must be an integer in 0 .. {MAX_RADIUS}, got {radius!r}")
-        if interp not in TAPS:
-            raise LftError(f"interp must be nearest, linear or cubic, got {interp!r}")
-        sl = check_slopes(slopes)
+        sl = _sweep_arguments(radius, interp, slopes)
 
     B, A, H, W, C, strides, kind = _field(lf, angRes, "aif_dtype", aif_dtype, before_device=sweep_arguments)
     aif_dtype = lf.dtype if aif_dtype is None else aif_dtype
@@ -261,17 +439,45 @@ def regularize(cost: torch.Tensor, slopes: Sequence[float], p1: float, p2: float
 _SGM_KEYS = ("p1", "p2", "paths", "guide", "edge_gain")
 
 
-def _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, how) -> DisparityResult:
-    """``disparity`` with regularize=how: the sweep's E, refocus's stack when all_in_focus, then ``regularize``."""
+def _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, how, occlusion=None) -> DisparityResult:
+    """``disparity`` with regularize=how: the sweep's E, refocus's stack when all_in_focus, then ``regularize``.  With occlusion
+    the sweep is lft_disparity_occ's, and `subset` its choice volume gathered at the regularized index (lft_occ_gather)."""
     from . import refocus as Rf
     if not isinstance(how, dict) or set(how) - set(_SGM_KEYS) or not {"p1", "p2"} <= set(how):
         raise LftError(f"regularize must be None or a dict with p1, p2 and any of paths, guide, edge_gain, got {how!r}")
     if aif_dtype is not None and aif_dtype not in _CLASS:
         raise LftError(f"aif_dtype must be torch.uint8 or torch.float32, got {aif_dtype}")
     _sgm_arguments(None, slopes, how["p1"], how["p2"], how.get("paths", 8), how.get("edge_gain", 0.0), how.get("guide") is not None, None, False)
-    swept = disparity(lf, slopes, angRes, aperture, interp, radius, cost_volume=True, centre=centre)
+    if occlusion is None:
+        swept, choice = disparity(lf, slopes, angRes, aperture, interp, radius, cost_volume=True, centre=centre), None
+    else:
+        _occlusion_arguments(occlusion)
+        swept, choice = _disparity_occ(lf, slopes, angRes, aperture, interp, radius, False, True, None, centre, occlusion, choice_volume=True)
     stack = Rf.refocus(lf, slopes, angRes, aperture, interp, out_dtype=torch.float32, centre=centre) if all_in_focus else None
-    return regularize(swept.cost, slopes, stack=stack, aif_dtype=(aif_dtype or lf.dtype) if all_in_focus else None, aggregated=cost_volume, **how)
+    res = regularize(swept.cost, slopes, stack=stack, aif_dtype=(aif_dtype or lf.dtype) if all_in_focus else None, aggregated=cost_volume, **how)
+    if choice is None:
+        return res
+    return OcclusionDisparityResult(*res, gather_choice(res.index, choice), swept.subsets_kept)
+
+
+def gather_choice(index: torch.Tensor, choice: torch.Tensor) -> torch.Tensor:
+    """subset[..., y, x] = choice[..., index[..., y, x], y, x] on the GPU (lft_occ_gather, enqueue only): index int32 [H, W] or
+    [B, H, W], choice uint8 [D, H, W] or [B, D, H, W]; an index outside 0 .. D-1 is clamped into it."""
+    for name, t, dtype in (("index", index, torch.int32), ("choice", choice, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise LftError(f"the {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    batch = index.dim() == 3
+    if index.dim() not in (2, 3) or choice.dim() != index.dim() + 1 or choice.shape[-2:] != index.shape[-2:] or choice.shape[:-3] != index.shape[:-2] \
+            or choice.shape[-3] < 1:
+        raise LftError(f"an index of {tuple(index.shape)} does not gather from a choice volume of {tuple(choice.shape)}")
+    if index.device.type != "cuda" or choice.device != index.device:
+        raise LftError(f"the index and the choice volume must be on one GPU, got {index.device} and {choice.device} (there is no CPU path)")
+    B, D, H, W = (int(n) for n in (choice.shape if batch else (1,) + tuple(choice.shape)))
+    index, choice = index.contiguous(), choice.contiguous()
+    subset = torch.empty(index.shape, dtype=torch.uint8, device=index.device)
+    if B and H and W:
+        _lib.enqueue("lft_occ_gather", index.device, index.data_ptr(), choice.data_ptr(), B, D, H, W, subset.data_ptr())
+    return subset
 
 
 def disparity_error(a: torch.Tensor, b: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None,

@@ -417,14 +417,14 @@ def densify(lf: torch.Tensor, disparity: torch.Tensor, factor: int, d_range, ang
 
 def leave_one_out(lf: torch.Tensor, slopes: Sequence[float], positions=None, angRes: Optional[int] = None, sigma: float = 0.75,
                   interp: str = "linear", radius: int = 2, disparity: Optional[torch.Tensor] = None, reference=None, regularize: Optional[dict] = None,
-                  **kw) -> List[float]:
+                  occlusion=None, **kw) -> List[float]:
     """PSNR (dB, peak 1) of every held-out view (u, v) of `positions` (default: all, in (u, v) order) predicted from the others:
     the disparity is swept at (u, v) with that view's aperture weight 0 (``disparity.disparity(centre=(u, v))``), the view rendered
     there with the gaussian blend and the view excluded, and compared on the GPU over the interior left by the reach of one view
     step, ceil(max|slope|) + 1 pixels: the nearest views carry the gaussian's weight.  With `disparity` (a map [H, W] at
     `reference`, default the centre) nothing is swept: every held-out view is rendered from that map, the slopes give d_range, and
     the interior is left by the splat's reach where that is larger.  regularize goes to the sweeps (``disparity.disparity``: None, or
-    the arguments of the semi-global aggregation).  kw goes to ``render``, `visibility` included: with it the views that do not see a
+    the arguments of the semi-global aggregation), and so does occlusion (None, or the subsets of the occlusion-aware cost).  kw goes to ``render``, `visibility` included: with it the views that do not see a
     pixel's surface leave its blend.  An angularly inconsistent field scores
     low however good its single views are.  A view reproduced exactly scores inf."""
     from . import disparity as Dm
@@ -452,7 +452,8 @@ def leave_one_out(lf: torch.Tensor, slopes: Sequence[float], positions=None, ang
         ap = np.ones((A, A))
         ap[u, v] = 0.0
         if disparity is None:
-            dr, ref = Dm.disparity(views, sl, aperture=ap, interp=interp, radius=radius, centre=(u, v), regularize=regularize).disparity, (u, v)
+            dr, ref = Dm.disparity(views, sl, aperture=ap, interp=interp, radius=radius, centre=(u, v), regularize=regularize,
+                                   occlusion=occlusion).disparity, (u, v)
         else:
             dr, ref = disparity, reference
         got = render(views, dr, [(u, v)], d_range, reference=ref, blend="gaussian", sigma=sigma, exclude=ap == 0, interp=interp,

@@ -2,6 +2,7 @@
 
   python tools/disparity.py --lf scene.mat --angRes 5 --out_dir out/ --slopes=-2:2:33 --radius 2 [--aperture full|disk|gaussian]
                             [--interp nearest|linear|cubic] [--regularize [--p1 P1 --p2 P2] [--paths 4|8] [--edge_gain G]]
+                            [--occlusion [halves|quadrants] [--margin B] [--min_views N]]
                             [--path_pre_pth LFT_5x5_4x.pth.tar --scale_factor 4 [--precision ..] [--self_ensemble ..]] [--bicubic]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C]; its centre angRes x angRes views are used.  Without
@@ -14,7 +15,11 @@ all_in_focus.png and disparity.npy (fp32 [H, W], slope units) from one lft_amd.d
 the bicubic ones: the mean absolute disparity difference over the pixels where the bicubic sweep is confident, and their share.
 --regularize aggregates the cost volume along --paths paths before the selection (lft_amd.disparity.regularize): the penalties
 default to lft_amd.disparity.penalties_from_cost of the winner-take-all sweep, and with --edge_gain the guide is the channel mean of
-that sweep's all-in-focus image.  Without these flags the files keep their bytes."""
+that sweep's all-in-focus image.  --occlusion scores every slope also by the variance of the views of each half (or quadrant) of the
+aperture, so that the band round a foreground edge gets the background's slope (lft_amd.disparity.disparity(occlusion=)): a subset
+wins where it is --margin times better than the whole aperture, subsets with fewer than --min_views views are dropped, and
+<out_dir>/occlusion.png shows which subset set the cost at the chosen slope (0 black: all views agree; subset p as grey 63 p).
+Without these flags the files keep their bytes."""
 import argparse
 import json
 import os
@@ -37,6 +42,11 @@ def grey(x: torch.Tensor, lo: float, hi: float) -> np.ndarray:
     return g[..., None].expand(-1, -1, 3).contiguous().cpu().numpy()
 
 
+def occlusion_arguments(args):
+    """The `occlusion` dict of lft_amd.disparity.disparity for --occlusion, or None without it."""
+    return dict(subsets=args.occlusion, margin=args.margin, min_views=args.min_views) if args.occlusion else None
+
+
 def regularize_arguments(views, slopes, args, guided=True):
     """The `regularize` dict of lft_amd.disparity.disparity for --regularize, or None without it.  Penalties not given on the
     command line come from ``penalties_from_cost`` on the winner-take-all sweep's cost (this synchronises); with --edge_gain > 0 and
@@ -45,7 +55,7 @@ def regularize_arguments(views, slopes, args, guided=True):
         return None
     want_guide = guided and args.edge_gain > 0
     wta = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus=want_guide,
-                              aif_dtype=torch.float32, cost_volume=True)
+                              aif_dtype=torch.float32, cost_volume=True, occlusion=occlusion_arguments(args))
     p1, p2 = disparity.penalties_from_cost(wta.cost)
     how = dict(p1=p1 if args.p1 is None else args.p1, p2=p2 if args.p2 is None else args.p2, paths=args.paths)
     if want_guide:
@@ -56,12 +66,15 @@ def regularize_arguments(views, slopes, args, guided=True):
 def write_maps(out_dir, views, slopes, args, prefix=""):
     """views: [A, A, H, W, 3] on the GPU (uint8, or float32 in [0, 1]).  Returns the paths written."""
     r = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus=True,
-                            aif_dtype=torch.uint8, regularize=regularize_arguments(views, slopes, args))
+                            aif_dtype=torch.uint8, regularize=regularize_arguments(views, slopes, args), occlusion=occlusion_arguments(args))
     paths = [os.path.join(out_dir, prefix + name) for name in ("disparity.png", "confidence.png", "all_in_focus.png", "disparity.npy")]
     png.write_png(paths[0], grey(r.disparity, min(slopes), max(slopes)))
     png.write_png(paths[1], grey(r.confidence, 0.0, 1.0))
     png.write_png(paths[2], r.all_in_focus.cpu().numpy())
     np.save(paths[3], r.disparity.cpu().numpy())
+    if r.subset is not None:
+        paths.append(os.path.join(out_dir, prefix + "occlusion.png"))
+        png.write_png(paths[-1], (r.subset * 63)[..., None].expand(-1, -1, 3).contiguous().cpu().numpy())
     return paths
 
 
@@ -79,6 +92,10 @@ def main(argv=None):
     ap.add_argument("--p2", type=float, default=None, help="penalty of a larger jump (default: the mean cost)")
     ap.add_argument("--paths", type=int, default=8, choices=(4, 8))
     ap.add_argument("--edge_gain", type=float, default=0.0, help="p2 falls by this times the step of the guide, not below p1")
+    ap.add_argument("--occlusion", nargs="?", const="halves", default=None, choices=disparity.SUBSET_MODES,
+                    help="occlusion-aware cost from partial apertures: the subsets of the views (default halves); also writes occlusion.png")
+    ap.add_argument("--margin", type=float, default=2.0, help="a subset wins where it is this many times better than the whole aperture, >= 1")
+    ap.add_argument("--min_views", type=int, default=2, help="subsets with fewer views of non-zero weight are dropped, >= 2")
     ap.add_argument("--min_confidence", type=float, default=0.5, help="pixels counted by the printed disparity_error")
     ap.add_argument("--path_pre_pth", default=None, help="checkpoint in the reference's format: sweep the super-resolved views")
     ap.add_argument("--scale_factor", type=int, default=4)
@@ -108,7 +125,7 @@ def main(argv=None):
     if sr is not None and base is not None:
         # one set of penalties for both sides: the bicubic (trusted) side's, and no guide
         err, share = disparity.disparity_error(sr, base, slopes, min_confidence=args.min_confidence, aperture=args.aperture,
-                                               interp=args.interp, radius=args.radius, **({"regularize": regularize_arguments(base, slopes, args, guided=False)} if args.regularize else {}))
+                                               interp=args.interp, radius=args.radius, occlusion=occlusion_arguments(args), **({"regularize": regularize_arguments(base, slopes, args, guided=False)} if args.regularize else {}))
         print(json.dumps({"disparity_error": err, "confident_share": share, "min_confidence": args.min_confidence,
                           "against": "bicubic", "slopes": [min(slopes), max(slopes), len(slopes)], "radius": args.radius}))
     print(f"{args.out_dir}: {len(paths)} files, {len(slopes)} slopes from {min(slopes):g} to {max(slopes):g}")

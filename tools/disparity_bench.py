@@ -15,7 +15,10 @@ where the two pick the same slope (their costs differ by fp32 rounding and the c
   python tools/disparity_bench.py [--rounds 3] [--reps 200] [--torch_reps 10] [--warmup 3] [--out profiles/disparity_bench.txt]
   python tools/disparity_bench.py --regularize [--rounds 3] [--reps 200] [--warmup 3] [--out profiles/sgm_bench.txt]
 
---regularize times the semi-global aggregation of that workload's cost volume instead (``regularize_bench``)."""
+  python tools/disparity_bench.py --occlusion [--rounds 3] [--reps 200] [--warmup 3] [--out profiles/occlusion_bench.txt]
+
+--regularize times the semi-global aggregation of that workload's cost volume instead (``regularize_bench``).
+--occlusion times the plain and the occlusion-aware sweep of that workload alternately instead (``occlusion_bench``)."""
 import argparse
 import json
 import os
@@ -79,9 +82,40 @@ def regularize_bench(args, lf, slopes):
     return lines
 
 
+def occlusion_bench(args, lf, slopes):
+    """--occlusion: one JSON line.  ``maps_ms`` is the unchanged `disparity.disparity` (k_sweep_cost + k_disparity_pick),
+    ``halves_ms`` and ``quadrants_ms`` the same call with occlusion= (k_sweep_cost_occ + k_disparity_pick + k_occ_gather), the
+    three alternating in the same rounds of one process.  The byte contract of the new sweep: the views are read once per slope, as
+    for the plain one; V plus one byte per pixel and slope is written; the pick reads V and writes three maps; the gather reads
+    the index and one byte per pixel and writes one.  ``subsets_per_view`` is the mean number of subsets a view belongs to: the
+    accumulation is about 1 + that many times the plain one, on the same bytes read."""
+    calls = {"maps_ms": lambda: disparity.disparity(lf, slopes, interp="linear", radius=RADIUS),
+             "halves_ms": lambda: disparity.disparity(lf, slopes, interp="linear", radius=RADIUS, occlusion="halves"),
+             "quadrants_ms": lambda: disparity.disparity(lf, slopes, interp="linear", radius=RADIUS, occlusion="quadrants")}
+    for _ in range(args.warmup):
+        for f in calls.values():
+            f()
+    torch.cuda.synchronize()
+    rounds = [{k: round(timed(f, args.reps), 4) for k, f in calls.items()} for _ in range(args.rounds)]
+    best = {k: min(r[k] for r in rounds) for k in calls}
+    read = D * A * A * H * W * C
+    vol = D * H * W * 4
+    nbytes = read + 2 * vol + 3 * H * W * 4
+    nbytes_occ = nbytes + D * H * W + H * W * (4 + 1 + 1)
+    per_view = {mode: float((disparity.subset_table(A, "full", None, mode)[0] != 0).sum()) / (A * A) for mode in ("halves", "quadrants")}
+    return [json.dumps({"bench": "disparity_occlusion", "device": torch.cuda.get_device_name(0), "A": A, "view": [H, W, C], "in": "uint8", "D": D,
+                        "interp": "linear", "radius": RADIUS, "aperture": "full", "margin": 2.0, "reps": args.reps, "rounds": rounds,
+                        "maps_ms_best": best["maps_ms"], "halves_ms_best": best["halves_ms"], "quadrants_ms_best": best["quadrants_ms"],
+                        "halves_over_plain": round(best["halves_ms"] / best["maps_ms"], 3), "quadrants_over_plain": round(best["quadrants_ms"] / best["maps_ms"], 3),
+                        "subsets_per_view": per_view, "contract_bytes": nbytes, "contract_bytes_occlusion": nbytes_occ,
+                        "maps_GBps": round(nbytes / (best["maps_ms"] * 1e-3) / 1e9, 1), "halves_GBps": round(nbytes_occ / (best["halves_ms"] * 1e-3) / 1e9, 1),
+                        "quadrants_GBps": round(nbytes_occ / (best["quadrants_ms"] * 1e-3) / 1e9, 1)})]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--regularize", action="store_true", help="time the semi-global aggregation beside the sweep instead (one line per path count)")
+    ap.add_argument("--occlusion", action="store_true", help="time the plain and the occlusion-aware sweep alternately instead (one line)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--torch_reps", type=int, default=10)
@@ -91,8 +125,8 @@ def main():
     dev = torch.device("cuda", 0)
     slopes = [float(x) for x in np.linspace(-2.0, 2.0, D)]
     lf = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (A, A, H, W, C)).astype(np.uint8)).to(dev)
-    if args.regularize:
-        lines = regularize_bench(args, lf, slopes)
+    if args.regularize or args.occlusion:
+        lines = regularize_bench(args, lf, slopes) if args.regularize else occlusion_bench(args, lf, slopes)
         print("\n".join(lines))
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
