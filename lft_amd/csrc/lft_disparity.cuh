@@ -39,6 +39,8 @@
 //                     max(q - fl(m*m), 0) goes to LDS -- the element-indexed layout has a pixel's channels next to each other --
 //                     and each lane adds the channels of four pixels, c = 0 first.  V leaves as fp32 into the caller's volume
 //                     [B, D, H, W]; with a stack pointer m leaves too, [B, D, H, W, C], for the all-in-focus gather.
+//                     The body is sweep_cost<T, C, TAPS, OCC>, written once for this kernel and for k_sweep_cost_occ
+//                     (lft_occlusion.cuh, which describes what OCC adds); k_refocus keeps its own copy of the pipeline, see below.
 //   k_disparity_pick  one workgroup per (batch element, 16 x 16 tile), one pixel per lane: four times the workgroups of the sweep,
 //                     because each walks the D slopes one after the other behind two barriers and only other workgroups hide
 //                     that.  Per slope the V tile with a halo of r (clamped coordinates)
@@ -87,11 +89,19 @@ struct PickArgs {
     int aif_f32;
 };
 
-template <typename T, int C, int TAPS>
-__global__ __launch_bounds__(256) void k_sweep_cost(SweepArgs a) {
+constexpr int kOccMaxP = 4;                                          // LFT_OCC_MAX_SUBSETS of include/lft_hip_occlusion.h
+
+// The body of k_sweep_cost (OCC false; the last four arguments are not read) and of k_sweep_cost_occ (lft_occlusion.cuh; OCC true:
+// subsets [P, A*A], 1 <= P <= kOccMaxP, the margin beta and the choice volume [B, D, H, W] or null): the window pipeline and both
+// tails, written once.  What the subsets add stands under `if constexpr (OCC)`.  Sharing moved instructions in all 48 kernels (no
+// scratch, LDS equal, no occupancy step crossed) but not the time: parent against shared, alternating in fresh processes on an
+// MI355X, maps_ms 0.5075 .. 0.5114 against 0.5084 .. 0.5125, halves_ms 1.0218 .. 1.0238 against 1.0175 .. 1.0206, quadrants_ms
+// 0.9922 .. 0.9980 against 0.9876 .. 0.9918 (profiles/sweep_refactor_ab.txt; uint8, C = 3, linear only).
+template <typename T, int C, int TAPS, bool OCC>
+__device__ __forceinline__ void sweep_cost(const SweepArgs& a, const float* subsets, int P, float beta, uint8_t* choice) {
 #pragma clang fp contract(off)
-    // the window pipeline below is k_refocus's, statement for statement, up to the second accumulator.  It is a copy on purpose:
-    // one inlined function serving both kernels changed k_refocus's instructions and cost its linear stack 0.8 %
+    // the window pipeline below is k_refocus's, statement for statement, up to the second accumulator.  Of k_refocus it is a copy
+    // on purpose: one inlined function serving both changed k_refocus's instructions and cost its linear stack 0.8 %
     constexpr int NR = kRfTile + TAPS - 1;
     constexpr int RW = NR * C;
     constexpr int NE = NR * RW;
@@ -115,9 +125,15 @@ __global__ __launch_bounds__(256) void k_sweep_cost(SweepArgs a) {
 
     const int prow = tid / RW, pj = tid % RW, pxw = pj / C, pc = pj % C;
     T stage[NLD];
-    float m[NACC], q[NACC];
+    float m[NACC], q[NACC], mp[OCC ? kOccMaxP : 1][NACC], qp[OCC ? kOccMaxP : 1][NACC];
 #pragma unroll
-    for (int r = 0; r < NACC; ++r) { m[r] = 0.0f; q[r] = 0.0f; }
+    for (int r = 0; r < NACC; ++r) {
+        m[r] = 0.0f; q[r] = 0.0f;
+        if constexpr (OCC) {
+#pragma unroll
+            for (int p = 0; p < kOccMaxP; ++p) { mp[p][r] = 0.0f; qp[p][r] = 0.0f; }
+        }
+    }
 
     auto next_active = [&](int n) {
         while (n < nv && recs[n * kRfRec + 11]) ++n;
@@ -168,6 +184,7 @@ __global__ __launch_bounds__(256) void k_sweep_cost(SweepArgs a) {
             }
         }
         __syncthreads();
+        float sv[OCC ? NACC : 1];                                    // this view's samples: every subset it belongs to reads them
 #pragma unroll
         for (int r = 0; r < NACC; ++r) {
             const int i = tid + 256 * r;
@@ -175,33 +192,100 @@ __global__ __launch_bounds__(256) void k_sweep_cost(SweepArgs a) {
             float s = wx[0] * t[0];
 #pragma unroll
             for (int k = 1; k < TAPS; ++k) s = __fmaf_rn(wx[k], t[k * C], s);
+            if constexpr (OCC) sv[r] = s;
             m[r] = __fmaf_rn(aw, s, m[r]);
             q[r] = __fmaf_rn(aw * s, s, q[r]);
+        }
+        if constexpr (OCC) {
+#pragma unroll
+            for (int p = 0; p < kOccMaxP; ++p) {
+                if (p >= P) break;
+                const float bw = subsets[p * nv + cur];              // the same for every lane: a scalar load and a scalar branch
+                if (bw != 0.0f) {
+#pragma unroll
+                    for (int r = 0; r < NACC; ++r) {
+                        mp[p][r] = __fmaf_rn(bw, sv[r], mp[p][r]);
+                        qp[p][r] = __fmaf_rn(bw * sv[r], sv[r], qp[p][r]);
+                    }
+                }
+            }
         }
         if (nxt < nv) commit();
         __syncthreads();
         cur = nxt;
     }
 
-    // every lane is past the last column pass: tmp takes the variances, element-indexed, pitch OW
+    // every lane is past the last column pass: tmp takes the variances, element-indexed, pitch OW (of one moment pair at a time with subsets)
     const size_t pix = ((size_t)b * a.D + d) * a.H * a.W;             // first pixel of this (b, slope) plane
     const int nb = nx * C;
+    if constexpr (!OCC) {
 #pragma unroll
-    for (int r = 0; r < NACC; ++r) {
-        const int i = tid + 256 * r, y = i / OW, e = i % OW;
-        tmp[i] = fmaxf(q[r] - m[r] * m[r], 0.0f);                    // the square rounded on its own: one view (a = 1) gives exactly 0
-        if (a.stack && y < ny && e < nb) a.stack[(pix + (size_t)(y0 + y) * a.W + x0) * C + e] = m[r];
-    }
-    __syncthreads();
+        for (int r = 0; r < NACC; ++r) {
+            const int i = tid + 256 * r, y = i / OW, e = i % OW;
+            tmp[i] = fmaxf(q[r] - m[r] * m[r], 0.0f);                    // the square rounded on its own: one view (a = 1) gives exactly 0
+            if (a.stack && y < ny && e < nb) a.stack[(pix + (size_t)(y0 + y) * a.W + x0) * C + e] = m[r];
+        }
+        __syncthreads();
 #pragma unroll
-    for (int r = 0; r < NPIX; ++r) {
-        const int i = tid + 256 * r, y = i / kRfTile, x = i % kRfTile;
-        float v = tmp[i * C];
+        for (int r = 0; r < NPIX; ++r) {
+            const int i = tid + 256 * r, y = i / kRfTile, x = i % kRfTile;
+            float v = tmp[i * C];
 #pragma unroll
-        for (int c = 1; c < C; ++c) v += tmp[i * C + c];
-        if (y < ny && x < nx) a.vol[pix + (size_t)(y0 + y) * a.W + x0 + x] = v;
+            for (int c = 1; c < C; ++c) v += tmp[i * C + c];
+            if (y < ny && x < nx) a.vol[pix + (size_t)(y0 + y) * a.W + x0 + x] = v;
+        }
+    } else {
+        auto channel_sum = [&](const float* mm, const float* qq, float* v) {   // V of this lane's NPIX pixels; ends behind a barrier
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int r = 0; r < NACC; ++r) tmp[tid + 256 * r] = fmaxf(qq[r] - mm[r] * mm[r], 0.0f);   // the square rounded on its own
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < NPIX; ++r) {
+                const int i = tid + 256 * r;
+                float s = tmp[i * C];
+#pragma unroll
+                for (int c = 1; c < C; ++c) s += tmp[i * C + c];
+                v[r] = s;
+            }
+            __syncthreads();                                             // the next pair's variances overwrite tmp
+        };
+        if (a.stack) {
+#pragma unroll
+            for (int r = 0; r < NACC; ++r) {
+                const int i = tid + 256 * r, y = i / OW, e = i % OW;
+                if (y < ny && e < nb) a.stack[(pix + (size_t)(y0 + y) * a.W + x0) * C + e] = m[r];
+            }
+        }
+        float vfull[NPIX], t[NPIX], vp[NPIX];
+        int arg[NPIX];
+#pragma unroll
+        for (int r = 0; r < NPIX; ++r) { t[r] = 0.0f; arg[r] = 0; }
+        channel_sum(m, q, vfull);
+#pragma unroll
+        for (int p = 0; p < kOccMaxP; ++p) {
+            if (p >= P) break;                                           // uniform: every lane meets the same barriers
+            channel_sum(mp[p], qp[p], vp);
+#pragma unroll
+            for (int r = 0; r < NPIX; ++r)
+                if (p == 0 || vp[r] < t[r]) { t[r] = vp[r]; arg[r] = p + 1; }   // strict: the lowest p wins an exact tie
+        }
+#pragma unroll
+        for (int r = 0; r < NPIX; ++r) {
+            const int i = tid + 256 * r, y = i / kRfTile, x = i % kRfTile;
+            if (y < ny && x < nx) {
+                const size_t o = pix + (size_t)(y0 + y) * a.W + x0 + x;
+                const float U = beta * t[r];
+                const bool whole = vfull[r] <= U;
+                a.vol[o] = whole ? vfull[r] : U;
+                if (choice) choice[o] = whole ? (uint8_t)0 : (uint8_t)arg[r];
+            }
+        }
     }
 }
+
+template <typename T, int C, int TAPS>
+__global__ __launch_bounds__(256) void k_sweep_cost(SweepArgs a) { sweep_cost<T, C, TAPS, false>(a, nullptr, 0, 0.0f, nullptr); }
 
 // The selection (steps 4-7) of one pixel, written once: k_disparity_pick feeds it E_k, k_sgm_pick (lft_sgm.cuh) S_k, in k order.
 // It keeps the best value and its k, the value before it, the value after it (caught by the pending flag), the last value and the

@@ -304,46 +304,78 @@ static size_t disparity_floats(int B, int D, int H, int W, int C, int flags, siz
     *vol_floats = (size_t)B * D * H * W;
     return *vol_floats * (size_t)(flags & LFT_DISPARITY_AIF ? 1 + C : 1);
 }
-int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
-    if (!out_bytes) return fail(LFT_ERR_ARG, "lft_disparity: out_bytes is null");
-    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "lft_disparity: %d channels (1 .. 4)", C);
-    if (D < 1) return fail(LFT_ERR_ARG, "lft_disparity: %d slopes", D);
-    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "lft_disparity: unknown flags 0x%x", flags);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "lft_disparity: negative size in B = %d, views of %d x %d", B, H, W);
+// The body of the two scratch-size queries.  `who` starts every message; with_choice: the bytes of the choice volume [B, D, H, W]
+// behind the floats, rounded up to whole dwords.
+static int disparity_scratch_bytes(const char* who, bool with_choice, int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
+    if (!out_bytes) return fail(LFT_ERR_ARG, "%s: out_bytes is null", who);
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "%s: %d channels (1 .. 4)", who, C);
+    if (D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, D);
+    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, views of %d x %d", who, B, H, W);
     size_t vol = 0;
     const size_t n = disparity_floats(B, D, H, W, C, flags, &vol);
-    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
-    *out_bytes = n * sizeof(float);
+    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "%s: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", who, B, D, H, W);
+    *out_bytes = n * sizeof(float) + (with_choice && n ? (vol + 3) / 4 * 4 : 0);
     return 0;
 }
-int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
-                  const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
-                  float* cost, void* aif, int aif_class, void* stream) {
+int lft_disparity_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
+    return disparity_scratch_bytes("lft_disparity", false, B, D, H, W, C, flags, out_bytes);
+}
+// k_occ_gather over the B * H * W pixels, one per lane of `blocks` workgroups (lft_occlusion.cuh)
+static int enqueue_occ_gather(const int* index, const unsigned char* choice, unsigned char* subset, int B, int D, int H, int W, long long blocks, hipStream_t st) {
+    const OccGatherArgs g{index, choice, subset, D, (size_t)H * W, (size_t)B * H * W};
+    k_occ_gather<<<dim3((unsigned)blocks), 256, 0, st>>>(g);
+    LFT_LAUNCH_OK("k_occ_gather");
+    return 0;
+}
+// What lft_disparity_occ adds to lft_disparity's arguments (lft_occlusion.cuh; declared in include/lft_hip_occlusion.h).
+struct OccAdds { const float* subsets; int P; float beta; unsigned char* subset; unsigned char* choice; };
+// The body of lft_disparity (occ == nullptr) and lft_disparity_occ: the checks in the order each has always made them, the sweep
+// of its kind, k_disparity_pick, and k_occ_gather when `subset` is asked for.  `who` starts every message.
+static int sweep_and_pick(const char* who, const OccAdds* occ, const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides,
+                          const void* table, const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence,
+                          int* index, float* cost, void* aif, int aif_class, void* stream) {
     WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
-    if (int rc = windowed_lf_ok("lft_disparity", l, aif_class, "all-in-focus", radius, !slopes || !scratch || !disparity || !confidence || !index, "sweeps"))
-        return rc;
+    const bool own_null = (occ && !occ->subsets) || !slopes || !scratch || !disparity || !confidence || !index;
+    if (int rc = windowed_lf_ok(who, l, aif_class, "all-in-focus", radius, own_null, "sweeps")) return rc;
+    if (occ && (occ->P < 1 || occ->P > LFT_OCC_MAX_SUBSETS)) return fail(LFT_ERR_ARG, "%s: %d subsets outside 1 .. %d", who, occ->P, LFT_OCC_MAX_SUBSETS);
+    if (occ && (!std::isfinite(occ->beta) || occ->beta < 1.0f)) return fail(LFT_ERR_ARG, "%s: margin %g must be finite and >= 1", who, occ->beta);
     if (!l.tiles) return 0;                                         // empty maps
     const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
-    if (ptiles * B > 0x7fffffffLL) return too_many_blocks("lft_disparity", l, "sweeps");
+    const long long gblocks = ((long long)B * H * W + 255) / 256;   // of k_occ_gather
+    if (ptiles * B > 0x7fffffffLL || (occ && gblocks > 0x7fffffffLL)) return too_many_blocks(who, l, "sweeps");
     size_t vol = 0;
-    if (!disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol))
-        return fail(LFT_ERR_SHAPE, "lft_disparity: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", B, D, H, W);
-    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "lft_disparity: scratch must be 4-byte aligned");
+    const size_t floats = disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol);
+    if (!floats) return fail(LFT_ERR_SHAPE, "%s: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", who, B, D, H, W);
+    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SweepArgs s{};
-    fill_windowed(s, l);
-    s.vol = static_cast<float*>(scratch); s.stack = aif ? s.vol + vol : nullptr;
+    SweepOccArgs s{};
+    fill_windowed(s.s, l);
+    s.s.vol = static_cast<float*>(scratch); s.s.stack = aif ? s.s.vol + vol : nullptr;
     const dim3 grid((unsigned)(l.tiles * D * B));
-    by_lf_class<false>(lf_class, [&](auto t) { sweep_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
-    LFT_LAUNCH_OK("k_sweep_cost");
+    if (occ) {
+        s.subsets = occ->subsets; s.P = occ->P; s.beta = occ->beta;
+        s.choice = occ->choice ? occ->choice : occ->subset ? reinterpret_cast<uint8_t*>(s.s.vol + floats) : nullptr;
+        by_lf_class<false>(lf_class, [&](auto t) { sweep_occ_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
+        LFT_LAUNCH_OK("k_sweep_cost_occ");
+    } else {
+        by_lf_class<false>(lf_class, [&](auto t) { sweep_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s.s); return 0; });
+        LFT_LAUNCH_OK("k_sweep_cost");
+    }
     PickArgs p{};
-    p.vol = s.vol; p.stack = s.stack; p.slopes = slopes;
+    p.vol = s.s.vol; p.stack = s.s.stack; p.slopes = slopes;
     p.H = H; p.W = W; p.D = D; p.C = C; p.r = radius; p.tiles_x = (int)ptiles_x; p.tiles = (int)ptiles;
     p.disparity = disparity; p.confidence = confidence; p.index = index; p.cost = cost; p.aif = aif;
     p.aif_f32 = aif_class == LFT_LF_FLOAT32;
     k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
     LFT_LAUNCH_OK("k_disparity_pick");
-    return 0;
+    return occ && occ->subset ? enqueue_occ_gather(index, s.choice, occ->subset, B, D, H, W, gblocks, st) : 0;
+}
+int lft_disparity(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
+                  const float* slopes, int D, int taps, int radius, void* scratch, float* disparity, float* confidence, int* index,
+                  float* cost, void* aif, int aif_class, void* stream) {
+    return sweep_and_pick("lft_disparity", nullptr, lf, lf_class, B, A, H, W, C, strides, table, slopes, D, taps, radius, scratch, disparity, confidence, index,
+                          cost, aif, aif_class, stream);
 }
 
 // ---- view synthesis (lft_views.cuh; declared in include/lft_hip_views.h) ----
@@ -567,60 +599,16 @@ int lft_sgm(const float* cost, int B, int D, int H, int W, int C, const float* s
 
 // ---- the sweep's occlusion-aware cost (lft_occlusion.cuh; declared in include/lft_hip_occlusion.h) ----
 static_assert(kOccMaxP == LFT_OCC_MAX_SUBSETS, "the header states how many subsets the kernel keeps accumulators for");
-// the bytes of the choice volume [B, D, H, W] behind lft_disparity's floats, rounded up to whole dwords
 int lft_disparity_occ_scratch_bytes(int B, int D, int H, int W, int C, int flags, size_t* out_bytes) {
-    const char* who = "lft_disparity_occ";
-    if (!out_bytes) return fail(LFT_ERR_ARG, "%s: out_bytes is null", who);
-    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "%s: %d channels (1 .. 4)", who, C);
-    if (D < 1) return fail(LFT_ERR_ARG, "%s: %d slopes", who, D);
-    if (flags & ~LFT_DISPARITY_AIF) return fail(LFT_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
-    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, views of %d x %d", who, B, H, W);
-    size_t vol = 0;
-    const size_t n = disparity_floats(B, D, H, W, C, flags, &vol);
-    if (!n && B && H && W) return fail(LFT_ERR_SHAPE, "%s: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", who, B, D, H, W);
-    *out_bytes = n * sizeof(float) + (n ? (vol + 3) / 4 * 4 : 0);
-    return 0;
+    return disparity_scratch_bytes("lft_disparity_occ", true, B, D, H, W, C, flags, out_bytes);
 }
 int lft_disparity_occ(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table,
                       const float* subsets, int P, float beta, const float* slopes, int D, int taps, int radius, void* scratch,
                       float* disparity, float* confidence, int* index, unsigned char* subset, unsigned char* choice, float* cost,
                       void* aif, int aif_class, void* stream) {
-    const char* who = "lft_disparity_occ";
-    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
-    if (int rc = windowed_lf_ok(who, l, aif_class, "all-in-focus", radius, !subsets || !slopes || !scratch || !disparity || !confidence || !index, "sweeps"))
-        return rc;
-    if (P < 1 || P > LFT_OCC_MAX_SUBSETS) return fail(LFT_ERR_ARG, "%s: %d subsets outside 1 .. %d", who, P, LFT_OCC_MAX_SUBSETS);
-    if (!std::isfinite(beta) || beta < 1.0f) return fail(LFT_ERR_ARG, "%s: margin %g must be finite and >= 1", who, beta);
-    if (!l.tiles) return 0;                                         // empty maps
-    const long long ptiles_x = ((long long)W + kDpTile - 1) / kDpTile, ptiles = ptiles_x * (((long long)H + kDpTile - 1) / kDpTile);
-    const long long gblocks = ((long long)B * H * W + 255) / 256;
-    if (ptiles * B > 0x7fffffffLL || gblocks > 0x7fffffffLL) return too_many_blocks(who, l, "sweeps");
-    size_t vol = 0;
-    const size_t floats = disparity_floats(B, D, H, W, C, aif ? LFT_DISPARITY_AIF : 0, &vol);
-    if (!floats) return fail(LFT_ERR_SHAPE, "%s: the cost volume of %d x %d x %d x %d needs more than 2^40 bytes", who, B, D, H, W);
-    if ((uintptr_t)scratch & 3) return fail(LFT_ERR_ARG, "%s: scratch must be 4-byte aligned", who);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    SweepOccArgs s{};
-    fill_windowed(s.s, l);
-    s.s.vol = static_cast<float*>(scratch); s.s.stack = aif ? s.s.vol + vol : nullptr;
-    s.subsets = subsets; s.P = P; s.beta = beta;
-    s.choice = choice ? choice : subset ? reinterpret_cast<uint8_t*>(s.s.vol + floats) : nullptr;
-    const dim3 grid((unsigned)(l.tiles * D * B));
-    by_lf_class<false>(lf_class, [&](auto t) { sweep_occ_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, st>>>(s); return 0; });
-    LFT_LAUNCH_OK("k_sweep_cost_occ");
-    PickArgs p{};
-    p.vol = s.s.vol; p.stack = s.s.stack; p.slopes = slopes;
-    p.H = H; p.W = W; p.D = D; p.C = C; p.r = radius; p.tiles_x = (int)ptiles_x; p.tiles = (int)ptiles;
-    p.disparity = disparity; p.confidence = confidence; p.index = index; p.cost = cost; p.aif = aif;
-    p.aif_f32 = aif_class == LFT_LF_FLOAT32;
-    k_disparity_pick<<<dim3((unsigned)(ptiles * B)), 256, 0, st>>>(p);
-    LFT_LAUNCH_OK("k_disparity_pick");
-    if (subset) {
-        const OccGatherArgs g{index, s.choice, subset, D, (size_t)H * W, (size_t)B * H * W};
-        k_occ_gather<<<dim3((unsigned)gblocks), 256, 0, st>>>(g);
-        LFT_LAUNCH_OK("k_occ_gather");
-    }
-    return 0;
+    const OccAdds occ{subsets, P, beta, subset, choice};
+    return sweep_and_pick("lft_disparity_occ", &occ, lf, lf_class, B, A, H, W, C, strides, table, slopes, D, taps, radius, scratch, disparity, confidence, index,
+                          cost, aif, aif_class, stream);
 }
 int lft_occ_gather(const int* index, const unsigned char* choice, int B, int D, int H, int W, unsigned char* subset, void* stream) {
     const char* who = "lft_occ_gather";
@@ -630,10 +618,7 @@ int lft_occ_gather(const int* index, const unsigned char* choice, int B, int D, 
     const double blocks = std::ceil((double)B * H * W / 256.0);
     if (blocks > 2147483647.0) return fail(LFT_ERR_SHAPE, "%s: %d maps of %d x %d need more than 2^31 blocks", who, B, H, W);
     if (!index || !choice || !subset) return fail(LFT_ERR_ARG, "%s: null pointer", who);
-    const OccGatherArgs g{index, choice, subset, D, (size_t)H * W, (size_t)B * H * W};
-    k_occ_gather<<<dim3((unsigned)blocks), 256, 0, static_cast<hipStream_t>(stream)>>>(g);
-    LFT_LAUNCH_OK("k_occ_gather");
-    return 0;
+    return enqueue_occ_gather(index, choice, subset, B, D, H, W, (long long)blocks, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

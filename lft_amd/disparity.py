@@ -187,6 +187,12 @@ def check_slopes(slopes) -> Tuple[float, ...]:
     return tuple(float(s) for s in sl)
 
 
+def _finite_number(name: str, v, lo: int) -> None:
+    """The refusal of a host float that is no finite number in [lo, the largest float32]: margin, p1, p2, edge_gain."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo <= v <= float(np.finfo(np.float32).max):
+        raise LftError(f"{name} must be a finite number >= {lo} (as float32), got {v!r}")
+
+
 SUBSET_MODES = ("halves", "quadrants")
 _OCC_KEYS = ("subsets", "margin", "min_views")
 
@@ -201,8 +207,7 @@ def _occlusion_arguments(occlusion) -> Tuple[object, float, int]:
     subsets, margin, min_views = occlusion.get("subsets", "halves"), occlusion.get("margin", 2.0), occlusion.get("min_views", 2)
     if isinstance(subsets, str) and subsets not in SUBSET_MODES:
         raise LftError(f"subsets must be halves, quadrants or a boolean array [P, A, A], got {subsets!r}")
-    if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) or not 1 <= margin <= float(np.finfo(np.float32).max):
-        raise LftError(f"margin must be a finite number >= 1 (as float32), got {margin!r}")
+    _finite_number("margin", margin, 1)
     if isinstance(min_views, bool) or not isinstance(min_views, (int, np.integer)) or min_views < 2:
         raise LftError(f"min_views must be an integer >= 2, got {min_views!r}")
     return subsets, float(margin), int(min_views)
@@ -254,39 +259,50 @@ def _sweep_arguments(radius, interp, slopes) -> Tuple[float, ...]:
     return check_slopes(slopes)
 
 
-def _disparity_occ(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion,
-                   choice_volume: bool = False) -> Tuple[OcclusionDisparityResult, Optional[torch.Tensor]]:
-    """``disparity`` with `occlusion`: one call of lft_disparity_occ.  Also returns the choice volume, uint8 [D, H, W] ([B, D, H, W]
-    for a batch), when asked for."""
-    sl, how = (), ()
+def _new_maps(B: int, H: int, W: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """disparity, confidence and index [B, H, W], for an entry point to fill."""
+    return tuple(torch.empty(B, H, W, dtype=t, device=device) for t in (torch.float32, torch.float32, torch.int32))
 
-    def sweep_arguments():
+
+def _result(kind: str, maps, aif, cost, *occ):
+    """The maps, image and volume [B, ...] of an entry point in the layout of the caller's input (``refocus._as_given``), as a
+    DisparityResult, or with occ = (subset, subsets_kept) as an OcclusionDisparityResult."""
+    fields = [_as_given(kind, t) for t in maps] + [_as_given(kind, aif, image=True), _as_given(kind, cost)]
+    return OcclusionDisparityResult(*fields, _as_given(kind, occ[0]), occ[1]) if occ else DisparityResult(*fields)
+
+
+def _sweep(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion=None, choice_volume: bool = False):
+    """One plane sweep and its selection: one call of lft_disparity, or with `occlusion` of lft_disparity_occ.  Returns (the
+    result, the choice volume uint8 [D, H, W] ([B, D, H, W] for a batch) when asked for, else None)."""
+    sl, how = (), None
+
+    def sweep_arguments():                  # radius, interp, slopes and occlusion are refused before a tensor off the GPU
         nonlocal sl, how
         sl = _sweep_arguments(radius, interp, slopes)
-        how = _occlusion_arguments(occlusion)
+        how = None if occlusion is None else _occlusion_arguments(occlusion)
 
     B, A, H, W, C, strides, kind = _field(lf, angRes, "aif_dtype", aif_dtype, before_device=sweep_arguments)
     aif_dtype = lf.dtype if aif_dtype is None else aif_dtype
-    subsets, margin, min_views = how
-    dev = lf.device
+    dev, D = lf.device, len(sl)
     table = _device_table(A, sl, aperture, interp, dev, centre)
-    btable, kept = _device_subsets(A, aperture, centre, subsets, min_views, dev)
-    D = len(sl)
-    disp = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-    conf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-    index = torch.empty(B, H, W, dtype=torch.int32, device=dev)
-    subset = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
-    choice = torch.empty(B, D, H, W, dtype=torch.uint8, device=dev) if choice_volume else None
+    maps = _new_maps(B, H, W, dev)
     cost = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if cost_volume else None
     aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if all_in_focus else None
+    name, with_subsets, with_subset, occ, choice = "lft_disparity", (), (), (), None
+    if how is not None:
+        subsets, margin, min_views = how
+        btable, kept = _device_subsets(A, aperture, centre, subsets, min_views, dev)
+        subset = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+        choice = torch.empty(B, D, H, W, dtype=torch.uint8, device=dev) if choice_volume else None
+        # lft_disparity_occ takes lft_disparity's arguments with (subsets, P, beta) after the table and (subset, choice) after the index
+        name, with_subsets = "lft_disparity_occ", (btable.data_ptr(), len(kept), margin)
+        with_subset, occ = (subset.data_ptr(), choice.data_ptr() if choice_volume else None), (subset, kept)
     if B and H and W:
-        scratch = _device_scratch(_scratch, "lft_disparity_occ_scratch_bytes", (B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0), dev)
-        _lib.enqueue("lft_disparity_occ", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), btable.data_ptr(),
-                     len(kept), margin, _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius), scratch.data_ptr(), disp.data_ptr(),
-                     conf.data_ptr(), index.data_ptr(), subset.data_ptr(), choice.data_ptr() if choice_volume else None,
+        scratch = _device_scratch(_scratch, name + "_scratch_bytes", (B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0), dev)
+        _lib.enqueue(name, dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), *with_subsets,
+                     _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius), scratch.data_ptr(), *(t.data_ptr() for t in maps), *with_subset,
                      cost.data_ptr() if cost_volume else None, aif.data_ptr() if all_in_focus else None, _CLASS[aif_dtype])
-    return OcclusionDisparityResult(*(_as_given(kind, t) for t in (disp, conf, index)), _as_given(kind, aif, image=True), _as_given(kind, cost),
-                                    _as_given(kind, subset), kept), _as_given(kind, choice)
+    return _result(kind, maps, aif, cost, *occ), _as_given(kind, choice)
 
 
 def occlusion_volume(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
@@ -294,8 +310,7 @@ def occlusion_volume(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional
     """The whole `choice` volume of ``disparity(..., occlusion=occlusion)``, uint8 [D, H, W] ([B, D, H, W] for a batch): per pixel
     and slope 0 where the whole aperture set the raw cost V, else the kept subset (1-based) that did.  It does not depend on the
     aggregation radius."""
-    _, choice = _disparity_occ(lf, slopes, angRes, aperture, interp, 0, False, False, None, centre, occlusion, choice_volume=True)
-    return choice
+    return _sweep(lf, slopes, angRes, aperture, interp, 0, False, False, None, centre, occlusion, choice_volume=True)[1]
 
 
 def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
@@ -323,30 +338,7 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     SGM's index.  Without it nothing changes (the five-field result answers None for both names): the same launches, the same bits."""
     if regularize is not None:
         return _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, regularize, occlusion)
-    if occlusion is not None:
-        return _disparity_occ(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion)[0]
-    sl = ()
-
-    def sweep_arguments():                  # radius, interp and slopes are refused before a tensor off the GPU
-        nonlocal sl
-        sl = _sweep_arguments(radius, interp, slopes)
-
-    B, A, H, W, C, strides, kind = _field(lf, angRes, "aif_dtype", aif_dtype, before_device=sweep_arguments)
-    aif_dtype = lf.dtype if aif_dtype is None else aif_dtype
-    table = _device_table(A, sl, aperture, interp, lf.device, centre)
-    D = len(sl)
-    dev = lf.device
-    disp = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-    conf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-    index = torch.empty(B, H, W, dtype=torch.int32, device=dev)
-    cost = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if cost_volume else None
-    aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if all_in_focus else None
-    if B and H and W:
-        scratch = _device_scratch(_scratch, "lft_disparity_scratch_bytes", (B, D, H, W, C, _lib.DISPARITY_AIF if all_in_focus else 0), dev)
-        _lib.enqueue("lft_disparity", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(),
-                     _device_slopes(sl, dev).data_ptr(), D, TAPS[interp], int(radius), scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(),
-                     index.data_ptr(), cost.data_ptr() if cost_volume else None, aif.data_ptr() if all_in_focus else None, _CLASS[aif_dtype])
-    return DisparityResult(*(_as_given(kind, t) for t in (disp, conf, index)), _as_given(kind, aif, image=True), _as_given(kind, cost))
+    return _sweep(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion)[0]
 
 
 def penalties_from_cost(cost: torch.Tensor, p1_rel: float = 0.1, p2_rel: float = 1.0) -> Tuple[float, float]:
@@ -366,8 +358,7 @@ def _sgm_arguments(D: Optional[int], slopes, p1, p2, paths, edge_gain, has_guide
     if isinstance(paths, bool) or paths not in (4, 8):
         raise LftError(f"paths must be 4 or 8, got {paths!r}")
     for name, v in (("p1", p1), ("p2", p2), ("edge_gain", edge_gain)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v <= float(np.finfo(np.float32).max):
-            raise LftError(f"{name} must be a finite number >= 0 (as float32), got {v!r}")
+        _finite_number(name, v, 0)
     if np.float32(p2) < np.float32(p1):
         raise LftError(f"p2 must not be below p1, got p1 = {p1!r}, p2 = {p2!r}")
     if np.float32(edge_gain) > 0 and not has_guide:
@@ -420,9 +411,7 @@ def regularize(cost: torch.Tensor, slopes: Sequence[float], p1: float, p2: float
     channels = stack is not None and stack.dim() == cost.dim() + 1
     C = int(stack.shape[-1]) if channels else 1
     aif_dtype = torch.float32 if aif_dtype is None else aif_dtype
-    disp = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-    conf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-    index = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    maps = _new_maps(B, H, W, dev)
     S = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if aggregated else None
     aif = torch.empty(B, H, W, C, dtype=aif_dtype, device=dev) if stack is not None else None
     if B and H and W:
@@ -430,10 +419,9 @@ def regularize(cost: torch.Tensor, slopes: Sequence[float], p1: float, p2: float
         scratch = _device_scratch(_scratch, "lft_sgm_scratch_bytes", (B, D, H, W, int(paths)), dev)
         _lib.enqueue("lft_sgm", dev, cost.data_ptr(), B, D, H, W, C, _device_slopes(sl, dev).data_ptr(), int(paths), float(p1), float(p2),
                      None if guide is None else guide.data_ptr(), float(edge_gain), None if stack is None else stack.data_ptr(),
-                     scratch.data_ptr(), disp.data_ptr(), conf.data_ptr(), index.data_ptr(), None if S is None else S.data_ptr(),
+                     scratch.data_ptr(), *(t.data_ptr() for t in maps), None if S is None else S.data_ptr(),
                      None if aif is None else aif.data_ptr(), _CLASS[aif_dtype])
-    kind = ("batch" if batch else "views") + ("5" if channels else "4")
-    return DisparityResult(*(_as_given(kind, t) for t in (disp, conf, index)), _as_given(kind, aif, image=True), _as_given(kind, S))
+    return _result(("batch" if batch else "views") + ("5" if channels else "4"), maps, aif, S)
 
 
 _SGM_KEYS = ("p1", "p2", "paths", "guide", "edge_gain")
@@ -445,14 +433,9 @@ def _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_f
     from . import refocus as Rf
     if not isinstance(how, dict) or set(how) - set(_SGM_KEYS) or not {"p1", "p2"} <= set(how):
         raise LftError(f"regularize must be None or a dict with p1, p2 and any of paths, guide, edge_gain, got {how!r}")
-    if aif_dtype is not None and aif_dtype not in _CLASS:
-        raise LftError(f"aif_dtype must be torch.uint8 or torch.float32, got {aif_dtype}")
     _sgm_arguments(None, slopes, how["p1"], how["p2"], how.get("paths", 8), how.get("edge_gain", 0.0), how.get("guide") is not None, None, False)
-    if occlusion is None:
-        swept, choice = disparity(lf, slopes, angRes, aperture, interp, radius, cost_volume=True, centre=centre), None
-    else:
-        _occlusion_arguments(occlusion)
-        swept, choice = _disparity_occ(lf, slopes, angRes, aperture, interp, radius, False, True, None, centre, occlusion, choice_volume=True)
+    # aif_dtype goes along for its refusal only: the sweep gathers no image here
+    swept, choice = _sweep(lf, slopes, angRes, aperture, interp, radius, False, True, aif_dtype, centre, occlusion, choice_volume=occlusion is not None)
     stack = Rf.refocus(lf, slopes, angRes, aperture, interp, out_dtype=torch.float32, centre=centre) if all_in_focus else None
     res = regularize(swept.cost, slopes, stack=stack, aif_dtype=(aif_dtype or lf.dtype) if all_in_focus else None, aggregated=cost_volume, **how)
     if choice is None:

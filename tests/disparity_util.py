@@ -9,27 +9,26 @@ import numpy as np
 import refocus_util as RU
 
 
-def moments_np(views, table, taps):
-    """views [A, A, H, W, C] -> fp64 (m, q), each [D, H, W, C]: the aperture-weighted first and second moments of the samples."""
+def samples_np(views, table, taps):
+    """views [A, A, H, W, C] -> (d, n, a, s) per slope d and view n = u * A + v that is not skipped, in that order: the aperture
+    weight a and the fp64 samples s [H, W, C], rows first, clamped taps, each sum in tap order."""
     A, _, H, W, C = views.shape
     x = views.astype(np.float64) / 255.0 if views.dtype == np.uint8 else views.astype(np.float64)
-    D = table.shape[0]
-    m, q = np.zeros((D, H, W, C)), np.zeros((D, H, W, C))
     ys, xs = np.arange(H), np.arange(W)
-    for d in range(D):
-        for u in range(A):
-            for v in range(A):
-                r = table[d, u * A + v]
-                if r["skip"]:
-                    continue
-                rows = np.zeros((H, W, C))
-                for k in range(taps):
-                    rows += float(r["wy"][k]) * x[u, v][np.clip(ys + int(r["oy"]) + k, 0, H - 1)]
-                s = np.zeros((H, W, C))
-                for k in range(taps):
-                    s += float(r["wx"][k]) * rows[:, np.clip(xs + int(r["ox"]) + k, 0, W - 1)]
-                m[d] += float(r["a"]) * s
-                q[d] += float(r["a"]) * s * s
+    for d, n in np.ndindex(table.shape):
+        r = table[d, n]
+        if not r["skip"]:
+            rows = sum(float(r["wy"][k]) * x[n // A, n % A][np.clip(ys + int(r["oy"]) + k, 0, H - 1)] for k in range(taps))
+            s = sum(float(r["wx"][k]) * rows[:, np.clip(xs + int(r["ox"]) + k, 0, W - 1)] for k in range(taps))
+            yield d, n, float(r["a"]), s
+
+
+def moments_np(views, table, taps):
+    """views [A, A, H, W, C] -> fp64 (m, q), each [D, H, W, C]: the aperture-weighted first and second moments of the samples."""
+    m, q = np.zeros((2, table.shape[0]) + views.shape[2:])
+    for d, _, a, s in samples_np(views, table, taps):
+        m[d] += a * s
+        q[d] += a * s * s
     return m, q
 
 

@@ -52,31 +52,19 @@ def subset_table_np(A, a, centre, subsets, min_views=2):
 def occ_cost_np(views, table, taps, btable, beta):
     """views [A, A, H, W, C], table [D, A*A] of RECORD, btable fp32 [P', A*A], beta -> fp64 dict: V_full [D, H, W], Vp [P', D, H, W],
     U, V, choice (uint8 [D, H, W]) and m [D, H, W, C].  A view is a member of p iff btable[p, view] != 0 (and it is not skipped)."""
-    A, _, H, W, C = views.shape
-    x = views.astype(np.float64) / 255.0 if views.dtype == np.uint8 else views.astype(np.float64)
-    D, P = table.shape[0], btable.shape[0]
+    shape = (table.shape[0],) + views.shape[2:]
+    P = btable.shape[0]
     b = btable.astype(np.float64)
     beta = float(np.float32(beta))
-    m, q = np.zeros((D, H, W, C)), np.zeros((D, H, W, C))
-    mp, qp = np.zeros((P, D, H, W, C)), np.zeros((P, D, H, W, C))
-    ys, xs = np.arange(H), np.arange(W)
-    for d in range(D):
-        for n in range(A * A):
-            r = table[d, n]
-            if r["skip"]:
-                continue
-            rows = np.zeros((H, W, C))
-            for k in range(taps):
-                rows += float(r["wy"][k]) * x[n // A, n % A][np.clip(ys + int(r["oy"]) + k, 0, H - 1)]
-            s = np.zeros((H, W, C))
-            for k in range(taps):
-                s += float(r["wx"][k]) * rows[:, np.clip(xs + int(r["ox"]) + k, 0, W - 1)]
-            m[d] += float(r["a"]) * s
-            q[d] += float(r["a"]) * s * s
-            for p in range(P):
-                if b[p, n] != 0:
-                    mp[p, d] += b[p, n] * s
-                    qp[p, d] += b[p, n] * s * s
+    m, q = np.zeros(shape), np.zeros(shape)
+    mp, qp = np.zeros((P,) + shape), np.zeros((P,) + shape)
+    for d, n, a, s in DU.samples_np(views, table, taps):
+        m[d] += a * s
+        q[d] += a * s * s
+        for p in range(P):
+            if b[p, n] != 0:
+                mp[p, d] += b[p, n] * s
+                qp[p, d] += b[p, n] * s * s
     V_full = np.maximum(q - m * m, 0.0).sum(-1)
     Vp = np.maximum(qp - mp * mp, 0.0).sum(-1)
     t = Vp.min(0)

@@ -179,9 +179,13 @@ def test_header_declares_and_library_exports_the_entry_points():
                       "through the existing k_disparity_pick unchanged", "0 where all views agree",
                       "No result may depend on the tile, the launch shape or the arrival order"):
             assert words in flat, words
-    # the plain sweep's kernels are not touched by the new file: it holds a copy
+    # the sweep is written once, in the plain sweep's file: both kernels are wrappers of that body, and the new file repeats none
+    # of the window pipeline
     plain_src = open(os.path.join(_lib.CSRC, "lft_disparity.cuh")).read()
-    assert "occ" not in plain_src.replace("occupancy", "") and "k_sweep_cost_occ" in kernels and "k_occ_gather" in kernels
+    assert plain_src.count("void sweep_cost(") == 1 and "void sweep_cost(" not in kernels
+    assert "void k_sweep_cost(SweepArgs a) { sweep_cost<T, C, TAPS, false>(" in plain_src
+    assert "void k_sweep_cost_occ(SweepOccArgs oa) { sweep_cost<T, C, TAPS, true>(" in kernels and "k_occ_gather" in kernels
+    assert not any(step in kernels for step in ("next_active", "fetch(", "commit(", "__fmaf_rn"))
 
 
 def test_scratch_query():

@@ -3,7 +3,7 @@
 takes the kernels' general paths, and one small shape per angular kernel variant (k_ang for up to 25 views, every k_ang_multi
 form from 36 to 121 views) under each library given, each in its own process; prints whether the outputs are bit-identical.
   tools/out_bits.py ab_so/liblft_base0.so lft_amd/liblft_hip.so
---lightfield: the light-field analysis instead -- refocus, disparity, regularize, render with and without the visibility test and
+--lightfield: the light-field analysis instead -- refocus, disparity with and without the occlusion-aware cost, regularize, render with and without the visibility test and
 warp_disparity over shapes small enough that every tile is ragged, one hash per output of every case.
   tools/out_bits.py --lightfield ab_so/liblft_base0.so lft_amd/liblft_hip.so
 --pipeline: the data and objective kernels instead -- lf_prepare, luma, merge, view_metrics, the three losses, Adam, the guarded step
@@ -46,8 +46,10 @@ def child_lightfield():
     def show(case, result):
         named = zip(getattr(result, "_fields", ("maps", "holes")), result) if isinstance(result, tuple) else [("out", result)]
         for name, t in named:
-            if t is not None:
+            if isinstance(t, torch.Tensor):
                 print(f"{case} {name}", hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16], flush=True)
+            elif t is not None:
+                print(f"{case} {name}", t, flush=True)                  # subsets_kept
 
     def field(rng, A, H, W, C, dtype):
         """(light field, angRes argument, leading shape of its maps): C = 1 a batch [2, 1, A*H, A*W], else views [A, A, H, W, C]."""
@@ -67,6 +69,9 @@ def child_lightfield():
     targets = [(0.25, 1.5), (1.0, 0.4), (1.75, 1.9)]
     rng = np.random.default_rng(7)
     A, H, W = 3, 40, 37
+    masks = np.zeros((3, A, A), bool)                                   # one view (dropped: fewer than min_views), a row, every view
+    masks[0, 0, 0], masks[1, 1, :], masks[2] = True, True, True
+    occlusions = (("halves", "halves"), ("quadrants", dict(subsets="quadrants", margin=1.5)), ("array", dict(subsets=masks, margin=1.25)))
     for C, din, dout in itertools.product((1, 3), (U8, F32), (U8, F32)):
         lf, ang, lead = field(rng, A, H, W, C, din)
         tag = f"A{A} {H}x{W} C{C} {str(din)[6:]}->{str(dout)[6:]}"
@@ -75,6 +80,14 @@ def child_lightfield():
             for radius in (0, 2):
                 swept = Dm.disparity(lf, slopes, ang, interp=interp, radius=radius, all_in_focus=True, cost_volume=True, aif_dtype=dout)
                 show(f"{tag} disparity {interp} r{radius}", swept)
+            for name, occ in occlusions:
+                show(f"{tag} disparity {interp} occlusion {name}",
+                     Dm.disparity(lf, slopes, ang, interp=interp, all_in_focus=True, cost_volume=True, aif_dtype=dout, occlusion=occ))
+            show(f"{tag} disparity {interp} occlusion halves maps only", Dm.disparity(lf, slopes, ang, interp=interp, occlusion="halves"))
+            show(f"{tag} occlusion_volume {interp}", Dm.occlusion_volume(lf, slopes, ang, interp=interp, occlusion=occlusions[-1][1]))
+            show(f"{tag} disparity {interp} occlusion quadrants regularize",
+                 Dm.disparity(lf, slopes, ang, interp=interp, all_in_focus=True, cost_volume=True, aif_dtype=dout, occlusion="quadrants",
+                              regularize=dict(p1=0.002, p2=0.03)))
         stack = Rf.refocus(lf, slopes, ang, interp="linear", out_dtype=F32)
         guide = depth(rng, lead, H, W, 1.0).nan_to_num(0.0, 0.0, 0.0)
         p1, p2 = 0.002, 0.03
