@@ -101,6 +101,20 @@ __global__ void k_pe_tables(float* __restrict__ ang_pe, T* __restrict__ spa_img,
 // writes channels-last tokens [B,V,h,w,64].  One thread = 8 channels of one token.
 // ------------------------------------------------------------------------------------------
 constexpr int kConv0Tok = 128;          // tokens per workgroup
+// View (a1, a2) of image b inside the LR mosaic [B,1,A*h,A*w]; row stride A*w.
+LFT_DEV const float* lr_view(const float* __restrict__ lr, int im, int A, int h, int w) {
+    const int V = A * A, b = im / V, v = im - b * V, a1 = v / A, a2 = v - a1 * A;
+    return lr + (size_t)b * (A * h) * (A * w) + (size_t)(a1 * h) * (A * w) + a2 * w;
+}
+// The nine taps of one token, branch-free: all are loaded from clamped (readable) positions and masked at use -- a conditional
+// load is a masked branch per tap, nine dependent round trips instead of nine loads in flight.
+LFT_DEV void conv0_taps_load(const float* __restrict__ img, int ldi, int y, int x, int h, int w, float (&val)[9]) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {                                           // clamped (readable) positions; masked at use
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        val[t] = img[min(max(yy, 0), h - 1) * ldi + min(max(xx, 0), w - 1)];
+    }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void k_conv0(const float* __restrict__ lr, const float* __restrict__ w0,
                                                T* __restrict__ out, int B, int A, int h, int w) {
@@ -109,10 +123,9 @@ __global__ __launch_bounds__(256) void k_conv0(const float* __restrict__ lr, con
     // bank conflicts).  9 taps padded to 12 floats per channel = three 16-byte reads; channel groups 100 floats apart put the
     // eight distinct addresses of a 16-lane group on disjoint banks.
     __shared__ __attribute__((aligned(16))) float wl[8 * 100];
-    const int hw = h * w, im = blockIdx.y, V = A * A;
+    const int hw = h * w, im = blockIdx.y;
     const int cg = threadIdx.x & 7;
-    const int b = im / V, v = im - b * V, a1 = v / A, a2 = v - a1 * A;
-    const float* img = lr + (size_t)b * (A * h) * (A * w) + (size_t)(a1 * h) * (A * w) + a2 * w;
+    const float* img = lr_view(lr, im, A, h, w);
     // kConv0Tok tokens per workgroup, 32 per pass: the weight staging and the barrier above are paid once per 128 tokens
     // (3 200 workgroups of 32 tokens spent most of their time in that prologue).
     // The kernel is a latency chain, not a throughput problem (13 MB out, 60 MFLOP): round 4 issues the taps of ALL passes before
@@ -123,13 +136,7 @@ __global__ __launch_bounds__(256) void k_conv0(const float* __restrict__ lr, con
     for (int pass = 0; pass < NP; ++pass) {
         const int p = min(blockIdx.x * kConv0Tok + pass * 32 + (int)(threadIdx.x >> 3), hw - 1);
         const int y = p / w, x = p - y * w;
-        // branch-free: all nine taps are loaded from clamped (readable) positions, then selected -- a conditional load is a
-        // masked branch per tap, nine dependent round trips instead of nine loads in flight.
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-            val[pass][t] = img[min(max(yy, 0), h - 1) * (A * w) + min(max(xx, 0), w - 1)];
-        }
+        conv0_taps_load(img, A * w, y, x, h, w, val[pass]);
     }
     {   // all three loads of a thread in flight before the first LDS write (as a load / wait / write loop: three serialised round trips)
         float wv[3];
@@ -257,6 +264,32 @@ LFT_DEV void conv3x3_tile(const char* lds_in, const char* zero_row, int tl, int 
         }
     }
 }
+template <int NT> LFT_DEV void lrelu_acc(f32x16 (&a)[NT]) {            // LeakyReLU(0.2)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[nt][i] = lrelu02_fast(a[nt][i]);
+}
+
+// A workgroup's tile of NW x 32 consecutive tokens of one view image, and this lane's place in it (k_conv64, k_conv64_lr,
+// k_conv0_recomputed, k_spa1).  Lane = token r of wave `wave` (MFMA column), hh its row half.  Neighbouring tiles share halo rows,
+// so xcd_tile puts them on one XCD.  SWAVE: the wave index as a scalar, for a loop that strides by it (k_conv64_lr).
+template <int NW, bool SWAVE = false> struct ViewTile {
+    int lane, r, hh, wave, hw, im, p0, tl, p, t0, nvalid;
+    bool ok;
+    __device__ __forceinline__ ViewTile(int h, int w) {
+        constexpr int TT = 32 * NW;                                       // tokens per workgroup tile
+        lane = threadIdx.x & 63; r = lane & 31; hh = lane >> 5;
+        wave = SWAVE ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
+        hw = h * w;
+        const int tpi = (hw + TT - 1) / TT, bid = xcd_tile(blockIdx.x, gridDim.x);
+        im = bid / tpi; p0 = (bid % tpi) * TT;
+        tl = wave * 32 + r; p = p0 + tl;                                  // token inside the tile, inside the image
+        ok = p < hw;
+        t0 = p0 + wave * 32; nvalid = max(0, min(32, hw - t0));           // this wave's 32 consecutive tokens
+    }
+    __device__ __forceinline__ size_t tile_off(int ch) const { return ((size_t)im * hw + min(t0, hw - 1)) * ch; }   // of [token][ch]
+};
 
 // conv_init[i]: 64 -> 64 + LeakyReLU(0.2); the last one adds conv_init0's output (reference LFT.py:26-33,66).
 // A workgroup = NW waves x 32 consecutive tokens of one view image; all its waves share one weight ring, so the
@@ -286,11 +319,6 @@ constexpr int kW01K = 96, kW01Frags = 12;
 // of the W01 product, taken as fragments (acc_frags), then holds channels 16 ks + 8 h + j in element j of fragment ks
 // -- the natural order of a token row in memory, so conv_init.2 consumes the tile with the stream it always had.
 __host__ __device__ __forceinline__ int conv01_row_channel(int rho) { return (rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1); }
-// View (a1, a2) of image b inside the LR mosaic [B,1,A*h,A*w]; row stride A*w (see k_conv0).
-LFT_DEV const float* lr_view(const float* __restrict__ lr, int im, int A, int h, int w) {
-    const int V = A * A, b = im / V, v = im - b * V, a1 = v / A, a2 = v - a1 * A;
-    return lr + (size_t)b * (A * h) * (A * w) + (size_t)(a1 * h) * (A * w) + a2 * w;
-}
 // LR pixels of a workgroup tile in LDS: the image rows of the tile's slots plus two rows above and below, two zero
 // columns left and right; everything outside the view is stored as zero (lr~), so a 5 x 5 patch is 25 unconditional reads.
 template <int NW> struct LrStage {
@@ -309,13 +337,6 @@ LFT_DEV void conv0_w_stage(const float* __restrict__ w0, float* wl) {       // t
     for (int k = 0; k < 3; ++k) {
         const int i = (int)threadIdx.x + 256 * k, ch = i / 9, t = i - ch * 9;
         if (i < 576) wl[t * 64 + ch] = wv[k];
-    }
-}
-LFT_DEV void conv0_taps_load(const float* __restrict__ img, int ldi, int y, int x, int h, int w, float (&val)[9]) {
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {                                           // clamped (readable) positions; masked at use
-        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-        val[t] = img[min(max(yy, 0), h - 1) * ldi + min(max(xx, 0), w - 1)];
     }
 }
 template <typename T>
@@ -344,51 +365,53 @@ LFT_DEV void conv0_token_acc(const float (&tap)[9], const float* wl, int y, int 
 }
 struct ConvLr { const float* lr; const float* w0; int A; };   // RES == 2: LR mosaic, conv_init0 weights (fp32), angular resolution
 
+// Dynamic LDS of k_conv64 and k_conv64_lr, byte offsets: weight ring | input tile | NW tile I/O scratches | zero row | extra.
+// extra: conv_init0's weights (k_conv64<T, 2>) or the staged LR pixels (k_conv64_lr); one size, total_lr, serves both.
+template <typename T, int NW = kNwConv> struct ConvLds {
+    static constexpr int in = WRing<T, kConv64Chunk, NW>::LDS_BYTES;
+    static __host__ __device__ int scr(int w, int wave) { return in + ConvIn<T, NW>::bytes(w) + wave * TileIO<2, T>::BYTES; }
+    static __host__ __device__ int zero_row(int w) { return scr(w, NW); }
+    static __host__ __device__ int extra(int w) { return zero_row(w) + kConvZeroRow; }
+    static __host__ __device__ int total(int w) { return extra(w); }
+    static __host__ __device__ int total_lr(int w) { return extra(w) + (LrStage<NW>::bytes(w) > kConv0WBytes ? LrStage<NW>::bytes(w) : kConv0WBytes); }
+};
+
 // RES: 0 no residual; 1 the residual tile is read from `res`; 2 the residual is conv_init0 of the LR pixels, recomputed
 // (16-bit front end: x0 is never written).
 template <typename T, int RES, int NW = kNwConv>
 __global__ __launch_bounds__(64 * NW) void k_conv64(const T* __restrict__ in, T* __restrict__ out, const T* __restrict__ res,
                                                    const T* __restrict__ wstream, int nimg, int h, int w, ConvLr cl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int TT = 32 * NW;                                       // tokens per workgroup tile
-    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = threadIdx.x >> 6;
-    const int hw = h * w, tpi = (hw + TT - 1) / TT;
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);                  // neighbouring tiles (shared halo rows) on one XCD
-    const int im = bid / tpi, p0 = (bid % tpi) * TT;
-    const int tl = wave * 32 + r, p = p0 + tl;
-    const bool ok = p < hw;
-    const int t0 = p0 + wave * 32, nvalid = max(0, min(32, hw - t0));                 // this wave's 32 consecutive tokens
-    const size_t tile_off = ((size_t)im * hw + min(t0, hw - 1)) * 64;
-    char* lds_in = smem + WRing<T, kConv64Chunk, NW>::LDS_BYTES;
-    char* scr = lds_in + ConvIn<T, NW>::bytes(w) + wave * TileIO<2, T>::BYTES;        // wave-private tile I/O scratch
-    char* zero_row = lds_in + ConvIn<T, NW>::bytes(w) + NW * TileIO<2, T>::BYTES;
-    float* wl = reinterpret_cast<float*>(zero_row + kConvZeroRow);                    // RES == 2 only
-    const int pc = min(p, hw - 1), yc = pc / w, xc = pc - yc * w;
+    using L = ConvLds<T, NW>;
+    const ViewTile<NW> t(h, w);
+    const size_t tile_off = t.tile_off(64);
+    char* lds_in = smem + L::in;
+    char* scr = smem + L::scr(w, t.wave);                                             // wave-private tile I/O scratch
+    char* zero_row = smem + L::zero_row(w);
+    float* wl = reinterpret_cast<float*>(smem + L::extra(w));                         // RES == 2 only
+    const int pc = min(t.p, t.hw - 1), yc = pc / w, xc = pc - yc * w;
     f32x16 rr[2];
     float tap[9];
-    if constexpr (RES == 1) load_tile<2, T>(res + tile_off, nvalid, lane, rr, scr);   // first: its latency hides under the tile
-    if constexpr (RES == 2) conv0_taps_load(lr_view(cl.lr, im, cl.A, h, w), cl.A * w, yc, xc, h, w, tap);
+    if constexpr (RES == 1) load_tile<2, T>(res + tile_off, t.nvalid, t.lane, rr, scr);   // first: its latency hides under the tile
+    if constexpr (RES == 2) conv0_taps_load(lr_view(cl.lr, t.im, cl.A, h, w), cl.A * w, yc, xc, h, w, tap);
     WRing<T, kConv64Chunk, NW> ring;
     ring.init(wstream, smem, 72);
-    stage_conv_input<T, NW>(in + (size_t)im * hw * 64, p0, hw, w, lds_in);
+    stage_conv_input<T, NW>(in + (size_t)t.im * t.hw * 64, t.p0, t.hw, w, lds_in);
     clear_zero_row(zero_row);
     if constexpr (RES == 2) conv0_w_stage(cl.w0, wl);
     wait_staged();
     __syncthreads();                                                                 // ... and everybody else's
     LFT_NOTE_ASM_("USE", kNoteConvIn, 0);
-    if constexpr (RES == 2) conv0_token_acc<T>(tap, wl, yc, xc, h, w, hh, rr);
+    if constexpr (RES == 2) conv0_token_acc<T>(tap, wl, yc, xc, h, w, t.hh, rr);
     f32x16 acc[2];
     zero_acc<2>(acc);
-    conv3x3_tile<2, T, NW>(lds_in, zero_row, tl, p / w, p % w, ok, h, w, hh, ring, acc);
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[nt][i] = lrelu02_fast(acc[nt][i]);
+    conv3x3_tile<2, T, NW>(lds_in, zero_row, t.tl, t.p / w, t.p % w, t.ok, h, w, t.hh, ring, acc);
+    lrelu_acc<2>(acc);
     if constexpr (RES != 0) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) acc[nt] += rr[nt];
     }
-    store_tile<2, T>(out + tile_off, nvalid, lane, acc, scr);
+    store_tile<2, T>(out + tile_off, t.nvalid, t.lane, acc, scr);
 }
 
 // conv_init.0 composed with conv_init0, then conv_init.2: LR mosaic -> tb (16-bit precisions).  Same tile as k_conv64; the
@@ -403,26 +426,20 @@ __global__ __launch_bounds__(64 * NW) void k_conv64_lr(const float* __restrict__
     static_assert(sizeof(T) == 2, "16-bit operand types only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using CI = ConvIn<T, NW>;
+    using L = ConvLds<T, NW>;
     constexpr int TT = 32 * NW;
-    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int hw = h * w, tpi = (hw + TT - 1) / TT;
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);
-    const int im = bid / tpi, p0 = (bid % tpi) * TT;
-    const int tl = wave * 32 + r, p = p0 + tl;
-    const bool ok = p < hw;
-    const int t0 = p0 + wave * 32, nvalid = max(0, min(32, hw - t0));
-    const size_t tile_off = ((size_t)im * hw + min(t0, hw - 1)) * 64;
-    char* lds_in = smem + WRing<T, kConv64Chunk, NW>::LDS_BYTES;
-    char* scr = lds_in + CI::bytes(w) + wave * TileIO<2, T>::BYTES;
-    char* zero_row = lds_in + CI::bytes(w) + NW * TileIO<2, T>::BYTES;
-    float* lrs = reinterpret_cast<float*>(zero_row + kConvZeroRow);
+    const ViewTile<NW, true> vt(h, w);
+    char* lds_in = smem + L::in;
+    char* scr = smem + L::scr(w, vt.wave);
+    char* zero_row = smem + L::zero_row(w);
+    float* lrs = reinterpret_cast<float*>(smem + L::extra(w));
     WRing<T, kConv64Chunk, NW> ring;
     ring.init(wstream, smem, kW01Frags + 72);
     // LR pixels: rows y_first - 2 .. y_last + 2 of the view, columns -2 .. w + 1
     const int nslots = CI::slots(w), LW = LrStage<NW>::width(w);
-    const int y_first = max(p0 - w - 1, 0) / w, y_last = min(p0 + TT + w, hw - 1) / w;
+    const int y_first = max(vt.p0 - w - 1, 0) / w, y_last = min(vt.p0 + TT + w, vt.hw - 1) / w;
     {
-        const float* img = lr_view(lr, im, A, h, w);
+        const float* img = lr_view(lr, vt.im, A, h, w);
         const int n = (y_last - y_first + 5) * LW, ldi = A * w;
         for (int i = threadIdx.x; i < n; i += 64 * NW) {
             const int row = i / LW, yy = y_first - 2 + row, xx = i - row * LW - 2;
@@ -434,9 +451,9 @@ __global__ __launch_bounds__(64 * NW) void k_conv64_lr(const float* __restrict__
     Frag<ConvLrOp> wf[kW01Frags];                                      // packed as ConvLrOp whatever T is: same 1 KiB pieces
 #pragma unroll
     for (int i = 0; i < kW01Frags; ++i) wf[i].v = __builtin_bit_cast(H16<ConvLrOp>::v8, ring.next().v);   // the ring's first barrier also publishes the LR pixels
-    for (int ct = wave; ct * 32 < nslots; ct += NW) {
-        const int slot = ct * 32 + r;
-        const int q = min(max(p0 - w - 1 + slot, 0), hw - 1), y = q / w, x = q - y * w;
+    for (int ct = vt.wave; ct * 32 < nslots; ct += NW) {
+        const int slot = ct * 32 + vt.r;
+        const int q = min(max(vt.p0 - w - 1 + slot, 0), vt.hw - 1), y = q / w, x = q - y * w;
         const float* pl = lrs + (y - y_first) * LW + x;                 // lr~(y - 2 + a, x - 2 + b) = pl[a * LW + b]
         float P[5][5];
 #pragma unroll
@@ -460,52 +477,41 @@ __global__ __launch_bounds__(64 * NW) void k_conv64_lr(const float* __restrict__
         for (int ks = 0; ks < kW01K / 16; ++ks) {
             Frag<ConvLrOp> b;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) b.v[j] = (ConvLrOp)(hh ? masked(16 * ks + 8 + j) : masked(16 * ks + j));
+            for (int j = 0; j < 8; ++j) b.v[j] = (ConvLrOp)(vt.hh ? masked(16 * ks + 8 + j) : masked(16 * ks + j));
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) mma(wf[nt * (kW01K / 16) + ks], b, a01[nt]);
         }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) a01[nt][i] = lrelu02_fast(a01[nt][i]);
+        lrelu_acc<2>(a01);
         Frag<T> of[4];
         acc_frags<2, T>(a01, of);
         if (slot < nslots) {
             char* row = lds_in + slot * CI::ROW_BYTES;
             const int sw = CI::swz(slot);
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) store_raw16(row + (((2 * ks + hh) ^ sw) * 16), __builtin_bit_cast(raw16, of[ks].v));
+            for (int ks = 0; ks < 4; ++ks) store_raw16(row + (((2 * ks + vt.hh) ^ sw) * 16), __builtin_bit_cast(raw16, of[ks].v));
         }
     }
     wg_barrier_keep_vm();                                              // the computed tile is published (lgkmcnt(0) inside)
     f32x16 acc[2];
     zero_acc<2>(acc);
-    conv3x3_tile<2, T, NW>(lds_in, zero_row, tl, p / w, p % w, ok, h, w, hh, ring, acc);
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[nt][i] = lrelu02_fast(acc[nt][i]);
-    store_tile<2, T>(out + tile_off, nvalid, lane, acc, scr);
+    conv3x3_tile<2, T, NW>(lds_in, zero_row, vt.tl, vt.p / w, vt.p % w, vt.ok, h, w, vt.hh, ring, acc);
+    lrelu_acc<2>(acc);
+    store_tile<2, T>(out + vt.tile_off(64), vt.nvalid, vt.lane, acc, scr);
 }
 // Test hook (lft_conv0_fwd): the residual tile k_conv64<T, 2> computes, written out as tokens [ntok][64].
 template <typename T, int NW = kNwConv>
 __global__ __launch_bounds__(64 * NW) void k_conv0_recomputed(T* __restrict__ out, int nimg, int h, int w, ConvLr cl) {
     __shared__ __attribute__((aligned(16))) char sm[kConv0WBytes + NW * TileIO<2, T>::BYTES];
-    constexpr int TT = 32 * NW;
-    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = threadIdx.x >> 6;
-    const int hw = h * w, tpi = (hw + TT - 1) / TT;
-    const int im = blockIdx.x / tpi, p0 = (blockIdx.x % tpi) * TT;
-    const int t0 = p0 + wave * 32, nvalid = max(0, min(32, hw - t0));
-    const size_t tile_off = ((size_t)im * hw + min(t0, hw - 1)) * 64;
-    const int pc = min(p0 + wave * 32 + r, hw - 1), yc = pc / w, xc = pc - yc * w;
+    const ViewTile<NW> t(h, w);
+    const int pc = min(t.p, t.hw - 1), yc = pc / w, xc = pc - yc * w;
     float* wl = reinterpret_cast<float*>(sm);
     float tap[9];
-    conv0_taps_load(lr_view(cl.lr, im, cl.A, h, w), cl.A * w, yc, xc, h, w, tap);
+    conv0_taps_load(lr_view(cl.lr, t.im, cl.A, h, w), cl.A * w, yc, xc, h, w, tap);
     conv0_w_stage(cl.w0, wl);
     __syncthreads();
     f32x16 rr[2];
-    conv0_token_acc<T>(tap, wl, yc, xc, h, w, hh, rr);
-    store_tile<2, T>(out + tile_off, nvalid, lane, rr, sm + kConv0WBytes + wave * TileIO<2, T>::BYTES);
+    conv0_token_acc<T>(tap, wl, yc, xc, h, w, t.hh, rr);
+    store_tile<2, T>(out + t.tile_off(64), t.nvalid, t.lane, rr, sm + kConv0WBytes + t.wave * TileIO<2, T>::BYTES);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -522,13 +528,99 @@ __global__ __launch_bounds__(64 * NW) void k_conv0_recomputed(T* __restrict__ ou
 // Stream: Wq[2x4] Wk[2x4] Wv[2x4] Wo[2x4] W1[4x4] W2[2x8]  (64 fragments) -- small enough to live
 // in LDS for the whole kernel: a persistent workgroup DMAs it once and then walks over positions.
 // ------------------------------------------------------------------------------------------
-template <int NT_OUT, int KS, typename T>
-LFT_DEV void linear_lds(const char* wl, int f0, int lane, const Frag<T> (&x)[KS], f32x16 (&y)[NT_OUT]) {
+// The steps k_ang and k_ang_multi share, each written once.  A kernel hands over its operands through accessors: wfrag(f) is
+// fragment f of the weight stream (k_ang: from LDS; k_ang_multi: from LDS or, fp32, from L2), vfrag(j, s2) the V operand of
+// key tile j (k_ang: its own accumulators; k_ang_multi: what the waves published in LDS).  No helper holds a barrier.
+constexpr int kLdsParams = 1024;   // 256 LayerNorm floats
+// Dynamic LDS of both kernels, byte offsets: the 64 weight fragments (WLDS) | LayerNorm parameters | KV published K / V
+// fragments | one tile I/O scratch per wave.  k_ang: <T, true, 0, 4>.
+template <typename T, bool WLDS, int KV, int NWAVE> struct AngLds {
+    static constexpr int FB = 1024 * FragInfo<T>::PIECES;              // bytes of one fragment
+    static constexpr int ln = WLDS ? 64 * FB : 0, kv = ln + kLdsParams, scr = kv + KV * FB, total = scr + NWAVE * TileIO<2, T>::BYTES;
+};
+template <int NT_OUT, int KS, typename T, typename WF>
+LFT_DEV void linear_frags(const WF& wfrag, int f0, const Frag<T> (&x)[KS], f32x16 (&y)[NT_OUT]) {
 #pragma unroll
     for (int nt = 0; nt < NT_OUT; ++nt)
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            mma(frag_from_pieces(wl + (f0 + nt * KS + ks) * 1024 * FragInfo<T>::PIECES, lane, T()), x[ks], y[nt]);
+        for (int ks = 0; ks < KS; ++ks) mma(wfrag(f0 + nt * KS + ks), x[ks], y[nt]);
+}
+// n = LN(x + PE) of a tile of 32 views; nf: n as operand (Q, K), xf: the raw tokens as operand (V, reference LFT.py:230-232).
+// pe: this tile's piece of the lane-major position table.
+template <typename T>
+LFT_DEV void ang_prologue(const f32x16 (&x)[2], const float* __restrict__ pe, bool ok, const float* lds_ln, int lane, int hh,
+                          unsigned& bad, Frag<T> (&nf)[4], Frag<T> (&xf)[4]) {
+    typename RawPiece<float>::type pr[8];
+    load_lane_major_raw<2, float>(pe, lane, pr);
+    f32x16 n[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) n[nt] = x[nt];
+    add_acc_raw<2, float>(n, pr, ok);
+    layernorm_acc<2, sizeof(T) == 2>(n, lds_ln, lds_ln + 64, hh, bad);
+    acc_frags<2, T>(n, nf);
+    acc_frags<2, T>(x, xf);
+}
+// Softmax numerators of one head over CT score tiles, in place; only the last tile has a compile-time live count (registers
+// LASTLIVE .. 15 of it are a view for no lane: probability 0 without computing it).  m: start value of the row maximum.  The
+// kernels are bound by vector-instruction issue: subtract and sum as register pairs (v_pk_add_f32).  The row sum is left to the
+// caller in two parts, the pair sums and -- returned -- the last probability of an odd LASTLIVE (0 for an even one).
+template <int CT, int LASTLIVE>
+LFT_DEV float ang_softmax(f32x16 (&S)[CT], float m, f32x2& sum2) {
+#pragma unroll
+    for (int j = 0; j < CT; ++j)
+#pragma unroll
+        for (int i = 0; i < (j == CT - 1 ? LASTLIVE : 16); ++i) m = fmaxf(m, S[j][i]);
+    m = xhalf_max(m);
+    const f32x2 mm = {m, m};
+    float odd = 0.0f;
+    sum2 = f32x2{0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < CT; ++j) {
+        const int live = j == CT - 1 ? LASTLIVE : 16;
+#pragma unroll
+        for (int i = 0; i + 1 < live; i += 2) {
+            f32x2 d = f32x2{S[j][i], S[j][i + 1]} - mm;
+            d[0] = fast_exp2(d[0]); d[1] = fast_exp2(d[1]);
+            S[j][i] = d[0]; S[j][i + 1] = d[1];
+            sum2 += d;
+        }
+        if (live & 1) odd = S[j][live - 1] = fast_exp2(S[j][live - 1] - m);
+#pragma unroll
+        for (int i = live; i < 16; ++i) S[j][i] = 0.0f;
+    }
+    return odd;
+}
+// O^T of head hd in a fresh accumulator: with V's 32 channels (4 heads) as the A operand every row of the product is computed,
+// the head's own 8 rows = registers 4*(hd&3)..+3 are kept, normalised by the row sum -- cheaper than zeroing the other heads'
+// channels of V per head (8 v_cndmask per head and fragment in kernels bound by vector-instruction issue).
+template <int CT, typename T, typename VF>
+LFT_DEV void ang_pv_keep(const VF& vfrag, const f32x16 (&S)[CT], float sum, int hd, f32x16& o) {
+    const float inv = sizeof(T) == 2 ? fast_rcp(xhalf_sum(sum)) : 1.0f / xhalf_sum(sum);
+    f32x16 oh;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) oh[i] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < CT; ++j)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) mma(vfrag(j, s2), acc_to_frag(S[j], s2, T()), oh);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[4 * (hd & 3) + i] = oh[4 * (hd & 3) + i] * inv;
+}
+// The per-token tail, in place: x = x + O Wo^T; x += W2 relu(W1 LN'(x)).  FAST2: the second LayerNorm in its fast form.
+template <typename T, bool FAST2, typename WF>
+LFT_DEV void ang_tail(const WF& wfrag, const f32x16 (&o)[2], const float* lds_ln, int hh, unsigned& bad, f32x16 (&x)[2]) {
+    Frag<T> of[4], nf[4], hf[8];
+    acc_frags<2, T>(o, of);
+    linear_frags<2, 4, T>(wfrag, 24, of, x);
+    f32x16 n[2], hid[4];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) n[nt] = x[nt];
+    layernorm_acc<2, FAST2>(n, lds_ln + 128, lds_ln + 192, hh, bad);
+    acc_frags<2, T>(n, nf);
+    zero_acc<4>(hid);
+    linear_frags<4, 4, T>(wfrag, 32, nf, hid);
+    acc_frags_relu<4>(hid, hf);
+    linear_frags<2, 8, T>(wfrag, 48, hf, x);
 }
 
 // NLIVE: accumulator registers 0 .. NLIVE-1 of a score tile can hold an existing view (register i <-> view rows
@@ -552,7 +644,9 @@ __global__ __launch_bounds__(256, 2) void k_ang(const T* __restrict__ X, T* __re
             glds_piece(g + piece * 1024, smem + piece * 1024, lane);
         }
     }
-    float* lds_ln = reinterpret_cast<float*>(smem + 64 * FB);
+    using L = AngLds<T, true, 0, 4>;
+    float* lds_ln = reinterpret_cast<float*>(smem + L::ln);
+    const auto wfrag = [&](int f) { return frag_from_pieces(smem + f * FB, lane, T()); };
     LFT_STAMP(0);
     const raw16 lnv = params_load(ln, 256);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own LDS-DMA pieces landed, then publish (see WRing::next)
@@ -565,88 +659,45 @@ __global__ __launch_bounds__(256, 2) void k_ang(const T* __restrict__ X, T* __re
     f32x16 negmask;                                                                       // 0 for key rows < V, -inf beyond
 #pragma unroll
     for (int i = 0; i < 16; ++i) negmask[i] = acc_row(i, hh) >= V ? -INFINITY : 0.0f;
-    char* scr = reinterpret_cast<char*>(lds_ln) + 1024 + wave * TileIO<2, T>::BYTES;        // wave-private tile I/O scratch
+    char* scr = smem + L::scr + wave * TileIO<2, T>::BYTES;                                 // wave-private tile I/O scratch
     const size_t vstride = (size_t)hw * 64 * sizeof(T);                                   // one view to the next, same position
     for (int pix = blockIdx.x * 4 + wave; pix < npix; pix += gridDim.x * 4) {
         asm volatile("" ::: "memory");    // keep the (loop-invariant) LDS weight reads inside the loop: hoisted, they cost 256+ VGPRs
         const int b = pix / hw, p = pix % hw;
         const size_t off0 = (((size_t)b * V) * hw + p) * 64;                              // view 0 of this position
 
-        f32x16 x[2], n[2];
+        f32x16 x[2];
         load_tile<2, T>(X + off0, V, lane, x, scr, vstride);                              // rows = views: 8 lanes x 16 B per row
         LFT_STAMP_IT(2, 5 * stamp_it);
-        {
-            typename RawPiece<float>::type pr[8];
-            load_lane_major_raw<2, float>(pe, lane, pr);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) n[nt] = x[nt];
-            add_acc_raw<2, float>(n, pr, ok);
-        }
-        layernorm_acc<2, sizeof(T) == 2>(n, lds_ln, lds_ln + 64, hh, bad);
         Frag<T> nf[4], xf[4];
-        acc_frags<2, T>(n, nf);
-        acc_frags<2, T>(x, xf);
+        ang_prologue<T>(x, pe, ok, lds_ln, lane, hh, bad, nf, xf);
 
         f32x16 q[2], k[2], v[2], o[2];
         zero_acc<2>(q); zero_acc<2>(k); zero_acc<2>(v);
-        linear_lds<2, 4, T>(smem, 0, lane, nf, q);
-        linear_lds<2, 4, T>(smem, 8, lane, nf, k);
+        linear_frags<2, 4, T>(wfrag, 0, nf, q);
+        linear_frags<2, 4, T>(wfrag, 8, nf, k);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)           // V[view, ch] = sum_k x[view, k] Wv[ch, k]: tokens are the A operand
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) mma(xf[ks], frag_from_pieces(smem + (16 + nt * 4 + ks) * FB, lane, T()), v[nt]);
+            for (int ks = 0; ks < 4; ++ks) mma(xf[ks], wfrag(16 + nt * 4 + ks), v[nt]);
 
         LFT_STAMP_IT(3, 5 * stamp_it);
 #pragma unroll
         for (int hd = 0; hd < 8; ++hd) {
             const int nt = hd >> 2, s = (hd >> 1) & 1, half = hd & 1;
-            f32x16 S = negmask;                                    // rows of non-existent views start at -inf: no per-head masking
-            mma(frag_half(acc_to_frag(k[nt], s, T()), half), acc_to_frag(q[nt], s, T()), S);   // S^T[kv, q]
-            float m = S[0];
-#pragma unroll
-            for (int i = 1; i < NLIVE; ++i) m = fmaxf(m, S[i]);
-            m = xhalf_max(m);
-            // the kernel is bound by vector-instruction issue: subtract and sum as register pairs (v_pk_add_f32)
-            const f32x2 mm = {m, m};
-            f32x2 sum2 = {0.0f, 0.0f};
-#pragma unroll
-            for (int i = 0; i + 1 < NLIVE; i += 2) {
-                f32x2 d = f32x2{S[i], S[i + 1]} - mm;
-                d[0] = fast_exp2(d[0]); d[1] = fast_exp2(d[1]);
-                S[i] = d[0]; S[i + 1] = d[1];
-                sum2 += d;
-            }
+            f32x16 S[1] = {negmask};                               // rows of non-existent views start at -inf: no per-head masking
+            mma(frag_half(acc_to_frag(k[nt], s, T()), half), acc_to_frag(q[nt], s, T()), S[0]);   // S^T[kv, q]
+            // Inherited, and not the same in k_ang_multi: the row maximum starts at the first score (there: -inf), and an odd
+            // last probability joins the row sum after the two pair sums (there: before).
+            f32x2 sum2;
+            const float odd = ang_softmax<1, NLIVE>(S, S[0][0], sum2);
             float sum = sum2[0] + sum2[1];
-            if constexpr (NLIVE & 1) { S[NLIVE - 1] = fast_exp2(S[NLIVE - 1] - m); sum += S[NLIVE - 1]; }
-#pragma unroll
-            for (int i = NLIVE; i < 16; ++i) S[i] = 0.0f;    // rows that are no view for any lane: probability 0 without computing it
-            const float inv = sizeof(T) == 2 ? fast_rcp(xhalf_sum(sum)) : 1.0f / xhalf_sum(sum);
-            // O^T of this head in a fresh accumulator: with V's 32 channels (4 heads) as the A operand every row of the product
-            // is computed, the head's own 8 rows = registers 4*(hd&3)..+3 are kept (normalised) -- cheaper than zeroing the other
-            // heads' channels of V per head (8 v_cndmask per head in a kernel bound by vector-instruction issue)
-            f32x16 oh;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) oh[i] = 0.0f;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) mma(acc_to_frag(v[nt], s2, T()), acc_to_frag(S, s2, T()), oh);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[nt][4 * (hd & 3) + i] = oh[4 * (hd & 3) + i] * inv;
+            if constexpr (NLIVE & 1) sum += odd;
+            ang_pv_keep<1, T>([&](int, int s2) { return acc_to_frag(v[nt], s2, T()); }, S, sum, hd, o[nt]);
         }
 
         LFT_STAMP_IT(4, 5 * stamp_it);
-        Frag<T> of[4];
-        acc_frags<2, T>(o, of);
-        linear_lds<2, 4, T>(smem, 24, lane, of, x);              // t = x + O Wo^T
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) n[nt] = x[nt];
-        layernorm_acc<2, sizeof(T) == 2>(n, lds_ln + 128, lds_ln + 192, hh, bad);
-        acc_frags<2, T>(n, nf);
-        f32x16 hid[4];
-        zero_acc<4>(hid);
-        linear_lds<4, 4, T>(smem, 32, lane, nf, hid);
-        Frag<T> hf[8];
-        acc_frags_relu<4>(hid, hf);
-        linear_lds<2, 8, T>(smem, 48, lane, hf, x);
+        ang_tail<T, sizeof(T) == 2>(wfrag, o, lds_ln, hh, bad, x);
         LFT_STAMP_IT(5, 5 * stamp_it);
         store_tile<2, T>(Y + off0, V, lane, x, scr, vstride);
         LFT_STAMP_IT(6, 5 * stamp_it);
@@ -677,10 +728,11 @@ __global__ __launch_bounds__(64 * CT * NG) void k_ang_multi(const T* __restrict_
     unsigned bad = 0;                                                  // non-finite activation seen (layernorm_acc)
     const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave_all / CT, wave = wave_all % CT;             // position group, column tile inside the position
+    using L = AngLds<T, WLDS, NG * CT * 8, NG * CT>;
     char* lds_w = smem;                                            // 64 weight fragments when WLDS
-    float* lds_ln = reinterpret_cast<float*>(smem + (WLDS ? 64 * FB : 0));
-    char* lds_kv = reinterpret_cast<char*>(lds_ln) + 1024 + (size_t)grp * CT * 8 * FB;   // per group [CT][8] fragments: K (nt, s) then V (nt, s)
-    char* scr = reinterpret_cast<char*>(lds_ln) + 1024 + (size_t)NG * CT * 8 * FB + wave_all * TileIO<2, T>::BYTES;   // wave-private tile I/O scratch
+    float* lds_ln = reinterpret_cast<float*>(smem + L::ln);
+    char* lds_kv = smem + L::kv + (size_t)grp * CT * 8 * FB;          // per group [CT][8] fragments: K (nt, s) then V (nt, s)
+    char* scr = smem + L::scr + wave_all * TileIO<2, T>::BYTES;       // wave-private tile I/O scratch
     if (WLDS) {
         const char* g = reinterpret_cast<const char*>(ws);
         for (int piece = wave_all; piece < 64 * FragInfo<T>::PIECES; piece += CT * NG) glds_piece(g + piece * 1024, lds_w + piece * 1024, lane);
@@ -709,20 +761,11 @@ __global__ __launch_bounds__(64 * CT * NG) void k_ang_multi(const T* __restrict_
         const int pix = min(base + grp, npix - 1);
         const int b = pix / hw, p = pix % hw;
         const size_t off = (((size_t)b * V + min(wave * 32, V - 1)) * hw + p) * 64;   // first view of this column tile
-        f32x16 x[2], n[2];
+        f32x16 x[2];
         if constexpr (sizeof(T) == 2) load_tile<2, T>(X + off, nrows, lane, x, scr, vstride);   // rows = views, coalesced through the scratch
         else load_acc<2, T>(X + (((size_t)b * V + min(view, V - 1)) * hw + p) * 64, ok, hh, x);   // fp32 build: already register-bound, keep the direct form
-        {
-            typename RawPiece<float>::type pr[8];
-            load_lane_major_raw<2, float>(pe + (size_t)wave * 2048, lane, pr);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) n[nt] = x[nt];
-            add_acc_raw<2, float>(n, pr, ok);
-        }
-        layernorm_acc<2, sizeof(T) == 2>(n, lds_ln, lds_ln + 64, hh, bad);
         Frag<T> nf[4], xf[4];
-        acc_frags<2, T>(n, nf);
-        acc_frags<2, T>(x, xf);
+        ang_prologue<T>(x, pe + (size_t)wave * 2048, ok, lds_ln, lane, hh, bad, nf, xf);
         f32x16 q[2], o[2];
         zero_acc<2>(q);
         {
@@ -759,72 +802,26 @@ __global__ __launch_bounds__(64 * CT * NG) void k_ang_multi(const T* __restrict_
             const int nt = hd >> 2, s = (hd >> 1) & 1, half = hd & 1;
             const Frag<T> qf = acc_to_frag(q[nt], s, T());
             f32x16 S[CT];
-            float m = -INFINITY;
 #pragma unroll
             for (int j = 0; j < CT; ++j) {
-                const int live = j == CT - 1 ? LASTLIVE : 16;
                 if (j == CT - 1) S[j] = negmask;
                 else {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) S[j][i] = 0.0f;
                 }
                 mma(frag_half(frag_from_pieces(lds_kv + (j * 8 + nt * 2 + s) * FB, lane, T()), half), qf, S[j]);   // S^T[kv, q]
-#pragma unroll
-                for (int i = 0; i < live; ++i) m = fmaxf(m, S[j][i]);
             }
-            m = xhalf_max(m);
-            const f32x2 mm = {m, m};                               // register pairs: v_pk_add_f32 (as in k_ang)
-            f32x2 sum2 = {0.0f, 0.0f};
-#pragma unroll
-            for (int j = 0; j < CT; ++j) {
-                const int live = j == CT - 1 ? LASTLIVE : 16;
-#pragma unroll
-                for (int i = 0; i + 1 < live; i += 2) {
-                    f32x2 d = f32x2{S[j][i], S[j][i + 1]} - mm;
-                    d[0] = fast_exp2(d[0]); d[1] = fast_exp2(d[1]);
-                    S[j][i] = d[0]; S[j][i + 1] = d[1];
-                    sum2 += d;
-                }
-                if (live & 1) { S[j][live - 1] = fast_exp2(S[j][live - 1] - m); sum2[0] += S[j][live - 1]; }
-#pragma unroll
-                for (int i = live; i < 16; ++i) S[j][i] = 0.0f;     // rows that are no view for any lane
-            }
-            const float inv = sizeof(T) == 2 ? fast_rcp(xhalf_sum(sum2[0] + sum2[1])) : 1.0f / xhalf_sum(sum2[0] + sum2[1]);
-            // O^T of this head in a fresh accumulator (all 32 channel rows of the product are computed, the head's own 8 rows =
-            // registers 4*(hd&3)..+3 are kept): cheaper than zeroing the other heads' channels of V per head and fragment
-            f32x16 oh;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) oh[i] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < CT; ++j)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-                    mma(frag_from_pieces(lds_kv + (j * 8 + 4 + nt * 2 + s2) * FB, lane, T()), acc_to_frag(S[j], s2, T()), oh);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[nt][4 * (hd & 3) + i] = oh[4 * (hd & 3) + i] * inv;
+            // Inherited, and not the same in k_ang: the row maximum starts at -inf (there: the first score), and an odd last
+            // probability joins the first pair sum before the two are added (there: after).
+            f32x2 sum2;
+            const float odd = ang_softmax<CT, LASTLIVE>(S, -INFINITY, sum2);
+            if constexpr (LASTLIVE & 1) sum2[0] += odd;
+            ang_pv_keep<CT, T>([&](int j, int s2) { return frag_from_pieces(lds_kv + (j * 8 + 4 + nt * 2 + s2) * FB, lane, T()); },
+                               S, sum2[0] + sum2[1], hd, o[nt]);
         }
-        Frag<T> of[4];
-        acc_frags<2, T>(o, of);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) mma(wfrag(24 + nt * 4 + ks), of[ks], x[nt]);         // t = x + O Wo^T
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) n[nt] = x[nt];
-        layernorm_acc<2>(n, lds_ln + 128, lds_ln + 192, hh, bad);
-        acc_frags<2, T>(n, nf);
-        f32x16 hid[4];
-        zero_acc<4>(hid);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) mma(wfrag(32 + nt * 4 + ks), nf[ks], hid[nt]);
-        Frag<T> hf[8];
-        acc_frags_relu<4>(hid, hf);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) mma(wfrag(48 + nt * 8 + ks), hf[ks], x[nt]);
+        // The second LayerNorm in its exact form in every precision, where k_ang (and the first one here) take the fast form in
+        // 16 bit: inherited from the copy this kernel began as, not a decision.
+        ang_tail<T, false>(wfrag, o, lds_ln, hh, bad, x);
         if constexpr (sizeof(T) == 2) store_tile<2, T>(Y + off, active ? nrows : 0, lane, x, scr, vstride);
         else store_acc<2, T>(Y + (((size_t)b * V + min(view, V - 1)) * hw + p) * 64, ok && active, hh, x);
     }

@@ -23,30 +23,55 @@ constexpr int kSpaOcc = 2;        // k_spa1 / k_spa2 workgroups per CU (launch b
 // streamed into the CU once per 32*NW tokens, and one ring barrier serves NW waves.
 // k_up is light on registers: eight waves share one weight stream (48 -> 42 us at B = 4).
 constexpr int kNwSpa1 = 4, kNwSpa2 = 4, kNwUp = 8;
+// Dynamic LDS of the three ring kernels, byte offsets.  k_spa1: weight ring | conv input tile, aliased by the NW tile I/O
+// scratches once it is dead (so at least as large as they are) | LayerNorm parameters | zero row.  k_spa2: ring | LayerNorm
+// parameters | NW scratches.  k_up: ring | NW scratches.
+template <typename T, int CH, int NW = kNwSpa1> struct Spa1Lds {
+    static constexpr int in = WRing<T, CH, NW>::LDS_BYTES;
+    static __host__ __device__ int ln(int w) { return in + (ConvIn<T, NW>::bytes(w) > NW * TileIO<4, T>::BYTES ? ConvIn<T, NW>::bytes(w) : NW * TileIO<4, T>::BYTES); }
+    static __host__ __device__ int zero_row(int w) { return ln(w) + kLdsParams; }
+    static __host__ __device__ int total(int w) { return zero_row(w) + kConvZeroRow; }
+};
+template <typename T, int NW = kNwSpa2> struct Spa2Lds {
+    static constexpr int ln = WRing<T, kSpaChunk, NW>::LDS_BYTES, scr = ln + kLdsParams, total = scr + NW * TileIO<4, T>::BYTES;
+};
+template <typename T, int NW = kNwUp> struct UpLds {
+    static constexpr int scr = WRing<T, kUpChunk, NW>::LDS_BYTES, total = scr + NW * TileIO<2, T>::BYTES;
+};
+// One in_proj matrix of k_spa1: nf through the ring in two 64-channel halves, each stored as soon as it is produced -- lane-major
+// (LM, at lm_off) or row-major [token][128] (at tile_off).  32 accumulator registers instead of 64 keep the kernel inside
+// 256 VGPRs (2 waves/SIMD) without scratch spills -- a spill reload forces s_waitcnt vmcnt(0), which drains the weight DMA and
+// every output store in flight.
+template <bool LM, typename T, typename Ring>
+LFT_DEV void spa1_project(Ring& ring, const Frag<T> (&nf)[8], T* __restrict__ dst, size_t lm_off, size_t tile_off, int nvalid, int lane, char* scr) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        f32x16 a[2];
+        zero_acc<2>(a);
+        linear_ring<2, 8, T>(ring, nf, a);
+        if constexpr (LM) store_tile_lm<2, T>(dst + lm_off + half * 2048, lane, a);
+        else store_tile<2, T, 128>(dst + tile_off + 64 * half, nvalid, lane, a, scr);
+    }
+}
 template <typename T, bool PE_ONLY, int CH = kSpaChunk, bool TOKLM = false, bool WITH_Q = true, int NW = kNwSpa1>   // TOKLM: the token tile goes to part B in lane-major tile format
 __global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa1(const T* __restrict__ X, const T* __restrict__ ws,
                                               const float* __restrict__ ln, const T* __restrict__ petok,
                                               T* __restrict__ TOK, T* __restrict__ Q, T* __restrict__ K, T* __restrict__ Vv,
                                               T* __restrict__ pe_out, int nimg, int h, int w, unsigned* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5, wave = threadIdx.x >> 6;
-    constexpr int TT = 32 * NW;                                       // tokens per workgroup tile
-    const int hw = h * w, tpi = (hw + TT - 1) / TT;
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);                  // neighbouring tiles (shared halo rows) on one XCD
-    const int im = bid / tpi, p0 = (bid % tpi) * TT;
-    const int tl = wave * 32 + r, p = p0 + tl;
-    const bool ok = p < hw;
+    using L = Spa1Lds<T, CH, NW>;
+    const ViewTile<NW> vt(h, w);
     LFT_STAMP(0);
     typename RawPiece<T>::type pe_raw[16];                                    // position tokens of this lane's token, kept packed
-    if (!PE_ONLY) load_lane_major_raw<4, T>(petok + (size_t)((p0 >> 5) + wave) * 4096, lane, pe_raw);   // early, 8 coalesced loads
-    char* lds_in = smem + WRing<T, CH, NW>::LDS_BYTES;
-    float* lds_ln = reinterpret_cast<float*>(lds_in + max(ConvIn<T, NW>::bytes(w), NW * TileIO<4, T>::BYTES));   // the tile I/O scratch aliases the conv input
-    char* zero_row = reinterpret_cast<char*>(lds_ln) + 1024;           // behind the 256 LayerNorm floats
+    if (!PE_ONLY) load_lane_major_raw<4, T>(petok + (size_t)((vt.p0 >> 5) + vt.wave) * 4096, vt.lane, pe_raw);   // early, 8 coalesced loads
+    char* lds_in = smem + L::in;
+    float* lds_ln = reinterpret_cast<float*>(smem + L::ln(w));
+    char* zero_row = smem + L::zero_row(w);
     raw16 lnv = raw16{0u, 0u, 0u, 0u};
     if (!PE_ONLY) lnv = params_load(ln, 256);                         // norm.{weight,bias}; ln is null in the pack-time PE_ONLY launch
     WRing<T, CH, NW> ring;
     ring.init(ws, smem, PE_ONLY ? 144 : (WITH_Q ? 240 : 208));
-    stage_conv_input<T, NW>(X + (size_t)im * hw * 64, p0, hw, w, lds_in);
+    stage_conv_input<T, NW>(X + (size_t)vt.im * vt.hw * 64, vt.p0, vt.hw, w, lds_in);
     clear_zero_row(zero_row);
     LFT_STAMP(12);
     wait_staged();
@@ -57,64 +82,39 @@ __global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa1(const T* __restrict__
     LFT_STAMP(1);
     f32x16 t[4];
     zero_acc<4>(t);
-    conv3x3_tile<4, T, NW>(lds_in, zero_row, tl, p / w, p % w, ok, h, w, hh, ring, t);
+    conv3x3_tile<4, T, NW>(lds_in, zero_row, vt.tl, vt.p / w, vt.p % w, vt.ok, h, w, vt.hh, ring, t);
     LFT_STAMP(2);
     if (PE_ONLY) {
-        store_lane_major<4, T>(pe_out + (size_t)((p0 >> 5) + wave) * 4096, lane, t);   // lane-major table, one 32-token tile per wave
+        store_lane_major<4, T>(pe_out + (size_t)((vt.p0 >> 5) + vt.wave) * 4096, vt.lane, t);   // lane-major table, one 32-token tile per wave
         return;
     }
     // Tile I/O scratch aliases the (now dead) conv input tile: every wave must be done reading it first.
     __syncthreads();
     LFT_STAMP(3);
-    const int t0 = p0 + wave * 32, nvalid = max(0, min(32, hw - t0));
-    const size_t tile_off = ((size_t)im * hw + min(t0, hw - 1)) * 128;
-    char* scr = lds_in + wave * TileIO<4, T>::BYTES;
-    if constexpr (TOKLM) store_tile_lm<4, T>(TOK + ((size_t)im * hw + t0) * 128, lane, t);   // hw % (32 NW) == 0: every tile is full
+    const int lane = vt.lane, nvalid = vt.nvalid;
+    const size_t tile_off = vt.tile_off(128);
+    char* scr = lds_in + vt.wave * TileIO<4, T>::BYTES;
+    if constexpr (TOKLM) store_tile_lm<4, T>(TOK + ((size_t)vt.im * vt.hw + vt.t0) * 128, lane, t);   // hw % (32 NW) == 0: every tile is full
     else store_tile<4, T>(TOK + tile_off, nvalid, lane, t, scr);
     LFT_STAMP(4);
     Frag<T> nf[8];
-    // Each projection is produced and stored in two 64-channel halves: 32 accumulator registers instead of 64
-    // keep the kernel inside 256 VGPRs (2 waves/SIMD) without scratch spills -- a spill reload forces
-    // s_waitcnt vmcnt(0), which drains the weight DMA and every output store in flight.
+    // Each projection is produced and stored in two 64-channel halves (spa1_project).
     // bf16 + lane-major hand-off: Q, K and V leave in the same lane-major tile form as the tokens (16-byte stores straight
     // from the accumulators, no LDS transposition): k_spa_b gathers its K / V halo tiles from that form by LDS-DMA -- whole
     // 128-byte lines per 8 tokens, where a row-major [token][128] tensor gives half a line per token and head pair.
     constexpr bool QKVLM = TOKLM && sizeof(T) == 2;
-    const size_t lm_off = ((size_t)im * hw + t0) * 128;               // this wave's 32-token tile in a lane-major [tile][k-step][lane][8] tensor
+    const size_t lm_off = ((size_t)vt.im * vt.hw + vt.t0) * 128;               // this wave's 32-token tile in a lane-major [tile][k-step][lane][8] tensor
     acc_frags<4, T>(t, nf);                    // V = tok Wv^T first (raw tokens, reference LFT.py:185); tok is then normalised in place
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        f32x16 a[2];
-        zero_acc<2>(a);
-        linear_ring<2, 8, T>(ring, nf, a);
-        if constexpr (QKVLM) store_tile_lm<2, T>(Vv + lm_off + half * 2048, lane, a);
-        else store_tile<2, T, 128>(Vv + tile_off + 64 * half, nvalid, lane, a, scr);
-    }
+    spa1_project<QKVLM>(ring, nf, Vv, lm_off, tile_off, nvalid, lane, scr);
     LFT_STAMP(6);
-    add_acc_raw<4, T>(t, pe_raw, ok);
+    add_acc_raw<4, T>(t, pe_raw, vt.ok);
     unsigned bad = 0;
-    layernorm_acc<4, sizeof(T) == 2>(t, lds_ln, lds_ln + 128, hh, bad);        // also the overflow detector for the token embedding
+    layernorm_acc<4, sizeof(T) == 2>(t, lds_ln, lds_ln + 128, vt.hh, bad);        // also the overflow detector for the token embedding
     acc_frags<4, T>(t, nf);
     LFT_STAMP(7);
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        f32x16 a[2];
-        zero_acc<2>(a);
-        linear_ring<2, 8, T>(ring, nf, a);
-        if constexpr (QKVLM) store_tile_lm<2, T>(K + lm_off + half * 2048, lane, a);
-        else store_tile<2, T, 128>(K + tile_off + 64 * half, nvalid, lane, a, scr);
-    }
+    spa1_project<QKVLM>(ring, nf, K, lm_off, tile_off, nvalid, lane, scr);
     LFT_STAMP(9);
-    if constexpr (WITH_Q) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            f32x16 a[2];
-            zero_acc<2>(a);
-            linear_ring<2, 8, T>(ring, nf, a);
-            if constexpr (QKVLM) store_tile_lm<2, T>(Q + lm_off + half * 2048, lane, a);
-            else store_tile<2, T, 128>(Q + tile_off + 64 * half, nvalid, lane, a, scr);
-        }
-    }
+    if constexpr (WITH_Q) spa1_project<QKVLM>(ring, nf, Q, lm_off, tile_off, nvalid, lane, scr);
     LFT_STAMP(11);
     publish_status(status, bad);
 }
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa2(const T* __restrict__
     const long long t0 = ((long long)blockIdx.x * NW + wave) * 32;                    // this wave's 32 consecutive tokens
     const int nvalid = (int)max(0LL, min(32LL, ntok - t0));
     const long long tb = min(t0, ntok - 1);
-    char* scr = smem + WRing<T, kSpaChunk, NW>::LDS_BYTES + 1024 + wave * TileIO<4, T>::BYTES;   // wave-private tile I/O scratch
+    char* scr = smem + Spa2Lds<T, NW>::scr + wave * TileIO<4, T>::BYTES;               // wave-private tile I/O scratch
     WRing<T, kSpaChunk, NW> ring;
     LFT_STAMP(16);
     ring.init(ws, smem, 176);                 // first: the weight DMA is in flight while the activation tiles are fetched
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(64 * NW, kSpaOcc) void k_spa2(const T* __restrict__
     load_tile_frags<8, T>(O + tb * 128, nvalid, lane, f, scr);
     f32x16 sk[2];
     if (SKIP) load_tile<2, T>(skip + tb * 64, nvalid, lane, sk, scr);
-    float* lds_ln = reinterpret_cast<float*>(smem + WRing<T, kSpaChunk, NW>::LDS_BYTES);
+    float* lds_ln = reinterpret_cast<float*>(smem + Spa2Lds<T, NW>::ln);
     params_store(lds_ln, 256, params_load(ln + 256, 256));            // feed_forward.0.{weight,bias}; the tile loads above were waited for anyway; published by the first ring barrier
     LFT_STAMP(17);
     linear_ring<4, 8, T>(ring, f, t);
@@ -727,7 +727,7 @@ __global__ __launch_bounds__(64 * NW) void k_up(const T* __restrict__ X, const T
     const long long tok = ok ? tok_raw : ntok - 1;
     const long long t0 = tok_raw - r;
     const int nvalid = (int)max(0LL, min(32LL, ntok - t0));
-    char* scr = smem + WRing<T, kUpChunk, NW>::LDS_BYTES + (threadIdx.x >> 6) * TileIO<2, T>::BYTES;
+    char* scr = smem + UpLds<T, NW>::scr + (threadIdx.x >> 6) * TileIO<2, T>::BYTES;
     WRing<T, kUpChunk, NW> ring;
     ring.init(ws, smem, nchunk * (4 + 2 * GT));         // first: the weight DMA is in flight while the tile is fetched
     f32x16 x[2];

@@ -29,6 +29,8 @@ constexpr int kFragsConv = 72, kFragsAng = 64, kFragsSpa1 = 240, kFragsSpa1NoQ =
 // 16-bit part B (k_spa_b) runs the 1x1x1 conv folded into the FFN's second Linear: kSpaBFrags fragments (lft_kernels_b.cuh)
 inline int frags_spa2(int prec) { return prec == LFT_PREC_F32 ? kFragsSpa2 : kSpaBFrags; }
 inline int frags_up(const Dims& d) { return d.nchunk * (4 + 2 * d.gt); }
+// Workgroup tiles of NW x 32 tokens in one view image (ViewTile)
+inline int view_tiles(const Dims& d, int NW) { return (d.hw + 32 * NW - 1) / (32 * NW); }
 
 struct PackedLayout {
     size_t conv0_w, ln_ang[kLayers], ln_spa[kLayers], ang_pe, petok[kLayers], spa_pe_img;
@@ -46,7 +48,7 @@ PackedLayout packed_layout(const Dims& d, int prec) {
     L.conv0_w = take(576 * 4);
     for (int l = 0; l < kLayers; ++l) { L.ln_ang[l] = take(256 * 4); L.ln_spa[l] = take(512 * 4); }
     L.ang_pe = take((size_t)((d.V + 31) / 32) * 2048 * 4);                       // lane-major, per 32-view tile
-    for (int l = 0; l < kLayers; ++l) L.petok[l] = take((size_t)((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1)) * kNwSpa1 * 4096 * esz);   // lane-major, per 32-token tile
+    for (int l = 0; l < kLayers; ++l) L.petok[l] = take((size_t)view_tiles(d, kNwSpa1) * kNwSpa1 * 4096 * esz);   // lane-major, per 32-token tile
     L.spa_pe_img = take((size_t)d.hw * 64 * esz);
     // The W01 fragments sit directly in front of conv_init.2's stream (fragb is a multiple of 256): k_conv64_lr reads both as one
     const bool lp = prec != LFT_PREC_F32;
@@ -97,17 +99,14 @@ int make_fwd(int B, int A, int h, int w, int s, int prec, void* stream, Fwd* c) 
     return 0;
 }
 
-// Dynamic LDS sizes (bytes) and the opt-in above the 64 KiB default (a workgroup may use all 160 KiB of a CU).
-template <typename T> size_t lds_conv64(int w) { return WRing<T, kConv64Chunk, kNwConv>::LDS_BYTES + ConvIn<T, kNwConv>::bytes(w) + kNwConv * TileIO<2, T>::BYTES + kConvZeroRow; }
+// Dynamic LDS sizes (bytes): the total of the layout each kernel takes its pointers from (ConvLds, Spa1Lds, Spa2Lds, UpLds, AngLds).
+template <typename T> size_t lds_conv64(int w) { return ConvLds<T>::total(w); }
 // The 16-bit front end: k_conv64_lr adds the staged LR pixels, k_conv64<T, 2> conv_init0's weights; one size serves both
-template <typename T> size_t lds_conv64_lr(int w) { return lds_conv64<T>(w) + std::max<size_t>(LrStage<kNwConv>::bytes(w), kConv0WBytes); }
-constexpr size_t kLdsParams = 1024;   // 256 LayerNorm floats
-template <typename T, int CH = kSpaChunk> size_t lds_spa1(int w) {      // the tile I/O scratch aliases the conv input tile, which must be large enough for it
-    return WRing<T, CH, kNwSpa1>::LDS_BYTES + std::max<size_t>(ConvIn<T, kNwSpa1>::bytes(w), (size_t)kNwSpa1 * TileIO<4, T>::BYTES) + kLdsParams + kConvZeroRow;
-}
-template <typename T> size_t lds_spa2() { return WRing<T, kSpaChunk, kNwSpa2>::LDS_BYTES + kLdsParams + kNwSpa2 * TileIO<4, T>::BYTES; }
-template <typename T> size_t lds_up() { return WRing<T, kUpChunk, kNwUp>::LDS_BYTES + kNwUp * TileIO<2, T>::BYTES; }
-template <typename T> size_t lds_ang() { return (size_t)kFragsAng * 1024 * FragInfo<T>::PIECES + kLdsParams + 4 * TileIO<2, T>::BYTES; }
+template <typename T> size_t lds_conv64_lr(int w) { return ConvLds<T>::total_lr(w); }
+template <typename T, int CH = kSpaChunk> size_t lds_spa1(int w) { return Spa1Lds<T, CH>::total(w); }
+template <typename T> size_t lds_spa2() { return Spa2Lds<T>::total; }
+template <typename T> size_t lds_up() { return UpLds<T>::total; }
+template <typename T> size_t lds_ang() { return AngLds<T, true, 0, 4>::total; }
 
 void conv_ops(std::vector<PackOp>& v, const float* w, int nout) {   // [nout][64][3][3] == [nout][576], k index c*9 + tap
     for (int tap = 0; tap < 9; ++tap)
@@ -250,7 +249,7 @@ int pack_impl(const Fwd& c, const float* const* P, void* packed) {
             if ((rc = run_pack<T>(ops, at<T>(packed, c.L.s_spa2[l]), frags_spa2(c.prec), st))) return rc;
         }
         // embedded spatial position tokens of this layer (reference LFT.py:180), [h*w][128] in the activation type
-        if ((rc = launch_spa1<T, true>((unsigned)((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1)), at<T>(packed, c.L.spa_pe_img), at<T>(packed, c.L.s_spa1[l]), nullptr, nullptr,
+        if ((rc = launch_spa1<T, true>((unsigned)view_tiles(d, kNwSpa1), at<T>(packed, c.L.spa_pe_img), at<T>(packed, c.L.s_spa1[l]), nullptr, nullptr,
                                        nullptr, nullptr, nullptr, nullptr, at<T>(packed, c.L.petok[l]), 1, c, nullptr))) return rc;
         LFT_LAUNCH_OK("k_spa1<pe>");
     }
@@ -269,24 +268,34 @@ int pack_impl(const Fwd& c, const float* const* P, void* packed) {
 
 // ---------------------------------------------------------------------------- stages
 // The front end as it was before the composition, and as fp32 still runs it: conv_init0 to memory, three 64 -> 64 convs.
+// conv_init0 to memory (tokens [B,V,h,w,64])
+template <typename T>
+int launch_conv0(const Fwd& c, const void* packed, const float* lr, T* x0) {
+    const Dims& d = c.d;
+    k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)(d.B * d.V)), 256, 0, c.st>>>(lr, at<float>(packed, c.L.conv0_w), x0, d.B, d.A, d.h, d.w);
+    LFT_LAUNCH_OK("k_conv0");
+    return 0;
+}
+// conv_init.<2 i> over every view image; the caller has allowed `lds` for this RES (before its first launch, so that a view too
+// wide is refused with nothing launched)
+template <typename T, int RES>
+int launch_conv64(const Fwd& c, const void* packed, size_t lds, int i, const T* in, T* out, const T* res = nullptr, ConvLr cl = ConvLr{}) {
+    const Dims& d = c.d;
+    const int nimg = d.B * d.V;
+    k_conv64<T, RES><<<nimg * view_tiles(d, kNwConv), 64 * kNwConv, lds, c.st>>>(in, out, res, at<T>(packed, c.L.s_conv[i]), nimg, d.h, d.w, cl);
+    LFT_LAUNCH_OK("k_conv64");
+    return 0;
+}
 template <typename T>
 int init_features_x0(const Fwd& c, const void* packed, const float* lr, T* x0, T* ta, T* tb, T* feat) {
-    const Dims& d = c.d;
-    const hipStream_t st = c.st;
-    const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
-    const size_t lds = lds_conv64<T>(d.w);
+    const size_t lds = lds_conv64<T>(c.d.w);
     int rc;
     if ((rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64"))) return rc;
     if ((rc = allow_lds(k_conv64<T, 1>, lds, "k_conv64"))) return rc;
-    k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, st>>>(lr, at<float>(packed, c.L.conv0_w), x0, d.B, d.A, d.h, d.w);
-    LFT_LAUNCH_OK("k_conv0");
-    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(x0, ta, nullptr, at<T>(packed, c.L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
-    LFT_LAUNCH_OK("k_conv64");
-    k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(ta, tb, nullptr, at<T>(packed, c.L.s_conv[1]), nimg, d.h, d.w, ConvLr{});
-    LFT_LAUNCH_OK("k_conv64");
-    k_conv64<T, 1><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, x0, at<T>(packed, c.L.s_conv[2]), nimg, d.h, d.w, ConvLr{});
-    LFT_LAUNCH_OK("k_conv64");
-    return 0;
+    if ((rc = launch_conv0<T>(c, packed, lr, x0))) return rc;
+    if ((rc = launch_conv64<T, 0>(c, packed, lds, 0, x0, ta))) return rc;
+    if ((rc = launch_conv64<T, 0>(c, packed, lds, 1, ta, tb))) return rc;
+    return launch_conv64<T, 1>(c, packed, lds, 2, tb, feat, x0);
 }
 // 16-bit: two launches.  conv_init0 is composed into conv_init.0 (k_conv64_lr: LR mosaic -> tb) and recomputed for the
 // residual of conv_init.4 (k_conv64<T, 2>); x0 and ta are never written.  Both launches carry the name "k_conv64": the
@@ -296,31 +305,28 @@ int init_features(const Fwd& c, const void* packed, const float* lr, T* x0, T* t
     if constexpr (sizeof(T) == 4) return init_features_x0<T>(c, packed, lr, x0, ta, tb, feat);
     else {
         const Dims& d = c.d;
-        const hipStream_t st = c.st;
-        const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
+        const int nimg = d.B * d.V, nwg = nimg * view_tiles(d, kNwConv);
         const size_t lds = lds_conv64_lr<T>(d.w);
         int rc;
         if (c.L.s_w01 + kW01Frags * 1024 != c.L.s_conv[1]) return fail(LFT_ERR_ARG, "internal: W01 fragments are not in front of conv_init.2's stream");
         if ((rc = allow_lds(k_conv64_lr<T>, lds, "k_conv64"))) return rc;
         if ((rc = allow_lds(k_conv64<T, 2>, lds, "k_conv64"))) return rc;
-        k_conv64_lr<T><<<nwg, 64 * kNwConv, lds, st>>>(lr, tb, at<T>(packed, c.L.s_w01), d.A, nimg, d.h, d.w);
+        k_conv64_lr<T><<<nwg, 64 * kNwConv, lds, c.st>>>(lr, tb, at<T>(packed, c.L.s_w01), d.A, nimg, d.h, d.w);
         LFT_LAUNCH_OK("k_conv64");
-        k_conv64<T, 2><<<nwg, 64 * kNwConv, lds, st>>>(tb, feat, nullptr, at<T>(packed, c.L.s_conv[2]), nimg, d.h, d.w,
-                                                      ConvLr{lr, at<float>(packed, c.L.conv0_w), d.A});
-        LFT_LAUNCH_OK("k_conv64");
-        return 0;
+        return launch_conv64<T, 2>(c, packed, lds, 2, tb, feat, nullptr, ConvLr{lr, at<float>(packed, c.L.conv0_w), d.A});
     }
 }
+// Grid of the persistent angular kernels, `per_wg` positions per workgroup: what the positions need, at most what 256 CUs hold by LDS
+inline unsigned ang_grid(int npix, int per_wg, size_t lds) { return std::min<unsigned>(blocks_for(npix, per_wg), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds)); }
 template <typename T, int CT, int LL>      // LL: score registers of the last key tile that can hold a view, which covers rows acc_row(i, 0) and acc_row(i, 1) = +4 of register i
 int ang_multi(const Fwd& c, const void* packed, int l, const T* in, T* out, unsigned* status) {
     const Dims& d = c.d;
     constexpr bool WLDS = sizeof(T) == 2;                                   // fp32 weights (128 KiB) stay in L2
     constexpr int NG = (sizeof(T) == 2 && CT <= 3) ? 2 : 1;                 // positions per workgroup (they share the LDS weights)
-    constexpr size_t FB = 1024 * FragInfo<T>::PIECES;
-    const size_t lds = (WLDS ? 64 * FB : 0) + 1024 + (size_t)NG * CT * 8 * FB + (size_t)NG * CT * TileIO<2, T>::BYTES;
+    const size_t lds = AngLds<T, WLDS, NG * CT * 8, NG * CT>::total;
     const int npix = d.B * d.hw;
     int rc;
-    const unsigned grid = std::min<unsigned>(blocks_for(npix, NG), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds));
+    const unsigned grid = ang_grid(npix, NG, lds);
     if ((rc = allow_lds(k_ang_multi<T, CT, WLDS, NG, LL>, lds, "k_ang_multi"))) return rc;
     k_ang_multi<T, CT, WLDS, NG, LL><<<grid, 64 * CT * NG, lds, c.st>>>(in, out, at<T>(packed, c.L.s_ang[l]), at<float>(packed, c.L.ln_ang[l]),
                                                                      at<float>(packed, c.L.ang_pe), d.V, d.hw, npix, status);
@@ -349,7 +355,7 @@ int ang_block(const Fwd& c, const void* packed, int l, const T* in, T* out, unsi
     const int npix = d.B * d.hw;
     const size_t lds = lds_ang<T>();
     int rc;
-    const unsigned grid = std::min<unsigned>(blocks_for(npix, 4), 256u * (unsigned)std::max<size_t>(1, kMaxLds / lds));
+    const unsigned grid = ang_grid(npix, 4, lds);
     // V <= 25 (5 x 5 and smaller): score rows 25..31 are never a view
     if ((rc = allow_lds(k_ang<T, 13>, lds, "k_ang"))) return rc;
     k_ang<T, 13><<<grid, 256, lds, c.st>>>(in, out, at<T>(packed, c.L.s_ang[l]), at<float>(packed, c.L.ln_ang[l]),
@@ -361,7 +367,7 @@ int ang_block(const Fwd& c, const void* packed, int l, const T* in, T* out, unsi
 template <typename T>
 int spa_part_a(const Fwd& c, const void* packed, int l, const T* in, void* ws) {
     const Dims& d = c.d;
-    const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwSpa1 - 1) / (32 * kNwSpa1));
+    const int nimg = d.B * d.V, nwg = nimg * view_tiles(d, kNwSpa1);
     int rc;
     if ((rc = launch_spa1<T, false>((unsigned)nwg, in, at<T>(packed, c.L.s_spa1[l]), at<float>(packed, c.L.ln_spa[l]), at<T>(packed, c.L.petok[l]),
                                     at<T>(ws, c.W.tok), at<T>(ws, c.W.q), at<T>(ws, c.W.k), at<T>(ws, c.W.v), nullptr, nimg, c, at<unsigned>(ws, c.W.status)))) return rc;
@@ -473,14 +479,10 @@ int kernel_time_impl(const Fwd& c, const char* name, const void* packed, void* w
         if (k == "k_spa1") return spa_part_a<T>(c, packed, 1, xa, ws);
         if (k == "k_spa_b" || k == "k_spa_attn+k_spa2") return spa_part_b<T>(c, packed, 1, nullptr, xb, ws);
         if (k == "k_conv64") {
-            const int nimg = d.B * d.V, nwg = nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv));
             const size_t lds = lds_conv64<T>(d.w);
-            int rc;
-            if ((rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64"))) return rc;
+            if (int rc = allow_lds(k_conv64<T, 0>, lds, "k_conv64")) return rc;
             // input: xb, which every forward writes (the 16-bit front end no longer writes x0); output: x0, which nothing reads
-            k_conv64<T, 0><<<nwg, 64 * kNwConv, lds, st>>>(xb, x0, nullptr, at<T>(packed, c.L.s_conv[0]), nimg, d.h, d.w, ConvLr{});
-            LFT_LAUNCH_OK("k_conv64");
-            return 0;
+            return launch_conv64<T, 0>(c, packed, lds, 0, xb, x0);
         }
         return fail(LFT_ERR_ARG, "lft_kernel_time: unknown kernel %s", name);
     };
@@ -634,17 +636,15 @@ int lft_conv0_fwd(const void* packed, const float* lr, void* x0_out, int recompu
         using T = decltype(t);
         const Dims& d = c.d;
         const int nimg = d.B * d.V;
-        const float* w0 = at<float>(packed, c.L.conv0_w);
         if constexpr (sizeof(T) == 2) {
             if (recomputed) {
-                k_conv0_recomputed<T><<<nimg * ((d.hw + 32 * kNwConv - 1) / (32 * kNwConv)), 64 * kNwConv, 0, c.st>>>(static_cast<T*>(x0_out), nimg, d.h, d.w, ConvLr{lr, w0, d.A});
+                k_conv0_recomputed<T><<<nimg * view_tiles(d, kNwConv), 64 * kNwConv, 0, c.st>>>(static_cast<T*>(x0_out), nimg, d.h, d.w,
+                                                                                                ConvLr{lr, at<float>(packed, c.L.conv0_w), d.A});
                 LFT_LAUNCH_OK("k_conv0_recomputed");
                 return 0;
             }
         }
-        k_conv0<T><<<dim3((unsigned)((d.hw + kConv0Tok - 1) / kConv0Tok), (unsigned)nimg), 256, 0, c.st>>>(lr, w0, static_cast<T*>(x0_out), d.B, d.A, d.h, d.w);
-        LFT_LAUNCH_OK("k_conv0");
-        return 0;
+        return launch_conv0<T>(c, packed, lr, static_cast<T*>(x0_out));
     });
 }
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Bit-level regression of the inference output against another build: the forward of BASELINE configs[1], a ragged 2x shape that
 takes the kernels' general paths, and one small shape per angular kernel variant (k_ang for up to 25 views, every k_ang_multi
-form from 36 to 121 views) under each library given, each in its own process; prints whether the outputs are bit-identical.
+form from 36 to 121 views, and the two-position forms once more with an odd position count) under each library given, each in its
+own process, with the outputs of lft_init_features_fwd and of lft_ang_block_fwd (layer 0) beside it; prints whether all are bit-identical.
   tools/out_bits.py ab_so/liblft_base0.so lft_amd/liblft_hip.so
 --lightfield: the light-field analysis instead -- refocus, disparity with and without the occlusion-aware cost, regularize, render with and without the visibility test and
 warp_disparity over shapes small enough that every tile is ragged, one hash per output of every case.
@@ -22,15 +23,34 @@ def child():
     from types import SimpleNamespace
     import torch
     from model import LFT
-    from lft_amd.params import deterministic_state, synthetic_lr
+    from lft_amd import _lib, module
+    from lft_amd.params import deterministic_state, param_table, synthetic_lr
+    ACT = {"bf16": (_lib.PREC_BF16, torch.bfloat16), "fp16": (_lib.PREC_F16, torch.float16), "fp32": (_lib.PREC_F32, torch.float32)}
+
+    def digest(t):
+        return hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:16]
+
+    # 3x5 at B = 1: 15 positions, so a k_ang_multi workgroup that holds two positions (16-bit, A = 6, 8, 9) ends on an inactive group
     for A, s, B, h, w in ((5, 4, 2, 32, 32), (3, 2, 1, 13, 22), (2, 4, 1, 6, 12),
-                          (6, 2, 1, 8, 8), (8, 2, 1, 8, 8), (9, 2, 1, 8, 8), (10, 2, 1, 8, 8), (11, 2, 1, 8, 8)):
+                          (6, 2, 1, 8, 8), (8, 2, 1, 8, 8), (9, 2, 1, 8, 8), (10, 2, 1, 8, 8), (11, 2, 1, 8, 8),
+                          (6, 2, 1, 3, 5), (8, 2, 1, 3, 5), (9, 2, 1, 3, 5)):
         for prec in ("bf16", "fp16", "fp32"):
+            sd = deterministic_state(64, s, seed=1)
+            lr = torch.from_numpy(synthetic_lr(B, A, h, w, seed=0)).cuda()
             net = LFT.get_model(SimpleNamespace(channels=64, angRes=A, scale_factor=s), precision=prec, streams=1).cuda().eval()
-            net.load_state_dict({k: torch.from_numpy(v) for k, v in deterministic_state(64, s, seed=1).items()})
+            net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
             with torch.no_grad():
-                out = net(torch.from_numpy(synthetic_lr(B, A, h, w, seed=0)).cuda())
-            print(f"A{A} s{s} B{B} {h}x{w} {prec}", hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:16], flush=True)
+                out = net(lr)
+            # the first two stages on their own, called as tests/test_gpu_parity.py calls them: a changed bit there cannot hide
+            # behind the rounding of the stages after it
+            p, dtype = ACT[prec]
+            packed = module.pack_weights([torch.from_numpy(sd[n]).cuda() for n, _, _ in param_table(64, s)], A, h, w, s, p, _lib.stream_ptr("cuda"))
+            work = torch.empty(_lib.workspace_bytes(B, A, h, w, s, p), dtype=torch.uint8, device="cuda")
+            feat = torch.empty(B, A * A, h, w, 64, dtype=dtype, device="cuda")
+            ang = torch.empty_like(feat)
+            _lib.enqueue("lft_init_features_fwd", "cuda", packed.data_ptr(), lr.data_ptr(), feat.data_ptr(), work.data_ptr(), B, A, h, w, s, p)
+            _lib.enqueue("lft_ang_block_fwd", "cuda", packed.data_ptr(), 0, feat.data_ptr(), ang.data_ptr(), B, A, h, w, s, p)
+            print(f"A{A} s{s} B{B} {h}x{w} {prec}", digest(out), "init_features", digest(feat), "ang_block0", digest(ang), flush=True)
 
 
 def child_lightfield():
