@@ -1,12 +1,14 @@
 // lft_lightfield.hip -- what handles light fields around the network, in the C ABI of liblft_hip.so (include/lft_hip.h): scene
 // tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity, view
-// synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h) and the sweep's
-// occlusion-aware cost (declared in include/lft_hip_occlusion.h).
+// synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h), the sweep's
+// occlusion-aware cost (declared in include/lft_hip_occlusion.h) and the all-in-focus image from the winning partial aperture
+// (declared in include/lft_hip_aif.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
 #include "../../include/lft_hip_visibility.h"
 #include "../../include/lft_hip_occlusion.h"
+#include "../../include/lft_hip_aif.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
@@ -18,6 +20,7 @@
 #include "lft_visibility.cuh" // view synthesis with a per-view visibility test, the warp of a map to other positions (lft_view_render_visible)
 #include "lft_sgm.cuh"       // semi-global aggregation of a cost volume: the path scans, the sum and the selection (lft_sgm)
 #include "lft_occlusion.cuh" // the sweep's cost from partial apertures: min over the whole aperture and up to four subsets (lft_disparity_occ)
+#include "lft_aif.cuh"       // the all-in-focus image from the winning partial aperture: one gather pass over the views (lft_aif_at)
 
 namespace {
 
@@ -619,6 +622,29 @@ int lft_occ_gather(const int* index, const unsigned char* choice, int B, int D, 
     if (blocks > 2147483647.0) return fail(LFT_ERR_SHAPE, "%s: %d maps of %d x %d need more than 2^31 blocks", who, B, H, W);
     if (!index || !choice || !subset) return fail(LFT_ERR_ARG, "%s: null pointer", who);
     return enqueue_occ_gather(index, choice, subset, B, D, H, W, (long long)blocks, static_cast<hipStream_t>(stream));
+}
+
+// ---- the all-in-focus image from the winning partial aperture (lft_aif.cuh; declared in include/lft_hip_aif.h) ----
+int lft_aif_at(const void* lf, int lf_class, int B, int A, int H, int W, int C, const long long* strides, const void* table, int D,
+               const float* subsets, int P, const int* index, const unsigned char* subset, int taps, void* aif, int aif_class, void* stream) {
+    const char* who = "lft_aif_at";
+    WindowedLf l{lf, lf_class, B, A, H, W, C, strides, table, D, taps, 0, 0};
+    if (int rc = windowed_lf_ok(who, l, aif_class, "output", 0, false, "stacks")) return rc;          // lft_refocus's rules and words
+    if (P < 0 || P > LFT_OCC_MAX_SUBSETS) return fail(LFT_ERR_ARG, "%s: %d subsets outside 0 .. %d", who, P, LFT_OCC_MAX_SUBSETS);
+    if (!subsets != !P) return fail(LFT_ERR_ARG, "%s: the subsets table must be null exactly when P = 0, got %s with P = %d", who, subsets ? "a table" : "null", P);
+    if (!l.tiles) return 0;                                         // an empty image
+    if (!index || !aif) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    const long long rtiles = l.tiles_x * (((long long)H + kVwRows - 1) / kVwRows);
+    if (rtiles * B > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: %d images of %d x %d need more than 2^31 blocks", who, B, H, W);
+    AifArgs a{};
+    fill_windowed(a, l);
+    a.subsets = subsets; a.P = P; a.index = index; a.subset = subset;
+    a.rtiles_x = (int)l.tiles_x; a.rtiles = (int)rtiles;
+    a.out = aif; a.out_f32 = aif_class == LFT_LF_FLOAT32;
+    const dim3 grid((unsigned)(rtiles * B));
+    by_lf_class<false>(lf_class, [&](auto t) { aif_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
+    LFT_LAUNCH_OK("k_aif_at");
+    return 0;
 }
 
 }  // extern "C"

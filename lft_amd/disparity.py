@@ -120,18 +120,48 @@ The inputs, the table, the samples `s`, the aperture `a` (fp64 on the host, sum 
 - Read together with `index`, `subset` is an occlusion-edge map: 0 where all views agree.
 
 No result may depend on the tile, the launch shape or the arrival order.
+
+All-in-focus image from the winning partial aperture
+----------------------------------------------------
+With `occlusion` the map is right next to a foreground edge, but `all_in_focus=True` is still gathered from `m`, the mean over all
+views, which mixes the background with the foreground the far-side views see.  ``all_in_focus_at`` and
+``disparity(..., occlusion=, all_in_focus="subset")`` render the mean of the subset that won, at the slope that won (lft_aif_at,
+csrc/lft_aif.cuh: k_aif_at, one launch; declared in include/lft_hip_aif.h).
+
+**Inputs.**
+- The light field, layout classes, six strides, refocus table `[D, A·A]` of `lft_refocus_record`, `taps` ∈ {1, 2, 4} and the centre
+  are those of `lft_refocus`.
+- `subsets`: DEVICE fp32 `[P, A·A]`, the rows `b_p` of `lft_disparity_occ`. `0 ≤ P ≤ LFT_OCC_MAX_SUBSETS`. `subsets` is NULL iff
+  `P = 0`.
+- `index`: int32 `[B, H, W]`. A value outside `0 .. D−1` is clamped into it, as in `lft_occ_gather`.
+- `subset`: NULL, or uint8 `[B, H, W]`. `0` means the whole aperture. `p ≥ 1` means row `p−1` of `subsets`. NULL and any id above
+  `P` count as 0.
+
+**Output** `aif[b, y, x, c]`, fp32 or uint8 by `rf_byte`.
+- Let `k` be the clamped index and `p` the id of the pixel.
+- Over the views `n` in (u, v) order, each view has a weight and a membership. For `p = 0` the weight is `w_n = a` of record
+  `(k, n)`, and the view is skipped iff the record's `skip` is set. For `p ≥ 1` the weight is `w_n = b_p[n]`, and the view is
+  skipped iff `b_p[n] == 0` or the record's `skip` is set.
+- The sample `s` is refocus's sample from record `(k, n)`. It uses offsets `oy, ox` and clamped taps. The row pass over `wy` comes
+  first, then the column pass over `wx`. Every step after a sum's first product is one explicit FMA, with contraction off.
+- `acc = fma(w_n, s, acc)` from `acc = 0`.
+
+**Consequences.**
+- `p = 0`: the bits of `lft_refocus`'s stack (fp32 and uint8) at `k`.
+- `p ≥ 1`: the bits of `lft_refocus` run with a table whose `a` / `skip` columns are `b_p` / `b_p == 0`, at `k`.
+- A pixel's bits must not depend on the tile, on the launch shape, on its neighbours' `k` or `p`, or on which code path served it.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import LftError
-from .refocus import TAPS, Aperture, _CLASS, _aperture, _as_given, _centre, _device_scratch, _device_table, _field
+from .refocus import TAPS, Aperture, _CLASS, _aperture, _as_given, _centre, _device_scratch, _device_table, _field, _layout
 
 MAX_RADIUS = 8
 
@@ -314,7 +344,7 @@ def occlusion_volume(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional
 
 
 def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None, aperture: Aperture = "full",
-              interp: str = "linear", radius: int = 2, all_in_focus: bool = False, cost_volume: bool = False,
+              interp: str = "linear", radius: int = 2, all_in_focus: Union[bool, str] = False, cost_volume: bool = False,
               aif_dtype=None, centre=None, regularize: Optional[dict] = None, occlusion=None) -> DisparityResult:
     """The disparity map of a light field on the GPU, on lf's device and current stream (enqueue only).
 
@@ -335,7 +365,18 @@ def disparity(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] =
     result is then an ``OcclusionDisparityResult``, DisparityResult's fields and then `subset` and `subsets_kept`: `subset` is 0
     where the whole aperture set the cost at the index and else the kept subset (1-based) that did, `subsets_kept` says which of
     the given subsets those ids stand for; with regularize, SGM runs on the new E and `subset` is the choice volume gathered at
-    SGM's index.  Without it nothing changes (the five-field result answers None for both names): the same launches, the same bits."""
+    SGM's index.  Without it nothing changes (the five-field result answers None for both names): the same launches, the same bits.
+    all_in_focus="subset" (it needs occlusion): the image is ``all_in_focus_at`` of this call's index and subset, the mean of the
+    winning subset's views and not of all of them; the sweep then keeps no stack (with regularize no stack is computed either), and
+    every other field has the bits of the same call with all_in_focus=True."""
+    if isinstance(all_in_focus, str):
+        if all_in_focus != "subset":
+            raise LftError(f"all_in_focus must be False, True or subset, got {all_in_focus!r}")
+        if occlusion is None:
+            raise LftError("all_in_focus = subset needs occlusion: the image is rendered from the subset that set the cost")
+        res = disparity(lf, slopes, angRes, aperture, interp, radius, False, cost_volume, aif_dtype, centre, regularize, occlusion)
+        image = all_in_focus_at(lf, slopes, res.index, res.subset, angRes, aperture, interp, centre, occlusion, aif_dtype)
+        return res._replace(all_in_focus=image)
     if regularize is not None:
         return _sweep_and_regularize(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, regularize, occlusion)
     return _sweep(lf, slopes, angRes, aperture, interp, radius, all_in_focus, cost_volume, aif_dtype, centre, occlusion)[0]
@@ -461,6 +502,56 @@ def gather_choice(index: torch.Tensor, choice: torch.Tensor) -> torch.Tensor:
     if B and H and W:
         _lib.enqueue("lft_occ_gather", index.device, index.data_ptr(), choice.data_ptr(), B, D, H, W, subset.data_ptr())
     return subset
+
+
+def all_in_focus_at(lf: torch.Tensor, slopes: Sequence[float], index: torch.Tensor, subset: Optional[torch.Tensor] = None,
+                    angRes: Optional[int] = None, aperture: Aperture = "full", interp: str = "linear", centre=None, occlusion=None,
+                    out_dtype=None) -> torch.Tensor:
+    """The all-in-focus image at a given index map, each pixel the mean of the views of its subset (the module docstring has the
+    definition), on lf's device and current stream (one launch of lft_aif_at, enqueue only).
+
+      views  [A, A, H, W, C] (C <= 4) or [A, A, H, W]   index, subset [H, W]     ->  [H, W, C] or [H, W]
+      mosaic [A*H, A*W] with angRes                       index, subset [H, W]     ->  [H, W]
+      batch  [B, 1, A*H, A*W] with angRes                 index, subset [B, H, W]  ->  [B, H, W]
+
+    Layouts, strides, input classes, slopes, aperture, interp and centre are ``disparity``'s.  index: int32, k per pixel, clamped
+    into 0 .. D-1.  subset: None (the whole aperture everywhere), or uint8 of index's shape: 0 the whole aperture, p >= 1 the p-th
+    kept subset of `occlusion` ("halves", "quadrants" or a dict with subsets / min_views, as for ``disparity``; ids are positions
+    in the kept list, and an id above their number counts as 0).  A subset map without occlusion is refused.  out_dtype (default:
+    the input's) is torch.float32, the unclipped sum, or torch.uint8: clip to [0, 1], * 255, round half to even.  With the index
+    and subset of ``disparity(..., occlusion=)`` this is the image of ``all_in_focus="subset"``."""
+    sl, how = (), None
+
+    def arguments():                        # everything that needs no device, the maps' shapes included
+        nonlocal sl, how
+        sl = _sweep_arguments(0, interp, slopes)
+        how = None if occlusion is None else _occlusion_arguments(occlusion)
+        if subset is not None and how is None:
+            raise LftError("a subset map needs occlusion: it says which subsets the ids stand for")
+        B, _, H, W, _, _, kind = _layout(lf, angRes)
+        shape = (B, H, W) if kind.startswith("batch") else (H, W)
+        for name, t, dtype in (("index", index, torch.int32), ("subset", subset, torch.uint8)):
+            if t is None and name == "subset":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
+                raise LftError(f"the {name} must be a {dtype} tensor of shape {list(shape)}, got {getattr(t, 'dtype', type(t).__name__)} "
+                               f"{tuple(getattr(t, 'shape', ()))}")
+            if t.device != lf.device:
+                raise LftError(f"the {name} is on {t.device}, the light field on {lf.device}")
+
+    B, A, H, W, C, strides, kind = _field(lf, angRes, "out_dtype", out_dtype, before_device=arguments)
+    out_dtype = lf.dtype if out_dtype is None else out_dtype
+    dev = lf.device
+    table = _device_table(A, sl, aperture, interp, dev, centre)
+    btable, kept = _device_subsets(A, aperture, centre, how[0], how[2], dev) if how is not None else (None, ())
+    aif = torch.empty(B, H, W, C, dtype=out_dtype, device=dev)
+    if B and H and W:
+        index = index.contiguous()
+        subset = None if subset is None else subset.contiguous()
+        _lib.enqueue("lft_aif_at", dev, lf.data_ptr(), _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), len(sl),
+                     None if btable is None else btable.data_ptr(), len(kept), index.data_ptr(), None if subset is None else subset.data_ptr(),
+                     TAPS[interp], aif.data_ptr(), _CLASS[out_dtype])
+    return _as_given(kind, aif, image=True)
 
 
 def disparity_error(a: torch.Tensor, b: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = None,

@@ -2,7 +2,7 @@
 
   python tools/disparity.py --lf scene.mat --angRes 5 --out_dir out/ --slopes=-2:2:33 --radius 2 [--aperture full|disk|gaussian]
                             [--interp nearest|linear|cubic] [--regularize [--p1 P1 --p2 P2] [--paths 4|8] [--edge_gain G]]
-                            [--occlusion [halves|quadrants] [--margin B] [--min_views N]]
+                            [--occlusion [halves|quadrants] [--margin B] [--min_views N] [--subset_aif]]
                             [--path_pre_pth LFT_5x5_4x.pth.tar --scale_factor 4 [--precision ..] [--self_ensemble ..]] [--bicubic]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C]; its centre angRes x angRes views are used.  Without
@@ -19,6 +19,8 @@ that sweep's all-in-focus image.  --occlusion scores every slope also by the var
 aperture, so that the band round a foreground edge gets the background's slope (lft_amd.disparity.disparity(occlusion=)): a subset
 wins where it is --margin times better than the whole aperture, subsets with fewer than --min_views views are dropped, and
 <out_dir>/occlusion.png shows which subset set the cost at the chosen slope (0 black: all views agree; subset p as grey 63 p).
+--subset_aif (it needs --occlusion) renders all_in_focus.png from the views of that subset and not from all of them
+(lft_amd.disparity.disparity(all_in_focus="subset")): no ghost of the foreground in the band round a depth edge.
 Without these flags the files keep their bytes."""
 import argparse
 import json
@@ -65,7 +67,7 @@ def regularize_arguments(views, slopes, args, guided=True):
 
 def write_maps(out_dir, views, slopes, args, prefix=""):
     """views: [A, A, H, W, 3] on the GPU (uint8, or float32 in [0, 1]).  Returns the paths written."""
-    r = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus=True,
+    r = disparity.disparity(views, slopes, aperture=args.aperture, interp=args.interp, radius=args.radius, all_in_focus="subset" if args.subset_aif else True,
                             aif_dtype=torch.uint8, regularize=regularize_arguments(views, slopes, args), occlusion=occlusion_arguments(args))
     paths = [os.path.join(out_dir, prefix + name) for name in ("disparity.png", "confidence.png", "all_in_focus.png", "disparity.npy")]
     png.write_png(paths[0], grey(r.disparity, min(slopes), max(slopes)))
@@ -96,6 +98,7 @@ def main(argv=None):
                     help="occlusion-aware cost from partial apertures: the subsets of the views (default halves); also writes occlusion.png")
     ap.add_argument("--margin", type=float, default=2.0, help="a subset wins where it is this many times better than the whole aperture, >= 1")
     ap.add_argument("--min_views", type=int, default=2, help="subsets with fewer views of non-zero weight are dropped, >= 2")
+    ap.add_argument("--subset_aif", action="store_true", help="all_in_focus.png from the views of the subset that set the cost (needs --occlusion)")
     ap.add_argument("--min_confidence", type=float, default=0.5, help="pixels counted by the printed disparity_error")
     ap.add_argument("--path_pre_pth", default=None, help="checkpoint in the reference's format: sweep the super-resolved views")
     ap.add_argument("--scale_factor", type=int, default=4)
@@ -105,6 +108,8 @@ def main(argv=None):
     ap.add_argument("--patch_size_for_test", type=int, default=32)
     ap.add_argument("--stride_for_test", type=int, default=16)
     args = ap.parse_args(argv)
+    if args.subset_aif and not args.occlusion:
+        ap.error("--subset_aif needs --occlusion")
 
     dev = torch.device("cuda", 0)
     slopes = parse_slopes(args.slopes)

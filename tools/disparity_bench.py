@@ -16,9 +16,12 @@ where the two pick the same slope (their costs differ by fp32 rounding and the c
   python tools/disparity_bench.py --regularize [--rounds 3] [--reps 200] [--warmup 3] [--out profiles/sgm_bench.txt]
 
   python tools/disparity_bench.py --occlusion [--rounds 3] [--reps 200] [--warmup 3] [--out profiles/occlusion_bench.txt]
+  python tools/disparity_bench.py --subset_aif [--rounds 3] [--reps 200] [--warmup 3] [--out profiles/aif_subset_bench.txt]
 
 --regularize times the semi-global aggregation of that workload's cost volume instead (``regularize_bench``).
---occlusion times the plain and the occlusion-aware sweep of that workload alternately instead (``occlusion_bench``)."""
+--occlusion times the plain and the occlusion-aware sweep of that workload alternately instead (``occlusion_bench``).
+--subset_aif times the occlusion-aware call with the all-in-focus image from all views, the same call with the image from the winning
+subset, and that image's pass alone, alternately instead (``subset_aif_bench``)."""
 import argparse
 import json
 import os
@@ -112,10 +115,49 @@ def occlusion_bench(args, lf, slopes):
                         "quadrants_GBps": round(nbytes_occ / (best["quadrants_ms"] * 1e-3) / 1e9, 1)})]
 
 
+def subset_aif_bench(args, lf, slopes):
+    """--subset_aif: one JSON line.  ``aif_true_ms`` is `disparity.disparity(occlusion="halves", all_in_focus=True)` (k_sweep_cost_occ
+    writing its fp32 stack + k_disparity_pick gathering from it + k_occ_gather), ``aif_subset_ms`` the same call with
+    all_in_focus="subset" (the sweep without the stack, the pick, the gather, then k_aif_at), ``aif_at_ms`` `disparity.all_in_focus_at`
+    alone on that call's index and subset; the three alternate in the same rounds of one process.  The workload's views are noise, so
+    that index differs from pixel to pixel and nearly every wave of k_aif_at reads its records per lane: ``aif_at_uniform_ms`` is the
+    same pass on a constant index and subset, where every wave reads them through a uniform address.  The byte contract of k_aif_at:
+    the views read once, 4 + 1 bytes of maps in per pixel, the image out; ``aif_at_hbm_peak_share`` is that contract over the best
+    time over the specified 8.0 TB/s.  ``stack_bytes_dropped`` is what the sweep no longer writes and the pick no longer reads from."""
+    kw = dict(interp="linear", radius=RADIUS, occlusion="halves")
+    res = disparity.disparity(lf, slopes, **kw)
+    flat_index, flat_subset = torch.full_like(res.index, D // 2), torch.ones_like(res.subset)
+    calls = {"aif_true_ms": lambda: disparity.disparity(lf, slopes, all_in_focus=True, **kw),
+             "aif_subset_ms": lambda: disparity.disparity(lf, slopes, all_in_focus="subset", **kw),
+             "aif_at_ms": lambda: disparity.all_in_focus_at(lf, slopes, res.index, res.subset, interp="linear", occlusion="halves"),
+             "aif_at_uniform_ms": lambda: disparity.all_in_focus_at(lf, slopes, flat_index, flat_subset, interp="linear", occlusion="halves")}
+    for _ in range(args.warmup):
+        for f in calls.values():
+            f()
+    same = all(torch.equal(x, y) for x, y in zip(calls["aif_true_ms"]()[:3], calls["aif_subset_ms"]()[:3]))
+    # a wave of k_aif_at is two rows of a 32-pixel-wide tile: the share of them with one (index, subset) pair
+    pair = (res.index.long() * 8 + res.subset.long()).reshape(H // 2, 2, W // 32, 32).permute(0, 2, 1, 3).reshape(-1, 64)
+    uniform = float((pair == pair[:, :1]).all(1).double().mean())
+    torch.cuda.synchronize()
+    rounds = [{k: round(timed(f, args.reps), 4) for k, f in calls.items()} for _ in range(args.rounds)]
+    best = {k: min(r[k] for r in rounds) for k in calls}
+    nbytes = A * A * H * W * C + H * W * (4 + 1) + H * W * C
+    return [json.dumps({"bench": "disparity_subset_aif", "device": torch.cuda.get_device_name(0), "A": A, "view": [H, W, C], "in": "uint8", "out": "uint8", "D": D,
+                        "interp": "linear", "radius": RADIUS, "aperture": "full", "occlusion": "halves", "margin": 2.0, "reps": args.reps, "rounds": rounds,
+                        "aif_true_ms_best": best["aif_true_ms"], "aif_subset_ms_best": best["aif_subset_ms"], "aif_at_ms_best": best["aif_at_ms"],
+                        "aif_at_uniform_ms_best": best["aif_at_uniform_ms"], "waves_uniform_share": round(uniform, 4),
+                        "subset_over_true": round(best["aif_subset_ms"] / best["aif_true_ms"], 3),
+                        "subset_faster_in_every_round": all(r["aif_subset_ms"] < r["aif_true_ms"] for r in rounds), "maps_bitwise_equal": same,
+                        "subset_share_nonzero": round(float((res.subset != 0).double().mean()), 4),
+                        "aif_at_contract_bytes": nbytes, "aif_at_GBps": round(nbytes / (best["aif_at_ms"] * 1e-3) / 1e9, 1),
+                        "aif_at_hbm_peak_share": round(nbytes / (best["aif_at_ms"] * 1e-3) / HBM_PEAK, 4), "stack_bytes_dropped": D * H * W * C * 4})]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--regularize", action="store_true", help="time the semi-global aggregation beside the sweep instead (one line per path count)")
     ap.add_argument("--occlusion", action="store_true", help="time the plain and the occlusion-aware sweep alternately instead (one line)")
+    ap.add_argument("--subset_aif", action="store_true", help="time the occlusion-aware call with either all-in-focus image and the subset image's pass alone (one line)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--torch_reps", type=int, default=10)
@@ -125,8 +167,8 @@ def main():
     dev = torch.device("cuda", 0)
     slopes = [float(x) for x in np.linspace(-2.0, 2.0, D)]
     lf = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (A, A, H, W, C)).astype(np.uint8)).to(dev)
-    if args.regularize or args.occlusion:
-        lines = regularize_bench(args, lf, slopes) if args.regularize else occlusion_bench(args, lf, slopes)
+    if args.regularize or args.occlusion or args.subset_aif:
+        lines = regularize_bench(args, lf, slopes) if args.regularize else occlusion_bench(args, lf, slopes) if args.occlusion else subset_aif_bench(args, lf, slopes)
         print("\n".join(lines))
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
