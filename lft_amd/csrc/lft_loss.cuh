@@ -29,15 +29,21 @@ struct LossFoldArgs {
     double inv_n, inv_nt[4], inv_T, w_pix, w_epi;          // inv_nt[t] = 0 for a difference that does not exist
 };
 
-template <int PEN> __device__ inline float loss_rho(float x, float eps2) {
-    if constexpr (PEN == LFT_LOSS_L1) return fabsf(x);
+// rho and rho' of the three penalties, in the type of x: fp32 here, fp64 for the focal term (lft_focal.cuh).  The one place they
+// are written
+__device__ inline float loss_abs(float x) { return fabsf(x); }
+__device__ inline double loss_abs(double x) { return fabs(x); }
+__device__ inline float loss_sqrt(float x) { return sqrtf(x); }
+__device__ inline double loss_sqrt(double x) { return sqrt(x); }
+template <int PEN, typename T> __device__ inline T loss_rho(T x, T eps2) {
+    if constexpr (PEN == LFT_LOSS_L1) return loss_abs(x);
     else if constexpr (PEN == LFT_LOSS_MSE) return x * x;
-    else return sqrtf(x * x + eps2);
+    else return loss_sqrt(x * x + eps2);
 }
-template <int PEN> __device__ inline float loss_drho(float x, float eps2) {
-    if constexpr (PEN == LFT_LOSS_L1) return (float)(x > 0.0f) - (float)(x < 0.0f);
-    else if constexpr (PEN == LFT_LOSS_MSE) return 2.0f * x;
-    else return x / sqrtf(x * x + eps2);
+template <int PEN, typename T> __device__ inline T loss_drho(T x, T eps2) {
+    if constexpr (PEN == LFT_LOSS_L1) return (T)(x > (T)0) - (T)(x < (T)0);
+    else if constexpr (PEN == LFT_LOSS_MSE) return (T)2 * x;
+    else return x / loss_sqrt(x * x + eps2);
 }
 // d = sr - hr of VEC consecutive pixels from element i (VEC = 4: i is a multiple of 4 behind 16-byte aligned pointers)
 template <int VEC> __device__ inline void loss_load(const float* __restrict__ sr, const float* __restrict__ hr, long long i, float (&o)[VEC]) {

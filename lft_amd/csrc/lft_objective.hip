@@ -1,9 +1,11 @@
 // lft_objective.hip -- losses and optimizer steps in the C ABI of liblft_hip.so (include/lft_hip.h): L1, the light-field loss,
-// the structural term, Adam, the guarded step and the EMA of the weights.
+// the structural term, the focal-stack term with the adjoint of refocus, Adam, the guarded step and the EMA of the weights.
 #include "lft_host.cuh"
+#include "../../include/lft_hip_focal.h"
 #include "lft_optim.cuh"     // guarded Adam step: gradient statistics, skip / clip decision, update (lft_adam_step_guarded)
 #include "lft_loss.cuh"      // pixel + EPI-gradient loss with L1 / MSE / Charbonnier penalty (lft_lf_loss)
 #include "lft_ssim_loss.cuh" // structural term 1 - SSIM and its gradient, fp64 inside (lft_ssim_loss)
+#include "lft_focal.cuh"     // focal-stack term: refocused residual, its penalty, the adjoint of refocus (lft_focal_loss, lft_refocus_adjoint)
 
 // ================================================================================ C ABI
 extern "C" {
@@ -130,6 +132,95 @@ int lft_ssim_loss(const float* sr, const float* hr, int B, int A, int H, int W, 
     k_ssim_loss_fold<<<1, kSsimThreads, 0, st>>>(part, s.nblocks, f, total, ssim_out);
     LFT_LAUNCH_OK("k_ssim_loss_fold");
     return 0;
+}
+// ---- focal-stack term and the adjoint of refocus (lft_focal.cuh) ----
+namespace {
+struct FocalShape { long long n_stack, n_mosaic, res_blocks, adj_blocks; int tiles_x, tiles; };
+// the rules lft_focal_loss and lft_refocus_adjoint share, under the caller's name
+int focal_shape(const char* who, int B, int D, int A, int H, int W, int taps, FocalShape* s) {
+    if (taps != 1 && taps != 2 && taps != 4) return fail(LFT_ERR_ARG, "%s: %d taps: 1 (nearest), 2 (linear) and 4 (cubic) are supported", who, taps);
+    if (D < 1 || D > LFT_FOCAL_MAX_D) return fail(LFT_ERR_ARG, "%s: %d slopes outside 1 .. %d", who, D, LFT_FOCAL_MAX_D);
+    if (B < 1 || A < 1 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "%s: sizes must be positive, got B %d A %d H %d W %d", who, B, A, H, W);
+    if ((long long)A * A > 128) return fail(LFT_ERR_SHAPE, "%s: A * A = %lld views, at most 128 are supported", who, (long long)A * A);
+    if ((long long)A * H * A * W > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: a mosaic of %d x %d views of %d x %d spans more than 2^31 - 1 elements", who, A, A, H, W);
+    s->tiles_x = (W + kFocalTileX - 1) / kFocalTileX;
+    s->tiles = s->tiles_x * ((H + kFocalTileY - 1) / kFocalTileY);
+    s->n_stack = (long long)B * D * H * W;
+    s->n_mosaic = (long long)B * A * A * H * W;
+    s->res_blocks = (long long)B * D * s->tiles;
+    s->adj_blocks = (long long)B * A * A * s->tiles;
+    if (s->res_blocks > 0x7fffffffLL || s->adj_blocks > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "%s: %d images of %d x %d need more than 2^31 - 1 blocks of %d x %d pixels", who, B, H, W, kFocalTileX, kFocalTileY);
+    return 0;
+}
+FocalArgs focal_args(int A, int H, int W, int D, const FocalShape& s, const void* table, int accumulate) {
+    FocalArgs a = {};
+    a.A = A; a.H = H; a.W = W; a.D = D; a.tiles_x = s.tiles_x; a.tiles = s.tiles;
+    a.table = static_cast<const int*>(table); a.accumulate = accumulate;
+    return a;
+}
+int focal_adjoint(const float* G, const FocalArgs& a, const FocalShape& s, int taps, float* out, hipStream_t st) {
+    if (int rc = dispatch<1, 2, 4>(taps, [&](auto TAPS) {
+            k_focal_adjoint<TAPS><<<(unsigned)s.adj_blocks, kFocalThreads, 0, st>>>(G, a, out);
+            return 0;
+        })) return rc;
+    LFT_LAUNCH_OK("k_focal_adjoint");
+    return 0;
+}
+}  // namespace
+int lft_focal_loss_scratch_bytes(int B, int D, int A, int H, int W, size_t* out_bytes) {
+    const char* who = "lft_focal_loss_scratch_bytes";
+    if (!out_bytes) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    FocalShape s;
+    if (int rc = focal_shape(who, B, D, A, H, W, 1, &s)) return rc;
+    *out_bytes = align256((size_t)s.res_blocks * sizeof(double)) + (size_t)s.n_stack * sizeof(float);
+    return 0;
+}
+int lft_focal_loss(const float* sr, const float* hr, int B, int A, int H, int W, const void* table, int D, int taps, int penalty,
+                   float eps, float w_focal, float* dsr, float gscale, int accumulate, float* total, float* focal_out, float* residual,
+                   void* scratch, void* stream) {
+    const char* who = "lft_focal_loss";
+    FocalShape s;                                                   // sizes first: an empty tensor's pointer may be null
+    if (int rc = focal_shape(who, B, D, A, H, W, taps, &s)) return rc;
+    if (!sr || !hr || !table || !total || !focal_out || !scratch) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if ((((uintptr_t)sr | (uintptr_t)hr | (uintptr_t)table | (uintptr_t)dsr | (uintptr_t)total | (uintptr_t)focal_out | (uintptr_t)residual) & 3) ||
+        ((uintptr_t)scratch & 7))
+        return fail(LFT_ERR_ARG, "%s: sr, hr, table, dsr, total, focal_out and residual must be 4-byte aligned, scratch 8-byte aligned", who);
+    if (penalty != LFT_LOSS_L1 && penalty != LFT_LOSS_MSE && penalty != LFT_LOSS_CHARBONNIER) return fail(LFT_ERR_ARG, "%s: unknown penalty %d", who, penalty);
+    if (penalty == LFT_LOSS_CHARBONNIER && !(eps > 0.0f)) return fail(LFT_ERR_ARG, "%s: the Charbonnier eps must be positive, got %g", who, (double)eps);
+    if (!(w_focal > 0.0f) || !std::isfinite(w_focal)) return fail(LFT_ERR_ARG, "%s: w_focal must be positive and finite, got %g", who, (double)w_focal);
+    if (std::isnan(gscale)) return fail(LFT_ERR_ARG, "%s: gscale is NaN", who);
+    if (accumulate != 0 && accumulate != 1) return fail(LFT_ERR_ARG, "%s: accumulate must be 0 or 1, got %d", who, accumulate);
+    if (overlaps(dsr, sr, hr, s.n_mosaic)) return fail(LFT_ERR_ARG, "%s: dsr overlaps sr or hr", who);
+    FocalArgs a = focal_args(A, H, W, D, s, table, accumulate);
+    a.eps2 = (double)eps * (double)eps;
+    a.c = (double)gscale * (double)w_focal / (double)s.n_stack;
+    const FocalFoldArgs f = {1.0 / (double)s.n_stack, (double)w_focal, accumulate};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(scratch);
+    float* G = dsr ? at<float>(scratch, align256((size_t)s.res_blocks * sizeof(double))) : nullptr;
+    if (int rc = dispatch<LFT_LOSS_L1, LFT_LOSS_MSE, LFT_LOSS_CHARBONNIER>(penalty, [&](auto PEN) {
+            return dispatch<1, 2, 4>(taps, [&](auto TAPS) {
+                k_focal_residual<PEN, TAPS><<<(unsigned)s.res_blocks, kFocalThreads, 0, st>>>(sr, hr, a, residual, G, part);
+                return 0;
+            });
+        })) return rc;
+    LFT_LAUNCH_OK("k_focal_residual");
+    k_focal_fold<<<1, kFocalThreads, 0, st>>>(part, s.res_blocks, f, total, focal_out);
+    LFT_LAUNCH_OK("k_focal_fold");
+    return dsr ? focal_adjoint(G, a, s, taps, dsr, st) : 0;
+}
+int lft_refocus_adjoint(const float* stack_grad, int B, int A, int H, int W, const void* table, int D, int taps, float* out,
+                        int accumulate, void* stream) {
+    const char* who = "lft_refocus_adjoint";
+    FocalShape s;
+    if (int rc = focal_shape(who, B, D, A, H, W, taps, &s)) return rc;
+    if (!stack_grad || !table || !out) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (((uintptr_t)stack_grad | (uintptr_t)table | (uintptr_t)out) & 3) return fail(LFT_ERR_ARG, "%s: stack_grad, table and out must be 4-byte aligned", who);
+    if (accumulate != 0 && accumulate != 1) return fail(LFT_ERR_ARG, "%s: accumulate must be 0 or 1, got %d", who, accumulate);
+    if ((uintptr_t)out < (uintptr_t)(stack_grad + s.n_stack) && (uintptr_t)stack_grad < (uintptr_t)(out + s.n_mosaic))
+        return fail(LFT_ERR_ARG, "%s: out overlaps stack_grad", who);
+    return focal_adjoint(stack_grad, focal_args(A, H, W, D, s, table, accumulate), s, taps, out, static_cast<hipStream_t>(stream));
 }
 int lft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                   int step, float gscale, float weight_decay, void* stream) {

@@ -324,7 +324,8 @@ class PipelinedForward:
 
 class get_loss(nn.Module):
     """Mean absolute error between SR and HR mosaics (reference model/LFT.py:269-277).  If ``args`` carries an ``lft_loss`` attribute
-    (a spec of lft_amd.loss.LFLoss: a dict or a penalty name), ``get_loss(args)`` is that LFLoss instead, for ``args.angRes`` views."""
+    (a spec of lft_amd.loss.LFLoss: a dict or a penalty name, the ssim_* and focal_* keys among its keys), ``get_loss(args)`` is that
+    LFLoss instead, for ``args.angRes`` views."""
 
     def __new__(cls, args=None):
         if args is not None and hasattr(args, "lft_loss"):

@@ -122,6 +122,14 @@ def shift_table(A: int, slopes: Sequence[float], aperture: Aperture = "full", in
     return tab
 
 
+def parse_slopes(text: str):
+    """The slopes of a command line: LO:HI:N (N slopes from LO to HI) or a comma list."""
+    if ":" in text:
+        lo, hi, n = text.split(":")
+        return [float(x) for x in np.linspace(float(lo), float(hi), int(n))]
+    return [float(x) for x in text.split(",")]
+
+
 _tables: Dict[tuple, torch.Tensor] = {}
 
 
@@ -222,6 +230,36 @@ def refocus(lf: torch.Tensor, slopes: Sequence[float], angRes: Optional[int] = N
     _lib.enqueue("lft_refocus", lf.device, lf.data_ptr() or None, _CLASS[lf.dtype], B, A, H, W, C, strides, table.data_ptr(), D, TAPS[interp],
                  out.data_ptr() or None, _CLASS[out_dtype])
     return _as_given(kind, out, image=True)
+
+
+def refocus_adjoint(stack_grad: torch.Tensor, slopes: Sequence[float], angRes: int, aperture: Aperture = "full", interp: str = "cubic",
+                    centre=None, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """The adjoint of ``refocus`` on a batch of mosaics (lft_refocus_adjoint, include/lft_hip_focal.h): a contiguous float32 stack
+    gradient [B, D, H, W] on the GPU -> the mosaic [B, 1, A*H, A*W] whose view (u, v) collects, through the clamped taps, what every
+    stack pixel took from it: <refocus(x), g> = <x, refocus_adjoint(g)>.  out / accumulate: a mosaic to write, or to add to.  Only
+    enqueues, on stack_grad's device and current stream; no autograd hook on ``refocus`` itself."""
+    if not isinstance(stack_grad, torch.Tensor) or stack_grad.dtype != torch.float32 or stack_grad.dim() != 4 or not stack_grad.is_contiguous():
+        raise LftError("the stack gradient must be a contiguous float32 tensor [B, D, H, W]")
+    if interp not in TAPS:
+        raise LftError(f"interp must be nearest, linear or cubic, got {interp!r}")
+    A = int(angRes)
+    if A < 1:
+        raise LftError(f"angRes must be positive, got {angRes}")
+    B, D, H, W = (int(d) for d in stack_grad.shape)
+    nslopes = np.array(slopes, dtype=np.float64).reshape(-1).size
+    if nslopes != D:
+        raise LftError(f"{nslopes} slopes for a stack of {D} slices")
+    if accumulate and out is None:
+        raise LftError("accumulate adds to `out`: pass the mosaic that holds the other terms")
+    if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, 1, A * H, A * W) or out.device != stack_grad.device):
+        raise LftError(f"out must be a contiguous float32 tensor [{B}, 1, {A * H}, {A * W}] on the device of the stack gradient")
+    if stack_grad.device.type != "cuda":
+        raise LftError(f"the stack gradient must be on the GPU, got a tensor on {stack_grad.device} (there is no CPU path)")
+    table = _device_table(A, slopes, aperture, interp, stack_grad.device, centre)
+    out = torch.empty(B, 1, A * H, A * W, dtype=torch.float32, device=stack_grad.device) if out is None else out
+    _lib.enqueue("lft_refocus_adjoint", stack_grad.device, stack_grad.data_ptr() or None, B, A, H, W, table.data_ptr(), D, TAPS[interp],
+                 out.data_ptr() or None, int(bool(accumulate)))
+    return out
 
 
 def _views(lf, angRes: Optional[int]):

@@ -341,8 +341,9 @@ class TrainStep:
         self._scratch = torch.empty(1024 + 1, dtype=torch.float32, device=dev)
         # loss: None or 'l1' -- the reference's L1 through lft_l1_loss, the bits of every earlier version; an lft_amd.loss.LFLoss (or
         # its spec) other than pure L1 -- lft_lf_loss at the same place, (total, P, E) of the last step in last_loss_terms; with
-        # ssim_weight > 0 lft_ssim_loss follows it, adds to the same dout and total, and leaves S in a fourth entry
-        self.loss, self.last_loss_terms, self._loss_scratch, self._ssim_scratch = None, None, {}, {}
+        # ssim_weight > 0 lft_ssim_loss follows it, adds to the same dout and total, and leaves S in a fourth entry; with focal_weight > 0
+        # lft_focal_loss follows both in the same way and leaves F in a fifth (the fourth is then 0 without the SSIM term)
+        self.loss, self.last_loss_terms, self._loss_scratch, self._ssim_scratch, self._focal_scratch = None, None, {}, {}, {}
         if loss is not None and loss != "l1":
             from .loss import LFLoss
             loss = LFLoss.from_spec(loss)
@@ -352,10 +353,11 @@ class TrainStep:
                 raise ValueError(f"the loss was built for angRes {loss.angRes}, the network has {self.A}")
             if not loss.is_plain_l1():
                 self.loss = loss
-                self.last_loss_terms = torch.zeros(4 if loss.ssim_weight > 0.0 else 3, dtype=torch.float32, device=dev)
+                self.last_loss_terms = torch.zeros(5 if loss.focal_weight > 0.0 else 4 if loss.ssim_weight > 0.0 else 3, dtype=torch.float32, device=dev)
 
     def _loss_scratch_for(self, hr):
-        """Scratch of lft_lf_loss (and of lft_ssim_loss) for this batch shape: allocated once, outside any capture."""
+        """Scratch of lft_lf_loss (and of lft_ssim_loss, and of lft_focal_loss with its device table) for this batch shape: allocated
+        once, outside any capture."""
         key = tuple(hr.shape)
         B, _, R, C = hr.shape
         if self.loss.ssim_weight > 0.0 and (R // self.A < 11 or C // self.A < 11):      # before anything is allocated, enqueued or captured
@@ -366,6 +368,12 @@ class TrainStep:
         if self.loss.ssim_weight > 0.0 and key not in self._ssim_scratch:
             from .loss import ssim_scratch_bytes
             self._ssim_scratch[key] = torch.empty(ssim_scratch_bytes(B, self.A, R // self.A, C // self.A), dtype=torch.uint8, device=hr.device)
+        if self.loss.focal_weight > 0.0 and key not in self._focal_scratch:
+            from .loss import focal_scratch_bytes
+            from .refocus import _device_table
+            _device_table(self.A, self.loss.focal_slopes, "full", self.loss.focal_interp, hr.device)      # cached: the step finds it there
+            self._focal_scratch[key] = torch.empty(focal_scratch_bytes(B, len(self.loss.focal_slopes), self.A, R // self.A, C // self.A),
+                                                   dtype=torch.uint8, device=hr.device)
         return self._loss_scratch[key]
 
     def _fwd_loss_bwd(self, lr_in, hr, tape, dout, loss, on_bucket=None):
@@ -375,7 +383,7 @@ class TrainStep:
             _lib.enqueue("lft_l1_loss", lr_in.device, out.data_ptr(), hr.data_ptr(), n, dout.data_ptr(), 1.0 / n, loss.data_ptr(),
                          self._scratch.data_ptr())
         else:
-            from .loss import lf_loss, ssim_loss
+            from .loss import focal_loss, lf_loss, ssim_loss
             lf = self.loss.has_lf_terms()
             if lf:
                 lf_loss(out, hr, self.A, self.loss.penalty, self.loss.eps, self.loss.pixel_weight, self.loss.epi_weight, dsr=dout,
@@ -383,6 +391,10 @@ class TrainStep:
             if self.loss.ssim_weight > 0.0:                    # P and E stay 0 in the pure structural objective
                 ssim_loss(out, hr, self.A, self.loss.ssim_range, self.loss.ssim_weight, dsr=dout, accumulate=lf,
                           total=self.last_loss_terms[0:1], ssim_out=self.last_loss_terms[3:4], scratch=self._ssim_scratch[tuple(hr.shape)])
+            if self.loss.focal_weight > 0.0:                   # S stays 0 without the SSIM term
+                focal_loss(out, hr, self.A, self.loss.focal_slopes, self.loss.focal_interp, "full", self.loss.penalty, self.loss.eps,
+                           self.loss.focal_weight, dsr=dout, accumulate=lf or self.loss.ssim_weight > 0.0, total=self.last_loss_terms[0:1],
+                           focal_out=self.last_loss_terms[4:5], scratch=self._focal_scratch[tuple(hr.shape)])
         if on_bucket is None:
             train_backward(self.params, lr_in, tape, dout, self.A, self.s, grads=self.flat_grads, math=self.math)
         else:

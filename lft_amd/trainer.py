@@ -291,7 +291,7 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
     loss: an lft_amd.loss.LFLoss, its spec (a dict) or a penalty name -- the objective of TrainStep(loss=...); None: the reference's L1.
     The components are summed on the device and the epoch line gains 'pix %.5f, epi %.5f' (the means of the pixel and the EPI term;
     not for a spec that is the plain L1, which runs the reference's kernel) and, with ssim_weight > 0, ', ssim %.5f', the epoch mean of
-    the structural term's S.  The spec goes into the state file; a resume with another
+    the structural term's S, and with focal_weight > 0 ', focal %.5f', the epoch mean of the focal-stack term's F.  The spec goes into the state file; a resume with another
     one continues and says so."""
     import torch.distributed as dist
     from .train import TrainStep
@@ -338,7 +338,7 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         if max_batches_per_epoch:
             batches = batches[:max_batches_per_epoch]
         total = torch.zeros(3 if batch_metrics else 1, device=dev)
-        terms = torch.zeros(3 if ts.last_loss_terms is None else ts.last_loss_terms.numel(), device=dev)   # (total, P, E[, S]) of TrainStep(loss=...)
+        terms = torch.zeros(3 if ts.last_loss_terms is None else ts.last_loss_terms.numel(), device=dev)   # (total, P, E[, S[, F]]) of TrainStep(loss=...)
         last = None
         for ix in batches:
             a, b = source.get(ix)
@@ -371,10 +371,12 @@ def fit(net, source, epochs: int, batch_size: int, lr: float = 2e-4, n_steps: in
         else:
             msg = "The %dth Train, loss is: %.5f, lr %.3g" % (epoch + 1, history[-1], ts.lr)
         if ts.last_loss_terms is not None:
-            pix, epi, *ssim = (terms[1:] / max(1, len(batches))).tolist()
+            pix, epi, *more = (terms[1:] / max(1, len(batches))).tolist()
             msg += ", pix %.5f, epi %.5f" % (pix, epi)
-            if ssim:                                               # the epoch mean of S, the structural term's SSIM
-                msg += ", ssim %.5f" % ssim[0]
+            if more and ts.loss.ssim_weight > 0.0:                 # the epoch mean of S, the structural term's SSIM
+                msg += ", ssim %.5f" % more[0]
+            if len(more) > 1:                                      # the epoch mean of F, the focal-stack term
+                msg += ", focal %.5f" % more[1]
         if last is not None and not batch_metrics:
             with torch.no_grad():
                 msg += ", psnr(last batch) %.3f" % psnr_gpu(net(last[0]), last[1])

@@ -25,11 +25,7 @@ from lft_amd import colour, png, refocus  # noqa: E402
 import super_resolve  # noqa: E402  (the loader of the scene and of the network)
 
 
-def parse_slopes(text: str):
-    if ":" in text:
-        lo, hi, n = text.split(":")
-        return [float(x) for x in np.linspace(float(lo), float(hi), int(n))]
-    return [float(x) for x in text.split(",")]
+parse_slopes = refocus.parse_slopes      # LO:HI:N or a comma list; tools/disparity.py and tools/view_path.py take it from here
 
 
 def write_stack(out_dir, views, slopes, args, prefix=""):

@@ -15,7 +15,11 @@ both series, the only fair way to see a difference of this size.
 "loss_ms" holds the event-timed milliseconds of the loss launches alone -- lft_lf_loss and, alternating with it in this one process on
 the same tensors, lft_l1_loss (medians over 50 calls each).
 --ssim_weight W / --ssim_range R: the objective gains W * (1 - SSIM) (lft_ssim_loss right after lft_lf_loss, accumulating into the same
-gradient); "loss_ms" then also times that call."""
+gradient); "loss_ms" then also times that call.
+--focal_weight W / --focal_slopes=LO:HI:N / --focal_interp I: the objective gains W * F, the penalty on the focal stack of SR - HR
+(lft_focal_loss after the other terms); "loss_ms" then also times that call, and with --alternate R a second TrainStep with the same
+objective WITHOUT the focal term alternates with it ("ms_per_step_rounds": "focal" and "no_focal").  "loss_ms" gains
+"lft_focal_loss_standalone": the call alone (not accumulating, with its gradient) on the step's tensors."""
 import argparse, json, os, sys, time
 from types import SimpleNamespace
 
@@ -30,7 +34,7 @@ def time_loss_launches(ts, hr, calls=50):
     """Median event-timed milliseconds of one lft_lf_loss call (the step's objective) and of one lft_l1_loss call on the same tensors,
     the two alternating."""
     from lft_amd import _lib
-    from lft_amd.loss import lf_loss, ssim_loss
+    from lft_amd.loss import focal_loss, lf_loss, ssim_loss
     sr, dout = ts.last_out, torch.empty_like(hr)
     n = sr.numel()
     scratch = ts._loss_scratch_for(hr)
@@ -47,9 +51,16 @@ def time_loss_launches(ts, hr, calls=50):
         ssim_loss(sr, hr, ts.A, ts.loss.ssim_range, ts.loss.ssim_weight, dsr=dout, accumulate=ts.loss.has_lf_terms(),
                   total=ts.last_loss_terms[0:1], ssim_out=ts.last_loss_terms[3:4], scratch=ts._ssim_scratch[tuple(hr.shape)])
 
+    def run_focal(accumulate=True):
+        focal_loss(sr, hr, ts.A, ts.loss.focal_slopes, ts.loss.focal_interp, "full", ts.loss.penalty, ts.loss.eps, ts.loss.focal_weight, dsr=dout,
+                   accumulate=accumulate and (ts.loss.has_lf_terms() or ts.loss.ssim_weight > 0.0), total=ts.last_loss_terms[0:1],
+                   focal_out=ts.last_loss_terms[4:5], scratch=ts._focal_scratch[tuple(hr.shape)])
+
     runs = [("lft_l1_loss", run_l1)] + ([("lft_lf_loss", run_lf)] if ts.loss.has_lf_terms() else [])
     if ts.loss.ssim_weight > 0.0:
         runs.append(("lft_ssim_loss", run_ssim))
+    if ts.loss.focal_weight > 0.0:
+        runs += [("lft_focal_loss", run_focal), ("lft_focal_loss_standalone", lambda: run_focal(False))]
     ms = {name: [] for name, _ in runs}
     for i in range(calls + 5):
         for name, run in runs:
@@ -112,9 +123,12 @@ def main():
     ap.add_argument("--epi_weight", type=float, default=0.0, help="weight of the EPI-gradient term of --loss")
     ap.add_argument("--ssim_weight", type=float, default=0.0, help="weight of the structural term 1 - SSIM (lft_ssim_loss)")
     ap.add_argument("--ssim_range", type=float, default=2.0, help="data range of that SSIM; 2 is what fit and evaluate report with")
+    ap.add_argument("--focal_weight", type=float, default=0.0, help="weight of the focal-stack term (lft_focal_loss)")
+    ap.add_argument("--focal_slopes", default="-1:1:3", help="the slopes that term refocuses to: LO:HI:N or a comma list")
+    ap.add_argument("--focal_interp", default="linear", choices=["nearest", "linear", "cubic"])
     args = ap.parse_args()
-    if args.alternate and args.ema_decay is None:
-        ap.error("--alternate compares with and without the EMA: it needs --ema_decay")
+    if args.alternate and args.ema_decay is None and args.focal_weight == 0.0:
+        ap.error("--alternate compares with and without the EMA or the focal term: it needs --ema_decay or --focal_weight")
     from lft_amd import dp, train as T
     from lft_amd.params import deterministic_state, synthetic_lr
     from model import LFT
@@ -137,6 +151,10 @@ def main():
     spec = None if args.loss is None and args.ssim_weight == 0.0 else {"penalty": args.loss or "l1", "epi_weight": args.epi_weight}
     if args.ssim_weight > 0.0:
         spec.update(ssim_weight=args.ssim_weight, ssim_range=args.ssim_range)
+    base_spec = spec                                     # the objective without the focal term: what --alternate compares with
+    if args.focal_weight > 0.0:
+        from lft_amd.refocus import parse_slopes
+        spec = dict(spec or {"penalty": "l1"}, focal_weight=args.focal_weight, focal_slopes=parse_slopes(args.focal_slopes), focal_interp=args.focal_interp)
     ts = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard, ema_decay=args.ema_decay, loss=spec)
 
     def sync():
@@ -155,12 +173,16 @@ def main():
     dt = dp.barrier_max_seconds(time.perf_counter() - t0, dev)
     rounds = None
     if args.alternate:
-        base = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard)
+        with_name = "focal" if args.focal_weight > 0.0 else "ema"
+        if args.focal_weight > 0.0:
+            base = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard, ema_decay=args.ema_decay, loss=base_spec)
+        else:
+            base = T.TrainStep(new_net(), lr=2e-4, math=args.math, graph=not args.no_graph, guard=args.guard)
         for _ in range(args.warmup):
             base.step(lr, hr)
-        rounds = {"ema": [], "no_ema": []}
+        rounds = {with_name: [], "no_" + with_name: []}
         for _ in range(args.alternate):
-            for name, step in (("no_ema", base), ("ema", ts)):
+            for name, step in (("no_" + with_name, base), (with_name, ts)):
                 sync()
                 t1 = time.perf_counter()
                 for _ in range(args.steps):

@@ -52,6 +52,9 @@ def parse_args(argv=None):
     ap.add_argument("--epi_weight", type=float, default=0.0, help="weight of the EPI-gradient term (the penalty on the gradients of the epipolar-plane images)")
     ap.add_argument("--ssim_weight", type=float, default=0.0, help="weight of the structural term 1 - SSIM (the mean over all views of the SSIM the epoch line reports)")
     ap.add_argument("--ssim_range", type=float, default=2.0, help="data range of that SSIM; 2 is what the epoch line and the tests report with")
+    ap.add_argument("--focal_weight", type=float, default=0.0, help="weight of the focal-stack term: the penalty on the refocused difference SR - HR (lft_focal_loss)")
+    ap.add_argument("--focal_slopes", default="-1:1:3", help="the slopes that term refocuses to: LO:HI:N or a comma list, HR pixels per view step")
+    ap.add_argument("--focal_interp", default="linear", choices=["nearest", "linear", "cubic"], help="the interpolation of that refocus")
     args = ap.parse_args(argv)
     if args.resume and args.use_pre_pth:
         ap.error("--resume restores the weights of its own epoch: it cannot be combined with --use_pre_pth")
@@ -60,11 +63,14 @@ def parse_args(argv=None):
 
 def loss_spec(args):
     """The spec for fit(loss=...), or None for the reference's L1 (which keeps the lft_l1_loss step)."""
-    if args.loss == "l1" and args.pixel_weight == 1.0 and args.epi_weight == 0.0 and args.ssim_weight == 0.0:
+    if args.loss == "l1" and args.pixel_weight == 1.0 and args.epi_weight == 0.0 and args.ssim_weight == 0.0 and args.focal_weight == 0.0:
         return None
     spec = {"penalty": args.loss, "eps": args.charbonnier_eps, "pixel_weight": args.pixel_weight, "epi_weight": args.epi_weight}
     if args.ssim_weight > 0.0:
         spec.update(ssim_weight=args.ssim_weight, ssim_range=args.ssim_range)
+    if args.focal_weight > 0.0:
+        from lft_amd.refocus import parse_slopes
+        spec.update(focal_weight=args.focal_weight, focal_slopes=parse_slopes(args.focal_slopes), focal_interp=args.focal_interp)
     return spec
 
 
