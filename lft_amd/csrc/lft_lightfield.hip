@@ -1,15 +1,17 @@
 // lft_lightfield.hip -- what handles light fields around the network, in the C ABI of liblft_hip.so (include/lft_hip.h): scene
 // tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity, view
 // synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h), the sweep's
-// occlusion-aware cost (declared in include/lft_hip_occlusion.h) and the all-in-focus image from the winning partial aperture
-// (declared in include/lft_hip_aif.h).
+// occlusion-aware cost (declared in include/lft_hip_occlusion.h), the all-in-focus image from the winning partial aperture
+// (declared in include/lft_hip_aif.h) and scene tiling with a per-patch integer shear (declared in include/lft_hip_shear.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
 #include "../../include/lft_hip_visibility.h"
 #include "../../include/lft_hip_occlusion.h"
 #include "../../include/lft_hip_aif.h"
+#include "../../include/lft_hip_shear.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
+#include "lft_shear.cuh"     // scene tiling with a per-patch integer shear, the vote that chooses it (lft_scene_divide_shear, lft_shear_vote)
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
@@ -644,6 +646,63 @@ int lft_aif_at(const void* lf, int lf_class, int B, int A, int H, int W, int C, 
     const dim3 grid((unsigned)(rtiles * B));
     by_lf_class<false>(lf_class, [&](auto t) { aif_kernel<decltype(t)>(C, taps)<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a); return 0; });
     LFT_LAUNCH_OK("k_aif_at");
+    return 0;
+}
+
+// ---- scene tiling with a per-patch integer shear (lft_shear.cuh; declared in include/lft_hip_shear.h) ----
+static_assert(kShearMax == LFT_SHEAR_MAX, "the header states the largest shear the vote keeps a count for");
+// What the two tiling calls judge after their pointers: lft_scene_divide's tiling with its words, then what the shear adds.
+// *kmax: the largest |k| whose cut stays inside the patch's border.
+static int shear_tiling_ok(const char* who, int A, int h0, int w0, int patch, int stride, int* nu, int* nv, int* kmax) {
+    if (int rc = scene_counts(h0, w0, patch, stride, nu, nv)) return rc;
+    if ((patch - stride) % 2) return fail(LFT_ERR_SHAPE, "%s: patch - stride = %d is odd: the border must be the same on both sides", who, patch - stride);
+    const int bdr = (patch - stride) / 2, u0 = A / 2, R = std::max(u0, A - 1 - u0);
+    *kmax = R == 0 ? LFT_SHEAR_MAX : std::min(LFT_SHEAR_MAX, bdr / R);
+    return 0;
+}
+int lft_scene_divide_shear(const float* scene, const int* shear, float* patches, int A, int h0, int w0, int patch, int stride, void* stream) {
+    const char* who = "lft_scene_divide_shear";
+    int nu, nv, kmax;
+    if (!scene || !shear || !patches) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (A < 1) return fail(LFT_ERR_ARG, "%s: angRes %d", who, A);
+    if (int rc = shear_tiling_ok(who, A, h0, w0, patch, stride, &nu, &nv, &kmax)) return rc;
+    // this launch: one block row per row of a patch mosaic, one block plane per patch; the scene mosaic is indexed in int
+    if ((long long)A * patch > 65535 || (long long)nu * nv > 65535)
+        return fail(LFT_ERR_SHAPE, "%s: patch mosaics of %lld rows and %d x %d patches need more than 65535 blocks in the grid's y or z", who, (long long)A * patch, nu, nv);
+    if ((long long)A * h0 > 0x7fffffffLL || (long long)A * w0 > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: a scene mosaic of %d x %d views of %d x %d has more than 2^31 rows or columns", who, A, A, h0, w0);
+    const dim3 grid((unsigned)((A * patch + 255) / 256), (unsigned)(A * patch), (unsigned)(nu * nv));
+    k_scene_divide_shear<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(scene, shear, patches, A, h0, w0, patch, stride, nv, kmax);
+    LFT_LAUNCH_OK("k_scene_divide_shear");
+    return 0;
+}
+int lft_scene_integrate_shear(const float* sr_patches, const int* shear, float* sr_scene, int A, int h0, int w0, int patch, int stride, int s, void* stream) {
+    const char* who = "lft_scene_integrate_shear";
+    int nu, nv, kmax;
+    if (!sr_patches || !shear || !sr_scene) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (A < 1 || s < 1) return fail(LFT_ERR_ARG, "%s: angRes %d, scale factor %d", who, A, s);
+    if (int rc = shear_tiling_ok(who, A, h0, w0, patch, stride, &nu, &nv, &kmax)) return rc;
+    // this launch: one block row per row of the SR scene mosaic; its columns, the patch index and a patch mosaic's side are ints
+    if ((long long)A * h0 * s > 65535) return fail(LFT_ERR_SHAPE, "%s: an SR scene mosaic of %lld rows needs more than 65535 blocks in the grid's y", who, (long long)A * h0 * s);
+    if ((long long)A * w0 * s > 0x7fffffffLL || (long long)nu * nv > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "%s: an SR scene mosaic of %lld columns in %d x %d patches is indexed beyond 2^31", who, (long long)A * w0 * s, nu, nv);
+    if ((long long)patch * s * A > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: SR patch mosaics of %lld pixels a side", who, (long long)patch * s * A);
+    const dim3 grid((unsigned)((A * w0 * s + 255) / 256), (unsigned)(A * h0 * s));
+    k_scene_integrate_shear<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(sr_patches, shear, sr_scene, A, patch * s, stride * s, h0 * s, w0 * s, nv, s, kmax);
+    LFT_LAUNCH_OK("k_scene_integrate_shear");
+    return 0;
+}
+int lft_shear_vote(const int* index, const float* confidence, const int* slopes, int B, int H, int W, int D, int margin, float min_confidence, int* counts,
+                   int* shear, void* stream) {
+    const char* who = "lft_shear_vote";
+    if (!index || !confidence || !slopes || !counts || !shear) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    if (B < 0 || H < 1 || W < 1) return fail(LFT_ERR_SHAPE, "%s: B = %d, maps of %d x %d", who, B, H, W);
+    if (D < 1 || D > 2 * LFT_SHEAR_MAX + 1) return fail(LFT_ERR_SHAPE, "%s: %d slopes outside 1 .. %d", who, D, 2 * LFT_SHEAR_MAX + 1);
+    if (margin < 0 || 2LL * margin >= std::min(H, W)) return fail(LFT_ERR_SHAPE, "%s: margin %d leaves nothing of maps of %d x %d", who, margin, H, W);
+    if (!std::isfinite(min_confidence)) return fail(LFT_ERR_ARG, "%s: min_confidence %g must be finite", who, min_confidence);
+    if (B == 0) return 0;                                           // nothing to vote on
+    const VoteArgs a{index, confidence, slopes, H, W, D, margin, min_confidence, counts, shear};
+    k_shear_vote<<<dim3((unsigned)B), 256, 0, static_cast<hipStream_t>(stream)>>>(a);
+    LFT_LAUNCH_OK("k_shear_vote");
     return 0;
 }
 

@@ -1,7 +1,7 @@
 """Super-resolve one raw RGB light field and write its views as PNG files (GPU box).
 
   python tools/super_resolve.py --angRes 5 --scale_factor 4 --path_pre_pth LFT_5x5_4x.pth.tar --lf scene.mat --out_dir out/
-                                [--self_ensemble dihedral|flips|none] [--precision fp32|bf16|fp16] [--bicubic] [--mosaic]
+                                [--self_ensemble dihedral|flips|none] [--precision fp32|bf16|fp16] [--bicubic] [--mosaic] [--shear auto|K]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C] (uint8, or single / double in [0, 1]); its centre angRes x angRes
 views are the LOW-resolution input.  Writes <out_dir>/view_<u>_<v>.png, 8-bit RGB, one per view (lft_amd.colour.super_resolve_lf:
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from lft_amd import colour, png, prepare, trainer  # noqa: E402
+from lft_amd import colour, png, prepare, scene, trainer  # noqa: E402
 
 
 def write_views(out_dir: str, views: torch.Tensor, prefix: str, mosaic_name=None):
@@ -62,13 +62,17 @@ def main(argv=None):
     ap.add_argument("--mosaic", action="store_true", help="also write the whole array of views as one PNG")
     ap.add_argument("--patch_size_for_test", type=int, default=32)
     ap.add_argument("--stride_for_test", type=int, default=16)
+    ap.add_argument("--shear", default=None, help="auto, or a whole number of LR pixels per view step: per-patch disparity compensation")
     args = ap.parse_args(argv)
+    shear = scene.parse_shear(args.shear)
+    if isinstance(shear, int):
+        scene.check_shear_limit(shear, args.angRes, args.patch_size_for_test, args.stride_for_test)
 
     dev = torch.device("cuda", 0)
     net = load_model(args, dev)
     lf = load_field(args.lf, args.angRes, dev)
     os.makedirs(args.out_dir, exist_ok=True)
-    sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble)
+    sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble, shear=shear)
     paths = write_views(args.out_dir, sr, "view", "mosaic.png" if args.mosaic else None)
     if args.bicubic:
         paths += write_views(args.out_dir, colour.bicubic_lf(lf, args.angRes, args.scale_factor), "bicubic",
