@@ -108,9 +108,9 @@ def bicubic_lf(lf, A: int, s: int, out_dtype=torch.uint8, device=None) -> torch.
 
 @torch.no_grad()
 def super_resolve_lf(net, lf, patch: int = 32, stride: int = 16, max_batch: int = 64, ensemble=None,
-                     out_dtype=torch.uint8, shear=None) -> torch.Tensor:
+                     out_dtype=torch.uint8, shear=None, blend=None) -> torch.Tensor:
     """Super-resolved RGB views [A, A, s*H, s*W, 3] of a low-resolution RGB light field: ``luma`` -> the network over the whole
-    scene (``scene.super_resolve_scene``: any precision of `net`, any ``ensemble=`` or ``shear=``) -> ``merge``.  A loaded array goes to the
+    scene (``scene.super_resolve_scene``: any precision of `net`, any ``ensemble=``, ``shear=`` or ``blend=``) -> ``merge``.  A loaded array goes to the
     device of the network's parameters."""
     from . import scene
     A, s = net.angRes, net.factor
@@ -118,5 +118,5 @@ def super_resolve_lf(net, lf, patch: int = 32, stride: int = 16, max_batch: int 
     if isinstance(lf, np.ndarray):
         dev = next(net.parameters()).device
     t = _field(lf, A, dev)
-    sr_y = scene.super_resolve_scene(net, luma(t, A), patch, stride, max_batch, ensemble, shear)
+    sr_y = scene.super_resolve_scene(net, luma(t, A), patch, stride, max_batch, ensemble, shear, **({} if blend is None else {"blend": blend}))
     return merge(t, sr_y, A, s, out_dtype)

@@ -2,7 +2,8 @@
 // tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity, view
 // synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h), the sweep's
 // occlusion-aware cost (declared in include/lft_hip_occlusion.h), the all-in-focus image from the winning partial aperture
-// (declared in include/lft_hip_aif.h) and scene tiling with a per-patch integer shear (declared in include/lft_hip_shear.h).
+// (declared in include/lft_hip_aif.h), scene tiling with a per-patch integer shear (declared in include/lft_hip_shear.h) and
+// windowed blending of overlapping SR patches (declared in include/lft_hip_blend.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
@@ -10,8 +11,10 @@
 #include "../../include/lft_hip_occlusion.h"
 #include "../../include/lft_hip_aif.h"
 #include "../../include/lft_hip_shear.h"
+#include "../../include/lft_hip_blend.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_shear.cuh"     // scene tiling with a per-patch integer shear, the vote that chooses it (lft_scene_divide_shear, lft_shear_vote)
+#include "lft_blend.cuh"     // windowed blending of overlapping SR patches into the SR scene (lft_scene_integrate_blend)
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
@@ -703,6 +706,31 @@ int lft_shear_vote(const int* index, const float* confidence, const int* slopes,
     const VoteArgs a{index, confidence, slopes, H, W, D, margin, min_confidence, counts, shear};
     k_shear_vote<<<dim3((unsigned)B), 256, 0, static_cast<hipStream_t>(stream)>>>(a);
     LFT_LAUNCH_OK("k_shear_vote");
+    return 0;
+}
+
+// ---- windowed blending of overlapping SR patches (lft_blend.cuh; declared in include/lft_hip_blend.h) ----
+int lft_scene_integrate_blend(const float* sr_patches, const int* shear, const float* window, float* sr_scene, int A, int h0, int w0, int patch, int stride,
+                              int s, void* stream) {
+    const char* who = "lft_scene_integrate_blend";
+    int nu, nv, kmax;
+    if (!sr_patches || !window || !sr_scene) return fail(LFT_ERR_ARG, "%s: null pointer", who);      // shear may be null: no shear
+    if (A < 1) return fail(LFT_ERR_ARG, "%s: angRes %d", who, A);
+    if (s != 2 && s != 4) return fail(LFT_ERR_ARG, "%s: scale factor %d (2 or 4)", who, s);
+    if (int rc = shear_tiling_ok(who, A, h0, w0, patch, stride, &nu, &nv, &kmax)) return rc;
+    // this launch: k_scene_integrate_shear's grid and its limits, and the window table in LDS
+    if ((long long)patch * s > LFT_BLEND_MAX_PZ) return fail(LFT_ERR_SHAPE, "%s: a window of %lld entries (at most %d)", who, (long long)patch * s, LFT_BLEND_MAX_PZ);
+    if ((long long)A * h0 * s > 65535) return fail(LFT_ERR_SHAPE, "%s: an SR scene mosaic of %lld rows needs more than 65535 blocks in the grid's y", who, (long long)A * h0 * s);
+    if ((long long)A * w0 * s > 0x7fffffffLL || (long long)nu * nv > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "%s: an SR scene mosaic of %lld columns in %d x %d patches is indexed beyond 2^31", who, (long long)A * w0 * s, nu, nv);
+    if ((long long)patch * s * A > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: SR patch mosaics of %lld pixels a side", who, (long long)patch * s * A);
+    const dim3 grid((unsigned)((A * w0 * s + 255) / 256), (unsigned)(A * h0 * s));
+    // the candidates per axis, ceil(2*pz/S) - 1: up to 3 the kernel has them written out, beyond that it loops
+    const int nc = (2 * patch + stride - 1) / stride - 1;
+    const auto kernel = nc == 1 ? k_scene_integrate_blend<1> : nc == 2 ? k_scene_integrate_blend<2> : nc == 3 ? k_scene_integrate_blend<3> : k_scene_integrate_blend<0>;
+    kernel<<<grid, 256, (size_t)patch * s * sizeof(float), static_cast<hipStream_t>(stream)>>>(sr_patches, shear, window, sr_scene, A, patch * s, stride * s, h0 * s,
+                                                                                           w0 * s, nu, nv, s, kmax);
+    LFT_LAUNCH_OK("k_scene_integrate_blend");
     return 0;
 }
 

@@ -36,11 +36,28 @@ aligns the views.
 - `shear[b] = slopes[j*]`, where `j*` has the largest count. On a tie the smallest `|slope|` wins, then the smaller slope. If every
   count is 0 the result is 0.
 - Counts are integers, so arrival order cannot matter.
+
+Windowed blending of overlapping SR patches
+-------------------------------------------
+``integrate`` keeps the central `stride·s` square of every SR patch and drops the rest; the kept squares meet edge to edge, so an
+error that differs from patch to patch shows as a seam.  With `blend=` every SR patch pixel that shows a scene pixel contributes to
+it, weighted by a separable window over the patch (lft_scene_integrate_blend: one gather kernel, with or without `shear=`;
+csrc/lft_blend.cuh, declared in include/lft_hip_blend.h).  `blend=None` is the crop and runs the kernels it always ran.
+
+All sizes are in SR pixels.  `pz = patch·s`, `S = stride·s`, `bdr = (pz − S)/2` (an odd `patch − stride` is refused), `u0 = A // 2`,
+`sk_n = s·clamp(shear[n], ±kmax)`, or 0 without shear.  Pixel `(a, b)` of view `(u, v)` of SR patch `n = ku·nv + kv` shows scene pixel
+`Y = ku·S + a − bdr + sk_n·(u − u0)`, `X = kv·S + b − bdr + sk_n·(v − u0)`: the sheared integrate's map, read backwards.  The pixel
+contributes iff `0 ≤ Y < h0·s` and `0 ≤ X < w0·s`; that drops the reflected margin and everything beyond the extended view, so no
+zero-filled position ever contributes.  With the window table `w[0..pz)`, fp32 and strictly positive,
+`out = Σ (w[a]·w[b])·sub[n,u,a,v,b] / Σ w[a]·w[b]`, summed over the contributing patches in ascending `ku`, then `kv`, every operation
+one rounded fp32 operation and the quotient correctly rounded.  The tables (``window_table``) are built in fp64 and rounded once:
+`"hann"`: `sin²(π(i+½)/pz)`, `"linear"`: `min(i+½, pz−i−½)·2/pz`, `"flat"`: 1.
 """
 from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -92,6 +109,50 @@ def _shear_tensor(shear, n: int, like: torch.Tensor) -> torch.Tensor:
     return shear.contiguous()
 
 
+WINDOWS = ("hann", "linear", "flat")
+_windows = {}                                           # (kind, pz, device) -> the window table on that device
+
+
+def window_table(kind: str, pz: int) -> np.ndarray:
+    """The window table of `kind` over a patch side of pz SR pixels: built in fp64, rounded once to fp32 [pz]; every entry is
+    positive and the table is symmetric."""
+    if kind not in WINDOWS:
+        raise LftError(f"blend must be None, one of {', '.join(WINDOWS)}, or a float32 tensor, got {kind!r}")
+    if isinstance(pz, bool) or int(pz) != pz or not 1 <= pz <= _lib.BLEND_MAX_PZ:
+        raise LftError(f"a window of {pz!r} entries (1 .. {_lib.BLEND_MAX_PZ})")
+    c = np.arange(int(pz), dtype=np.float64) + 0.5
+    w = {"hann": lambda: np.sin(np.pi * c / pz) ** 2, "linear": lambda: np.minimum(c, pz - c) * 2.0 / pz, "flat": lambda: np.ones(int(pz))}[kind]()
+    return w.astype(np.float32)
+
+
+def blend_window(kind: str, pz: int, device=None) -> torch.Tensor:
+    """``window_table(kind, pz)`` on `device` (default: the current HIP device), float32 [pz]; made once per device and kept."""
+    table = window_table(kind, pz)                      # a wrong kind or size is refused before the device is asked for
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    key = (kind, int(pz), str(device))
+    if key not in _windows:
+        _windows[key] = torch.from_numpy(table).to(device)
+    return _windows[key]
+
+
+def clear_cache() -> None:
+    """Drop the cached window tables."""
+    _windows.clear()
+
+
+def check_blend(blend, ang: int, patch: int, stride: int, scale: int) -> None:
+    """What the blended integrate refuses without a device: a `blend` that is neither a window's name nor a float32 tensor
+    [patch*scale], a tiling without the same border on both sides, a scale factor other than 2 or 4."""
+    if isinstance(blend, str):
+        window_table(blend, patch * scale)
+    elif not isinstance(blend, torch.Tensor) or blend.dtype != torch.float32 or tuple(blend.shape) != (patch * scale,):
+        raise LftError(f"blend must be None, one of {', '.join(WINDOWS)}, or a float32 tensor of shape [{patch * scale}] (positive weights over the SR "
+                       f"patch side), got {getattr(blend, 'dtype', type(blend).__name__)} {tuple(getattr(blend, 'shape', ()))}")
+    if scale not in (2, 4):
+        raise LftError(f"blend: scale factor must be 2 or 4, got {scale}")
+    shear_limit(ang, patch, stride)                     # the tiling: angRes, stride <= patch, an even patch - stride
+
+
 def divide(scene: torch.Tensor, ang: int, patch: int = 32, stride: int = 16, shear=None) -> torch.Tensor:
     """scene: float32 [A*h0, A*w0] on a HIP device -> [numU*numV, 1, A*patch, A*patch].
     shear: None, or int32 [numU*numV] on the scene's device: view (u, v) of patch n is cut shear[n]*(u - u0), shear[n]*(v - u0)
@@ -114,18 +175,34 @@ def divide(scene: torch.Tensor, ang: int, patch: int = 32, stride: int = 16, she
     return out
 
 
-def integrate(sr_patches: torch.Tensor, ang: int, h0: int, w0: int, scale: int, patch: int = 32, stride: int = 16, shear=None) -> torch.Tensor:
+def integrate(sr_patches: torch.Tensor, ang: int, h0: int, w0: int, scale: int, patch: int = 32, stride: int = 16, shear=None, blend=None) -> torch.Tensor:
     """sr_patches: float32 [numU*numV, 1, A*patch*s, A*patch*s] -> SR scene mosaic [A*h0*s, A*w0*s].
     shear: None, or the int32 [numU*numV] the patches were cut with (``divide``): every SR patch is put back s*shear[n] pixels per
-    view step against the cut."""
-    if shear is not None:
+    view step against the cut.
+    blend: None (the crop: the central stride*s square of every patch, today's kernels), "hann", "linear" or "flat"
+    (``window_table``), or a float32 tensor [patch*s] of positive weights on the patches' device: the window-weighted mean of every
+    SR patch pixel that shows a scene pixel (the module docstring has the definition), with or without `shear`."""
+    if blend is not None:
+        check_blend(blend, ang, patch, stride, scale)
+    if shear is not None or blend is not None:
         nu, nv = scene_counts(h0, w0, patch, stride)
-        shear = _shear_tensor(shear, nu * nv, sr_patches)
+        if shear is not None:
+            shear = _shear_tensor(shear, nu * nv, sr_patches)
+        if blend is not None:
+            side = ang * patch * scale
+            if not isinstance(sr_patches, torch.Tensor) or tuple(sr_patches.shape) != (nu * nv, 1, side, side):
+                raise LftError(f"sr_patches must be [{nu * nv}, 1, {side}, {side}] for this tiling, got {tuple(getattr(sr_patches, 'shape', ()))}")
+            if isinstance(blend, torch.Tensor) and blend.device != sr_patches.device:
+                raise LftError(f"blend is on {blend.device}, the patches on {sr_patches.device}")
         if not sr_patches.is_cuda:
             raise LftError("sr_patches must be a float32 tensor on a HIP device")
     x = sr_patches.contiguous().float()
     out = torch.empty((ang * h0 * scale, ang * w0 * scale), dtype=torch.float32, device=x.device)
-    if shear is None:
+    if blend is not None:
+        w = blend_window(blend, patch * scale, x.device) if isinstance(blend, str) else blend.contiguous()
+        _lib.enqueue("lft_scene_integrate_blend", x.device, x.data_ptr(), None if shear is None else shear.data_ptr(), w.data_ptr(), out.data_ptr(),
+                     ang, h0, w0, patch, stride, scale)
+    elif shear is None:
         _lib.enqueue("lft_scene_integrate", x.device, x.data_ptr(), out.data_ptr(), ang, h0, w0, patch, stride, scale)
     else:
         _lib.enqueue("lft_scene_integrate_shear", x.device, x.data_ptr(), shear.data_ptr(), out.data_ptr(), ang, h0, w0, patch, stride, scale)
@@ -192,7 +269,8 @@ def estimate_shear(patches: torch.Tensor, ang: int, max_shear=None, min_confiden
 
 
 @torch.no_grad()
-def super_resolve_scene(net, scene: torch.Tensor, patch: int = 32, stride: int = 16, max_batch: int = 64, ensemble=None, shear=None) -> torch.Tensor:
+def super_resolve_scene(net, scene: torch.Tensor, patch: int = 32, stride: int = 16, max_batch: int = 64, ensemble=None, shear=None,
+                        blend=None) -> torch.Tensor:
     """Equivalent of the body of the reference's test() for one scene (test.py:79-101), batched.
     ensemble: None, or a mode of lft_amd.ensemble.MASKS ("dihedral", "flips", "none") / an 8-bit mask -- geometric self-ensemble:
     every patch goes through the network in its E dihedral variants (chunks of max(1, max_batch // E) patches) and
@@ -201,9 +279,14 @@ def super_resolve_scene(net, scene: torch.Tensor, patch: int = 32, stride: int =
     refused), an int32 tensor [numU*numV] on the scene's device (one k per patch, clamped to the limit), or "auto":
     ``estimate_shear`` on the unsheared patches.  The patches are cut with it and the SR patches put back against it (the module
     docstring has the definition).  shear together with ensemble is refused: the dihedral variants of a sheared patch are not
-    sheared patches of the variant scene, and that pairing is not built."""
+    sheared patches of the variant scene, and that pairing is not built.
+    blend: None (the crop of ``integrate``: today's launches, today's bits), or a window of ``integrate``'s `blend=`: the SR patches
+    are blended where they overlap, with or without `shear`.  With `ensemble` the variants of every patch are averaged by
+    lft_amd.ensemble.merge and the merged patches blended: two launches in place of lft_scene_integrate_ens."""
     A, s = net.angRes, net.factor
     h0, w0 = scene.shape[0] // A, scene.shape[1] // A
+    if blend is not None:
+        check_blend(blend, A, patch, stride, s)
     if shear is not None:
         if ensemble is not None:
             raise LftError("shear together with ensemble is not supported: pass one of them")
@@ -219,12 +302,23 @@ def super_resolve_scene(net, scene: torch.Tensor, patch: int = 32, stride: int =
         mask = ens.mask_of(ensemble)
         per = max(1, max_batch // len(ens.codes_of(mask)))
         outs = [net(ens.expand(patches[i:i + per], mask)) for i in range(0, patches.shape[0], per)]
+        if blend is not None:
+            return integrate(ens.merge(torch.cat(outs, dim=0), mask), A, h0, w0, s, patch, stride, blend=blend)
         return integrate_ensemble(torch.cat(outs, dim=0), mask, A, h0, w0, s, patch, stride)
     if isinstance(shear, str):                      # auto: the sweep sees the unsheared patches, the network the re-cut ones
         shear = estimate_shear(patches, A, stride=stride)
         patches = divide(scene, A, patch, stride, shear)
     outs = [net(patches[i:i + max_batch]) for i in range(0, patches.shape[0], max_batch)]
-    return integrate(torch.cat(outs, dim=0), A, h0, w0, s, patch, stride, shear)
+    return integrate(torch.cat(outs, dim=0), A, h0, w0, s, patch, stride, shear, blend)
+
+
+def parse_blend(text):
+    """The --blend option of the tools: None or "none" (the crop), or a window's name."""
+    if text is None or text == "none":
+        return None
+    if text not in WINDOWS:
+        raise LftError(f"--blend takes none, {', '.join(WINDOWS)}, got {text!r}")
+    return text
 
 
 def parse_shear(text):

@@ -2,6 +2,7 @@
 
   python tools/super_resolve.py --angRes 5 --scale_factor 4 --path_pre_pth LFT_5x5_4x.pth.tar --lf scene.mat --out_dir out/
                                 [--self_ensemble dihedral|flips|none] [--precision fp32|bf16|fp16] [--bicubic] [--mosaic] [--shear auto|K]
+                                [--blend hann|linear|flat]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C] (uint8, or single / double in [0, 1]); its centre angRes x angRes
 views are the LOW-resolution input.  Writes <out_dir>/view_<u>_<v>.png, 8-bit RGB, one per view (lft_amd.colour.super_resolve_lf:
@@ -63,8 +64,12 @@ def main(argv=None):
     ap.add_argument("--patch_size_for_test", type=int, default=32)
     ap.add_argument("--stride_for_test", type=int, default=16)
     ap.add_argument("--shear", default=None, help="auto, or a whole number of LR pixels per view step: per-patch disparity compensation")
+    ap.add_argument("--blend", default=None, help="hann, linear or flat: blend the overlapping SR patches with this window (default: the central crop)")
     args = ap.parse_args(argv)
     shear = scene.parse_shear(args.shear)
+    blend = scene.parse_blend(args.blend)
+    if blend is not None:
+        scene.check_blend(blend, args.angRes, args.patch_size_for_test, args.stride_for_test, args.scale_factor)
     if isinstance(shear, int):
         scene.check_shear_limit(shear, args.angRes, args.patch_size_for_test, args.stride_for_test)
 
@@ -72,7 +77,8 @@ def main(argv=None):
     net = load_model(args, dev)
     lf = load_field(args.lf, args.angRes, dev)
     os.makedirs(args.out_dir, exist_ok=True)
-    sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble, shear=shear)
+    sr = colour.super_resolve_lf(net, lf, args.patch_size_for_test, args.stride_for_test, ensemble=args.self_ensemble, shear=shear,
+                                 **({} if blend is None else {"blend": blend}))
     paths = write_views(args.out_dir, sr, "view", "mosaic.png" if args.mosaic else None)
     if args.bicubic:
         paths += write_views(args.out_dir, colour.bicubic_lf(lf, args.angRes, args.scale_factor), "bicubic",
