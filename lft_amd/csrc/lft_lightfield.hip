@@ -2,8 +2,9 @@
 // tiling, dihedral transforms and self-ensemble, view metrics, data preparation, the colour path, refocus, disparity, view
 // synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h), the sweep's
 // occlusion-aware cost (declared in include/lft_hip_occlusion.h), the all-in-focus image from the winning partial aperture
-// (declared in include/lft_hip_aif.h), scene tiling with a per-patch integer shear (declared in include/lft_hip_shear.h) and
-// windowed blending of overlapping SR patches (declared in include/lft_hip_blend.h).
+// (declared in include/lft_hip_aif.h), scene tiling with a per-patch integer shear (declared in include/lft_hip_shear.h),
+// windowed blending of overlapping SR patches (declared in include/lft_hip_blend.h) and the refinement of a selected disparity map
+// (declared in include/lft_hip_refine.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
@@ -12,6 +13,7 @@
 #include "../../include/lft_hip_aif.h"
 #include "../../include/lft_hip_shear.h"
 #include "../../include/lft_hip_blend.h"
+#include "../../include/lft_hip_refine.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_shear.cuh"     // scene tiling with a per-patch integer shear, the vote that chooses it (lft_scene_divide_shear, lft_shear_vote)
 #include "lft_blend.cuh"     // windowed blending of overlapping SR patches into the SR scene (lft_scene_integrate_blend)
@@ -26,6 +28,7 @@
 #include "lft_sgm.cuh"       // semi-global aggregation of a cost volume: the path scans, the sum and the selection (lft_sgm)
 #include "lft_occlusion.cuh" // the sweep's cost from partial apertures: min over the whole aperture and up to four subsets (lft_disparity_occ)
 #include "lft_aif.cuh"       // the all-in-focus image from the winning partial aperture: one gather pass over the views (lft_aif_at)
+#include "lft_refine.cuh"    // refinement of a selected map: cross-view check, farther-neighbour fill, guided weighted median (lft_disp_*)
 
 namespace {
 
@@ -731,6 +734,80 @@ int lft_scene_integrate_blend(const float* sr_patches, const int* shear, const f
     kernel<<<grid, 256, (size_t)patch * s * sizeof(float), static_cast<hipStream_t>(stream)>>>(sr_patches, shear, window, sr_scene, A, patch * s, stride * s, h0 * s,
                                                                                            w0 * s, nu, nv, s, kmax);
     LFT_LAUNCH_OK("k_scene_integrate_blend");
+    return 0;
+}
+
+// ---- refinement of a selected disparity map (lft_refine.cuh; declared in include/lft_hip_refine.h) ----
+static_assert(kRnMaxViews == LFT_REFINE_MAX_VIEWS && kRnMaxRadius == LFT_REFINE_MAX_RADIUS && kRnMaxFill == LFT_REFINE_MAX_FILL && kRnTable == LFT_REFINE_TABLE,
+              "the header states the limits the kernels are built for");
+// What the three calls judge of their maps after their own arguments: 0 with *empty set for a shape without work.
+static int refine_maps_ok(const char* who, int B, int H, int W, bool* empty) {
+    if (B < 0 || H < 0 || W < 0) return fail(LFT_ERR_SHAPE, "%s: negative size in B = %d, maps of %d x %d", who, B, H, W);
+    *empty = B == 0 || H == 0 || W == 0;
+    if (*empty) return 0;                                           // nothing to read or write
+    if (H > (1 << 24) || W > (1 << 24)) return fail(LFT_ERR_SHAPE, "%s: maps of %d x %d: pixel coordinates are fp32, at most 2^24", who, H, W);
+    if ((double)H * W > 2147483647.0) return fail(LFT_ERR_SHAPE, "%s: maps of %d x %d have more than 2^31 pixels", who, H, W);
+    return 0;
+}
+static int refine_near_ok(const char* who, int near) {
+    if (near != LFT_VIEW_NEAR_LARGER && near != LFT_VIEW_NEAR_SMALLER) return fail(LFT_ERR_ARG, "%s: near must be LFT_VIEW_NEAR_LARGER or LFT_VIEW_NEAR_SMALLER, got %d", who, near);
+    return 0;
+}
+static int refine_blocks_ok(const char* who, long long blocks, int B, int H, int W) {
+    if (blocks > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: %d maps of %d x %d need more than 2^31 blocks", who, B, H, W);
+    return 0;
+}
+int lft_disp_check(const float* disparity, const float* view_disparity, const float* deltas, int B, int N, int H, int W, float tau, int near, int min_agree,
+                   int max_conflict, unsigned char* valid, unsigned char* agree, unsigned char* conflict, void* stream) {
+    const char* who = "lft_disp_check";
+    bool empty;
+    if (N < 1 || N > LFT_REFINE_MAX_VIEWS) return fail(LFT_ERR_ARG, "%s: %d views outside 1 .. %d", who, N, LFT_REFINE_MAX_VIEWS);
+    if (!std::isfinite(tau) || tau < 0.0f) return fail(LFT_ERR_ARG, "%s: tau %g must be finite and >= 0", who, tau);
+    if (int rc = refine_near_ok(who, near)) return rc;
+    if (min_agree < 0 || max_conflict < 0) return fail(LFT_ERR_ARG, "%s: min_agree %d and max_conflict %d must be >= 0", who, min_agree, max_conflict);
+    if (int rc = refine_maps_ok(who, B, H, W, &empty)) return rc;
+    if (empty) return 0;
+    if (!disparity || !view_disparity || !deltas || !valid || !agree || !conflict) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    const long long per = ((long long)H * W + 255) / 256;
+    if (int rc = refine_blocks_ok(who, per * B, B, H, W)) return rc;
+    const CheckArgs a{disparity, view_disparity, deltas, tau, near == LFT_VIEW_NEAR_SMALLER, min_agree, max_conflict, H, W, N, (int)per, valid, agree, conflict};
+    k_disp_check<<<dim3((unsigned)(per * B)), 256, 0, static_cast<hipStream_t>(stream)>>>(a);
+    LFT_LAUNCH_OK("k_disp_check");
+    return 0;
+}
+int lft_disp_fill(const float* disparity, const unsigned char* valid, int B, int H, int W, int reach, int near, float* out, unsigned char* holes, void* stream) {
+    const char* who = "lft_disp_fill";
+    bool empty;
+    if (reach < 0 || reach > LFT_REFINE_MAX_FILL) return fail(LFT_ERR_ARG, "%s: reach %d outside 0 .. %d", who, reach, LFT_REFINE_MAX_FILL);
+    if (int rc = refine_near_ok(who, near)) return rc;
+    if (int rc = refine_maps_ok(who, B, H, W, &empty)) return rc;
+    if (empty) return 0;
+    if (!disparity || !out || !holes) return fail(LFT_ERR_ARG, "%s: null pointer", who);     // valid may be null: all valid
+    if (out == disparity) return fail(LFT_ERR_ARG, "%s: the fill does not work in place (out == disparity)", who);
+    const long long tiles_x = ((long long)W + kRfTile - 1) / kRfTile, rtiles = tiles_x * (((long long)H + kVwRows - 1) / kVwRows);
+    if (int rc = refine_blocks_ok(who, rtiles * B, B, H, W)) return rc;
+    const DispFillArgs a{disparity, valid, reach, near == LFT_VIEW_NEAR_SMALLER, H, W, (int)tiles_x, (int)rtiles, out, holes};
+    k_disp_fill<<<dim3((unsigned)(rtiles * B)), 256, 0, static_cast<hipStream_t>(stream)>>>(a);
+    LFT_LAUNCH_OK("k_disp_fill");
+    return 0;
+}
+int lft_disp_wmedian(const float* disparity, const unsigned char* valid, const unsigned char* guide, const unsigned short* table, int B, int H, int W, int C,
+                     int radius, float* out, unsigned char* flags, void* stream) {
+    const char* who = "lft_disp_wmedian";
+    bool empty;
+    if (C < 1 || C > 4) return fail(LFT_ERR_ARG, "%s: %d guide channels (1 .. 4)", who, C);
+    if (radius < 0 || radius > LFT_REFINE_MAX_RADIUS) return fail(LFT_ERR_ARG, "%s: radius %d outside 0 .. %d", who, radius, LFT_REFINE_MAX_RADIUS);
+    if (int rc = refine_maps_ok(who, B, H, W, &empty)) return rc;
+    if (empty) return 0;
+    if (!disparity || !guide || !table || !out || !flags) return fail(LFT_ERR_ARG, "%s: null pointer", who);     // valid may be null: all valid
+    if (out == disparity) return fail(LFT_ERR_ARG, "%s: the median does not work in place (out == disparity)", who);
+    const long long tiles_x = ((long long)W + kRnTileW - 1) / kRnTileW, tiles = tiles_x * (((long long)H + kRnTileH - 1) / kRnTileH);
+    if (int rc = refine_blocks_ok(who, tiles * B, B, H, W)) return rc;
+    const MedianArgs a{disparity, valid, guide, table, H, W, C, (int)tiles_x, (int)tiles, out, flags};
+    static void (*const kernel[kRnMaxRadius + 1])(MedianArgs) = {k_disp_wmedian<0>, k_disp_wmedian<1>, k_disp_wmedian<2>, k_disp_wmedian<3>,
+                                                                 k_disp_wmedian<4>, k_disp_wmedian<5>, k_disp_wmedian<6>, k_disp_wmedian<7>};
+    kernel[radius]<<<dim3((unsigned)(tiles * B)), 256, 0, static_cast<hipStream_t>(stream)>>>(a);
+    LFT_LAUNCH_OK("k_disp_wmedian");
     return 0;
 }
 

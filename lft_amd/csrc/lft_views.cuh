@@ -42,7 +42,8 @@
 //                  -- neighbouring lanes at neighbouring addresses except across depth edges --, the row pass, the column pass
 //                  and the two pairs of sums in registers.  No LDS, no barrier.
 // The steps shared with k_view_render_vis and k_view_fill (lft_visibility.cuh) are device functions here, each written once:
-// vw_fill (the fill search of step 2) and vw_sample (one view at (sy, sx): vw_axis twice, the view's base, the TAPS^2 * C gather, rows
+// vw_search (the farther-neighbour search of step 2, which k_disp_fill of lft_refine.cuh runs too), vw_fill (step 2 on the pre-fill
+// keys, through vw_search) and vw_sample (one view at (sy, sx): vw_axis twice, the view's base, the TAPS^2 * C gather, rows
 // then columns) for all of them; vw_pixel (the workgroup's id and the lane to batch element, target and pixel of a 32 x 8 tile) and
 // vw_fill_store (vw_fill, then Dt and holes written) for those two.  k_view_render keeps its own pixel decode, stores and quotient:
 // through the helpers it measured slower.  The two render algorithms stay two kernels.
@@ -167,6 +168,22 @@ __device__ __forceinline__ void vw_axis(float s, int n, int st, int (&off)[TAPS]
     }
 }
 
+// The farther-neighbour search of step 2, shared with k_disp_fill (lft_refine.cuh): key_at(y, x) is the key of a pixel that has a
+// value and 0 of one that has none.  The nearest keyed pixel to the left and to the right in the row, each within `fill` pixels;
+// if neither side has one, the same up and down the column.  Returns the farther of the two found (the smaller key for either
+// `near`), the one found, or 0 for none.
+template <typename KeyAt>
+__device__ __forceinline__ uint32_t vw_search(KeyAt key_at, int y, int x, int H, int W, int fill) {
+    uint32_t k0 = 0u, k1 = 0u;
+    for (int s = 1; s <= fill && x - s >= 0 && !k0; ++s) k0 = key_at(y, x - s);
+    for (int s = 1; s <= fill && x + s < W && !k1; ++s) k1 = key_at(y, x + s);
+    if (!k0 && !k1) {
+        for (int s = 1; s <= fill && y - s >= 0 && !k0; ++s) k0 = key_at(y - s, x);
+        for (int s = 1; s <= fill && y + s < H && !k1; ++s) k1 = key_at(y + s, x);
+    }
+    return k0 && k1 ? min(k0, k1) : (k0 | k1);
+}
+
 // The fill of one pixel from the pre-fill keys of its target (step 2): Dt[y,x], and whether the pixel was a hole.  The farther of
 // two found values has the smaller key for either `near`.  keys points at the target's plane, dr at the batch element's.
 __device__ __forceinline__ float vw_fill(const uint32_t* keys, const float* dr, int y, int x, int H, int W, int fill, int neg, float lo, float hi,
@@ -175,15 +192,9 @@ __device__ __forceinline__ float vw_fill(const uint32_t* keys, const float* dr, 
     hole = key == 0u;
     float d;
     if (hole) {
-        uint32_t k0 = 0u, k1 = 0u;
-        for (int s = 1; s <= fill && x - s >= 0 && !k0; ++s) k0 = keys[(size_t)y * W + x - s];
-        for (int s = 1; s <= fill && x + s < W && !k1; ++s) k1 = keys[(size_t)y * W + x + s];
-        if (!k0 && !k1) {
-            for (int s = 1; s <= fill && y - s >= 0 && !k0; ++s) k0 = keys[(size_t)(y - s) * W + x];
-            for (int s = 1; s <= fill && y + s < H && !k1; ++s) k1 = keys[(size_t)(y + s) * W + x];
-        }
-        if (k0 || k1) {
-            key = k0 && k1 ? min(k0, k1) : (k0 | k1);
+        const uint32_t found = vw_search([&](int yy, int xx) { return keys[(size_t)yy * W + xx]; }, y, x, H, W, fill);
+        if (found) {
+            key = found;
             d = vw_unkey(key);
             if (neg) d = -d;
         } else {

@@ -3,6 +3,7 @@
   python tools/disparity.py --lf scene.mat --angRes 5 --out_dir out/ --slopes=-2:2:33 --radius 2 [--aperture full|disk|gaussian]
                             [--interp nearest|linear|cubic] [--regularize [--p1 P1 --p2 P2] [--paths 4|8] [--edge_gain G]]
                             [--occlusion [halves|quadrants] [--margin B] [--min_views N] [--subset_aif]]
+                            [--refine [--refine_views cross|corners|all] [--tau T] [--median_radius R] [--median_sigma S] [--median_iterations I]]
                             [--path_pre_pth LFT_5x5_4x.pth.tar --scale_factor 4 [--precision ..] [--self_ensemble ..]] [--bicubic]
 
 The scene is a light-field .mat with the variable LF [U, V, H, W, C]; its centre angRes x angRes views are used.  Without
@@ -21,6 +22,12 @@ wins where it is --margin times better than the whole aperture, subsets with few
 <out_dir>/occlusion.png shows which subset set the cost at the chosen slope (0 black: all views agree; subset p as grey 63 p).
 --subset_aif (it needs --occlusion) renders all_in_focus.png from the views of that subset and not from all of them
 (lft_amd.disparity.disparity(all_in_focus="subset")): no ghost of the foreground in the band round a depth edge.
+--refine refines the map after the selection (lft_amd.refine.refine): the maps swept at --refine_views other positions say which
+pixels can be trusted (within --tau of each other, default the largest slope step), a weighted median of radius --median_radius
+guided by the centre view (--median_sigma, in units of the full range per channel) smooths the map along the image's edges, and what
+is left is filled from the farther neighbour.  It writes disparity_refined.png / .npy and valid.png (255 where the cross-view check
+trusts the raw map) beside the other files, and prints one JSON line with the share of invalid pixels and of pixels the median
+changed.  The sweeps at the other positions take --aperture, --interp, --radius, --regularize and --occlusion as the first does.
 Without these flags the files keep their bytes."""
 import argparse
 import json
@@ -33,7 +40,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from lft_amd import colour, disparity, png  # noqa: E402
+from lft_amd import colour, disparity, png, refine  # noqa: E402
 from refocus import parse_slopes  # noqa: E402  (tools/refocus.py)
 import super_resolve  # noqa: E402  (the loader of the scene and of the network)
 
@@ -77,6 +84,23 @@ def write_maps(out_dir, views, slopes, args, prefix=""):
     if r.subset is not None:
         paths.append(os.path.join(out_dir, prefix + "occlusion.png"))
         png.write_png(paths[-1], (r.subset * 63)[..., None].expand(-1, -1, 3).contiguous().cpu().numpy())
+    if args.refine:
+        paths += write_refined(out_dir, views, slopes, args, prefix)
+    return paths
+
+
+def write_refined(out_dir, views, slopes, args, prefix=""):
+    """--refine: disparity_refined.png / .npy and valid.png, and the JSON line.  Returns the paths written."""
+    r = refine.refine(views, slopes, positions=args.refine_views, tau=args.tau, radius=args.median_radius, sigma=args.median_sigma,
+                      iterations=args.median_iterations, sweep_radius=args.radius, aperture=args.aperture, interp=args.interp,
+                      regularize=regularize_arguments(views, slopes, args), occlusion=occlusion_arguments(args))
+    paths = [os.path.join(out_dir, prefix + name) for name in ("disparity_refined.png", "disparity_refined.npy", "valid.png")]
+    png.write_png(paths[0], grey(r.disparity, min(slopes), max(slopes)))
+    np.save(paths[1], r.disparity.cpu().numpy())
+    png.write_png(paths[2], grey(r.valid.float(), 0.0, 1.0))
+    changed = (r.disparity != r.raw.disparity) & (r.flags != 2)
+    print(json.dumps({"refine": prefix + "disparity_refined", "views": args.refine_views, "invalid_share": float((r.valid == 0).float().mean()),
+                      "median_changed_share": float(changed.float().mean()), "unfilled_share": float((r.flags == 2).float().mean())}))
     return paths
 
 
@@ -99,6 +123,12 @@ def main(argv=None):
     ap.add_argument("--margin", type=float, default=2.0, help="a subset wins where it is this many times better than the whole aperture, >= 1")
     ap.add_argument("--min_views", type=int, default=2, help="subsets with fewer views of non-zero weight are dropped, >= 2")
     ap.add_argument("--subset_aif", action="store_true", help="all_in_focus.png from the views of the subset that set the cost (needs --occlusion)")
+    ap.add_argument("--refine", action="store_true", help="cross-view check, guided weighted median and fill of the selected map; also writes disparity_refined.* and valid.png")
+    ap.add_argument("--refine_views", default="cross", choices=refine.WHICH, help="the other positions whose maps the check compares with")
+    ap.add_argument("--tau", type=float, default=None, help="two maps agree within this many slope units (default: the largest slope step)")
+    ap.add_argument("--median_radius", type=int, default=3, help="the median's window is (2 R + 1)^2, 0 .. 7")
+    ap.add_argument("--median_sigma", type=float, default=0.1, help="the guide's range weight falls by e per this share of the full range")
+    ap.add_argument("--median_iterations", type=int, default=1)
     ap.add_argument("--min_confidence", type=float, default=0.5, help="pixels counted by the printed disparity_error")
     ap.add_argument("--path_pre_pth", default=None, help="checkpoint in the reference's format: sweep the super-resolved views")
     ap.add_argument("--scale_factor", type=int, default=4)
