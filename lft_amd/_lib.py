@@ -29,9 +29,9 @@ def _header_text(header: str) -> str:
 globals().update({k: int(v) for k, v in re.findall(r"^#define LFT_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", _header_text("lft_hip.h"), flags=re.M)})
 # The headers added beside ABI 5 (lft_version unchanged), each with the prefix of its constants: VIEW_NEAR_LARGER, VIEW_NEAR_SMALLER,
 # VIEW_MAX_REACH, VIEW_MAX_FILL; SGM_MAX_D; VIS_MASK_VIEWS; OCC_MAX_SUBSETS; lft_hip_aif.h (AIF_) defines none; SHEAR_MAX; BLEND_MAX_PZ;
-# REFINE_MAX_VIEWS, REFINE_MAX_RADIUS, REFINE_MAX_FILL, REFINE_TABLE; FOCAL_MAX_D.
+# FIELD_MAX_VIEWS; REFINE_MAX_VIEWS, REFINE_MAX_RADIUS, REFINE_MAX_FILL, REFINE_TABLE; FOCAL_MAX_D.
 ADDON_HEADERS = {"lft_hip_views.h": "VIEW_", "lft_hip_sgm.h": "SGM_", "lft_hip_visibility.h": "VIS_", "lft_hip_occlusion.h": "OCC_", "lft_hip_aif.h": "AIF_",
-                 "lft_hip_shear.h": "SHEAR_", "lft_hip_blend.h": "BLEND_", "lft_hip_refine.h": "REFINE_", "lft_hip_focal.h": "FOCAL_"}
+                 "lft_hip_shear.h": "SHEAR_", "lft_hip_blend.h": "BLEND_", "lft_hip_field.h": "FIELD_", "lft_hip_refine.h": "REFINE_", "lft_hip_focal.h": "FOCAL_"}
 for _header, _prefix in ADDON_HEADERS.items():
     globals().update({k: int(v) for k, v in re.findall(r"^#define LFT_(%s\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$" % _prefix, _header_text(_header), flags=re.M)})
 
@@ -86,7 +86,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 #   lft_lightfield   scene tiling, dihedral transforms, view metrics, data preparation, colour, refocus, disparity, view synthesis
 #                    with and without the visibility test, semi-global aggregation, the sweep's occlusion-aware cost, the all-in-focus
 #                    image from the winning partial aperture, scene tiling with a per-patch integer shear, windowed blending of
-#                    overlapping SR patches, the refinement of a selected disparity map (check, fill, weighted median)
+#                    overlapping SR patches, angular tiling of a U x V field, the refinement of a selected disparity map (check, fill, weighted median)
 #   lft_objective    losses (the focal-stack term and the adjoint of refocus among them), Adam, the guarded step, the EMA
 # A unit emits the kernels of the headers it includes, so each includes only what it launches from.
 UNITS = ("lft_network", "lft_lightfield", "lft_objective")
@@ -202,7 +202,7 @@ LOSS_EXPORTS = ("lft_lf_loss_scratch_bytes", "lft_lf_loss")                     
 SSIM_LOSS_EXPORTS = ("lft_ssim_loss_scratch_bytes", "lft_ssim_loss")                                 # likewise
 REFOCUS_EXPORTS = ("lft_refocus",)                                                                   # likewise
 DISPARITY_EXPORTS = ("lft_disparity_scratch_bytes", "lft_disparity")                                 # likewise
-# View synthesis, semi-global aggregation, the visibility test, the occlusion-aware sweep, the subset's all-in-focus image, the sheared scene tiling, the blended integrate, the refinement of a disparity map and the focal-stack term are declared in headers of their own (ADDON_HEADERS) and bound from a table of their
+# View synthesis, semi-global aggregation, the visibility test, the occlusion-aware sweep, the subset's all-in-focus image, the sheared scene tiling, the blended integrate, the angular tiling of a field, the refinement of a disparity map and the focal-stack term are declared in headers of their own (ADDON_HEADERS) and bound from a table of their
 # own: _SIGS, EXPORTS, STREAM_LAST and TEST_EXPORTS are the two older headers' and keep their contents.
 _ADDON_PROTOTYPES = {h: _prototypes(h) for h in ADDON_HEADERS}
 _ADDON_SIGS = {name: (res, args) for protos in _ADDON_PROTOTYPES.values() for name, (res, args, _) in protos.items()}
@@ -216,11 +216,12 @@ OCCLUSION_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_occlusion.h"])     # lft_di
 AIF_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_aif.h"])                 # lft_aif_at
 SHEAR_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_shear.h"])             # lft_scene_divide_shear, lft_scene_integrate_shear, lft_shear_vote
 BLEND_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_blend.h"])             # lft_scene_integrate_blend
+FIELD_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_field.h"])             # lft_field_counts, lft_field_divide, lft_field_integrate
 REFINE_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_refine.h"])           # lft_disp_check, lft_disp_fill, lft_disp_wmedian
 FOCAL_EXPORTS = tuple(_ADDON_PROTOTYPES["lft_hip_focal.h"])             # lft_focal_loss_scratch_bytes, lft_focal_loss, lft_refocus_adjoint
 # what an older LFT_LIB_PATH build of the same ABI version (A/B runs) may lack: lib() binds everything else unconditionally
 OPTIONAL_EXPORTS = frozenset(TEST_EXPORTS + GUARD_EXPORTS + EMA_EXPORTS + LOSS_EXPORTS + SSIM_LOSS_EXPORTS + REFOCUS_EXPORTS + DISPARITY_EXPORTS + VIEW_EXPORTS
-                             + SGM_EXPORTS + VISIBILITY_EXPORTS + OCCLUSION_EXPORTS + AIF_EXPORTS + SHEAR_EXPORTS + BLEND_EXPORTS + REFINE_EXPORTS + FOCAL_EXPORTS)
+                             + SGM_EXPORTS + VISIBILITY_EXPORTS + OCCLUSION_EXPORTS + AIF_EXPORTS + SHEAR_EXPORTS + BLEND_EXPORTS + FIELD_EXPORTS + REFINE_EXPORTS + FOCAL_EXPORTS)
 BUCKET_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_size_t, c_size_t)     # lft_bucket_fn of include/lft_hip.h: 0 = go on, else stop
 
 

@@ -108,15 +108,31 @@ def bicubic_lf(lf, A: int, s: int, out_dtype=torch.uint8, device=None) -> torch.
 
 @torch.no_grad()
 def super_resolve_lf(net, lf, patch: int = 32, stride: int = 16, max_batch: int = 64, ensemble=None,
-                     out_dtype=torch.uint8, shear=None, blend=None) -> torch.Tensor:
+                     out_dtype=torch.uint8, shear=None, blend=None, views: str = "centre", astride=None, angular="flat") -> torch.Tensor:
     """Super-resolved RGB views [A, A, s*H, s*W, 3] of a low-resolution RGB light field: ``luma`` -> the network over the whole
     scene (``scene.super_resolve_scene``: any precision of `net`, any ``ensemble=``, ``shear=`` or ``blend=``) -> ``merge``.  A loaded array goes to the
-    device of the network's parameters."""
+    device of the network's parameters.
+    views: "centre" (the centre A x A views, as always) or "all": every view of a square U x U field, [U, U, s*H, s*W, 3], through
+    ``field.super_resolve_field`` with its `astride` and `angular` (A x A windows over the views, a weighted mean where they overlap)."""
     from . import scene
     A, s = net.angRes, net.factor
+    if views not in ("centre", "all"):
+        raise LftError(f"views must be centre or all, got {views!r}")
     dev = None
     if isinstance(lf, np.ndarray):
         dev = next(net.parameters()).device
+    if views == "all":
+        from . import field
+        shape = tuple(getattr(lf, "shape", ()))
+        if len(shape) != 5:
+            raise LftError(f"the light field must be [U, V, H, W, C], got shape {shape}")
+        U, V = int(shape[0]), int(shape[1])
+        if U != V:
+            raise LftError(f"super_resolve_lf(views=all): a light field of shape {shape} has {U} x {V} views; the colour path takes a square field "
+                           "(field.super_resolve_field takes U != V)")
+        t = _field(lf, U, dev)
+        sr_y = field.super_resolve_field(net, luma(t, U), U, V, patch, stride, max_batch, astride, angular, ensemble, shear, blend)
+        return merge(t, sr_y, U, s, out_dtype)
     t = _field(lf, A, dev)
     sr_y = scene.super_resolve_scene(net, luma(t, A), patch, stride, max_batch, ensemble, shear, **({} if blend is None else {"blend": blend}))
     return merge(t, sr_y, A, s, out_dtype)

@@ -3,8 +3,8 @@
 // synthesis (declared in include/lft_hip_views.h), semi-global aggregation (declared in include/lft_hip_sgm.h), the sweep's
 // occlusion-aware cost (declared in include/lft_hip_occlusion.h), the all-in-focus image from the winning partial aperture
 // (declared in include/lft_hip_aif.h), scene tiling with a per-patch integer shear (declared in include/lft_hip_shear.h),
-// windowed blending of overlapping SR patches (declared in include/lft_hip_blend.h) and the refinement of a selected disparity map
-// (declared in include/lft_hip_refine.h).
+// windowed blending of overlapping SR patches (declared in include/lft_hip_blend.h), angular tiling of a U x V field (declared in
+// include/lft_hip_field.h) and the refinement of a selected disparity map (declared in include/lft_hip_refine.h).
 #include "lft_host.cuh"
 #include "../../include/lft_hip_views.h"
 #include "../../include/lft_hip_sgm.h"
@@ -13,10 +13,12 @@
 #include "../../include/lft_hip_aif.h"
 #include "../../include/lft_hip_shear.h"
 #include "../../include/lft_hip_blend.h"
+#include "../../include/lft_hip_field.h"
 #include "../../include/lft_hip_refine.h"
 #include "lft_scene.cuh"     // scene tiling: divide into patch mosaics, integrate
 #include "lft_shear.cuh"     // scene tiling with a per-patch integer shear, the vote that chooses it (lft_scene_divide_shear, lft_shear_vote)
 #include "lft_blend.cuh"     // windowed blending of overlapping SR patches into the SR scene (lft_scene_integrate_blend)
+#include "lft_field.cuh"     // angular tiling: A x A windows over a U x V field, cut and put together (lft_field_divide, lft_field_integrate)
 #include "lft_metrics.cuh"
 #include "lft_prepare.cuh"    // data preparation (reference Generate_Data_for_*.m)
 #include "lft_ensemble.cuh"  // dihedral transforms: self-ensemble expand / merge / fused scene integrate, per-sample augmentation
@@ -734,6 +736,81 @@ int lft_scene_integrate_blend(const float* sr_patches, const int* shear, const f
     kernel<<<grid, 256, (size_t)patch * s * sizeof(float), static_cast<hipStream_t>(stream)>>>(sr_patches, shear, window, sr_scene, A, patch * s, stride * s, h0 * s,
                                                                                            w0 * s, nu, nv, s, kmax);
     LFT_LAUNCH_OK("k_scene_integrate_blend");
+    return 0;
+}
+
+// ---- angular tiling of a U x V field (lft_field.cuh; declared in include/lft_hip_field.h) ----
+// The windows of both axes: *mu, *mv.
+static int field_windows_ok(const char* who, int U, int V, int A, int astride, int* mu, int* mv) {
+    if (A < 1) return fail(LFT_ERR_ARG, "%s: angRes %d", who, A);
+    if (U < A || V < A || U > LFT_FIELD_MAX_VIEWS || V > LFT_FIELD_MAX_VIEWS)
+        return fail(LFT_ERR_SHAPE, "%s: a field of %d x %d views (each axis %d .. %d for angRes %d)", who, U, V, A, LFT_FIELD_MAX_VIEWS, A);
+    if (astride < 1 || astride > A) return fail(LFT_ERR_SHAPE, "%s: angular stride %d outside 1 .. angRes %d", who, astride, A);
+    *mu = U == A ? 1 : (U - A + astride - 1) / astride + 1;
+    *mv = V == A ? 1 : (V - A + astride - 1) / astride + 1;
+    return 0;
+}
+// the most windows one view lies in along an axis of L views in m windows
+static int field_multiplicity(int L, int A, int astride, int m) {
+    int most = 0;
+    for (int p = 0; p < L; ++p) {
+        int c = 0;
+        for (int i = 0; i < m; ++i) {
+            const int o = std::min(i * astride, L - A);
+            c += p >= o && p < o + A;
+        }
+        most = std::max(most, c);
+    }
+    return most;
+}
+int lft_field_counts(int U, int V, int A, int astride, int* mu, int* mv) {
+    const char* who = "lft_field_counts";
+    if (!mu || !mv) return fail(LFT_ERR_ARG, "%s: null pointer", who);
+    return field_windows_ok(who, U, V, A, astride, mu, mv);
+}
+int lft_field_divide(const float* field, const int* shear, float* patches, int U, int V, int A, int astride, int h0, int w0, int patch, int stride, void* stream) {
+    const char* who = "lft_field_divide";
+    int mu, mv, nu, nv, kmax = 0;
+    if (!field || !patches) return fail(LFT_ERR_ARG, "%s: null pointer", who);                          // shear may be null: the plain cut
+    if (int rc = field_windows_ok(who, U, V, A, astride, &mu, &mv)) return rc;
+    if (int rc = shear ? shear_tiling_ok(who, A, h0, w0, patch, stride, &nu, &nv, &kmax) : scene_counts(h0, w0, patch, stride, &nu, &nv)) return rc;
+    // this launch: one block row per row of a patch mosaic, one block plane per patch, the windows along x; the mosaics are indexed in int
+    const long long cb = ((long long)A * patch + 255) / 256;
+    if ((long long)A * patch > 65535 || (long long)nu * nv > 65535)
+        return fail(LFT_ERR_SHAPE, "%s: patch mosaics of %lld rows and %d x %d patches need more than 65535 blocks in the grid's y or z", who, (long long)A * patch, nu, nv);
+    if ((long long)U * h0 > 0x7fffffffLL || (long long)V * w0 > 0x7fffffffLL || (long long)mu * mv * nu * nv > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "%s: a field mosaic of %d x %d views of %d x %d in %d x %d windows of %d x %d patches is indexed beyond 2^31", who, U, V, h0, w0, mu, mv,
+                    nu, nv);
+    if (cb * mu * mv > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: %d x %d windows of %lld column blocks need more than 2^31 blocks in the grid's x", who, mu, mv, cb);
+    const FieldGeom f{U, V, A, astride, mu, mv, h0, w0, patch, stride, nu, nv, 1, kmax};
+    const dim3 grid((unsigned)(cb * mu * mv), (unsigned)(A * patch), (unsigned)(nu * nv));
+    k_field_divide<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(field, shear, patches, f, (int)cb);
+    LFT_LAUNCH_OK("k_field_divide");
+    return 0;
+}
+int lft_field_integrate(const float* sr_patches, const int* shear, const float* window, const float* angular, float* sr_field, int U, int V, int A, int astride,
+                        int h0, int w0, int patch, int stride, int s, void* stream) {
+    const char* who = "lft_field_integrate";
+    int mu, mv, nu, nv, kmax = 0;
+    if (!sr_patches || !angular || !sr_field) return fail(LFT_ERR_ARG, "%s: null pointer", who);         // shear may be null: no shear; window: the crop
+    if (A < 1) return fail(LFT_ERR_ARG, "%s: angRes %d", who, A);
+    if (s != 2 && s != 4) return fail(LFT_ERR_ARG, "%s: scale factor %d (2 or 4)", who, s);
+    if (int rc = field_windows_ok(who, U, V, A, astride, &mu, &mv)) return rc;
+    if (int rc = shear || window ? shear_tiling_ok(who, A, h0, w0, patch, stride, &nu, &nv, &kmax) : scene_counts(h0, w0, patch, stride, &nu, &nv)) return rc;
+    // this launch: k_scene_integrate_blend's grid and its limits, and the two tables in LDS
+    if ((long long)patch * s > LFT_BLEND_MAX_PZ) return fail(LFT_ERR_SHAPE, "%s: a window of %lld entries (at most %d)", who, (long long)patch * s, LFT_BLEND_MAX_PZ);
+    if ((long long)U * h0 * s > 65535) return fail(LFT_ERR_SHAPE, "%s: an SR field mosaic of %lld rows needs more than 65535 blocks in the grid's y", who, (long long)U * h0 * s);
+    if ((long long)V * w0 * s > 0x7fffffffLL || (long long)mu * mv * nu * nv > 0x7fffffffLL)
+        return fail(LFT_ERR_SHAPE, "%s: an SR field mosaic of %lld columns in %d x %d windows of %d x %d patches is indexed beyond 2^31", who, (long long)V * w0 * s, mu,
+                    mv, nu, nv);
+    if ((long long)patch * s * A > 0x7fffffffLL) return fail(LFT_ERR_SHAPE, "%s: SR patch mosaics of %lld pixels a side", who, (long long)patch * s * A);
+    const FieldGeom f{U, V, A, astride, mu, mv, h0 * s, w0 * s, patch * s, stride * s, nu, nv, s, kmax};
+    const dim3 grid((unsigned)((V * w0 * s + 255) / 256), (unsigned)(U * h0 * s));
+    // the crop with at most 2 windows a view lies in per axis has them written out; everything else, every blend included, loops
+    const int mult = std::max(field_multiplicity(U, A, astride, mu), field_multiplicity(V, A, astride, mv));
+    const auto kernel = window || mult > 2 ? k_field_integrate<0> : mult == 1 ? k_field_integrate<1> : k_field_integrate<2>;
+    kernel<<<grid, 256, ((size_t)A + (window ? (size_t)patch * s : 0)) * sizeof(float), static_cast<hipStream_t>(stream)>>>(sr_patches, shear, window, angular, sr_field, f);
+    LFT_LAUNCH_OK("k_field_integrate");
     return 0;
 }
 
